@@ -23,6 +23,12 @@ With --gpus N the frame's 8x8 pixel tiles are sharded over N ranks (one process 
 the caller used it, otherwise `bench.py --gpus N` starts its own N ranks as a child process, launch_ranks()); there is no collective in the timed region -- the RCCL framebuffer gather (all five planes,
 through the library's own C++ entry er_gather_pass) happens once after it and is reported as readback_ms.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: scene and device set-up, W warm-up
+steps, ONE timed region of exactly N steps, and the line (`value`, `ms_per_step` and the timed region's counts).  `--full` adds
+everything else, as before: five repeats of the timed region (`--repeats`), the roofline block (instrumented replay, single-pool
+trace phase, measured HBM peak, recorded PMC traffic), the frame's mean, `projected` and `cpu_baseline`.
+`--dump-outputs DIR` writes what a caller of the timed path receives after its last step as DIR/<name>.npy (dump_outputs()).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -164,6 +170,33 @@ def dry_run(rank, world):
     return 0
 
 
+DUMP_PLANES = ("beauty", "normal", "tangent", "bitangent")   # the planes a render fills (DENOISE is filled by er_denoise only)
+DUMP_MAX_PIXELS = 1 << 19       # larger frames are written as this many pixels: 4 planes x 16 B + an 8-byte index each = 36 MiB
+DUMP_SEED = 12345
+
+
+def dump_outputs(rm, out_dir):
+    """--dump-outputs DIR: what a caller of the timed path receives after its last step -- the four planes of the frame (RGBA
+    float32, reference get_pass) and the render's sample count (get_render_info) -- as DIR/<name>.npy, so that two builds can be
+    compared output for output.  A frame of more than DUMP_MAX_PIXELS pixels is written as a fixed sample of them (seed
+    DUMP_SEED, sorted, the same pixels in every plane and every run): plane arrays are then (n, 4), and pixel_index.npy holds the
+    flat pixel indices (y * width + x) as float64.  Returns the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n_px = rm.scene.x_res * rm.scene.y_res
+    idx = None
+    if n_px > DUMP_MAX_PIXELS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_px, DUMP_MAX_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+    names = ["pixel_index"] if idx is not None else []
+    for name in DUMP_PLANES:
+        plane = rm.get_pass(name)
+        np.save(os.path.join(out_dir, f"{name}.npy"), plane if idx is None else plane.reshape(-1, 4)[idx])
+        names.append(name)
+    np.save(os.path.join(out_dir, "samples_done.npy"), np.array([rm.get_render_info().samples], np.float64))
+    return names + ["samples_done"]
+
+
 CONFIGS = {
     # name: (description, default max_bounces, config spp)
     "C1": ("Cornell box, 12 triangles, 256x256", 4, 16),
@@ -223,10 +256,14 @@ def main():
     ap.add_argument("--sim-world", type=int, default=0, help="(diagnostic) render only rank --sim-rank's tiles of this many, no collective")
     ap.add_argument("--sim-rank", type=int, default=0)
     ap.add_argument("--no-projection", action="store_true", help="skip the `projected` block (N = 1 only): rank 0's share of a 2-, 4- and 8-way tile split rendered alone on this GPU")
-    ap.add_argument("--repeats", type=int, default=5, help="the timed region (exactly --steps steps between two barriers) is run this many times back to back; "
-                    "`value` is the median repeat, all of them are in `repeats`")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed region (exactly --steps steps between two barriers) is run this many times back to back; "
+                    "`value` is the median repeat, all of them are in `repeats` (default 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true", help="measure everything, not only the headline: five repeats, the roofline block (its own replays and "
+                    "an HBM peak kernel), the frame's mean, `projected` and `cpu_baseline`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the frame's planes and sample count as DIR/<name>.npy "
+                    "(a fixed sample of the pixels on frames of more than 512 Ki pixels)")
     args = ap.parse_args()
-    args.repeats = max(1, args.repeats)
+    args.repeats = max(1, args.repeats if args.repeats is not None else (5 if args.full else 1))
     max_bounces = args.max_bounces or CONFIGS[args.config][1]
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -433,14 +470,22 @@ def main():
     gather_path, gather_ms = gstate["path"], gstate["ms"]
     gather_ok = dist is None or (not gather_hung and not gstate["error"])
     beauty_mean = None
-    if rank == 0 and gather_ok:
+    if rank == 0 and gather_ok and args.full:
         img = rm.get_pass("beauty")
         assert np.isfinite(img).all()
         beauty_mean = float(img[..., :3].mean())
-    readback_ms = (time.perf_counter() - t_rb) * 1e3
+    readback_ms = (time.perf_counter() - t_rb) * 1e3 if (dist is not None or args.full) else None    # (a plain one-rank run reads nothing back)
+    if rank == 0 and args.dump_outputs:
+        if gather_ok:
+            written = dump_outputs(rm, args.dump_outputs)
+            print(f"bench.py: wrote {', '.join(n + '.npy' for n in written)} to {args.dump_outputs}", file=sys.stderr, flush=True)
+        else:
+            print("bench.py: --dump-outputs skipped: the frame was not gathered", file=sys.stderr, flush=True)
 
     result = None
-    if rank == 0:
+    roofline = None
+    sched = {abi.FLAG_WAVEFRONT: "wavefront", abi.FLAG_MEGAKERNEL: "megakernel", abi.FLAG_STREAM: "stream"}.get(prof["schedule"], "?")
+    if rank == 0 and args.full:
         # ---- roofline: algorithmic bytes from an instrumented replay of the same samples ----
         inst = manager(abi.FLAG_COUNTERS)
         n_inst = min(2, args.steps)
@@ -456,7 +501,6 @@ def main():
         path_b = path_bytes(ci, hdri_texels) / max(1, ci["bounce_samples"]) * my_samples
         t_launches = max(1, prof["trace_launches"])
         trace_ms_avg = prof["trace_ms"] / t_launches
-        sched = {abi.FLAG_WAVEFRONT: "wavefront", abi.FLAG_MEGAKERNEL: "megakernel", abi.FLAG_STREAM: "stream"}.get(prof["schedule"], "?")
         kernel_name = {"wavefront": "er_wf_trace", "megakernel": "er_render_kernel", "stream": "er_stream_kernel"}.get(sched, "?")
         if sched not in ("wavefront", "stream"):
             layout_b = path_b + (layout_b - trace_b)
@@ -526,6 +570,52 @@ def main():
             if os.path.exists(tf):
                 traffic = json.load(open(tf)).get("er_wf_trace_hbm_bytes_per_launch")
                 traffic_source = f"profiles/{os.path.basename(tf)}: PMC passes of an earlier run of this command, replayed (not measured in this run)"
+        roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                     # the same counter bytes as a rate over the timed region: what the L2s asked of the fabric (Infinity-Cache hits
+                     # are counted), against the spec peak and the peak measured in this job
+                     # (wavefront: `traffic` is per trace launch of one pool -- the shade launches' bytes are not in it)
+                     "traffic_GBps": round(traffic * (t_launches if sched == "wavefront" else launches) / wall_s / 1e9, 1) if traffic else None,
+                     "traffic_frac": round(traffic * (t_launches if sched == "wavefront" else launches) / wall_s / 1e9 / HBM_PEAK_GBS, 4) if traffic else None,
+                     # "L2/MALL-resident traffic must be reported separately from HBM".  What the traversal touches -- wide nodes +
+                     # 48-byte triangle records -- against the 256 MB Infinity Cache: a working set inside it is served by the L2s and that
+                     # cache (FETCH_SIZE, and so `traffic`, counts its hits), and "bound: hbm" then names the roofline the
+                     # metric is defined against, not the unit that limits the kernel (the tracer waves' instruction
+                     # streams; profiles/r06_c4_working_set_sweep.log: 57 MB -> 1 147 MB of the same frame costs 19 % of the rate)
+                     "resident": {"traversal_working_set_MB": round((accel["node_count"] * accel["node_bytes"] + 48.0 * scene.tri_count) / 1e6, 1),
+                                  "infinity_cache_MB": 256,
+                                  "where": "inside the Infinity Cache" if accel["node_count"] * accel["node_bytes"] + 48.0 * scene.tri_count <= 256e6 else "beyond the Infinity Cache"},
+                     "kernel": kernel_name,
+                     "definition": "achieved = all traversal bytes of the timed region (64 B/node visit + 36 B/triangle test, SURVEY 8d) / device time of the region"
+                                   + ("; the streaming schedule is ONE kernel (traversal and shading waves side by side): region time = its launch duration, nothing overlaps it" if sched == "stream" else ""),
+                     "peak_measured": round(peak_measured, 1) if peak_measured else None,
+                     "peak_measured_copy": round(copy_gbs, 1) if copy_gbs else None, "peak_measured_read": round(read_gbs, 1) if read_gbs else None,
+                     "frac_of_measured": round(achieved / peak_measured, 4) if peak_measured else None,
+                     "trace_phase": trace_phase,
+                     "launches": prof["trace_launches"], "empty_launches": prof["empty_launches"], "empty_ms": round(prof["empty_ms"], 3),
+                     "pools_side_by_side": max(1, int(prof.get("concurrency", 1))),
+                     "achieved_per_launch": round(per_launch, 2),
+                     "achieved_own_layout": round(achieved * layout_b / max(trace_b, 1.0), 2),
+                     "avg_launch_ms": round(trace_ms_avg, 5), "algorithmic_bytes_per_launch": round(trace_b / t_launches, 1),
+                     # rocprofv3 --stats also sees the warm-up call: for the one-kernel-per-call schedules its row is
+                     # (warm-up launch, timed launch), i.e. MaxNs = avg_launch_ms and AverageNs = their mean
+                     "warmup_launch_ms": round(region["warmup_ms"], 3) if region.get("warmup_ms") is not None else None,
+                     "trace_ms_total": round(prof["trace_ms"], 3), "shade_ms_total": round(prof["shade_ms"], 3),
+                     "region_ms": round(kernel_ms, 3),
+                     # SURVEY 8(d)'s FULL per-pixel-sample formula (64 V + 36 T + 112 H + 12 X + 4 ceil(log2 P) S + 112) over the same region: the
+                     # streaming kernel runs the whole path, so this is its algorithmic rate by the survey's definition; `achieved` / `frac` keep
+                     # to the traversal terms alone (north_star: "during BVH traversal"), as in every earlier round
+                     "whole_path_GBps": round(path_b / wall_s / 1e9, 2), "frac_whole_path": round(path_b / wall_s / 1e9 / HBM_PEAK_GBS, 4),
+                     "node_visits_per_ray": round(ci["node_visits"] / max(1, ci["rays"]), 2),
+                     "tri_tests_per_ray": round(ci["tri_tests"] / max(1, ci["rays"]), 2),
+                     # lane occupancy of er_wf_trace's loop in the instrumented replay: share of the 64 lanes that held a
+                     # ray / ran the node part / ran the triangle part, per loop iteration of a wave
+                     "trace_lanes": None if not ci.get("trace_wave_steps") else {
+                         "wave_steps": ci["trace_wave_steps"],
+                         "busy": round(ci["trace_busy_lanes"] / (64.0 * ci["trace_wave_steps"]), 4),
+                         "node": round(ci["trace_node_lanes"] / (64.0 * ci["trace_wave_steps"]), 4),
+                         "tri": round(ci["trace_tri_lanes"] / (64.0 * ci["trace_wave_steps"]), 4)}}
+    if rank == 0:
         value = samples / elapsed / 1e6
         result = {
             "metric": "Msamples/sec (rays traced x bounces) at 1920x1080, 1M-tri scene",
@@ -540,58 +630,14 @@ def main():
                        "schedule": sched, "schedule_fallback": schedule_fallback},
             "paths_per_s": round(paths / elapsed, 1), "rays_per_s": round(rays / elapsed, 1),
             "mean_path_length": round(samples / max(1, paths), 4),
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                         # the same counter bytes as a rate over the timed region: what the L2s asked of the fabric (Infinity-Cache hits
-                         # are counted, MI355X_MICROARCH.md), against the spec peak and the peak measured in this job
-                         # (wavefront: `traffic` is per trace launch of one pool -- the shade launches' bytes are not in it)
-                         "traffic_GBps": round(traffic * (t_launches if sched == "wavefront" else launches) / wall_s / 1e9, 1) if traffic else None,
-                         "traffic_frac": round(traffic * (t_launches if sched == "wavefront" else launches) / wall_s / 1e9 / HBM_PEAK_GBS, 4) if traffic else None,
-                         # "L2/MALL-resident traffic must be reported separately from HBM".  What the traversal touches -- wide nodes +
-                         # 48-byte triangle records -- against the 256 MB Infinity Cache: a working set inside it is served by the L2s and that
-                         # cache (FETCH_SIZE, and so `traffic`, counts its hits: MI355X_MICROARCH.md), and "bound: hbm" then names the roofline the
-                         # metric is defined against, not the unit that limits the kernel (the tracer waves' instruction
-                         # streams; profiles/r06_c4_working_set_sweep.log: 57 MB -> 1 147 MB of the same frame costs 19 % of the rate)
-                         "resident": {"traversal_working_set_MB": round((accel["node_count"] * accel["node_bytes"] + 48.0 * scene.tri_count) / 1e6, 1),
-                                      "infinity_cache_MB": 256,
-                                      "where": "inside the Infinity Cache" if accel["node_count"] * accel["node_bytes"] + 48.0 * scene.tri_count <= 256e6 else "beyond the Infinity Cache"},
-                         "kernel": kernel_name,
-                         "definition": "achieved = all traversal bytes of the timed region (64 B/node visit + 36 B/triangle test, SURVEY 8d) / device time of the region"
-                                       + ("; the streaming schedule is ONE kernel (traversal and shading waves side by side): region time = its launch duration, nothing overlaps it" if sched == "stream" else ""),
-                         "peak_measured": round(peak_measured, 1) if peak_measured else None,
-                         "peak_measured_copy": round(copy_gbs, 1) if copy_gbs else None, "peak_measured_read": round(read_gbs, 1) if read_gbs else None,
-                         "frac_of_measured": round(achieved / peak_measured, 4) if peak_measured else None,
-                         "trace_phase": trace_phase,
-                         "launches": prof["trace_launches"], "empty_launches": prof["empty_launches"], "empty_ms": round(prof["empty_ms"], 3),
-                         "pools_side_by_side": max(1, int(prof.get("concurrency", 1))),
-                         "achieved_per_launch": round(per_launch, 2),
-                         "achieved_own_layout": round(achieved * layout_b / max(trace_b, 1.0), 2),
-                         "avg_launch_ms": round(trace_ms_avg, 5), "algorithmic_bytes_per_launch": round(trace_b / t_launches, 1),
-                         # rocprofv3 --stats also sees the warm-up call: for the one-kernel-per-call schedules its row is
-                         # (warm-up launch, timed launch), i.e. MaxNs = avg_launch_ms and AverageNs = their mean
-                         "warmup_launch_ms": round(region["warmup_ms"], 3) if region.get("warmup_ms") is not None else None,
-                         "trace_ms_total": round(prof["trace_ms"], 3), "shade_ms_total": round(prof["shade_ms"], 3),
-                         "region_ms": round(kernel_ms, 3),
-                         # SURVEY 8(d)'s FULL per-pixel-sample formula (64 V + 36 T + 112 H + 12 X + 4 ceil(log2 P) S + 112) over the same region: the
-                         # streaming kernel runs the whole path, so this is its algorithmic rate by the survey's definition; `achieved` / `frac` keep
-                         # to the traversal terms alone (north_star: "during BVH traversal"), as in every earlier round
-                         "whole_path_GBps": round(path_b / wall_s / 1e9, 2), "frac_whole_path": round(path_b / wall_s / 1e9 / HBM_PEAK_GBS, 4),
-                         "node_visits_per_ray": round(ci["node_visits"] / max(1, ci["rays"]), 2),
-                         "tri_tests_per_ray": round(ci["tri_tests"] / max(1, ci["rays"]), 2),
-                         # lane occupancy of er_wf_trace's loop in the instrumented replay: share of the 64 lanes that held a
-                         # ray / ran the node part / ran the triangle part, per loop iteration of a wave
-                         "trace_lanes": None if not ci.get("trace_wave_steps") else {
-                             "wave_steps": ci["trace_wave_steps"],
-                             "busy": round(ci["trace_busy_lanes"] / (64.0 * ci["trace_wave_steps"]), 4),
-                             "node": round(ci["trace_node_lanes"] / (64.0 * ci["trace_wave_steps"]), 4),
-                             "tri": round(ci["trace_tri_lanes"] / (64.0 * ci["trace_wave_steps"]), 4)}},
+            "roofline": roofline,           # --full only: null in a plain run
             "accel": {"nodes": accel["node_count"], "node_bytes": accel["node_bytes"], "leaves": accel["leaf_count"],
                       "max_depth": accel["max_depth"], "build_ms": round(accel["build_ms"], 1), "builder": "device binned SAH" if accel["builder"] else "host binned SAH", "upload_ms": round(accel["upload_ms"], 2)},
             # every repeat of the timed region (each exactly `steps` steps between two barriers): `value` is the median one
             "repeats": {"k": K, "values": [round(v, 3) for v in rep_values], "median_index": mid, "min": round(min(rep_values), 3), "max": round(max(rep_values), 3),
                         "spread": round((max(rep_values) - min(rep_values)) / max(rep_values[mid], 1e-12), 5),
                         "region_ms": [round(r["kernel_ms"], 3) for r in reps], "elapsed_ms": [round(e * 1e3, 3) for e in rep_elapsed]},
-            "readback_ms": round(readback_ms, 2), "gather": gather_path, "beauty_mean": beauty_mean,
+            "readback_ms": round(readback_ms, 2) if readback_ms is not None else None, "gather": gather_path, "beauty_mean": beauty_mean,
             # the streaming schedule's configuration of this rank's share and its speculation counts over the render (zero on whole frames:
             # speculative samples exist in the kernel's form 2 only, i.e. on shares of at most 2 304 pixels per CU)
             "stream": (lambda si: {"pixels_per_cu": si["pixels_per_cu"], "form": si["form"], "waves": si["waves"], "tracers": si["tracers"], "large_regions": bool(si["large_regions"]), "lanes_busy": round(si["lanes_busy"], 4),
@@ -602,7 +648,7 @@ def main():
             "gather_ms": round(gather_ms, 3) if gather_ms is not None else None,
             "gather_bytes": (int(scene.x_res) * int(scene.y_res) * 16 * 5 * (world - 1) // world) if world > 1 else None,
         }
-        if world == 1 and shard_world == 1 and not args.no_projection:
+        if args.full and world == 1 and shard_world == 1 and not args.no_projection:
             # What the first SCALE record can be read against: rank 0's share of an N-way split of the SAME frame ((tx + ty) % N tiles),
             # rendered alone on this GPU with the same steps and warm-up -- every rank of a real N-GPU run does this much work side by side
             # (the soup's shares are alike; a frame of uneven cost has a slowest rank, which this does not show), then one gather.
@@ -637,7 +683,7 @@ def main():
             result["projected"] = {"what": "one GPU's share (rank 0 of N) of this frame rendered alone on this GPU, median of 3 launches of `steps` steps; "
                                            "speedup = whole-frame device time / share device time; excludes the framebuffer gather (one per read-back, outside the timed region)",
                                    "n_gpus": proj}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = args.cpu_threads or host_cores()
             # C4: ONE reference-style BVH build of the 10 M triangles (the expensive part, not timed), then the same bounded sample
             # of rows on all cores; the one-core leg would need a second build and is left out there

@@ -70,7 +70,10 @@ def _free_port():
 
 @pytest.mark.parametrize("world,res", [(2, (100, 60)), (3, (64, 40))])
 def test_gloo_framebuffer_gather(world, res):
-    import torch.multiprocessing as mp
+    # (the standard library's spawn context: torch is imported by the workers only.  Imported into the test process after the
+    # library has loaded ROCm's HIP runtime, torch would add its own HIP runtime and its librccl.so.1, and the library's RCCL
+    # communicator in tests/test_gpu_collective.py would then resolve to that RCCL, on a runtime that sees no device)
+    import multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()

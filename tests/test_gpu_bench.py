@@ -1,5 +1,6 @@
-"""bench.py's contract on a small frame: one JSON line with `roofline`, and a failure of the default schedule's timed region
-is reported as a DEGRADED measurement (top-level flag + exit code 3), not as a quiet success."""
+"""bench.py's contract on a small frame: one JSON line (with `roofline` under --full), a plain run that times exactly --steps
+steps and writes the same outputs every time with --dump-outputs, and a failure of the default schedule's timed region
+reported as a DEGRADED measurement (top-level flag + exit code 3), not as a quiet success."""
 import json
 import os
 import subprocess
@@ -12,23 +13,49 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ["--tris", "20000", "--width", "256", "--height", "192", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-trace-phase"]
 
 
-def _run(extra_env):
+def _run(extra_env, extra_args=()):
     env = dict(os.environ)
     env.update(extra_env)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + list(extra_args), cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, (p.stdout[-2000:], p.stderr[-2000:])
     return p.returncode, json.loads(lines[0])
 
 
 def test_bench_line_on_a_small_frame():
-    rc, line = _run({})
+    rc, line = _run({}, ["--full"])
     assert rc == 0
     assert line["degraded"] is False and line["config"]["schedule_fallback"] is None
     assert line["unit"] == "Msamples/s" and line["value"] > 0 and line["dtype"] == "f32"
     r = line["roofline"]
     assert r["bound"] == "hbm" and r["peak"] == 8000.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
     assert r["traffic"] is None and r["traffic_source"] is None      # counter bytes exist for the full C2 frame only, and say where they are from
+
+
+def test_a_plain_run_times_exactly_its_steps_and_dumps_the_same_frame_every_time(tmp_path):
+    """No --full: one timed region of exactly --steps steps, nothing measured beside it; --dump-outputs writes the frame's planes
+    and sample count, and a second run with the same arguments writes the same bits."""
+    import numpy as np
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        rc, line = _run({}, ["--dump-outputs", str(tmp_path / run)])
+        assert rc == 0
+        lines.append(line)
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in sorted(os.listdir(tmp_path / run))})
+    line = lines[0]
+    assert line["degraded"] is False and line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 3
+    assert line["roofline"] is None and "projected" not in line and "cpu_baseline" not in line and line["beauty_mean"] is None
+    assert line["repeats"]["k"] == 1 and abs(line["ms_per_step"] - line["repeats"]["elapsed_ms"][0] / 3) < 1e-3
+    assert abs(line["paths_per_s"] * line["repeats"]["elapsed_ms"][0] * 1e-3 - 256 * 192 * 3) < 256 * 192 * 3 * 1e-3   # the timed steps, no more
+    a, b = dumps
+    assert sorted(a) == ["beauty", "bitangent", "normal", "samples_done", "tangent"]
+    for name in ("beauty", "normal", "tangent", "bitangent"):
+        assert a[name].dtype == np.float32 and a[name].shape == (192, 256, 4)
+    assert a["samples_done"].dtype == np.float64 and a["samples_done"][0] >= 4
+    assert np.isfinite(a["beauty"]).all() and a["beauty"][..., :3].mean() > 0
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].tobytes() == b[name].tobytes(), name
 
 
 def test_a_failed_default_schedule_is_reported_as_degraded_and_exits_nonzero():

@@ -6,6 +6,7 @@ thousands of times per run, and with the slot records and per-pixel state in pla
 reports any hand-off the protocol leaves unordered.  This is where the protocol is argued exact; the GPU
 suite only keeps one regression run per call pattern.  No GPU needed."""
 import os
+import platform
 import subprocess
 
 import pytest
@@ -49,7 +50,13 @@ def _run(exe, *args, timeout=300):
     # on a heavily loaded box -- "put guard expired" in the 16-slot / 16-pixel case -- with one line of text and no state: NOTEBOOK.md.)
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1 exitcode=66", ER_MODEL_DEBUG="1")
     env.pop("LD_PRELOAD", None)      # (tools/sanitize_cpu.sh preloads the ASan runtime into python: not into a TSan binary)
-    return subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=timeout, env=env)
+    cmd = [exe] + [str(a) for a in args]
+    if exe.endswith("_tsan"):
+        # g++ 11's ThreadSanitizer expects the program and its libraries where 28 bits of mmap randomisation put them; a kernel
+        # that randomises more places them elsewhere and the runtime stops before main ("FATAL: ThreadSanitizer: unexpected memory
+        # mapping").  The TSan model therefore runs without address randomisation (setarch -R: a personality flag of that process).
+        cmd = ["setarch", platform.machine(), "-R"] + cmd
+    return subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
 
 
 # slots, pixels, samples, tracer waves, shader waves, log2(ray ring cells)

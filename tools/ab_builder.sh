@@ -1,5 +1,5 @@
 set -o pipefail
-for cfg in "C2 --steps 20 --warmup 5" "C4 --config C4 --steps 6 --warmup 4"; do
+for cfg in "C2 --full --steps 20 --warmup 5" "C4 --full --config C4 --steps 6 --warmup 4"; do
   set -- $cfg; name=$1; shift
   for b in ${BUILDERS:-host gpu host gpu}; do
     extra=""; [ $b = gpu ] && extra="--gpu-build"; [ $b = lbvh ] && { extra="--gpu-build"; export ER_GPU_BUILD_LBVH=1; }; [ $b != lbvh ] && unset ER_GPU_BUILD_LBVH

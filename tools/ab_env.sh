@@ -10,7 +10,7 @@ for r in $(seq 1 $reps); do
   for s in $settings; do
     i=$((i + 1))
     e=$s; [ "$s" = "-" ] && e="ER_AB_NONE=1"
-    if ! env $e timeout -k 10 400 python3 bench.py --no-cpu-baseline --no-projection "$@" > $out/run$i.log 2> $out/run$i.err; then echo "$s FAILED"; tail -n 5 $out/run$i.err; exit 1; fi
+    if ! env $e timeout -k 10 400 python3 bench.py --full --no-cpu-baseline --no-projection "$@" > $out/run$i.log 2> $out/run$i.err; then echo "$s FAILED"; tail -n 5 $out/run$i.err; exit 1; fi
     python3 -c "
 import json
 d=json.loads(open('$out/run$i.log').read().strip().splitlines()[-1]); r=d['roofline']; t=r.get('trace_lanes') or {}

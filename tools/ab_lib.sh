@@ -7,7 +7,7 @@ out=gpurun_out/ab_lib; mkdir -p $out
 i=0
 for r in $(seq 1 $reps); do for lib in $a $b; do
   i=$((i + 1))
-  if ! ELEVEN_HIP_LIB=$PWD/$lib timeout -k 10 400 python3 bench.py --no-cpu-baseline --no-projection --no-trace-phase "$@" > $out/$i.log 2> $out/$i.err; then echo "$lib FAILED"; tail -n 5 $out/$i.err; exit 1; fi
+  if ! ELEVEN_HIP_LIB=$PWD/$lib timeout -k 10 400 python3 bench.py --full --no-cpu-baseline --no-projection --no-trace-phase "$@" > $out/$i.log 2> $out/$i.err; then echo "$lib FAILED"; tail -n 5 $out/$i.err; exit 1; fi
   python3 -c "
 import json
 d=json.loads(open('$out/$i.log').read().strip().splitlines()[-1])

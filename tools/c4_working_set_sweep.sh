@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for t in $points; do
   d=$out/$t; mkdir -p $d
   args="--config C4 --blob-tris $t --steps 6 --warmup 2 --no-projection --no-cpu-baseline"
-  if ! timeout -k 10 400 python3 bench.py $args --repeats 3 > $d/bench.log 2> $d/bench.err; then echo "bench at $t FAILED"; tail -n 8 $d/bench.err; exit 1; fi
+  if ! timeout -k 10 400 python3 bench.py $args --full --repeats 3 > $d/bench.log 2> $d/bench.err; then echo "bench at $t FAILED"; tail -n 8 $d/bench.err; exit 1; fi
   pass() {
     name=$1; shift
     if ! timeout -k 10 400 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $d/$name -o run -- python3 bench.py $args --repeats 1 --no-trace-phase > $d/$name.log 2>&1; then

@@ -15,21 +15,21 @@ out=gpurun_out/record_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 if [ $stage = bench ] || [ $stage = all ]; then
-timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench.log 2> $out/bench.err
+timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench.log 2> $out/bench.err
 echo "bench done"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/stats.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o run -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/stats.log 2>&1
 python3 tools/kernel_launches.py $out/stats/run_kernel_trace.csv er_stream_kernel > $out/kernel_launches.txt
 echo "stats done"
-timeout -k 10 300 python3 bench.py --steps 64 --warmup 4 --no-cpu-baseline --no-projection > $out/bench_64.log 2> $out/bench_64.err
-timeout -k 10 200 python3 bench.py --config C1 --steps 16 --warmup 2 > $out/bench_c1.log 2> $out/bench_c1.err
-timeout -k 10 500 python3 bench.py --config C5 --steps 12 --warmup 3 > $out/bench_c5.log 2> $out/bench_c5.err
-timeout -k 10 300 python3 bench.py --config C5 --no-lights --steps 12 --warmup 3 --no-cpu-baseline --no-projection > $out/bench_c5_nolights.log 2> $out/bench_c5_nolights.err
-timeout -k 10 600 python3 bench.py --config C4 --steps 6 --warmup 4 > $out/bench_c4.log 2> $out/bench_c4.err
+timeout -k 10 300 python3 bench.py --full --steps 64 --warmup 4 --no-cpu-baseline --no-projection > $out/bench_64.log 2> $out/bench_64.err
+timeout -k 10 200 python3 bench.py --full --config C1 --steps 16 --warmup 2 > $out/bench_c1.log 2> $out/bench_c1.err
+timeout -k 10 500 python3 bench.py --full --config C5 --steps 12 --warmup 3 > $out/bench_c5.log 2> $out/bench_c5.err
+timeout -k 10 300 python3 bench.py --full --config C5 --no-lights --steps 12 --warmup 3 --no-cpu-baseline --no-projection > $out/bench_c5_nolights.log 2> $out/bench_c5_nolights.err
+timeout -k 10 600 python3 bench.py --full --config C4 --steps 6 --warmup 4 > $out/bench_c4.log 2> $out/bench_c4.err
 echo "configs done"
 for s in 2 4 8; do
-  timeout -k 10 200 python3 bench.py --sim-world $s --steps 20 --warmup 5 --no-cpu-baseline --no-projection > $out/bench_sim$s.log 2> $out/bench_sim$s.err
+  timeout -k 10 200 python3 bench.py --full --sim-world $s --steps 20 --warmup 5 --no-cpu-baseline --no-projection > $out/bench_sim$s.log 2> $out/bench_sim$s.err
 done
-ER_BENCH_REHEARSAL=1 timeout -k 10 400 python3 bench.py --gpus 2 --steps 8 --warmup 2 --no-cpu-baseline > $out/bench_rehearsal2.log 2> $out/bench_rehearsal2.err
+ER_BENCH_REHEARSAL=1 timeout -k 10 400 python3 bench.py --full --gpus 2 --steps 8 --warmup 2 --no-cpu-baseline > $out/bench_rehearsal2.log 2> $out/bench_rehearsal2.err
 echo "shares + rehearsal done"
 fi
 if [ $stage = pmc_c2 ] || [ $stage = all ]; then bash tools/pmc_passes.sh ${tag}_c2 full > $out/pmc_c2.log 2>&1 || { tail -20 $out/pmc_c2.log; exit 1; }; fi
