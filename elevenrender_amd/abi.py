@@ -96,6 +96,15 @@ class ErAccelInfo(C.Structure):
                 ("upload_ms", C.c_float), ("lift_bound", C.c_float), ("builder", C.c_uint32)]
 
 
+class ErAdaptiveParams(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("min_samples", C.c_uint32), ("interval", C.c_uint32)]
+
+
+class ErAdaptiveInfo(C.Structure):
+    _fields_ = [("enabled", C.c_uint32), ("owned_tiles", C.c_uint32), ("active_tiles", C.c_uint32), ("tests_done", C.c_uint32),
+                ("samples_rendered", C.c_uint32), ("next_test", C.c_uint32), ("pixel_samples", C.c_uint64), ("max_active_error", C.c_float)]
+
+
 class ErStreamInfo(C.Structure):   # include/eleven_hip_debug.h
     _fields_ = [("waves", C.c_uint32), ("tracers", C.c_uint32), ("large_regions", C.c_uint32), ("deal_pending", C.c_uint32), ("launches", C.c_uint32),
                 ("pixels_per_cu", C.c_uint32), ("lanes_busy", C.c_double), ("launch_ms", C.c_double), ("cost_spread", C.c_double),
@@ -133,6 +142,9 @@ SYMBOLS = {
     "er_unpack_owned": (C.c_int, [_P, C.c_int, C.c_uint32, _P]),
     "er_get_counters": (C.c_int, [_P, C.POINTER(ErCounters)]),
     "er_accel_info": (C.c_int, [_P, C.POINTER(ErAccelInfo)]),
+    "er_adaptive_set": (C.c_int, [_P, C.POINTER(ErAdaptiveParams)]),
+    "er_adaptive_info": (C.c_int, [_P, C.POINTER(ErAdaptiveInfo)]),
+    "er_read_tile_state": (C.c_int, [_P, _FP, C.POINTER(C.c_uint32)]),
     "er_get_profile": (C.c_int, [_P, C.POINTER(ErProfile)]),
     "er_denoise": (C.c_int, [_P, C.c_uint32, C.c_float]),
     "er_state_size": (C.c_int, [_P, C.POINTER(C.c_uint64)]),

@@ -130,6 +130,47 @@ static bool stream_xcd_aware(size_t owned_tiles, uint32_t blocks) {
     return xe ? atoi(xe) != 0 : owned_tiles * 64 > (size_t)blocks * ER_STREAM_SLOTS;
 }
 
+// The streaming kernel's form for a share of `tiles` tiles: waves per workgroup, tracer / shader split, keep rule, speculative
+// samples (er_render_begin for the owned share; an adaptive render again for every new active share, within the buffers begin made).
+static void stream_choose_form(ErScene* s, size_t tiles, bool lights_on, uint32_t flags) {
+    // The split between tracer and shader waves (shader waves at issue priority 1; finished and escaped paths handled in batches
+    // of their own, er_stream.hip).  Round 2: 10 + 6, round 3: 12 + 4 (11 + 5 with the point-light extension, whose shading
+    // step is a third longer); since round 4's shorter shading step:
+    // 13 tracer + 3 shader waves where the shading step is at its cheapest -- plain materials, a scene that lives in the caches
+    // (C2: 1 787 vs 1 715 Msamples/s at 12 + 4) -- and 12 + 4 where it costs more: textured materials (C5 without lights: 1 560 vs
+    // 1 489 at 13 + 3), point lights (C5: 1 350 vs 1 234), or a scene beyond the Infinity Cache (C4, 10 M triangles: 1 562 vs 1 483)
+    // (profiles/r04_sweep_split_after_shader_diet.log).  That is the split to begin with; after every completed call it follows how
+    // full the tracer lanes were (er_stream_adapt: a scene of another kind that starves 13 tracers gets 12 after its first call).
+    // (textured materials started at 12 + 4 until their textures were fused / pre-powered / one-channel, er_render_begin: C5 without
+    // lights now 1 712 vs 1 640 at 12 + 4; a textured scene whose shading step is still too long for 13 tracers reads < 0.85 full lanes
+    // after its first call and gets 12)
+    s->stream_tracers = (lights_on || s->tri_count > 4000000u) ? 12 : 13;
+    // A workgroup that owns hardly more pixels than it has slots (an eighth of a 1080p frame: 1 012 pixels per CU) cannot fill 12 tracer
+    // waves -- a pixel's samples are one RNG stream, so pixels in flight are all the parallelism there is -- and runs faster as 9 tracer +
+    // 3 shader waves of 168 registers (the shading step then spills 34 registers instead of 111 and three shader waves serve what four
+    // did): 1.23 vs 1.35 ms per pass at 1/8 (1 012 pixels per CU); at 1/6 (1 350 pixels) 16 waves are ahead again, 1.43 vs 1.47 (profiles/r04_sweep_small_shares.log)
+    s->stream_waves = 16;
+    uint32_t small_tracers = 9;
+    {
+        const size_t px_per_cu = tiles * 64 / std::max<uint32_t>(1u, s->stream_blocks);
+        // (round 6, profiles/r06_ab_long_pixels_and_split.log: with the shading step as short as it has become two shader waves serve ten tracers where
+        // the slots are nearly all taken -- 1/8 ... 1/11 of the C2 frame 4.5 ... 1.5 % faster, C5's 1/8 share 1 ... 3 % -- and from 1/12 down 9 + 3 is ahead by 2 %)
+        small_tracers = px_per_cu > ER_STREAM_TEN_TRACERS_SHARE ? 10u : 9u;
+        if (px_per_cu <= ER_STREAM_SMALL_SHARE) { s->stream_waves = 12; s->stream_tracers = small_tracers; }
+        // the lane occupancy says something about the balance of the two roles only where pixels are plentiful: a share of a few
+        // pixels per slot cannot fill the lanes whatever the split (an eighth of a 1080p frame: 0.59 at the fastest split)
+        // (nor in the instrumented kernel of ER_FLAG_COUNTERS, whose slower tracer loop shifts the balance)
+        s->stream_adapt = px_per_cu >= 4u * ER_STREAM_SLOTS && !(flags & ER_FLAG_COUNTERS);
+        s->stream_keep = px_per_cu <= ER_STREAM_KEEP_SHARE;      // (er_stream.hip s_front)
+        s->stream_spec_form = px_per_cu <= ER_STREAM_SPEC_SHARE;      // few pixels per slot: slots fall free, speculative samples can use them (er_stream.hip)
+    }
+    if (const char* e = getenv("ER_STREAM_SPEC_FORM")) s->stream_spec_form = atoi(e) != 0;      // A/B knob
+    if (const char* e = getenv("ER_STREAM_KEEP")) s->stream_keep = atoi(e) != 0;                // A/B knob
+    if (const char* e = getenv("ER_STREAM_WAVES")) { s->stream_waves = atoi(e) == 12 ? 12 : 16; s->stream_tracers = s->stream_waves == 12 ? small_tracers : ((lights_on || s->tri_count > 4000000u) ? 12u : 13u); }   // A/B knob
+    if (const char* e = getenv("ER_STREAM_TRACERS")) { s->stream_tracers = (uint32_t)std::min(13, std::max(1, atoi(e))); s->stream_adapt = false; }   // tuning knob: fixed split
+    if (const char* e = getenv("ER_STREAM_ADAPT")) s->stream_adapt = atoi(e) != 0;
+}
+
 static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     if (!s || !p) return fail(ER_ERR_INVALID_ARG, "er_render_begin: NULL argument");
     std::lock_guard<std::mutex> lk(s->mtx);
@@ -152,6 +193,8 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     }
     s->device = p->device;
     s->params = *p;
+    s->ad_on = false;      // (adaptive sampling is set per render, after its er_render_begin)
+    s->rendered = 0;
     s->params.world = world;
     if (s->params.max_bounces == 0) s->params.max_bounces = 5;   // the literal of reference src/kernel.cpp:508
     HIP_TRY(hipSetDevice(s->device));
@@ -441,42 +484,7 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, s->device));
         s->stream_blocks = (uint32_t)prop.multiProcessorCount;
-        // The split between tracer and shader waves (shader waves at issue priority 1; finished and escaped paths handled in batches
-        // of their own, er_stream.hip).  Round 2: 10 + 6, round 3: 12 + 4 (11 + 5 with the point-light extension, whose shading
-        // step is a third longer); since round 4's shorter shading step:
-        // 13 tracer + 3 shader waves where the shading step is at its cheapest -- plain materials, a scene that lives in the caches
-        // (C2: 1 787 vs 1 715 Msamples/s at 12 + 4) -- and 12 + 4 where it costs more: textured materials (C5 without lights: 1 560 vs
-        // 1 489 at 13 + 3), point lights (C5: 1 350 vs 1 234), or a scene beyond the Infinity Cache (C4, 10 M triangles: 1 562 vs 1 483)
-        // (profiles/r04_sweep_split_after_shader_diet.log).  That is the split to begin with; after every completed call it follows how
-        // full the tracer lanes were (er_stream_adapt: a scene of another kind that starves 13 tracers gets 12 after its first call).
-        // (textured materials started at 12 + 4 until their textures were fused / pre-powered / one-channel, er_render_begin above: C5 without
-        // lights now 1 712 vs 1 640 at 12 + 4; a textured scene whose shading step is still too long for 13 tracers reads < 0.85 full lanes
-        // after its first call and gets 12)
-        s->stream_tracers = (lights_on || s->tri_count > 4000000u) ? 12 : 13;
-        // A workgroup that owns hardly more pixels than it has slots (an eighth of a 1080p frame: 1 012 pixels per CU) cannot fill 12 tracer
-        // waves -- a pixel's samples are one RNG stream, so pixels in flight are all the parallelism there is -- and runs faster as 9 tracer +
-        // 3 shader waves of 168 registers (the shading step then spills 34 registers instead of 111 and three shader waves serve what four
-        // did): 1.23 vs 1.35 ms per pass at 1/8 (1 012 pixels per CU); at 1/6 (1 350 pixels) 16 waves are ahead again, 1.43 vs 1.47 (profiles/r04_sweep_small_shares.log)
-        s->stream_waves = 16;
-        uint32_t small_tracers = 9;
-        {
-            const size_t px_per_cu = owned.size() * 64 / std::max<uint32_t>(1u, s->stream_blocks);
-            // (round 6, profiles/r06_ab_long_pixels_and_split.log: with the shading step as short as it has become two shader waves serve ten tracers where
-            // the slots are nearly all taken -- 1/8 ... 1/11 of the C2 frame 4.5 ... 1.5 % faster, C5's 1/8 share 1 ... 3 % -- and from 1/12 down 9 + 3 is ahead by 2 %)
-            small_tracers = px_per_cu > ER_STREAM_TEN_TRACERS_SHARE ? 10u : 9u;
-            if (px_per_cu <= ER_STREAM_SMALL_SHARE) { s->stream_waves = 12; s->stream_tracers = small_tracers; }
-            // the lane occupancy says something about the balance of the two roles only where pixels are plentiful: a share of a few
-            // pixels per slot cannot fill the lanes whatever the split (an eighth of a 1080p frame: 0.59 at the fastest split)
-            // (nor in the instrumented kernel of ER_FLAG_COUNTERS, whose slower tracer loop shifts the balance)
-            s->stream_adapt = px_per_cu >= 4u * ER_STREAM_SLOTS && !(p->flags & ER_FLAG_COUNTERS);
-            s->stream_keep = px_per_cu <= ER_STREAM_KEEP_SHARE;      // (er_stream.hip s_front)
-            s->stream_spec_form = px_per_cu <= ER_STREAM_SPEC_SHARE;      // few pixels per slot: slots fall free, speculative samples can use them (er_stream.hip)
-        }
-        if (const char* e = getenv("ER_STREAM_SPEC_FORM")) s->stream_spec_form = atoi(e) != 0;      // A/B knob
-        if (const char* e = getenv("ER_STREAM_KEEP")) s->stream_keep = atoi(e) != 0;                // A/B knob
-        if (const char* e = getenv("ER_STREAM_WAVES")) { s->stream_waves = atoi(e) == 12 ? 12 : 16; s->stream_tracers = s->stream_waves == 12 ? small_tracers : ((lights_on || s->tri_count > 4000000u) ? 12u : 13u); }   // A/B knob
-        if (const char* e = getenv("ER_STREAM_TRACERS")) { s->stream_tracers = (uint32_t)std::min(13, std::max(1, atoi(e))); s->stream_adapt = false; }   // tuning knob: fixed split
-        if (const char* e = getenv("ER_STREAM_ADAPT")) s->stream_adapt = atoi(e) != 0;
+        stream_choose_form(s, owned.size(), lights_on, p->flags);
         s->stream_tracers_start = s->stream_tracers; s->stream_low_streak = 0; s->stream_up_budget = 1; s->stream_readings = 0;
         const size_t slots = (size_t)s->stream_blocks * ER_STREAM_SLOTS;
         if ((rc = upload(s->d_wf4, nullptr, slots * er_stream_record_bytes(lights_on) / sizeof(float4), s->stream)) != ER_OK) return rc;
@@ -683,18 +691,11 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
 
 static void er_stream_adapt(ErScene* s);
 
-static int er_render_samples_async_impl(ErScene* s, uint32_t n) {
-    if (!s) return fail(ER_ERR_INVALID_ARG, "er_render_samples: NULL scene");
-    std::lock_guard<std::mutex> lk(s->mtx);
-    if (!s->begun) return fail(ER_ERR_STATE, "er_render_samples: er_render_begin has not succeeded");
-    if ((s->params.flags & ER_FLAG_STREAM) && n >= (1u << 24))      // (its pixel-ring entries keep the samples left in 24 bits)
-        return fail(ER_ERR_INVALID_ARG, "er_render_samples: at most 16777215 samples per call in the streaming schedule");
-    HIP_TRY(hipSetDevice(s->device));
-    if (!s->timing_open) {
-        HIP_TRY(hipEventRecord(s->ev_start, s->stream));
-        s->timing_open = true;
-    }
-    if (n > 0) for (auto& u : s->unpacked) u.clear();     // other ranks' pixels gathered earlier are stale from here on
+// n more samples to every active tile (all owned tiles unless an adaptive render has stopped some), enqueued on the scene's stream;
+// the caller holds s->mtx.  The streaming kernel is handed the active tiles through its deal (d_deal), the wavefront and megakernel
+// schedules through the tile list of the scene descriptor they are launched with.
+static int enqueue_samples(ErScene* s, uint32_t n) {
+    const DevScene& D = s->ad_on ? s->ad_dev : s->dev;
     const bool count = (s->params.flags & ER_FLAG_COUNTERS) != 0;
     const bool single = (s->params.flags & (ER_FLAG_MEGAKERNEL | ER_FLAG_STREAM)) != 0;
     if (single && (s->params.flags & ER_FLAG_PROFILE) && n > 0) {
@@ -735,7 +736,7 @@ static int er_render_samples_async_impl(ErScene* s, uint32_t n) {
         int rc = launch(n);
         if (rc != ER_OK) return rc;
     } else if (s->params.flags & ER_FLAG_MEGAKERNEL) {
-        er_launch_render(s->dev, n, count, s->stream);
+        er_launch_render(D, n, count, s->stream);
     }
     if (single && (s->params.flags & ER_FLAG_PROFILE) && n > 0) {
         HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], s->stream));
@@ -772,15 +773,15 @@ static int er_render_samples_async_impl(ErScene* s, uint32_t n) {
             for (uint32_t p = 1; p < pools; p++) HIP_TRY(hipStreamWaitEvent(s->pool_streams[p - 1], s->pool_events[0], 0));
         }
         auto pool_stream = [&](uint32_t p) { return p == 0 ? s->stream : s->pool_streams[p - 1]; };
-        for (uint32_t p = 0; p < pools; p++) er_launch_wf_begin(s->dev, s->wf[p], n, pool_stream(p));
+        for (uint32_t p = 0; p < pools; p++) er_launch_wf_begin(D, s->wf[p], n, pool_stream(p));
         for (uint32_t it = 0; it < iters; it++) {
             for (uint32_t p = 0; p < pools; p++) {
                 hipStream_t st = pool_stream(p);
                 uint32_t* ray_log = prof ? s->d_ray_log.p + s->prof_used / 3 : nullptr;
                 if (prof) HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], st));
-                er_launch_wf_trace(s->dev, s->wf[p], it & 1, count, s->trace_blocks, ray_log, st);
+                er_launch_wf_trace(D, s->wf[p], it & 1, count, s->trace_blocks, ray_log, st);
                 if (prof) HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], st));
-                er_launch_wf_shade(s->dev, s->wf[p], it & 1, count, s->shade_blocks, st);
+                er_launch_wf_shade(D, s->wf[p], it & 1, count, s->shade_blocks, st);
                 if (prof) HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], st));
             }
         }
@@ -792,6 +793,25 @@ static int er_render_samples_async_impl(ErScene* s, uint32_t n) {
     }
     HIP_TRY(hipGetLastError());
     return ER_OK;
+}
+
+static int adaptive_render(ErScene* s, uint32_t n);
+
+static int er_render_samples_async_impl(ErScene* s, uint32_t n) {
+    if (!s) return fail(ER_ERR_INVALID_ARG, "er_render_samples: NULL scene");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_render_samples: er_render_begin has not succeeded");
+    if ((s->params.flags & ER_FLAG_STREAM) && n >= (1u << 24))      // (its pixel-ring entries keep the samples left in 24 bits)
+        return fail(ER_ERR_INVALID_ARG, "er_render_samples: at most 16777215 samples per call in the streaming schedule");
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->timing_open) {
+        HIP_TRY(hipEventRecord(s->ev_start, s->stream));
+        s->timing_open = true;
+    }
+    if (n > 0) for (auto& u : s->unpacked) u.clear();     // other ranks' pixels gathered earlier are stale from here on
+    if (s->ad_on) return adaptive_render(s, n);
+    s->rendered += n;
+    return enqueue_samples(s, n);
 }
 
 // The streaming kernel's waves give up instead of spinning forever if their workgroup makes no progress (er_stream.hip) and
@@ -1043,6 +1063,7 @@ static int er_state_import_impl(ErScene* s, const void* src, uint64_t bytes) {
     if (!s || !src) return fail(ER_ERR_INVALID_ARG, "er_state_import: NULL argument");
     std::lock_guard<std::mutex> lk(s->mtx);
     if (!s->begun) return fail(ER_ERR_STATE, "er_state_import: er_render_begin has not succeeded");
+    if (s->ad_on) return fail(ER_ERR_STATE, "er_state_import: resuming an adaptive render is not supported (er_adaptive_set)");
     StateHeader h;
     if (bytes < sizeof(h)) return fail(ER_ERR_INVALID_ARG, "er_state_import: truncated snapshot");
     memcpy(&h, src, sizeof(h));
@@ -1176,6 +1197,186 @@ static int er_accel_info_impl(ErScene* s, ErAccelInfo* out) {
     return ER_OK;
 }
 
+
+// ---- adaptive sampling (include/eleven_hip.h er_adaptive_set; the test and the compaction: er_adaptive.hip) ----
+// The active tiles live on the device as a list in the layout of er_adaptive.h (two buffers: a test reads one and compacts the kept
+// tiles into the other); the host keeps a copy, read back with the test's result in one copy, because the streaming schedule's deal
+// is made on the host.  Pack, unpack, gather, denoise and er_samples_done keep working on the whole owned share (s->dev).
+
+static uint32_t tile_pixels(const ErScene* s, uint32_t tile) {      // pixels of a tile inside the frame
+    const uint32_t tiles_x = (s->x_res + ER_TILE - 1) / ER_TILE, tx = tile % tiles_x, ty = tile / tiles_x;
+    return std::min<uint32_t>(ER_TILE, s->x_res - tx * ER_TILE) * std::min<uint32_t>(ER_TILE, s->y_res - ty * ER_TILE);
+}
+
+// After a change of the active list (the caller holds the mutex; the stream is idle): the descriptor the wavefront and megakernel
+// schedules are launched with, and -- `redeal` -- the streaming schedule's deal and form for the new share, within the buffers
+// er_render_begin allocated for the owned share (records, spill and pixel rings: a smaller share fits).
+static int adaptive_apply_list(ErScene* s, bool redeal) {
+    s->ad_dev = s->dev;
+    s->ad_dev.owned_tiles = s->d_ad_list[s->ad_cur].p + ER_AD_LIST;
+    s->ad_dev.owned_tile_count = (uint32_t)s->ad_active.size();
+    s->ad_active_px = 0;
+    for (uint32_t t : s->ad_active) s->ad_active_px += tile_pixels(s, t);
+    if (!redeal || !(s->params.flags & ER_FLAG_STREAM) || s->ad_active.empty()) return ER_OK;
+    // (a decision between the two deals still pending -- calls of one sample each until now -- is dropped: the default deal stays; the
+    // large regions, if already taken, stay taken for the new share)
+    const bool large = !s->stream_deal_pending && s->stream_deal_alt_n > 0 && s->stream_deal_off == s->stream_deal_alt_off;
+    if (s->stream_deal_pending) {
+        s->stream_deal_pending = false;
+        s->dev.tile_cost = s->ad_dev.tile_cost = nullptr;
+        HIP_TRY(hipMemcpyAsync(s->d_dev.p, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice, s->stream));
+        s->stream_deal_large.clear();
+    }
+    const uint32_t count = (uint32_t)s->ad_active.size(), tiles_x = (s->x_res + ER_TILE - 1) / ER_TILE;
+    std::vector<uint32_t> deal;
+    uint32_t most = er_stream_deal_tiles(s->ad_active.data(), count, tiles_x, s->stream_blocks, stream_xcd_aware(count, s->stream_blocks), deal,
+                                         large ? ER_STREAM_SUPER_TILE_LARGE : 0u);
+    // (whole super-tiles can leave one workgroup more tiles of a small share than it had of the owned one; the round-robin deal never
+    // does: ceil(count / blocks) <= ceil(owned / blocks) <= the owned share's largest, which the rings were sized for)
+    if ((size_t)most * 64u > s->stream_ring_cap) most = er_stream_deal_tiles(s->ad_active.data(), count, tiles_x, s->stream_blocks, false, deal);
+    if ((size_t)most * 64u > s->stream_ring_cap) return fail(ER_ERR_STATE, "er_render_samples: the active tiles do not fit the pixel rings");
+    int rc;
+    if ((rc = upload(s->d_deal, deal.data(), deal.size(), s->stream)) != ER_OK) return rc;
+    s->stream_deal_off = 0; s->stream_deal_n = (uint32_t)deal.size();
+    s->stream_deal_alt_off = 0; s->stream_deal_alt_n = 0;
+    stream_choose_form(s, count, s->stream_lights, s->params.flags);
+    s->stream_tracers_start = s->stream_tracers; s->stream_low_streak = 0; s->stream_up_budget = 1;
+    HIP_TRY(hipStreamSynchronize(s->stream));      // (`deal` goes out of scope)
+    return ER_OK;
+}
+
+// The test at s->ad_next samples: error plane, compaction, one read-back of the new list (the host waits for it here).
+static int adaptive_test(ErScene* s) {
+    const uint32_t count = (uint32_t)s->ad_active.size(), next = s->ad_cur ^ 1u;
+    er_launch_adaptive_test(s->dev, s->d_ad_list[s->ad_cur].p, count, s->d_ad_snap.p, s->ad_threshold, s->d_ad_err.p, s->d_ad_keep.p, s->d_ad_list[next].p, s->stream);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> out(ER_AD_LIST + (size_t)count);
+    HIP_TRY(hipMemcpyAsync(out.data(), s->d_ad_list[next].p, out.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    int rc = er_scene_stream_status(s, "er_render_samples");
+    if (rc != ER_OK) return rc;
+    const uint32_t kept = out[0];
+    if (kept > count) return fail(ER_ERR_STATE, "er_render_samples: the adaptive test returned more tiles than it was given");
+    s->ad_active.assign(out.begin() + ER_AD_LIST, out.begin() + ER_AD_LIST + kept);
+    memcpy(&s->ad_max_error, &out[1], sizeof(float));
+    s->ad_cur = next;
+    s->ad_tests++;
+    s->ad_next += s->ad_interval;
+    s->ad_snapped = false;
+    return adaptive_apply_list(s, kept != count);
+}
+
+// er_render_samples_async in adaptive mode: the n samples in chunks that end at every snapshot and test point, so that the test points
+// depend on the parameters alone and never on how the caller splits its calls.  The caller holds the mutex.
+static int adaptive_render(ErScene* s, uint32_t n) {
+    while (n > 0 && !s->ad_active.empty()) {
+        const uint32_t snap_at = s->ad_next - s->ad_interval;
+        if (s->rendered == snap_at && !s->ad_snapped) {
+            er_launch_adaptive_snapshot(s->dev, s->d_ad_list[s->ad_cur].p, (uint32_t)s->ad_active.size(), s->d_ad_snap.p, s->stream);
+            HIP_TRY(hipGetLastError());
+            s->ad_snapped = true;
+        }
+        const uint32_t stop = s->rendered < snap_at ? snap_at : s->ad_next;
+        const uint32_t k = std::min(n, stop - s->rendered);
+        int rc = enqueue_samples(s, k);
+        if (rc != ER_OK) return rc;
+        s->rendered += k;
+        n -= k;
+        s->ad_pixel_samples += (uint64_t)k * s->ad_active_px;
+        for (uint32_t t : s->ad_active) s->ad_tile_samples[t] += k;
+        if (s->rendered == s->ad_next && (rc = adaptive_test(s)) != ER_OK) return rc;
+    }
+    return ER_OK;
+}
+
+static int er_adaptive_set_impl(ErScene* s, const ErAdaptiveParams* p) {
+    if (!s) return fail(ER_ERR_INVALID_ARG, "er_adaptive_set: NULL scene");
+    ErAdaptiveParams q{};
+    if (p) {
+        q = *p;
+        if (!(q.threshold >= 0.0f)) return fail(ER_ERR_INVALID_ARG, "er_adaptive_set: threshold must be >= 0 (and not NaN)");
+        if (q.min_samples == 0) q.min_samples = 16;
+        if (q.interval == 0) q.interval = 8;
+        if (q.interval >= q.min_samples) return fail(ER_ERR_INVALID_ARG, "er_adaptive_set: interval must be smaller than min_samples");
+    }
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_adaptive_set: er_render_begin has not succeeded");
+    if (s->rendered > 0) return fail(ER_ERR_STATE, "er_adaptive_set: only between er_render_begin and the first sample");
+    if (!p) { s->ad_on = false; return ER_OK; }
+    HIP_TRY(hipSetDevice(s->device));
+    const std::vector<uint32_t> owned = s->tiles_of(s->params.rank, s->params.world);
+    const size_t n_tiles = (size_t)s->dev.tiles_x * s->dev.tiles_y;
+    std::vector<uint32_t> list(ER_AD_LIST + owned.size());
+    const float none = -1.0f;
+    list[0] = (uint32_t)owned.size();
+    memcpy(&list[1], &none, sizeof(float));
+    std::copy(owned.begin(), owned.end(), list.begin() + ER_AD_LIST);
+    const std::vector<float> err(n_tiles, -1.0f);
+    int rc;
+    if ((rc = upload(s->d_ad_list[0], list.data(), list.size(), s->stream)) != ER_OK) return rc;
+    if ((rc = upload(s->d_ad_list[1], nullptr, list.size(), s->stream)) != ER_OK) return rc;
+    if ((rc = upload(s->d_ad_keep, nullptr, owned.size(), s->stream)) != ER_OK) return rc;
+    if ((rc = upload(s->d_ad_snap, nullptr, owned.size() * 64, s->stream)) != ER_OK) return rc;
+    if ((rc = upload(s->d_ad_err, err.data(), err.size(), s->stream)) != ER_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));      // (`list` and `err` go out of scope)
+    s->ad_threshold = q.threshold;
+    s->ad_min = q.min_samples;
+    s->ad_interval = q.interval;
+    s->ad_next = q.min_samples;
+    s->ad_tests = 0;
+    s->ad_cur = 0;
+    s->ad_snapped = false;
+    s->ad_max_error = -1.0f;
+    s->ad_pixel_samples = 0;
+    s->ad_active = owned;
+    s->ad_tile_samples.assign(n_tiles, 0u);
+    s->ad_on = true;
+    return adaptive_apply_list(s, false);
+}
+
+static int er_adaptive_info_impl(ErScene* s, ErAdaptiveInfo* out) {
+    if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_adaptive_info: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_adaptive_info: er_render_begin has not succeeded");
+    *out = ErAdaptiveInfo{};
+    out->enabled = s->ad_on ? 1u : 0u;
+    out->owned_tiles = s->dev.owned_tile_count;
+    out->samples_rendered = s->rendered;
+    out->max_active_error = -1.0f;
+    if (s->ad_on) {
+        out->active_tiles = (uint32_t)s->ad_active.size();
+        out->tests_done = s->ad_tests;
+        out->next_test = s->ad_next;
+        out->pixel_samples = s->ad_pixel_samples;
+        out->max_active_error = s->ad_max_error;
+    } else {
+        uint64_t px = 0;
+        for (uint32_t t : s->tiles_of(s->params.rank, s->params.world)) px += tile_pixels(s, t);
+        out->active_tiles = s->dev.owned_tile_count;
+        out->pixel_samples = px * s->rendered;
+    }
+    return ER_OK;
+}
+
+static int er_read_tile_state_impl(ErScene* s, float* error, uint32_t* samples) {
+    if (!s) return fail(ER_ERR_INVALID_ARG, "er_read_tile_state: NULL scene");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_read_tile_state: er_render_begin has not succeeded");
+    const size_t n_tiles = (size_t)s->dev.tiles_x * s->dev.tiles_y;
+    if (samples) {
+        if (s->ad_on) {
+            std::copy(s->ad_tile_samples.begin(), s->ad_tile_samples.end(), samples);
+        } else {
+            std::fill(samples, samples + n_tiles, 0u);
+            for (uint32_t t : s->tiles_of(s->params.rank, s->params.world)) samples[t] = s->rendered;
+        }
+    }
+    if (error) {
+        if (s->ad_on) return read_back_locked(s, s->d_ad_err.p, error, n_tiles * sizeof(float), "er_read_tile_state");
+        std::fill(error, error + n_tiles, -1.0f);
+    }
+    return ER_OK;
+}
 }  // extern "C"
 
 // ---- the exported entry points: every body above runs inside guarded() (no exception crosses the C ABI) ----
@@ -1201,4 +1402,7 @@ int er_unpack_owned(ErScene* s, int pass, uint32_t src_rank, const void* dev_src
 int er_get_counters(ErScene* s, ErCounters* out) { return guarded("er_get_counters", [&]() -> int { return er_get_counters_impl(s, out); }); }
 int er_get_profile(ErScene* s, ErProfile* out) { return guarded("er_get_profile", [&]() -> int { return er_get_profile_impl(s, out); }); }
 int er_accel_info(ErScene* s, ErAccelInfo* out) { return guarded("er_accel_info", [&]() -> int { return er_accel_info_impl(s, out); }); }
+int er_adaptive_set(ErScene* s, const ErAdaptiveParams* p) { return guarded("er_adaptive_set", [&]() -> int { return er_adaptive_set_impl(s, p); }); }
+int er_adaptive_info(ErScene* s, ErAdaptiveInfo* out) { return guarded("er_adaptive_info", [&]() -> int { return er_adaptive_info_impl(s, out); }); }
+int er_read_tile_state(ErScene* s, float* error, uint32_t* samples) { return guarded("er_read_tile_state", [&]() -> int { return er_read_tile_state_impl(s, error, samples); }); }
 }  // extern "C"

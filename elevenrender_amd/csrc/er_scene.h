@@ -24,6 +24,7 @@
 #include "er_kernels.h"
 #include "er_wavefront.h"
 #include "er_stream.h"
+#include "er_adaptive.h"
 
 namespace erh {
 
@@ -205,6 +206,20 @@ struct ErScene {
     double stream_cost_spread = -1.0;                   //   (max - min) / mean of the XCDs' counted work under the large deal; < 0: not decided yet
     double stream_xcd_spread = 0.0;                     //   (latest - earliest XCD) / launch duration of the last completed call; < 0: not measured
     uint64_t stream_launches = 0, stream_adapted = 0;   //   launches enqueued / the launch whose measurements er_stream_adapt has already used
+    // adaptive sampling (er_adaptive_set, er_api.cpp): the active tiles as a device list in the layout of er_adaptive.h, two buffers
+    // that the test's compaction writes in turn; ad_dev = `dev` with owned_tiles pointing at the active list (wavefront, megakernel)
+    uint32_t rendered = 0;                // samples given to every active tile since er_render_begin (adaptive or not)
+    bool ad_on = false;
+    float ad_threshold = 0;
+    uint32_t ad_min = 0, ad_interval = 0, ad_next = 0, ad_tests = 0, ad_cur = 0;   // ad_cur: which of d_ad_list holds the active list
+    bool ad_snapped = false;              // the snapshot for the next test has been taken
+    float ad_max_error = -1.0f;
+    uint64_t ad_pixel_samples = 0, ad_active_px = 0;    // samples given to owned pixels; in-frame pixels of the active tiles
+    std::vector<uint32_t> ad_active, ad_tile_samples;   // host copy of the active list; samples per tile of the frame
+    DevBuf<uint32_t> d_ad_list[2], d_ad_keep;
+    DevBuf<float4> d_ad_snap;
+    DevBuf<float> d_ad_err;
+    DevScene ad_dev{};
     std::vector<WfState> wf;              // slot pools (see er_render_begin)
     std::vector<hipStream_t> pool_streams;   // pool 0 runs on `stream`, pool p > 0 on pool_streams[p - 1]
     std::vector<hipEvent_t> pool_events;     // [0] fork; [p] pool p has finished
@@ -237,6 +252,8 @@ struct ErScene {
         d_nodes.release(); d_nodes8.release(); d_isect.release(); d_attr.release(); d_passes.release(); d_plane.release(); d_materials.release();
         d_textures.release(); d_tex_pool.release(); d_lights.release(); d_cdf.release(); d_samples.release(); d_rng.release();
         d_owned.release(); d_counters.release(); d_wf4.release(); d_wf1.release(); d_spill.release(); d_guide.release(); d_ticket.release(); d_deal.release(); d_ray_log.release(); d_mat_fused.release(); d_mat_pre.release(); d_dev.release(); d_tile_cost.release(); d_px_draws.release();
+        d_ad_list[0].release(); d_ad_list[1].release(); d_ad_keep.release(); d_ad_snap.release(); d_ad_err.release();
+        ad_on = false; rendered = 0;
         for (auto& kv : d_rank_tiles) kv.second.release();
         d_rank_tiles.clear();
         d_gather_mine.release();

@@ -263,7 +263,17 @@ private:
         if (cl.count("start")) return start_render();
         if (cl.count("get_info")) {                                          // :282-300
             json::Value j = json::Value::object();
-            j["samples"] = rm.get_render_info().samples;
+            if (rm.pars.adaptive) {
+                // (a tile that stopped keeps its sample count: the plug-in's progress follows the samples the still-active tiles have
+                // received, + 1 as dev_samples[0]; a render with no active tile left is complete and reports its target)
+                const ErAdaptiveInfo ai = rm.adaptive_info();
+                j["samples"] = ai.active_tiles ? ai.samples_rendered + 1u : rm.pars.sampleTarget + 1u;
+                j["samples_rendered"] = ai.samples_rendered;
+                j["active_tiles"] = ai.active_tiles;
+                j["owned_tiles"] = ai.owned_tiles;
+            } else {
+                j["samples"] = rm.get_render_info().samples;
+            }
             // (extra keys, ignored by the plug-in: how the render is spread and how the render thread sizes its calls)
             j["gpus"] = rm.ranks();
             if (!rm.transport_used.empty()) j["transport"] = rm.transport_used;
@@ -335,6 +345,31 @@ private:
             if (rp.devices.size() != rp.gpus) throw std::runtime_error("config devices must list one ordinal per gpu");
         }
         if (const json::Value* v = j.if_contains("transport")) rp.transport = v->as_string();
+        // adaptive sampling (extension, include/eleven_hip.h er_adaptive_set): "adaptive": {"threshold": t, "min_samples": m, "interval": i},
+        // threshold a number >= 0 or "inf" (JSON has no infinity); min_samples / interval optional (0 or absent: 16 / 8)
+        if (const json::Value* v = j.if_contains("adaptive")) {
+            if (!v->is_object()) throw std::runtime_error("config adaptive must be an object {\"threshold\": t, \"min_samples\": m, \"interval\": i}");
+            const json::Value* t = v->if_contains("threshold");
+            if (!t) throw std::runtime_error("config adaptive needs a threshold");
+            double th = 0;
+            if (t->is_string() && t->as_string() == "inf") th = INFINITY;
+            else if (t->is_number()) th = t->as_double();
+            else throw std::runtime_error("config adaptive threshold must be a number or \"inf\"");
+            if (!(th >= 0)) throw std::runtime_error("config adaptive threshold must be >= 0");
+            auto count = [&](const char* key) -> uint32_t {
+                const json::Value* c = v->if_contains(key);
+                if (!c) return 0;
+                const long long x = c->as_int64();
+                if (x < 0 || x > 1000000) throw std::runtime_error(std::string("config adaptive ") + key + " out of range (0 .. 1000000)");
+                return (uint32_t)x;
+            };
+            rp.adaptive_params.threshold = (float)th;
+            rp.adaptive_params.min_samples = count("min_samples");
+            rp.adaptive_params.interval = count("interval");
+            const uint32_t m = rp.adaptive_params.min_samples ? rp.adaptive_params.min_samples : 16u, i = rp.adaptive_params.interval ? rp.adaptive_params.interval : 8u;
+            if (i >= m) throw std::runtime_error("config adaptive interval must be smaller than min_samples");
+            rp.adaptive = true;
+        }
         stop_render_thread();
         rm.pars = rp;
         scene.x_res = rp.width;
@@ -354,7 +389,8 @@ private:
                 // about 50 ms of work -- long enough to lose ~2 % to that, short enough that --get_pass (a sample-boundary
                 // snapshot, ordered behind the call in flight) and a restart answer within a frame or two of the viewer.
                 unsigned done = 0, n = 1;
-                while (done < target && !stop_) {
+                const bool adaptive = rm.pars.adaptive;
+                while (done < target && !stop_ && !(adaptive && rm.adaptive_info().active_tiles == 0)) {      // (adaptive: until no rank has an active tile)
                     n = std::min(n, target - done);
                     const auto t0 = std::chrono::steady_clock::now();
                     rm.render(n);

@@ -127,6 +127,9 @@ struct RenderParameters {   // src/kernel.h:51-69
     unsigned gpus = 1;
     std::vector<int> devices;
     std::string transport = "auto";
+    // adaptive sampling (extension, off by default): applied to every rank after er_render_begin (er_adaptive_set)
+    bool adaptive = false;
+    ErAdaptiveParams adaptive_params{};
 };
 
 inline int parsePass(std::string s) {   // src/kernel.cpp:50-73: unknown names -> BEAUTY
@@ -233,6 +236,8 @@ public:
             });
         for (auto& t : th) t.join();
         for (unsigned r = 0; r < ranks; r++) if (!errs[r].empty()) { std::string e = errs[r]; release(); throw std::runtime_error(e); }
+        if (pars.adaptive)
+            for (ErScene* e : ers_) if (er_adaptive_set(e, &pars.adaptive_params) != ER_OK) { std::string m = er_last_error(); release(); throw std::runtime_error(m); }
         // ---- the combine's communicators ----
         if (multi) {
             bool distinct = true;
@@ -296,6 +301,21 @@ public:
         if (ers_.size() > 1) lk.lock();
         denoise_unlocked(levels, colour_sigma);
         return get_pass_unlocked(ER_PASS_DENOISE);
+    }
+    // adaptive sampling over the ranks: the ranks' tiles summed, samples_rendered of the rank that is furthest ahead (each rank stops
+    // only its own tiles; the frame goes on while any rank has an active tile)
+    ErAdaptiveInfo adaptive_info() {
+        ErAdaptiveInfo sum{};
+        for (ErScene* e : ers_) {
+            ErAdaptiveInfo i{};
+            check(er_adaptive_info(e, &i));
+            sum.enabled = i.enabled;
+            sum.owned_tiles += i.owned_tiles;
+            sum.active_tiles += i.active_tiles;
+            sum.samples_rendered = std::max(sum.samples_rendered, i.samples_rendered);
+            sum.pixel_samples += i.pixel_samples;
+        }
+        return sum;
     }
     RenderInfo get_render_info() {   // src/Managers.cpp:211-232; several ranks: the one that is furthest behind
         RenderInfo i;

@@ -112,6 +112,27 @@ class RenderingManager:
         abi.check(self.lib.er_samples_done(self.handle, C.byref(v)))
         return RenderInfo(samples=v.value)
 
+    def set_adaptive(self, threshold, min_samples=0, interval=0):
+        """Adaptive sampling (er_adaptive_set): between start_rendering and the first sample.  Tiles whose noise falls below
+        `threshold` stop receiving samples; tests at min_samples (0 -> 16), then every `interval` (0 -> 8) samples.
+        threshold=None turns it off."""
+        p = None if threshold is None else C.byref(abi.ErAdaptiveParams(threshold, min_samples, interval))
+        abi.check(self.lib.er_adaptive_set(self.handle, p))
+
+    def adaptive_info(self):
+        a = abi.ErAdaptiveInfo()
+        abi.check(self.lib.er_adaptive_info(self.handle, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in abi.ErAdaptiveInfo._fields_}
+
+    def tile_state(self):
+        """(error[tiles_y, tiles_x] float32, samples[tiles_y, tiles_x] uint32): each tile's error at its last test (-1: untested,
+        untestable or not owned) and the samples it received (0: not owned)."""
+        tx, ty = (self.scene.x_res + 7) // 8, (self.scene.y_res + 7) // 8
+        err = np.empty((ty, tx), np.float32)
+        spp = np.empty((ty, tx), np.uint32)
+        abi.check(self.lib.er_read_tile_state(self.handle, err.ctypes.data_as(C.POINTER(C.c_float)), spp.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return err, spp
+
     def denoise(self, levels=0, colour_sigma=0.0):
         """Fill the DENOISE plane from BEAUTY + NORMAL (er_denoise); get_pass("denoise") then returns it."""
         abi.check(self.lib.er_denoise(self.handle, levels, colour_sigma))

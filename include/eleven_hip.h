@@ -256,6 +256,36 @@ int er_gather_pass(ErScene* scene, int pass, ErComm* comm, uint32_t root);
 
 int er_get_counters(ErScene* scene, ErCounters* out);
 
+/* Adaptive sampling (extension, off by default = reference behaviour): owned 8x8 tiles whose noise has fallen below a threshold
+ * stop receiving samples.  Tests run when min_samples, min_samples + interval, min_samples + 2 interval, ... samples have been
+ * rendered since er_render_begin, whatever the calls' sizes (a call that crosses a test point is split there inside the library,
+ * and er_render_samples_async then blocks at each test point inside the call, as the streaming schedule's first call does for its
+ * first sample).  A test compares every active tile's BEAUTY plane with a snapshot taken `interval` samples earlier: per pixel the
+ * standard error of the running mean, relative to the square root of its brightness; per tile E = the root mean square of those
+ * (csrc/er_adaptive.hip gives the exact operations).  A tile stays active iff E >= threshold or it has no testable pixel; a
+ * stopped tile never comes back (threshold 0: none stops; +inf: every testable tile stops at the first test).  Every pixel keeps
+ * its own RNG stream, so a tile that received k samples equals, bit for bit, the tile of a uniform render of k samples.
+ * er_adaptive_set: only between er_render_begin and the first sample (else ER_ERR_STATE); NULL = off; er_render_begin turns it
+ * off again.  Threshold negative or NaN, or interval >= min_samples: ER_ERR_INVALID_ARG.  er_state_import of an adaptive render:
+ * ER_ERR_STATE (resuming the adaptive state is not supported).  A call once no tile is active returns ER_OK and launches nothing. */
+typedef struct ErAdaptiveParams {
+    float threshold;
+    uint32_t min_samples;        /* 0 -> 16 */
+    uint32_t interval;           /* 0 -> 8 */
+} ErAdaptiveParams;
+typedef struct ErAdaptiveInfo {
+    uint32_t enabled, owned_tiles, active_tiles, tests_done;
+    uint32_t samples_rendered;   /* samples every still-active tile has received since er_render_begin */
+    uint32_t next_test;          /* samples_rendered at which the next test runs (0: not adaptive) */
+    uint64_t pixel_samples;      /* samples given, summed over owned pixels: the work spent */
+    float max_active_error;      /* largest E among the tiles kept at the last test (-1: none yet) */
+} ErAdaptiveInfo;
+int er_adaptive_set(ErScene* scene, const ErAdaptiveParams* params);
+int er_adaptive_info(ErScene* scene, ErAdaptiveInfo* out);
+/* Per tile of the frame (tiles_x * tiles_y each, row-major; either pointer may be NULL): the error E of its last test (-1: untested,
+ * untestable or not owned) and the samples it has received since er_render_begin (0: not owned). */
+int er_read_tile_state(ErScene* scene, float* error, uint32_t* samples);
+
 /* Per-kernel device time of the launches enqueued since the previous er_wait, measured with HIP events on
  * the library's stream (needs ER_FLAG_PROFILE; valid after er_wait). */
 typedef struct ErProfile {
