@@ -20,6 +20,7 @@ PASS_BEAUTY, PASS_DENOISE, PASS_NORMAL, PASS_TANGENT, PASS_BITANGENT, PASS_COUNT
 PASS_NAMES = {"beauty": 0, "denoise": 1, "normal": 2, "tangent": 3, "bitangent": 4}
 FLAG_POINT_LIGHTS, FLAG_COUNTERS, FLAG_MEGAKERNEL, FLAG_PROFILE, FLAG_FUSED, FLAG_WAVEFRONT, FLAG_GPU_BUILD, FLAG_MIS, FLAG_STREAM = 1, 2, 4, 8, 16, 32, 64, 128, 256
 FLAG_HOST_BUILD = 512
+FLAG_MESH_LIGHTS = 1024     # next-event estimation of emissive triangles (csrc/er_shade.h)
 
 
 class ErVec3(C.Structure):
@@ -105,6 +106,10 @@ class ErAdaptiveInfo(C.Structure):
                 ("samples_rendered", C.c_uint32), ("next_test", C.c_uint32), ("pixel_samples", C.c_uint64), ("max_active_error", C.c_float)]
 
 
+class ErLightInfo(C.Structure):
+    _fields_ = [("emitters", C.c_uint32), ("total_weight", C.c_float)]
+
+
 class ErStreamInfo(C.Structure):   # include/eleven_hip_debug.h
     _fields_ = [("waves", C.c_uint32), ("tracers", C.c_uint32), ("large_regions", C.c_uint32), ("deal_pending", C.c_uint32), ("launches", C.c_uint32),
                 ("pixels_per_cu", C.c_uint32), ("lanes_busy", C.c_double), ("launch_ms", C.c_double), ("cost_spread", C.c_double),
@@ -145,6 +150,7 @@ SYMBOLS = {
     "er_adaptive_set": (C.c_int, [_P, C.POINTER(ErAdaptiveParams)]),
     "er_adaptive_info": (C.c_int, [_P, C.POINTER(ErAdaptiveInfo)]),
     "er_read_tile_state": (C.c_int, [_P, _FP, C.POINTER(C.c_uint32)]),
+    "er_light_info": (C.c_int, [_P, C.POINTER(ErLightInfo)]),
     "er_get_profile": (C.c_int, [_P, C.POINTER(ErProfile)]),
     "er_denoise": (C.c_int, [_P, C.c_uint32, C.c_float]),
     "er_state_size": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
@@ -163,6 +169,7 @@ SYMBOLS = {
     "er_debug_eval": (C.c_int, [_P, C.c_int, _FP, C.c_uint32, C.c_uint32, _FP, C.c_uint32]),
     "er_debug_trace_rays": (C.c_int, [_P, _FP, _FP, C.c_uint32, _IP, _FP, _IP, _IP, _FP, _FP, _IP]),
     "er_debug_trace_pixel": (C.c_int, [_P, C.c_uint32, C.POINTER(ErTraceRec), C.c_int, C.POINTER(C.c_int)]),
+    "er_debug_read_light_table": (C.c_int, [_P, _IP, _FP, C.c_uint32]),
     "er_debug_set_host_alloc_limit": (None, [C.c_uint64]),
     "er_debug_set_gpu_build_failure": (None, [C.c_int]),
     "er_debug_closest_hit": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_float),

@@ -3,6 +3,7 @@
 // copy_scene, renderSetup, kernel_render_enqueue and RenderingManager::get_pass
 // (reference src/kernel.cpp:244-266,651-706; src/SYCLCopy.cpp:3-104; src/Managers.cpp:287-302).
 // There is NO CPU fallback: without a usable HIP device every compute entry point fails.
+#include <algorithm>
 #include <chrono>
 
 #include "er_scene.h"
@@ -445,6 +446,28 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     std::vector<uint32_t> guide;
     int buckets = er_build_cdf_guide(s->hdri_cdf.data(), s->hdri_tex.width * s->hdri_tex.height, guide);
     if ((rc = upload(s->d_guide, guide.data(), guide.size(), s->stream)) != ER_OK) return rc;
+    // ER_FLAG_MESH_LIGHTS: the emitter table, built on the device from the placed triangle records (er_lights.hip).  An empty table
+    // leaves the render as it would be without the flag.
+    if (p->flags & ER_FLAG_MESH_LIGHTS) {
+        std::vector<int32_t> etex;
+        for (const ErMaterial& m : s->materials)
+            if (m.emission_tex >= 0 && (size_t)m.emission_tex < s->textures.size()) etex.push_back(m.emission_tex);
+        std::sort(etex.begin(), etex.end());
+        etex.erase(std::unique(etex.begin(), etex.end()), etex.end());
+        ScopedDevBuf<int32_t> d_etex;
+        if ((rc = upload(d_etex, etex.data(), etex.size(), s->stream)) != ER_OK) return rc;
+        float* tab = nullptr;
+        HIP_TRY(er_lights_build(s->d_nodes8.p + n8_pieces, s->d_attr.p, s->tri_count, s->d_materials.p, s->d_textures.p, s->d_tex_pool.p, d_etex.p,
+                                (uint32_t)etex.size(), (uint32_t)s->textures.size(), &tab, &s->light_emitters, &s->light_total, s->stream));
+        s->d_light_tab.p = tab;
+        s->d_light_tab.n = tab ? (size_t)s->tri_count + 2 * (size_t)s->light_emitters : 0;
+        if (lights_on && s->light_emitters > 0)
+            return fail(ER_ERR_INVALID_ARG, "er_render_begin: ER_FLAG_POINT_LIGHTS and ER_FLAG_MESH_LIGHTS on a scene with both point lights and "
+                                            "emissive triangles: both need the one light-query record per slot");
+    }
+    const bool mesh_on = s->light_emitters > 0;
+    // the point-light or the emitter query: a second shadow record per slot
+    const bool query_on = lights_on || mesh_on;
 
     size_t npx = (size_t)s->x_res * s->y_res;
     if ((rc = upload(s->d_passes, nullptr, npx * ER_PASS_COUNT, s->stream)) != ER_OK) return rc;
@@ -484,14 +507,14 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, s->device));
         s->stream_blocks = (uint32_t)prop.multiProcessorCount;
-        stream_choose_form(s, owned.size(), lights_on, p->flags);
+        stream_choose_form(s, owned.size(), query_on, p->flags);
         s->stream_tracers_start = s->stream_tracers; s->stream_low_streak = 0; s->stream_up_budget = 1; s->stream_readings = 0;
         const size_t slots = (size_t)s->stream_blocks * ER_STREAM_SLOTS;
-        if ((rc = upload(s->d_wf4, nullptr, slots * er_stream_record_bytes(lights_on) / sizeof(float4), s->stream)) != ER_OK) return rc;
+        if ((rc = upload(s->d_wf4, nullptr, slots * er_stream_record_bytes(query_on) / sizeof(float4), s->stream)) != ER_OK) return rc;
         if ((rc = upload(s->d_wf1, nullptr, 32, s->stream)) != ER_OK) return rc;       // [1] status word, [2..5] the tracers' lane occupancy, [6..23] start / end per XCD, [24..26] speculative samples started / right / wrong
         if ((rc = upload(s->d_spill, nullptr, er_stream_spill_entries(s->stream_blocks), s->stream)) != ER_OK) return rc;
         s->stream_ctl = s->d_wf1.p;
-        s->stream_lights = lights_on;
+        s->stream_lights = query_on;
         HIP_TRY(hipMemsetAsync(s->stream_ctl, 0, 32 * sizeof(uint32_t), s->stream));
         s->stream_spec[0] = s->stream_spec[1] = s->stream_spec[2] = 0;
         // the workgroups' pixel rings: (pixel, samples left) entries, one per pixel of the workgroup's share
@@ -558,7 +581,7 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
         const size_t pool_tiles = (owned.size() + pools - 1) / pools;
         const size_t qcap = pool_tiles * 64;          // queue capacity of one pool
         size_t slots = owned.size() * 64;
-        const size_t sh = lights_on ? 2 : 1;          // shadow records per slot: [slot] HDRI query, [slot + slots] point light
+        const size_t sh = query_on ? 2 : 1;           // shadow records per slot: [slot] HDRI query, [slot + slots] point light / emitter
         const size_t qs_cap = qcap * sh;              // shadow-queue capacity of one pool
         const size_t q_words = 2 * qcap + 2 * qs_cap; // two closest + two shadow queues per pool
         if ((rc = upload(s->d_wf4, nullptr, slots * (7 + 4 * sh), s->stream)) != ER_OK) return rc;
@@ -655,6 +678,11 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     D.ext_flags = s->params.flags & (ER_FLAG_POINT_LIGHTS | ER_FLAG_MIS);
     D.lights = s->d_lights.p;
     D.light_count = (uint32_t)s->point_lights.size();
+    if (mesh_on) {      // (the words of the point lights, which this render does not sample: er_device.h)
+        D.ext_flags = (D.ext_flags & ~(uint32_t)ER_FLAG_POINT_LIGHTS) | ER_FLAG_MESH_LIGHTS;
+        D.mesh_lights = s->d_light_tab.p;
+        D.emitter_count = s->light_emitters;
+    }
     D.passes = s->d_passes.p;
     D.samples = s->d_samples.p;
     D.rng = s->d_rng.p;
@@ -1334,6 +1362,16 @@ static int er_adaptive_set_impl(ErScene* s, const ErAdaptiveParams* p) {
     return adaptive_apply_list(s, false);
 }
 
+static int er_light_info_impl(ErScene* s, ErLightInfo* out) {
+    if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_light_info: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_light_info: er_render_begin has not succeeded");
+    *out = ErLightInfo{};
+    out->emitters = s->light_emitters;
+    out->total_weight = s->light_total;
+    return ER_OK;
+}
+
 static int er_adaptive_info_impl(ErScene* s, ErAdaptiveInfo* out) {
     if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_adaptive_info: NULL argument");
     std::lock_guard<std::mutex> lk(s->mtx);
@@ -1404,5 +1442,6 @@ int er_get_profile(ErScene* s, ErProfile* out) { return guarded("er_get_profile"
 int er_accel_info(ErScene* s, ErAccelInfo* out) { return guarded("er_accel_info", [&]() -> int { return er_accel_info_impl(s, out); }); }
 int er_adaptive_set(ErScene* s, const ErAdaptiveParams* p) { return guarded("er_adaptive_set", [&]() -> int { return er_adaptive_set_impl(s, p); }); }
 int er_adaptive_info(ErScene* s, ErAdaptiveInfo* out) { return guarded("er_adaptive_info", [&]() -> int { return er_adaptive_info_impl(s, out); }); }
+int er_light_info(ErScene* s, ErLightInfo* out) { return guarded("er_light_info", [&]() -> int { return er_light_info_impl(s, out); }); }
 int er_read_tile_state(ErScene* s, float* error, uint32_t* samples) { return guarded("er_read_tile_state", [&]() -> int { return er_read_tile_state_impl(s, error, samples); }); }
 }  // extern "C"

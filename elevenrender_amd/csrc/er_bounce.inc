@@ -4,12 +4,14 @@
 // In scope at the point of inclusion (all plain locals of the including kernel):
 //   COUNT, EXT          compile-time bools (EXT = false compiles the extensions out)
 //   ER_BOUNCE_FUSE      macro, optional (default true): a compile-time bool; false compiles the fused-texel fetch of generate_hit_data out
+//   ER_BOUNCE_MESH      macro, optional (default false): a compile-time bool; true compiles ER_FLAG_MESH_LIGHTS in (needs EXT)
 //   S                   the DevScene
 //   Ray      ray        in: the ray that was traced; out: the continuation ray (unchanged when it left the scene)
 //   int      hslot      its closest hit (triangle slot), or < 0
 //   uint32_t rs         the pixel's RNG state
 //   F3       light, reduction;  uint32_t bounce      the path state of src/kernel.cpp:496-506
-//   float    prev_pdf   ER_FLAG_MIS: brdfpdf of the last opaque bounce, < 0 before the first one (read only if EXT)
+//   float    prev_pdf   ER_FLAG_MIS / ER_FLAG_MESH_LIGHTS: brdfpdf of the last opaque bounce, < 0 before the first one (read only if EXT)
+//   float    mesh_d     ER_FLAG_MESH_LIGHTS: distance from the last opaque bounce to ray.o (read and written only if ER_BOUNCE_MESH)
 //   bool     done       set when the path ends with this step (left the scene, or the bounce limit is reached)
 //   bool     pending, lpending   set when an HDRI / a point-light shadow query was handed to the hooks
 //   unsigned c_shaded, c_texels, c_hdri   counters
@@ -19,9 +21,9 @@
 //       HDRI shadow ray `sr`; occluded iff its closest hit is a triangle other than self_slot, i.e. iff some other
 //       triangle is hit nearer than d_self (the distance at which sr re-hits the triangle it leaves; inf if it does
 //       not).  Then light += occluded ? c_occ : c_vis.
-//   ER_BOUNCE_LIGHT_QUERY(lr, limit, l_vis, l_occ)
-//       point-light shadow ray; occluded iff some triangle is hit nearer than `limit`.  Then, AFTER the HDRI term,
-//       light += occluded ? l_occ : l_vis.
+//   ER_BOUNCE_LIGHT_QUERY(lr, self_slot, limit, l_vis, l_occ)
+//       point-light (self_slot -1) or emitter (self_slot = the emitter's slot) shadow ray; occluded iff some triangle other than
+//       self_slot is hit nearer than `limit`.  Then, AFTER the HDRI term, light += occluded ? l_occ : l_vis.
 //   ER_BOUNCE_FIRST_HIT(n, t, b)       first-bounce AOVs (src/kernel.cpp:581-585)
 // A kernel may trace at once inside a hook and add to `light` itself (megakernel, debug trace), or record the query and
 // add the selected contribution before `light` is touched again (wavefront, fused).
@@ -31,6 +33,11 @@
 {
     const int hw = S.hdri_tex.width, hh = S.hdri_tex.height;
     const bool er_mis = EXT && (S.ext_flags & ER_FLAG_MIS) != 0;
+#ifdef ER_BOUNCE_MESH
+    constexpr bool er_mesh = EXT && (ER_BOUNCE_MESH);      // (a non-empty emitter table: the host runs these instances only then)
+#else
+    constexpr bool er_mesh = false;
+#endif
     if (hslot < 0) {
         // src/kernel.cpp:517-522
         float u, v;
@@ -72,9 +79,11 @@
             float tcx = (float)(hw_pow2 ? (int)((unsigned)count & (unsigned)(hw - 1)) : count % hw);
             float tcy = (float)(hw_pow2 ? (int)((unsigned)count >> (31 - __builtin_clz((unsigned)hw))) : count / hw);
             float d1 = rng_next(rs), d2 = rng_next(rs), d3 = rng_next(rs);
-            const bool er_lights = EXT && (S.ext_flags & ER_FLAG_POINT_LIGHTS) != 0 && S.light_count > 0;
+            const bool er_lights = EXT && !er_mesh && (S.ext_flags & ER_FLAG_POINT_LIGHTS) != 0 && S.light_count > 0;
             float er_rl = 0.0f;
             if (er_lights) er_rl = rng_next(rs);     // the light pick: one extra draw, right after DisneySample's three
+            float er_mp = 0.0f, er_mu1 = 0.0f, er_mu2 = 0.0f;
+            if (er_mesh) { er_mp = rng_next(rs); er_mu1 = rng_next(rs); er_mu2 = rng_next(rs); }   // emitter pick and point: always three
             ER_TP(4);
             F3 wibrdf = DisneySample(hd, wo, N, d1, d2, d3);
             float nu = tcx / (float)hw, nv = tcy / (float)hh;
@@ -91,12 +100,25 @@
             // exactly zero they coincide and the query is skipped.
             float er_wnee = 1.0f;
             if (er_mis) er_wnee = 1.0f / (1.0f + DisneyPdf(hd, wo, N, wihdri) / hdripdf);   // balance heuristic, NEE direction
-            F3 c_vis = er_mis ? reduction * (hd.emission + (hdriValue * evalh * absdot / hdripdf) * er_wnee)
-                              : reduction * (hd.emission + hdriValue * evalh * absdot / hdripdf);
+            F3 er_em = hd.emission;
+            if (er_mesh && prev_pdf >= 0.0f) {
+                // emission found by a BRDF-sampled ray: balance heuristic against the emitter sample (rule 7)
+                const float er_ph = mesh_prob(S)[hslot];
+                if (er_ph > 0.0f) {
+                    F3 er_a, er_b, er_c, er_ng;
+                    float er_area;
+                    mesh_tri(S, (uint32_t)hslot, er_a, er_b, er_c, er_ng, er_area);
+                    const float er_dh = mesh_d + length(hit.position - ray.o);
+                    const float er_pl = er_ph * (er_dh * er_dh) / (er_area * __builtin_fabsf(dot(er_ng, ray.d)));
+                    er_em = er_em * (1.0f / (1.0f + er_pl / prev_pdf));
+                }
+            }
+            F3 c_vis = er_mis ? reduction * (er_em + (hdriValue * evalh * absdot / hdripdf) * er_wnee)
+                              : reduction * (er_em + hdriValue * evalh * absdot / hdripdf);
             if (evalh.x != 0.0f || evalh.y != 0.0f || evalh.z != 0.0f) {
                 // shadow query needed: occluded iff the closest hit is another triangle
-                F3 c_occ = er_mis ? reduction * (hd.emission + (f3s(0) * evalh * absdot / hdripdf) * er_wnee)
-                                  : reduction * (hd.emission + f3s(0) * evalh * absdot / hdripdf);
+                F3 c_occ = er_mis ? reduction * (er_em + (f3s(0) * evalh * absdot / hdripdf) * er_wnee)
+                                  : reduction * (er_em + f3s(0) * evalh * absdot / hdripdf);
                 Ray sr = make_ray(hd.position + N * 0.001f, wihdri);
                 F3 v0, v1, v2;
                 float4 qa, qb, qc4;
@@ -125,17 +147,55 @@
                 // a light whose BRDF term is exactly zero (below the shading normal's horizon) is skipped: no ray, no addition
                 if (er_evall.x != 0.0f || er_evall.y != 0.0f || er_evall.z != 0.0f) {
                     const F3 er_pl = er_value * er_evall * __builtin_fabsf(dot(er_dir, N)) / er_lpdf;   // :299-300
-                    ER_BOUNCE_LIGHT_QUERY(er_lr, er_limit, reduction * er_pl, reduction * f3s(0));
+                    ER_BOUNCE_LIGHT_QUERY(er_lr, -1, er_limit, reduction * er_pl, reduction * f3s(0));
                     lpending = true;
+                }
+            }
+            if (er_mesh && bounce + 1u < S.max_bounces) {
+                // an emitter sample (rules 3-6, er_shade.h); none at the last bounce, whose BRDF-sampled partner is never traced
+                const uint32_t er_k = mesh_slot(S, mesh_pick(S, er_mp));
+                if ((int)er_k != hslot) {
+                    F3 er_a, er_b, er_c, er_ng;
+                    float er_area;
+                    mesh_tri(S, er_k, er_a, er_b, er_c, er_ng, er_area);
+                    const float er_su = __builtin_sqrtf(er_mu1);
+                    const float er_b1 = er_su * (1.0f - er_mu2), er_b2 = er_su * er_mu2;
+                    const F3 er_p = er_a * (1.0f - er_su) + er_b * er_b1 + er_c * er_b2;
+                    const F3 er_toL = er_p - hd.position;
+                    const F3 er_dir = normalized(er_toL);
+                    const float er_dist = length(er_toL);
+                    const float er_cosl = dot(er_ng, er_dir);
+                    const F3 er_evall = er_cosl != 0.0f ? DisneyEval(hd, wo, N, er_dir) : f3s(0);
+                    if (er_evall.x != 0.0f || er_evall.y != 0.0f || er_evall.z != 0.0f) {
+                        // Le: the emission generate_hit_data would give at p's uv, times the opacity there (rule 4)
+                        const float4* er_q = S.tri_attr + (size_t)er_k * ER_ATTR_PIECES;
+                        const float4 er_q4 = er_q[4], er_q5 = er_q[5];
+                        const ErMaterial& er_m = S.materials[__builtin_bit_cast(int, er_q[6].x)];
+                        const float er_tu = er_q4.z + (er_q5.x - er_q4.z) * er_b1 + (er_q5.z - er_q4.z) * er_b2;
+                        const float er_tv = er_q4.w + (er_q5.y - er_q4.w) * er_b1 + (er_q5.w - er_q4.w) * er_b2;
+                        F3 er_le = er_m.emission_tex < 0 ? f3(er_m.emission.x, er_m.emission.y, er_m.emission.z)
+                                                         : tex_filtered(S, S.textures[er_m.emission_tex], er_tu, er_tv);
+                        const float er_op = er_m.opacity_tex < 0 ? er_m.opacity : tex_filtered(S, S.textures[er_m.opacity_tex], er_tu, er_tv).x;
+                        er_le = er_le * clampf(er_op, 0.0f, 1.0f);
+                        if (COUNT) c_texels += (er_m.emission_tex < 0 ? 0 : 1) + (er_m.opacity_tex < 0 ? 0 : 1);
+                        const float er_lpdf = mesh_prob(S)[er_k] * (er_dist * er_dist) / (er_area * __builtin_fabsf(er_cosl));
+                        const float er_wl = 1.0f / (1.0f + DisneyPdf(hd, wo, N, er_dir) / er_lpdf);
+                        const F3 er_ml = er_le * er_evall * __builtin_fabsf(dot(er_dir, N)) / er_lpdf * er_wl;
+                        const Ray er_lr = make_ray(hd.position + er_dir * 0.001f, er_dir);
+                        ER_BOUNCE_LIGHT_QUERY(er_lr, (int)er_k, length(er_p - er_lr.o), reduction * er_ml, reduction * f3s(0));
+                        lpending = true;
+                    }
                 }
             }
             ER_TP(5);
             float brdfpdf = DisneyPdf(hd, wo, N, wibrdf);
             reduction = reduction * (DisneyEval(hd, wo, N, wibrdf) * __builtin_fabsf(dot(wibrdf, N)) / brdfpdf);
-            if (er_mis) prev_pdf = brdfpdf;
+            if (er_mis || er_mesh) prev_pdf = brdfpdf;
             if (bounce == 0) { ER_BOUNCE_FIRST_HIT(hd.normal, hd.tangent, hd.bitangent); }
             ray = make_ray(hit.position + wibrdf * 0.001f, wibrdf);
+            if (er_mesh) mesh_d = 0.001f;          // (the new ray leaves 0.001 away from the bounce)
         } else {
+            if (er_mesh) mesh_d = mesh_d + length(hit.position - ray.o) + 0.001f;      // an opacity pass-through: the segment and the offset
             ray = make_ray(hit.position + ray.d * 0.001f, ray.d);
         }
         ER_TP(6);

@@ -56,7 +56,7 @@ void er_launch_debug_trace(const DevScene& S, const float* o, const float* d, ui
 }
 
 // ---- per-bounce trace of one pixel-sample: er_bounce.inc over the production traversal, queries traced at once ----
-template <bool EXT>
+template <bool EXT, bool MESH>
 __global__ __launch_bounds__(64) void er_debug_pixel_kernel(DevScene S, uint32_t idx, ErTraceRec* recs, int max_recs, int* count, uint2* spill) {
     // (one lane, speed irrelevant.  The first levels of the traversal stack live in LDS as in the production kernels -- trav_choose
     // addresses them as LDS -- the deeper levels and the exact re-trace's stack in the HBM scratch buffer)
@@ -75,6 +75,7 @@ __global__ __launch_bounds__(64) void er_debug_pixel_kernel(DevScene S, uint32_t
     F3 light = f3s(0), reduction = f3s(1), aov_n = f3s(0), aov_t = f3s(0), aov_b = f3s(0);
     uint32_t bounce = 0;
     float prev_pdf = -1.0f;
+    float mesh_d = 0.0f;
     while (true) {
         int info;
         c_rays++;
@@ -108,19 +109,21 @@ __global__ __launch_bounds__(64) void er_debug_pixel_kernel(DevScene S, uint32_t
             rec->shadow_tri = cs_ < 0 ? -1 : __builtin_bit_cast(int, S.tri_isect[(size_t)cs_ * 3].w);                                 \
         }                                                                                                                             \
     }
-#define ER_BOUNCE_LIGHT_QUERY(lr, limit, lv, lo)                                                                                     \
+#define ER_BOUNCE_LIGHT_QUERY(lr, self_slot, limit, lv, lo)                                                                          \
     {                                                                                                                                 \
         int info_;                                                                                                                    \
         c_rays++;                                                                                                                     \
-        const bool occ_ = trav_run_shadow<false>(S, s_stack, spill, s_stack2, (lr), -1, (limit), info_, c_nodes, c_tris);             \
+        const bool occ_ = trav_run_shadow<false>(S, s_stack, spill, s_stack2, (lr), (self_slot), (limit), info_, c_nodes, c_tris);    \
         light = light + (occ_ ? (lo) : (lv));                                                                                         \
         if (rec) rec->light_occ = occ_ ? 1 : 0;                                                                                       \
     }
 #define ER_BOUNCE_FIRST_HIT(n, t, b) aov_n = (n); aov_t = (t); aov_b = (b)
+#define ER_BOUNCE_MESH MESH
 #include "er_bounce.inc"
 #undef ER_BOUNCE_HDRI_QUERY
 #undef ER_BOUNCE_LIGHT_QUERY
 #undef ER_BOUNCE_FIRST_HIT
+#undef ER_BOUNCE_MESH
         (void)pending; (void)lpending; (void)traced;
         if (rec) {
             // the opacity test passed iff more than its one draw was taken (src/kernel.cpp:539: the opaque branch draws 4+)
@@ -146,8 +149,8 @@ __global__ __launch_bounds__(64) void er_debug_pixel_kernel(DevScene S, uint32_t
 }
 
 void er_launch_debug_pixel(const DevScene& S, uint32_t idx, ErTraceRec* recs, int max_recs, int* count, void* spill, hipStream_t stream) {
-    if (er_ext_active(S)) hipLaunchKernelGGL(er_debug_pixel_kernel<true>, dim3(1), dim3(64), 0, stream, S, idx, recs, max_recs, count, (uint2*)spill);
-    else hipLaunchKernelGGL(er_debug_pixel_kernel<false>, dim3(1), dim3(64), 0, stream, S, idx, recs, max_recs, count, (uint2*)spill);
+    auto k = er_mesh_active(S) ? er_debug_pixel_kernel<true, true> : er_ext_active(S) ? er_debug_pixel_kernel<true, false> : er_debug_pixel_kernel<false, false>;
+    hipLaunchKernelGGL(k, dim3(1), dim3(64), 0, stream, S, idx, recs, max_recs, count, (uint2*)spill);
 }
 
 // ---- the device functions of the path, one item per thread (known-answer tests against the oracle's entry points) ----

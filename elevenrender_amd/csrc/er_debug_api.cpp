@@ -185,6 +185,26 @@ static int er_debug_trace_pixel_impl(ErScene* s, uint32_t idx, ErTraceRec* recs,
     return ER_OK;
 }
 
+static int er_debug_read_light_table_impl(ErScene* s, int32_t* tri_index, float* cdf, uint32_t cap) {
+    if (!s) return fail(ER_ERR_INVALID_ARG, "er_debug_read_light_table: NULL scene");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_debug_read_light_table: er_render_begin has not succeeded");
+    const uint32_t m = std::min(cap, s->light_emitters);
+    if (m == 0) return ER_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    ScopedDevBuf<int32_t> d_tri;
+    ScopedDevBuf<float> d_cdf;
+    int rc;
+    if ((rc = upload(d_tri, (const int32_t*)nullptr, m, s->stream)) != ER_OK) return rc;
+    if ((rc = upload(d_cdf, (const float*)nullptr, m, s->stream)) != ER_OK) return rc;
+    er_launch_light_table_read(s->dev.tri_isect, s->d_light_tab.p, s->tri_count, s->light_emitters, m, d_tri.p, d_cdf.p, s->stream);
+    HIP_TRY(hipGetLastError());
+    if (tri_index) HIP_TRY(hipMemcpyAsync(tri_index, d_tri.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, s->stream));
+    if (cdf) HIP_TRY(hipMemcpyAsync(cdf, d_cdf.p, sizeof(float) * m, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return ER_OK;
+}
+
 static int er_debug_eval_impl(ErScene* s, int kind, const float* in, uint32_t n, uint32_t in_stride, float* out, uint32_t out_stride) {
     static const uint32_t need_in[ER_FN_COUNT] = {1, 7, 7, 29, 29, 29, 3, 2, 4, 1, 2, 3};
     static const uint32_t need_out[ER_FN_COUNT] = {32, 6, 18, 3, 1, 3, 2, 3, 3, 1, 1, 1};
@@ -298,6 +318,9 @@ int er_debug_trace_rays(ErScene* s, const float* origins, const float* dirs, uin
 }
 int er_debug_trace_pixel(ErScene* s, uint32_t idx, ErTraceRec* recs, int max_recs, int* count) {
     return guarded("er_debug_trace_pixel", [&]() -> int { return er_debug_trace_pixel_impl(s, idx, recs, max_recs, count); });
+}
+int er_debug_read_light_table(ErScene* s, int32_t* tri_index, float* cdf, uint32_t cap) {
+    return guarded("er_debug_read_light_table", [&]() -> int { return er_debug_read_light_table_impl(s, tri_index, cdf, cap); });
 }
 int er_debug_eval(ErScene* s, int kind, const float* in, uint32_t n, uint32_t in_stride, float* out, uint32_t out_stride) {
     return guarded("er_debug_eval", [&]() -> int { return er_debug_eval_impl(s, kind, in, n, in_stride, out, out_stride); });

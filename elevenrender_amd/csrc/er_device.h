@@ -84,10 +84,13 @@ struct DevScene {
     // camera_trig() below; cam_trig_valid = 0 makes camera_ray compute them itself (the other schedules' kernels leave it 0 or 1 alike)
     float cam_cx, cam_sx, cam_cy, cam_sy, cam_cz, cam_sz;
     uint32_t cam_trig_valid;
-    // build-defined extensions (er_shade.h): ER_FLAG_POINT_LIGHTS / ER_FLAG_MIS bits of the render flags
+    // build-defined extensions (er_shade.h): ER_FLAG_POINT_LIGHTS / ER_FLAG_MIS / ER_FLAG_MESH_LIGHTS bits of the render flags.
+    // The light the light-query record samples: the point lights, or -- ER_FLAG_MESH_LIGHTS set here, which er_render_begin does only
+    // for a non-empty emitter table and never together with ER_FLAG_POINT_LIGHTS -- the emitter table of er_lights.h.  One pair of
+    // words for both: the scene descriptor keeps its layout, and with it every kernel that does not sample emitters its code.
     uint32_t ext_flags;
-    const ErPointLight* lights;
-    uint32_t light_count;
+    union { const ErPointLight* lights; const float* mesh_lights; };
+    union { uint32_t light_count; uint32_t emitter_count; };
     // per-pixel state
     float4* passes;             // ER_PASS_COUNT x (x_res*y_res) float4 in the layout of er_pass_index (below): NOT plane after plane
     uint32_t* samples;

@@ -32,7 +32,7 @@ __global__ void er_setup_kernel(DevScene S) {
     S.samples[idx] = 1;
 }
 
-template <bool COUNT, bool EXT>
+template <bool COUNT, bool EXT, bool MESH>
 __global__ __launch_bounds__(64) void er_render_kernel(DevScene S, uint32_t n_samples) {
     __shared__ int s_stack[ER_STACK * 64];
     const int lane = threadIdx.x;
@@ -50,6 +50,7 @@ __global__ __launch_bounds__(64) void er_render_kernel(DevScene S, uint32_t n_sa
         uint32_t s = 0;
         uint32_t bounce = 0;
         float prev_pdf = -1.0f;
+        float mesh_d = 0.0f;
         bool fresh = true;
         Ray ray;
         F3 light, reduction, aov_n, aov_t, aov_b;
@@ -61,6 +62,7 @@ __global__ __launch_bounds__(64) void er_render_kernel(DevScene S, uint32_t n_sa
                 light = f3s(0); reduction = f3s(1); aov_n = f3s(0); aov_t = f3s(0); aov_b = f3s(0);
                 bounce = 0;
                 prev_pdf = -1.0f;
+                mesh_d = 0.0f;
                 fresh = false;
             }
             // ---- one iteration of the bounce loop, src/kernel.cpp:508-593 (er_shade.h), rays traced inline ----
@@ -78,18 +80,20 @@ __global__ __launch_bounds__(64) void er_render_kernel(DevScene S, uint32_t n_sa
         const int occ_ = trace<COUNT, true>(S, stack, (sr), (self_slot), (d_self), sd_, c_nodes, c_tris);         \
         light = light + (occ_ >= 0 ? (co) : (cv));                                                                \
     }
-#define ER_BOUNCE_LIGHT_QUERY(lr, limit, lv, lo)                                                                 \
-    {   /* point-light sample (ER_FLAG_POINT_LIGHTS): occluded iff a hit is nearer than the light */              \
+#define ER_BOUNCE_LIGHT_QUERY(lr, self_slot, limit, lv, lo)                                                      \
+    {   /* point-light / emitter sample: occluded iff another triangle is hit nearer than the light */           \
         float sd_;                                                                                                \
         c_rays++;                                                                                                 \
-        const int occ_ = trace<COUNT, true>(S, stack, (lr), -1, (limit), sd_, c_nodes, c_tris);                   \
+        const int occ_ = trace<COUNT, true>(S, stack, (lr), (self_slot), (limit), sd_, c_nodes, c_tris);          \
         light = light + (occ_ >= 0 ? (lo) : (lv));                                                                \
     }
 #define ER_BOUNCE_FIRST_HIT(n, t, b) aov_n = (n); aov_t = (t); aov_b = (b)
+#define ER_BOUNCE_MESH MESH
 #include "er_bounce.inc"
 #undef ER_BOUNCE_HDRI_QUERY
 #undef ER_BOUNCE_LIGHT_QUERY
 #undef ER_BOUNCE_FIRST_HIT
+#undef ER_BOUNCE_MESH
             (void)pending; (void)lpending;
             if (done) {
                 sa = accumulate_sample(S, idx, sa, light, aov_n, aov_t, aov_b);   // src/kernel.cpp:597-645
@@ -171,7 +175,7 @@ hipError_t er_probe_kernels(const char** which) {
     *which = "er_setup_kernel";
     if ((e = hipFuncGetAttributes(&a, (const void*)er_setup_kernel)) != hipSuccess) return e;
     *which = "er_render_kernel";
-    if ((e = hipFuncGetAttributes(&a, (const void*)er_render_kernel<false, false>)) != hipSuccess) return e;
+    if ((e = hipFuncGetAttributes(&a, (const void*)er_render_kernel<false, false, false>)) != hipSuccess) return e;
     if ((e = er_probe_wavefront(which)) != hipSuccess) return e;
     if ((e = er_probe_stream(which)) != hipSuccess) return e;
     if ((e = er_probe_gpu_build(which)) != hipSuccess) return e;
@@ -186,8 +190,9 @@ void er_launch_setup(const DevScene& S, hipStream_t stream) {
 }
 void er_launch_render(const DevScene& S, uint32_t n_samples, bool count, hipStream_t stream) {
     if (S.owned_tile_count == 0 || n_samples == 0) return;
-    const bool ext = er_ext_active(S);
-    auto k = count ? (ext ? er_render_kernel<true, true> : er_render_kernel<true, false>) : (ext ? er_render_kernel<false, true> : er_render_kernel<false, false>);
+    const bool ext = er_ext_active(S), mesh = er_mesh_active(S);
+    auto k = count ? (mesh ? er_render_kernel<true, true, true> : ext ? er_render_kernel<true, true, false> : er_render_kernel<true, false, false>)
+                   : (mesh ? er_render_kernel<false, true, true> : ext ? er_render_kernel<false, true, false> : er_render_kernel<false, false, false>);
     hipLaunchKernelGGL(k, dim3(S.owned_tile_count), dim3(64), 0, stream, S, n_samples);
 }
 // ---- denoise: edge-avoiding a-trous wavelet filter of the BEAUTY plane, guided by colour and

@@ -25,6 +25,7 @@
 #include "er_wavefront.h"
 #include "er_stream.h"
 #include "er_adaptive.h"
+#include "er_lights.h"
 
 namespace erh {
 
@@ -174,6 +175,9 @@ struct ErScene {
     DevBuf<ErMaterial> d_materials;
     DevBuf<float4> d_mat_pre;    // DevScene::mat_pre
     DevBuf<ErPointLight> d_lights;
+    DevBuf<float> d_light_tab;       // ER_FLAG_MESH_LIGHTS: the emitter table (er_lights.h), empty without emitters
+    uint32_t light_emitters = 0;     //   its entries
+    float light_total = 0.0f;        //   W, the sum of their weights
     DevBuf<DevTex> d_textures;
     DevBuf<float> d_tex_pool, d_cdf;
     DevBuf<uint32_t> d_samples, d_rng, d_owned;
@@ -253,6 +257,7 @@ struct ErScene {
         d_textures.release(); d_tex_pool.release(); d_lights.release(); d_cdf.release(); d_samples.release(); d_rng.release();
         d_owned.release(); d_counters.release(); d_wf4.release(); d_wf1.release(); d_spill.release(); d_guide.release(); d_ticket.release(); d_deal.release(); d_ray_log.release(); d_mat_fused.release(); d_mat_pre.release(); d_dev.release(); d_tile_cost.release(); d_px_draws.release();
         d_ad_list[0].release(); d_ad_list[1].release(); d_ad_keep.release(); d_ad_snap.release(); d_ad_err.release();
+        d_light_tab.release(); light_emitters = 0; light_total = 0.0f;
         ad_on = false; rendered = 0;
         for (auto& kv : d_rank_tiles) kv.second.release();
         d_rank_tiles.clear();

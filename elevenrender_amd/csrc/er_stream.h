@@ -66,6 +66,9 @@ struct WfState;
 // launch (the caller zeroes them before it); [5..6] the earliest start of a workgroup (caller: all ones) and [7 + 2 x ..] the latest end of
 // a wave of XCD x = workgroup index % 8 (caller: zero), wall_clock64() ticks.
 // S_dev: a device copy of S (the kernel reads the scene descriptor from constant memory, not from its arguments).
+// ER_FLAG_MESH_LIGHTS (er_mesh_active): er_launch_stream hands the launch to er_launch_stream_mesh (er_stream_mesh.hip)
+void er_launch_stream_mesh(const DevScene& S, const DevScene* S_dev, void* records, uint32_t slots, bool lights, void* spill, const uint32_t* deal, uint32_t deal_count, void* ring,
+                           uint32_t ring_cap, uint32_t* status, uint32_t n_samples, bool count, uint32_t blocks, uint32_t tracers, uint32_t waves, bool spec, bool keep, hipStream_t stream);
 void er_launch_stream(const DevScene& S, const DevScene* S_dev, void* records, uint32_t slots, bool lights, void* spill, const uint32_t* deal, uint32_t deal_count, void* ring,
                       uint32_t ring_cap, uint32_t* status, uint32_t n_samples, bool count, uint32_t blocks, uint32_t tracers, uint32_t waves, bool spec, bool keep, hipStream_t stream);
 // the deal of the owned tiles to the workgroups (device copy of `out` = `deal` above, deal_count = out.size()); returns the most tiles of one workgroup

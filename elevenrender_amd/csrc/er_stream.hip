@@ -360,7 +360,7 @@ __device__ __forceinline__ void st_write_result(const StState& W, uint32_t rec, 
 
 }  // namespace
 
-template <bool COUNT, bool EXT, uint32_t ST_THREADS, bool FUSE, int FORM>
+template <bool COUNT, bool EXT, bool MESH, uint32_t ST_THREADS, bool FUSE, int FORM>
 __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __attribute__((address_space(4)))* Sp, StState W, const uint32_t* deal, uint32_t deal_count, uint2* ring_base, uint32_t ring_cap,
                                                           uint32_t* status, uint32_t n_samples, uint32_t tracers, uint32_t refill_min, uint32_t batch_min, uint32_t fin_min) {
     // The scene descriptor lives in constant memory and is read with scalar loads where it is used.  As a by-value kernel argument its
@@ -821,10 +821,12 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                 ray.o = f3s(0);
                 ray.d = f3(0, 0, 1);
                 float prev_pdf = -1.0f;
+                float mesh_d = 0.0f;       // (MESH: ray_o.w)
                 if (!fin_only) {
                     float4 o = W.ray_o(slot), d = W.ray_d(slot);
                     ray.o = f3(o.x, o.y, o.z);
                     ray.d = f3(d.x, d.y, d.z);
+                    if (MESH) mesh_d = o.w;
                     int hslot = resolve_closest<COUNT>(S, stack, ray, W.hit(slot), W.hit2(slot), c_nodes, c_tris);
                     c_bounce++;
                     if (EXT) prev_pdf = d.w;
@@ -833,11 +835,11 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
     W.sh_d(slot) = make_float4((sr).d.x, (sr).d.y, (sr).d.z, (d_self));                                          \
     W.c_vis(slot) = make_float4((cv).x, (cv).y, (cv).z, 0.0f);                                                   \
     W.c_occ(slot) = make_float4((co).x, (co).y, (co).z, 0.0f)
-#define ER_BOUNCE_LIGHT_QUERY(lr, limit, lv, lo)                                                                \
+#define ER_BOUNCE_LIGHT_QUERY(lr, self_slot, limit, lv, lo)                                                     \
     {                                                                                                            \
         const uint32_t lq = slot + W.slots;                                                                      \
         const F3 lv_ = (lv), lo_ = (lo);                                                                         \
-        W.sh_o(lq) = make_float4((lr).o.x, (lr).o.y, (lr).o.z, __builtin_bit_cast(float, -1));                   \
+        W.sh_o(lq) = make_float4((lr).o.x, (lr).o.y, (lr).o.z, __builtin_bit_cast(float, (int)(self_slot)));     \
         W.sh_d(lq) = make_float4((lr).d.x, (lr).d.y, (lr).d.z, (limit));                                         \
         W.c_vis(lq) = make_float4(lv_.x, lv_.y, lv_.z, 0.0f);                                                    \
         W.c_occ(lq) = make_float4(lo_.x, lo_.y, lo_.z, 0.0f);                                                    \
@@ -847,10 +849,12 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
     W.aov_t(slot) = make_float4((t).x, (t).y, (t).z, 0.0f);                                                      \
     W.aov_b(slot) = make_float4((b).x, (b).y, (b).z, 0.0f)
 #define ER_BOUNCE_FUSE FUSE
+#define ER_BOUNCE_MESH MESH
 #include "er_bounce.inc"
 #undef ER_BOUNCE_HDRI_QUERY
 #undef ER_BOUNCE_LIGHT_QUERY
 #undef ER_BOUNCE_FIRST_HIT
+#undef ER_BOUNCE_MESH
                 }
                 bool alive = true, fin_next = false;
                 if (done && (pending || lpending)) {
@@ -868,7 +872,7 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                 push_light = EXT && lpending;
                 if (alive) {
                     if (!fin_next) {
-                        W.ray_o(slot) = make_float4(ray.o.x, ray.o.y, ray.o.z, 0.0f);
+                        W.ray_o(slot) = make_float4(ray.o.x, ray.o.y, ray.o.z, MESH ? mesh_d : 0.0f);
                         W.ray_d(slot) = make_float4(ray.d.x, ray.d.y, ray.d.z, EXT ? prev_pdf : -1.0f);
                     }
                     W.light(slot) = make_float4(light.x, light.y, light.z, __builtin_bit_cast(float, rs));
@@ -930,18 +934,19 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                     ray.o = f3s(0);
                     ray.d = f3(d.x, d.y, d.z);
                     float prev_pdf = EXT ? d.w : -1.0f;
+                    float mesh_d = 0.0f;
                     const int hslot = -1;
                     bool done = false, pending = false, lpending = false;
                     c_bounce++;
 // (the hooks belong to the hit branch, which `hslot = -1` compiles out)
 #define ER_BOUNCE_HDRI_QUERY(sr, self_slot, d_self, cv, co) ((void)(sr), (void)(self_slot), (void)(d_self), (void)(cv), (void)(co))
-#define ER_BOUNCE_LIGHT_QUERY(lr, limit, lv, lo) ((void)(lr), (void)(limit), (void)(lv), (void)(lo))
+#define ER_BOUNCE_LIGHT_QUERY(lr, self_slot, limit, lv, lo) ((void)(lr), (void)(self_slot), (void)(limit), (void)(lv), (void)(lo))
 #define ER_BOUNCE_FIRST_HIT(n, t, b) ((void)(n), (void)(t), (void)(b))
 #include "er_bounce.inc"
 #undef ER_BOUNCE_HDRI_QUERY
 #undef ER_BOUNCE_LIGHT_QUERY
 #undef ER_BOUNCE_FIRST_HIT
-                    (void)bounce; (void)done; (void)pending; (void)lpending; (void)prev_pdf;
+                    (void)bounce; (void)done; (void)pending; (void)lpending; (void)prev_pdf; (void)mesh_d;
                 }
                 // src/kernel.cpp:597-645
                 const float4 an = W.aov_n(slot), at = W.aov_t(slot), ab = W.aov_b(slot);
@@ -958,9 +963,10 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                 }
                 if (SPEC && spec_on) {
                     {   // the pixel's next guess: what this sample drew -- 5 for the camera ray, then per iteration that hit: 1 (opacity) + 4 for an opaque
-                        // one (HDRI cell, three for the BRDF sample), 5 with the light extension (src/kernel.cpp:492-493, 538-545; er_bounce.inc)
+                        // one (HDRI cell, three for the BRDF sample), 5 with the light extension, 7 with the emitter one (src/kernel.cpp:492-493,
+                        // 538-545; er_bounce.inc)
                         const uint32_t ta = W.tally_a(slot);
-                        const uint32_t per_opaque = (EXT && (S.ext_flags & ER_FLAG_POINT_LIGHTS) != 0 && S.light_count > 0) ? 5u : 4u;
+                        const uint32_t per_opaque = MESH ? 7u : (EXT && (S.ext_flags & ER_FLAG_POINT_LIGHTS) != 0 && S.light_count > 0) ? 5u : 4u;
                         uint32_t nd = 5u + ((ta >> 10) & 0x3FFu) + per_opaque * ((ta >> 20) & 0x3FFu);
                         nd = nd > ST_DRAWS_MASK ? 0u : nd;      // (longer than the field: no guess for this pixel)
                         // a saturating counter per pixel, as a branch predictor keeps one per branch: the guess stays while it is mostly right
@@ -1210,12 +1216,17 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
     }
 }
 
+// The instances with the emitter samples of ER_FLAG_MESH_LIGHTS (MESH = true) are compiled in a translation unit of their own,
+// er_stream_mesh.hip, which includes this file with ER_STREAM_MESH_TU defined: there the launcher below is er_launch_stream_mesh and
+// picks only those instances, and the other host functions are left to this one.  Each unit's device assembly gets its own split-wait
+// check (Makefile), and this one holds the 40 instances without the extension.
+#ifndef ER_STREAM_MESH_TU
 hipError_t er_probe_stream(const char** which) {
     hipFuncAttributes a;
     *which = "er_stream_kernel";
-    hipError_t e = hipFuncGetAttributes(&a, (const void*)er_stream_kernel<false, false, 1024u, false, 0>);
-    if (e == hipSuccess) e = hipFuncGetAttributes(&a, (const void*)er_stream_kernel<false, false, 768u, true, 0>);
-    return e != hipSuccess ? e : hipFuncGetAttributes(&a, (const void*)er_stream_kernel<false, false, 768u, true, 2>);
+    hipError_t e = hipFuncGetAttributes(&a, (const void*)er_stream_kernel<false, false, false, 1024u, false, 0>);
+    if (e == hipSuccess) e = hipFuncGetAttributes(&a, (const void*)er_stream_kernel<false, false, false, 768u, true, 0>);
+    return e != hipSuccess ? e : hipFuncGetAttributes(&a, (const void*)er_stream_kernel<false, false, false, 768u, true, 2>);
 }
 
 // Which workgroup renders which tiles.  Workgroups b and b + 8 run on the same XCD and share its 4 MB L2 (observed dispatch
@@ -1272,8 +1283,21 @@ uint32_t er_stream_deal_tiles(const uint32_t* owned, uint32_t count, uint32_t ti
     return maxk;
 }
 
-void er_launch_stream(const DevScene& S, const DevScene* S_dev, void* records, uint32_t slots, bool lights, void* spill, const uint32_t* deal, uint32_t deal_count, void* ring,
+#endif  // ER_STREAM_MESH_TU
+
+#ifdef ER_STREAM_MESH_TU
+#define ER_STREAM_LAUNCH er_launch_stream_mesh
+#else
+#define ER_STREAM_LAUNCH er_launch_stream
+#endif
+void ER_STREAM_LAUNCH(const DevScene& S, const DevScene* S_dev, void* records, uint32_t slots, bool lights, void* spill, const uint32_t* deal, uint32_t deal_count, void* ring,
                       uint32_t ring_cap, uint32_t* status, uint32_t n_samples, bool count, uint32_t blocks, uint32_t tracers, uint32_t waves, bool spec, bool keep, hipStream_t stream) {
+#ifndef ER_STREAM_MESH_TU
+    if (er_mesh_active(S)) {
+        er_launch_stream_mesh(S, S_dev, records, slots, lights, spill, deal, deal_count, ring, ring_cap, status, n_samples, count, blocks, tracers, waves, spec, keep, stream);
+        return;
+    }
+#endif
     static const uint32_t refill_min = [] {
         const char* e = getenv("ER_STREAM_REFILL_MIN");
         int v = e ? atoi(e) : 12;
@@ -1326,17 +1350,24 @@ void er_launch_stream(const DevScene& S, const DevScene* S_dev, void* records, u
     waves = waves == 12u ? 12u : 16u;
     if (tracers > waves - 1u) tracers = waves - 1u;      // at least one shader wave
     if (tracers < 1u) tracers = 1u;
-    const bool ext = er_ext_active(S);
     // (FUSE: an instance without the fused-texel path for scenes in which no material is fused, er_device.h generate_hit_data)
     const bool fuse = S.fused_any != 0u;
     auto pick = [&](auto with, auto without) { return fuse ? with : without; };
     // instances: counters x extensions x fused textures, in five forms: 16 waves plain / with the keep rule / with that and speculative samples,
     // 12 waves plain / with speculative samples (the plain forms are the code of round 5: whole frames, and the scenes that start no speculative samples)
+#ifdef ER_STREAM_MESH_TU
+    // (ER_FLAG_MESH_LIGHTS: EXT with the emitter samples, counters x fused textures x the five forms)
 #define ST_PICK(THREADS, SPECV)                                                                                                                                  \
-    (count ? (ext ? pick(er_stream_kernel<true, true, THREADS, true, SPECV>, er_stream_kernel<true, true, THREADS, false, SPECV>)                                 \
-                  : pick(er_stream_kernel<true, false, THREADS, true, SPECV>, er_stream_kernel<true, false, THREADS, false, SPECV>))                               \
-           : (ext ? pick(er_stream_kernel<false, true, THREADS, true, SPECV>, er_stream_kernel<false, true, THREADS, false, SPECV>)                               \
-                  : pick(er_stream_kernel<false, false, THREADS, true, SPECV>, er_stream_kernel<false, false, THREADS, false, SPECV>)))
+    (count ? pick(er_stream_kernel<true, true, true, THREADS, true, SPECV>, er_stream_kernel<true, true, true, THREADS, false, SPECV>)                           \
+           : pick(er_stream_kernel<false, true, true, THREADS, true, SPECV>, er_stream_kernel<false, true, true, THREADS, false, SPECV>))
+#else
+    const bool ext = er_ext_active(S);
+#define ST_PICK(THREADS, SPECV)                                                                                                                                  \
+    (count ? (ext ? pick(er_stream_kernel<true, true, false, THREADS, true, SPECV>, er_stream_kernel<true, true, false, THREADS, false, SPECV>)                   \
+                  : pick(er_stream_kernel<true, false, false, THREADS, true, SPECV>, er_stream_kernel<true, false, false, THREADS, false, SPECV>))                 \
+           : (ext ? pick(er_stream_kernel<false, true, false, THREADS, true, SPECV>, er_stream_kernel<false, true, false, THREADS, false, SPECV>)                 \
+                  : pick(er_stream_kernel<false, false, false, THREADS, true, SPECV>, er_stream_kernel<false, false, false, THREADS, false, SPECV>)))
+#endif
     auto k16 = ST_PICK(1024u, 0);
     auto k16k = ST_PICK(1024u, 1);
     auto k16s = ST_PICK(1024u, 2);
@@ -1356,7 +1387,11 @@ void er_launch_stream(const DevScene& S, const DevScene* S_dev, void* records, u
     else hipLaunchKernelGGL(k16, dim3(blocks), dim3(1024), 0, stream, dS, st, deal, deal_count, (uint2*)ring, ring_cap, status, n_samples, tracers, refill_min, batch_min, fin_min);
 }
 
+#undef ER_STREAM_LAUNCH
+
+#ifndef ER_STREAM_MESH_TU
 uint32_t er_stream_record_bytes(bool lights) { return lights ? ST_STRIDE_LIGHTS : ST_STRIDE_PLAIN; }
 // uint2 entries of the spill buffer: per workgroup 16 waves x ER_SPILL_PER_WAVE (er_trav.h): a tracer wave's stack levels beyond the LDS ones
 // (ER_STACK8 levels of the wide tree), a shader wave's exact re-trace stack (ER_STACK ints per lane, two per entry): 16 KB per wave, 67 MB on 256 CUs
 size_t er_stream_spill_entries(uint32_t blocks) { return (size_t)blocks * 16 * ER_SPILL_PER_WAVE; }
+#endif  // ER_STREAM_MESH_TU

@@ -20,7 +20,7 @@ struct DevScene;
 // One slot per owned pixel lane (owned_tile_count * 64).  All records are 16 bytes so a lane moves
 // its state with dwordx4 accesses.
 struct WfState {
-    float4* ray_o;     // closest-hit ray origin (xyz)
+    float4* ray_o;     // closest-hit ray origin (xyz), w = distance from the last opaque bounce (ER_FLAG_MESH_LIGHTS; 0 otherwise)
     float4* ray_d;     // closest-hit ray direction (xyz), w = brdfpdf of the last opaque bounce (ER_FLAG_MIS; < 0 none)
     int* hit;          // triangle slot of the closest hit, -1 = miss (written by trace)
     int* hit2;         // second surviving candidate (exact metric decides in shade), -1 none, -2 = re-trace exactly
@@ -42,9 +42,9 @@ struct WfState {
     uint32_t* counts;  // WF_COUNTS words
     uint2* spill;      // per persistent trace wave: ER_STACK8 x 64 stack entries beyond the LDS levels (er_trav.h)
     int* shade_stack;  // per shade wave: ER_BVH_MAX_DEPTH x 64 ints, the stack of the rare exact re-trace (in LDS until round 5: 16 KB per wave at depth 64)
-    uint32_t slots;    // owned_tile_count * 64.  With ER_FLAG_POINT_LIGHTS the shadow records (sh_o, sh_d, c_vis, c_occ,
+    uint32_t slots;    // owned_tile_count * 64.  With ER_FLAG_POINT_LIGHTS or ER_FLAG_MESH_LIGHTS the shadow records (sh_o, sh_d, c_vis, c_occ,
                        // occluded, occ_a, occ_b) have 2 * slots entries: [slot] = the HDRI query, [slot + slots] = the
-                       // point-light query of the same bounce; shadow-queue entries are these indices
+                       // light query of the same bounce; shadow-queue entries are these indices
     uint32_t pool, pools;   // this state drives the owned tiles t with t % pools == pool (see er_api.cpp: slot pools)
 };
 

@@ -262,7 +262,7 @@ __global__ __launch_bounds__(64, WF_TRACE_WAVES) void er_wf_trace(DevScene S, Wf
 #ifndef WF_SHADE_WAVES
 #define WF_SHADE_WAVES 4
 #endif
-template <bool COUNT, bool EXT>
+template <bool COUNT, bool EXT, bool MESH>
 __global__ __launch_bounds__(64, WF_SHADE_WAVES) void er_wf_shade(DevScene S, WfState W, uint32_t parity) {
     // queue entries are staged per wave and appended WF_STAGE tickets at a time: the two queue-length words are
     // single addresses, and one address takes ~90 atomics/us whatever the number of waves
@@ -353,8 +353,10 @@ __global__ __launch_bounds__(64, WF_SHADE_WAVES) void er_wf_shade(DevScene S, Wf
             bool done = fin_only;
             Ray ray;
             float prev_pdf = -1.0f;
+            float mesh_d = 0.0f;       // (MESH: ray_o.w)
             if (!fin_only) {
                 float4 o = W.ray_o[slot], d = W.ray_d[slot];
+                if (MESH) mesh_d = o.w;
                 ray.o = f3(o.x, o.y, o.z);
                 ray.d = f3(d.x, d.y, d.z);
                 int hslot = W.hit[slot];
@@ -372,11 +374,11 @@ __global__ __launch_bounds__(64, WF_SHADE_WAVES) void er_wf_shade(DevScene S, Wf
     W.sh_d[slot] = make_float4((sr).d.x, (sr).d.y, (sr).d.z, (d_self));                                          \
     W.c_vis[slot] = make_float4((cv).x, (cv).y, (cv).z, 0.0f);                                                   \
     W.c_occ[slot] = make_float4((co).x, (co).y, (co).z, 0.0f)
-#define ER_BOUNCE_LIGHT_QUERY(lr, limit, lv, lo)                                                                \
-    {   /* the point-light query of a slot lives in the second half of the shadow records */                    \
+#define ER_BOUNCE_LIGHT_QUERY(lr, self_slot, limit, lv, lo)                                                     \
+    {   /* the light query of a slot lives in the second half of the shadow records */                          \
         const uint32_t lq = slot + W.slots;                                                                      \
         const F3 lv_ = (lv), lo_ = (lo);                                                                         \
-        W.sh_o[lq] = make_float4((lr).o.x, (lr).o.y, (lr).o.z, __builtin_bit_cast(float, -1));                   \
+        W.sh_o[lq] = make_float4((lr).o.x, (lr).o.y, (lr).o.z, __builtin_bit_cast(float, (int)(self_slot)));     \
         W.sh_d[lq] = make_float4((lr).d.x, (lr).d.y, (lr).d.z, (limit));                                         \
         W.c_vis[lq] = make_float4(lv_.x, lv_.y, lv_.z, 0.0f);                                                    \
         W.c_occ[lq] = make_float4(lo_.x, lo_.y, lo_.z, 0.0f);                                                    \
@@ -385,10 +387,12 @@ __global__ __launch_bounds__(64, WF_SHADE_WAVES) void er_wf_shade(DevScene S, Wf
     W.aov_n[slot] = make_float4((n).x, (n).y, (n).z, 0.0f);                                                      \
     W.aov_t[slot] = make_float4((t).x, (t).y, (t).z, 0.0f);                                                      \
     W.aov_b[slot] = make_float4((b).x, (b).y, (b).z, 0.0f)
+#define ER_BOUNCE_MESH MESH
 #include "er_bounce.inc"
 #undef ER_BOUNCE_HDRI_QUERY
 #undef ER_BOUNCE_LIGHT_QUERY
 #undef ER_BOUNCE_FIRST_HIT
+#undef ER_BOUNCE_MESH
             }
             bool alive = true;
             if (done && (pending || lpending)) {
@@ -426,6 +430,7 @@ __global__ __launch_bounds__(64, WF_SHADE_WAVES) void er_wf_shade(DevScene S, Wf
                     reduction = f3s(1);
                     bounce = 0;
                     prev_pdf = -1.0f;
+                    mesh_d = 0.0f;
                     W.aov_n[slot] = make_float4(0, 0, 0, 0);
                     W.aov_t[slot] = make_float4(0, 0, 0, 0);
                     W.aov_b[slot] = make_float4(0, 0, 0, 0);
@@ -442,7 +447,7 @@ __global__ __launch_bounds__(64, WF_SHADE_WAVES) void er_wf_shade(DevScene S, Wf
             push_light = EXT && lpending;
             if (alive) {
                 if (!(next_entry & ER_WF_FINALIZE_ONLY)) {
-                    W.ray_o[slot] = make_float4(ray.o.x, ray.o.y, ray.o.z, 0.0f);
+                    W.ray_o[slot] = make_float4(ray.o.x, ray.o.y, ray.o.z, MESH ? mesh_d : 0.0f);
                     W.ray_d[slot] = make_float4(ray.d.x, ray.d.y, ray.d.z, EXT ? prev_pdf : -1.0f);
                 }
                 W.light[slot] = make_float4(light.x, light.y, light.z, __builtin_bit_cast(float, rs));
@@ -483,7 +488,7 @@ hipError_t er_probe_wavefront(const char** which) {
     *which = "er_wf_trace";
     if ((e = hipFuncGetAttributes(&a, (const void*)er_wf_trace<false>)) != hipSuccess) return e;
     *which = "er_wf_shade";
-    return hipFuncGetAttributes(&a, (const void*)er_wf_shade<false, false>);
+    return hipFuncGetAttributes(&a, (const void*)er_wf_shade<false, false, false>);
 }
 
 void er_launch_wf_begin(const DevScene& S, const WfState& W, uint32_t n_samples, hipStream_t stream) {
@@ -504,7 +509,8 @@ void er_launch_wf_trace(const DevScene& S, const WfState& W, uint32_t parity, bo
 }
 void er_launch_wf_shade(const DevScene& S, const WfState& W, uint32_t parity, bool count, uint32_t blocks, hipStream_t stream) {
     if (S.owned_tile_count == 0) return;
-    const bool ext = er_ext_active(S);
-    auto k = count ? (ext ? er_wf_shade<true, true> : er_wf_shade<true, false>) : (ext ? er_wf_shade<false, true> : er_wf_shade<false, false>);
+    const bool ext = er_ext_active(S), mesh = er_mesh_active(S);
+    auto k = count ? (mesh ? er_wf_shade<true, true, true> : ext ? er_wf_shade<true, true, false> : er_wf_shade<true, false, false>)
+                   : (mesh ? er_wf_shade<false, true, true> : ext ? er_wf_shade<false, true, false> : er_wf_shade<false, false, false>);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(64), 0, stream, S, W, parity);
 }

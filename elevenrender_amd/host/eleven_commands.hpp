@@ -22,7 +22,7 @@
 //   * `denoise: true` runs the library's own edge-avoiding filter (er_denoise) instead of OIDN;
 //   * sRGB textures are converted with the real transfer function -- the reference's fast_pow is broken for float
 //     (src/Math.hpp:12-20 zeroes every value above 0.04045), which cannot be intended;
-//   * config accepts the optional keys max_bounces (default 5), point_lights / mis (false), schedule, and gpus / devices /
+//   * config accepts the optional keys max_bounces (default 5), point_lights / mis / mesh_lights (false), schedule, and gpus / devices /
 //     transport: the frame's pixel tiles are dealt to `gpus` GPUs of this node driven by this one process, and --get_pass
 //     gathers the plane to the first of them (er_gather_pass: RCCL send/recv over xGMI, or in-process peer copies).
 #pragma once
@@ -276,6 +276,10 @@ private:
             }
             // (extra keys, ignored by the plug-in: how the render is spread and how the render thread sizes its calls)
             j["gpus"] = rm.ranks();
+            if (rm.pars.flags & ER_FLAG_MESH_LIGHTS) {      // (only with the key: a session without it answers as before)
+                j["mesh_lights"] = true;
+                j["emitters"] = rm.emitters();      // entries of the emitter table
+            }
             if (!rm.transport_used.empty()) j["transport"] = rm.transport_used;
             j["samples_per_call"] = samples_per_call_.load();
             im->write_message(Message::json_data(j));
@@ -318,6 +322,7 @@ private:
         if (const json::Value* v = j.if_contains("max_bounces")) rp.max_bounces = (unsigned)v->as_int64();
         if (const json::Value* v = j.if_contains("point_lights")) if (v->as_bool()) rp.flags |= ER_FLAG_POINT_LIGHTS;
         if (const json::Value* v = j.if_contains("mis")) if (v->as_bool()) rp.flags |= ER_FLAG_MIS;
+        if (const json::Value* v = j.if_contains("mesh_lights")) if (v->as_bool()) rp.flags |= ER_FLAG_MESH_LIGHTS;
         if (const json::Value* v = j.if_contains("schedule")) {
             const std::string& s = v->as_string();
             if (s == "stream") rp.flags |= ER_FLAG_STREAM;

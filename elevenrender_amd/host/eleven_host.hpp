@@ -304,6 +304,11 @@ public:
     }
     // adaptive sampling over the ranks: the ranks' tiles summed, samples_rendered of the rank that is furthest ahead (each rank stops
     // only its own tiles; the frame goes on while any rank has an active tile)
+    uint32_t emitters() {      // the emitter table of ER_FLAG_MESH_LIGHTS (every rank builds the same one)
+        ErLightInfo li{};
+        if (!ers_.empty() && ers_[0] && er_light_info(ers_[0], &li) != ER_OK) return 0;
+        return li.emitters;
+    }
     ErAdaptiveInfo adaptive_info() {
         ErAdaptiveInfo sum{};
         for (ErScene* e : ers_) {

@@ -124,6 +124,22 @@ class RenderingManager:
         abi.check(self.lib.er_adaptive_info(self.handle, C.byref(a)))
         return {n: getattr(a, n) for n, _ in abi.ErAdaptiveInfo._fields_}
 
+    def light_info(self):
+        """er_light_info: {'emitters': entries of the ER_FLAG_MESH_LIGHTS emitter table (0 without the flag or without emitters),
+        'total_weight': the sum of their area x luminance}."""
+        li = abi.ErLightInfo()
+        abi.check(self.lib.er_light_info(self.handle, C.byref(li)))
+        return {n: getattr(li, n) for n, _ in abi.ErLightInfo._fields_}
+
+    def debug_light_table(self):
+        """include/eleven_hip_debug.h er_debug_read_light_table: (input triangle index int32[n], cdf float32[n]) of the emitter table."""
+        n = self.light_info()["emitters"]
+        tri = np.zeros(n, np.int32)
+        cdf = np.zeros(n, np.float32)
+        if n:
+            abi.check(self.lib.er_debug_read_light_table(self.handle, tri.ctypes.data_as(C.POINTER(C.c_int32)), cdf.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return tri, cdf
+
     def tile_state(self):
         """(error[tiles_y, tiles_x] float32, samples[tiles_y, tiles_x] uint32): each tile's error at its last test (-1: untested,
         untestable or not owned) and the samples it received (0: not owned)."""

@@ -91,6 +91,16 @@ def cornell(x_res=256, y_res=256):
                          materials, camera=cam, x_res=x_res, y_res=y_res)
 
 
+def cornell_dim(x_res=256, y_res=256):
+    """C1 lit by its emitter: the light lowered to y = 0.7 with an emission of 0.3, and an HDRI of 0.002 grey, so that the light the
+    open front lets in is negligible beside the emitter's (ER_FLAG_MESH_LIGHTS measurements and tests)."""
+    sc = cornell(x_res, y_res)
+    sc.vertices[10:12, :, 1] = np.float32(0.7)
+    sc.materials[3] = abi.default_material(emission=(0.3, 0.3, 0.3))
+    sc.hdri = (np.full((1, 1, 3), 0.002, np.float32), 1, 1, 3, 0)
+    return sc
+
+
 def soup_geometry(n_tris, seed=12345):
     """C2 distribution: centroid c ~ U([-1,1]^2 x [2,4]); v0 = c, v1,v2 = c + U([-1,1]^3) * e, e = 2/cbrt(N)."""
     r = Rand(seed, 1)

@@ -116,6 +116,10 @@ typedef struct ErSceneDesc {
                                      bounce after the author's sketch src/kernel.cpp:269-301 (rules: csrc/er_shade.h) */
 #define ER_FLAG_MIS          128u /* extension, default off = reference behaviour (NEE and BRDF-sampled environment both
                                      counted in full, src/kernel.cpp:571-577): balance-heuristic weights per direction */
+#define ER_FLAG_MESH_LIGHTS  1024u /* extension, default off: next-event estimation of emissive triangles with balance-heuristic
+                                     MIS against the BRDF-sampled hits (rules: csrc/er_shade.h).  A scene without emitters renders
+                                     as without the flag; with ER_FLAG_POINT_LIGHTS on a scene that has both kinds of light,
+                                     er_render_begin returns ER_ERR_INVALID_ARG */
 #define ER_FLAG_COUNTERS     2u   /* count node visits / triangle tests (slower kernel variant) */
 /* Schedule selection (every schedule computes bit-identical results).  Default: the streaming schedule, at every frame size since
  * round 5 (C1 at 256 x 256: 1 186 Msamples/s against 849 for round 1's fused kernel, which was removed), except for a rank that owns
@@ -285,6 +289,14 @@ int er_adaptive_info(ErScene* scene, ErAdaptiveInfo* out);
 /* Per tile of the frame (tiles_x * tiles_y each, row-major; either pointer may be NULL): the error E of its last test (-1: untested,
  * untestable or not owned) and the samples it has received since er_render_begin (0: not owned). */
 int er_read_tile_state(ErScene* scene, float* error, uint32_t* samples);
+
+/* The emitter table of ER_FLAG_MESH_LIGHTS (csrc/er_shade.h): valid after er_render_begin (before it: ER_ERR_STATE; NULL argument:
+ * ER_ERR_INVALID_ARG).  emitters = 0 when the flag is off or the scene has no emitter; total_weight = the sum of area x luminance. */
+typedef struct ErLightInfo {
+    uint32_t emitters;
+    float total_weight;
+} ErLightInfo;
+int er_light_info(ErScene* scene, ErLightInfo* out);
 
 /* Per-kernel device time of the launches enqueued since the previous er_wait, measured with HIP events on
  * the library's stream (needs ER_FLAG_PROFILE; valid after er_wait). */

@@ -60,13 +60,18 @@ typedef struct ErTraceRec {
     float light[3];         /* accumulated radiance after this iteration */
     float reduction[3];     /* throughput after this iteration */
     int32_t shadow_occ;     /* HDRI shadow query: 1 occluded, 0 visible, -1 not traced */
-    int32_t light_occ;      /* point-light query (ER_FLAG_POINT_LIGHTS): 1 occluded, 0 visible, -1 none */
+    int32_t light_occ;      /* point-light / emitter query (ER_FLAG_POINT_LIGHTS / ER_FLAG_MESH_LIGHTS): 1 occluded, 0 visible, -1 none */
 } ErTraceRec;
 
 /* Runs ONE more sample of pixel idx -- bounce_step (csrc/er_shade.h) over the production traversal, every query traced
  * at once -- and records up to max_recs iterations.  The pixel's planes, sample count and RNG advance exactly as by
  * er_render_samples(scene, 1) restricted to that pixel.  *count = records written. */
 int er_debug_trace_pixel(struct ErScene* scene, uint32_t idx, ErTraceRec* recs, int max_recs, int* count);
+
+/* The emitter table of ER_FLAG_MESH_LIGHTS (er_light_info gives its length): for the first min(emitters, cap) entries, in table
+ * order (ascending triangle slot), the emitter's INPUT triangle index (ErSceneDesc order, mapped back through the BVH builder's
+ * permutation) and its CDF entry.  Either output may be NULL.  Before er_render_begin: ER_ERR_STATE. */
+int er_debug_read_light_table(struct ErScene* scene, int32_t* tri_index, float* cdf, uint32_t cap);
 
 /* The DEVICE functions of the path, one call per item, for known-answer tests against the oracle's function-level entry
  * points (SURVEY.md section 4 level 1: a1 RNG, a3 camera, a5 Tri::hit record, a6-a8 textures and mappings, a9 HDRI search /
