@@ -117,6 +117,10 @@ class ErStreamInfo(C.Structure):   # include/eleven_hip_debug.h
                 ("form", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ErStreamForm(C.Structure):   # include/eleven_hip_debug.h
+    _fields_ = [("waves", C.c_uint32), ("tracers", C.c_uint32), ("adapt", C.c_uint32), ("keep", C.c_uint32), ("spec", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class ErTraceRec(C.Structure):   # include/eleven_hip_debug.h; same layout as the oracle's OracleTraceRec
     _fields_ = [("bounce", C.c_int32), ("tri", C.c_int32), ("shadow_tri", C.c_int32), ("opaque", C.c_int32),
                 ("position", C.c_float * 3), ("wi", C.c_float * 3), ("light", C.c_float * 3), ("reduction", C.c_float * 3),
@@ -187,6 +191,12 @@ class ErError(RuntimeError):
 
 ABI_VERSION = 2     # include/eleven_hip.h ER_ABI_VERSION
 
+# Hooks of include/eleven_hip_debug.h that load() binds only if the library has them: tools/ab_libs.sh alternates this binding over
+# older builds of the library (ELEVEN_HIP_LIB), which need not export the newest hooks.
+OPTIONAL_SYMBOLS = {
+    "er_debug_stream_form": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(ErStreamForm)]),
+}
+
 
 def load():
     """Load libeleven_hip.so and declare its prototypes.  Raises if it is not built."""
@@ -201,6 +211,9 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    for name, (res, args) in OPTIONAL_SYMBOLS.items():
+        if hasattr(lib, name):
+            getattr(lib, name).restype, getattr(lib, name).argtypes = res, args
     if lib.er_abi_version() != ABI_VERSION:      # the structs below are filled completely by the library: a layout mismatch overwrites memory
         raise ErError(ER_ERR_STATE, f"{LIB_PATH} has ABI version {lib.er_abi_version()}, this binding was written for {ABI_VERSION}: rebuild")
     _lib = lib

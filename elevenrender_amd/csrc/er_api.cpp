@@ -123,70 +123,46 @@ void er_scene_destroy(ErScene* s) {
     delete s;
 }
 
-// which deal of tiles the streaming schedule uses for a share of `owned_tiles` tiles on `blocks` workgroups
-static bool stream_xcd_aware(size_t owned_tiles, uint32_t blocks) {
-    const char* xe = getenv("ER_STREAM_XCD_TILES");        // A/B knob: 0 = tiles dealt round-robin to the workgroups (round 2)
-    // (a share with no more pixels than slots -- an eighth of a 1080p frame -- has nothing waiting in its pixel rings; there the
-    // plain round-robin deal balances a little better: 1.392 vs 1.41 ms per pass, profiles/r03_ab_sim_world8_knobs.log)
-    return xe ? atoi(xe) != 0 : owned_tiles * 64 > (size_t)blocks * ER_STREAM_SLOTS;
-}
+// ---- er_render_begin: a sequence of stages, each with an explicit result ----
+namespace {
 
-// The streaming kernel's form for a share of `tiles` tiles: waves per workgroup, tracer / shader split, keep rule, speculative
-// samples (er_render_begin for the owned share; an adaptive render again for every new active share, within the buffers begin made).
-static void stream_choose_form(ErScene* s, size_t tiles, bool lights_on, uint32_t flags) {
-    // The split between tracer and shader waves (shader waves at issue priority 1; finished and escaped paths handled in batches
-    // of their own, er_stream.hip).  Round 2: 10 + 6, round 3: 12 + 4 (11 + 5 with the point-light extension, whose shading
-    // step is a third longer); since round 4's shorter shading step:
-    // 13 tracer + 3 shader waves where the shading step is at its cheapest -- plain materials, a scene that lives in the caches
-    // (C2: 1 787 vs 1 715 Msamples/s at 12 + 4) -- and 12 + 4 where it costs more: textured materials (C5 without lights: 1 560 vs
-    // 1 489 at 13 + 3), point lights (C5: 1 350 vs 1 234), or a scene beyond the Infinity Cache (C4, 10 M triangles: 1 562 vs 1 483)
-    // (profiles/r04_sweep_split_after_shader_diet.log).  That is the split to begin with; after every completed call it follows how
-    // full the tracer lanes were (er_stream_adapt: a scene of another kind that starves 13 tracers gets 12 after its first call).
-    // (textured materials started at 12 + 4 until their textures were fused / pre-powered / one-channel, er_render_begin: C5 without
-    // lights now 1 712 vs 1 640 at 12 + 4; a textured scene whose shading step is still too long for 13 tracers reads < 0.85 full lanes
-    // after its first call and gets 12)
-    s->stream_tracers = (lights_on || s->tri_count > 4000000u) ? 12 : 13;
-    // A workgroup that owns hardly more pixels than it has slots (an eighth of a 1080p frame: 1 012 pixels per CU) cannot fill 12 tracer
-    // waves -- a pixel's samples are one RNG stream, so pixels in flight are all the parallelism there is -- and runs faster as 9 tracer +
-    // 3 shader waves of 168 registers (the shading step then spills 34 registers instead of 111 and three shader waves serve what four
-    // did): 1.23 vs 1.35 ms per pass at 1/8 (1 012 pixels per CU); at 1/6 (1 350 pixels) 16 waves are ahead again, 1.43 vs 1.47 (profiles/r04_sweep_small_shares.log)
-    s->stream_waves = 16;
-    uint32_t small_tracers = 9;
-    {
-        const size_t px_per_cu = tiles * 64 / std::max<uint32_t>(1u, s->stream_blocks);
-        // (round 6, profiles/r06_ab_long_pixels_and_split.log: with the shading step as short as it has become two shader waves serve ten tracers where
-        // the slots are nearly all taken -- 1/8 ... 1/11 of the C2 frame 4.5 ... 1.5 % faster, C5's 1/8 share 1 ... 3 % -- and from 1/12 down 9 + 3 is ahead by 2 %)
-        small_tracers = px_per_cu > ER_STREAM_TEN_TRACERS_SHARE ? 10u : 9u;
-        if (px_per_cu <= ER_STREAM_SMALL_SHARE) { s->stream_waves = 12; s->stream_tracers = small_tracers; }
-        // the lane occupancy says something about the balance of the two roles only where pixels are plentiful: a share of a few
-        // pixels per slot cannot fill the lanes whatever the split (an eighth of a 1080p frame: 0.59 at the fastest split)
-        // (nor in the instrumented kernel of ER_FLAG_COUNTERS, whose slower tracer loop shifts the balance)
-        s->stream_adapt = px_per_cu >= 4u * ER_STREAM_SLOTS && !(flags & ER_FLAG_COUNTERS);
-        s->stream_keep = px_per_cu <= ER_STREAM_KEEP_SHARE;      // (er_stream.hip s_front)
-        s->stream_spec_form = px_per_cu <= ER_STREAM_SPEC_SHARE;      // few pixels per slot: slots fall free, speculative samples can use them (er_stream.hip)
-    }
-    if (const char* e = getenv("ER_STREAM_SPEC_FORM")) s->stream_spec_form = atoi(e) != 0;      // A/B knob
-    if (const char* e = getenv("ER_STREAM_KEEP")) s->stream_keep = atoi(e) != 0;                // A/B knob
-    if (const char* e = getenv("ER_STREAM_WAVES")) { s->stream_waves = atoi(e) == 12 ? 12 : 16; s->stream_tracers = s->stream_waves == 12 ? small_tracers : ((lights_on || s->tri_count > 4000000u) ? 12u : 13u); }   // A/B knob
-    if (const char* e = getenv("ER_STREAM_TRACERS")) { s->stream_tracers = (uint32_t)std::min(13, std::max(1, atoi(e))); s->stream_adapt = false; }   // tuning knob: fixed split
-    if (const char* e = getenv("ER_STREAM_ADAPT")) s->stream_adapt = atoi(e) != 0;
-}
+// Staging buffers of the asynchronous uploads of er_render_begin.  They live in er_render_begin_impl's frame, not in the stages',
+// until the stream has been synchronised at its end (HIP happens to make pageable host-to-device copies host-synchronous; this code
+// does not rely on it).
+struct BeginStaging {
+    ErBvhBuild bvh;
+    std::vector<ErTriIsect> isect;
+    std::vector<ErTriAttr> attr;
+    std::vector<float4> geom, mat_pre;
+    std::vector<DevTex> table;
+    std::vector<float> pool;
+    std::vector<DevFused> fused;
+    std::vector<uint32_t> guide, owned;
+    std::vector<int32_t> etex;      // ER_FLAG_MESH_LIGHTS: the textures that emit
+    StreamDeal deal;      // the owned share dealt to the CUs: what the schedule is chosen on, and what the streaming schedule starts with
+};
 
-static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
-    if (!s || !p) return fail(ER_ERR_INVALID_ARG, "er_render_begin: NULL argument");
-    std::lock_guard<std::mutex> lk(s->mtx);
-    uint32_t world = p->world ? p->world : 1;
+struct TexResult {      // what the scene descriptor needs of the texture stage
+    DevTex hdri{};
+    int buckets = 0;
+};
+
+// stage 1: arguments and device; the device's description comes back (its CU count is used by the schedules)
+int begin_check(const ErRenderParams* p, ErDeviceInfo& info) {
+    const uint32_t world = p->world ? p->world : 1;
     if (p->rank >= world) return fail(ER_ERR_INVALID_ARG, "er_render_begin: rank >= world");
     int ndev = er_device_count();
     if (ndev <= 0) return fail(ER_ERR_NO_DEVICE, "er_render_begin: no HIP device available (there is no CPU fallback)");
     if (p->device < 0 || p->device >= ndev) return fail(ER_ERR_NO_DEVICE, "er_render_begin: device ordinal out of range");
-    {
-        // the library carries gfx950 code objects only; launching on anything else faults inside the runtime
-        ErDeviceInfo info;
-        int irc = er_device_info(p->device, &info);
-        if (irc != ER_OK) return irc;
-        if (!info.compatible) return fail(ER_ERR_NO_DEVICE, std::string("er_render_begin: device arch '") + info.arch + "' is not gfx950");
-    }
+    // the library carries gfx950 code objects only; launching on anything else faults inside the runtime
+    int irc = er_device_info(p->device, &info);
+    if (irc != ER_OK) return irc;
+    if (!info.compatible) return fail(ER_ERR_NO_DEVICE, std::string("er_render_begin: device arch '") + info.arch + "' is not gfx950");
+    return ER_OK;
+}
+
+// ... the previous render's device state goes, the new one's stream and events are made
+int begin_open(ErScene* s, const ErRenderParams* p) {
     if (s->begun || s->stream) {
         (void)hipSetDevice(s->device);
         if (s->stream) (void)hipStreamSynchronize(s->stream);
@@ -196,32 +172,12 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     s->params = *p;
     s->ad_on = false;      // (adaptive sampling is set per render, after its er_render_begin)
     s->rendered = 0;
-    s->params.world = world;
+    s->params.world = p->world ? p->world : 1;
     if (s->params.max_bounces == 0) s->params.max_bounces = 5;   // the literal of reference src/kernel.cpp:508
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreate(&s->ev_start));
     HIP_TRY(hipEventCreate(&s->ev_stop));
-
-    // ---- acceleration structure: host binned-SAH build (default) or device linear-BVH build ----
-    // What the rest of this function needs from either builder:
-    size_t n = s->tri_count, n8_pieces = 0;
-    uint32_t bvh2_nodes = 0, wide_nodes = 0, wide_depth = 0, leaf_count = 0;
-    float bvh_lo[3] = {0, 0, 0}, bvh_hi[3] = {0, 0, 0}, lift_bound = 0;
-    double build_ms = 0;
-    bool built = false;
-    int rc;
-    EventPair ev;                       // destroyed on every return path
-    HIP_TRY(hipEventCreate(&ev.a));
-    HIP_TRY(hipEventCreate(&ev.b));
-    const hipEvent_t u0 = ev.a, u1 = ev.b;
-    // Staging buffers of the asynchronous uploads below.  They live until the stream has been synchronised at the
-    // end of this function (HIP happens to make pageable host-to-device copies host-synchronous; this code does
-    // not rely on it).
-    ErBvhBuild bvh;
-    std::vector<ErTriIsect> isect;
-    std::vector<ErTriAttr> attr;
-    std::vector<float4> geom;
     // Probe one kernel of every translation unit before the first launch: a library that carries no code object
     // this device can run (a stale or mis-targeted build) makes hipLaunchKernelGGL dereference a null function
     // inside the runtime (recorded in round 1: SIGSEGV under er_launch_setup after "No compatible code objects
@@ -233,17 +189,61 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
             return fail(ER_ERR_HIP, std::string("er_render_begin: libeleven_hip.so has no usable gfx950 code object for ") + (which ? which : "?") +
                                         " on this device (" + hipGetErrorString(pe) + "); rebuild with `make -C elevenrender_amd/csrc`");
     }
+    return ER_OK;
+}
+
+// stage 2, host builder: the triangle and attribute records in slot order, wide nodes and triangle records in ONE buffer, uploaded
+int accel_upload_host(ErScene* s, BeginStaging& B, const ErGpuBvhDevice& g) {
+    const ErBvhBuild& bvh = B.bvh;
+    std::vector<ErTriIsect>& isect = B.isect;
+    std::vector<ErTriAttr>& attr = B.attr;
+    const size_t n = s->tri_count, n8_pieces = g.n8_pieces;
+    int rc;
+    isect.resize(n + 1);      // +1: the wide traversal fetches triangles in pairs
+    attr.resize(n);
+    for (size_t slot = 0; slot < n; slot++) {
+        uint32_t id = bvh.slot_to_tri[slot];
+        const float* v = &s->vertices[(size_t)id * 9];
+        ErTriIsect& r = isect[slot];
+        memcpy(r.v0, v, 12); memcpy(r.v1, v + 3, 12); memcpy(r.v2, v + 6, 12);
+        r.tri_id = (int32_t)id;
+        r.lift = bvh.tri_lift[id];
+        r.sign = s->tangent_sign[id];
+        ErTriAttr& a = attr[slot];
+        memcpy(a.n, &s->normals[(size_t)id * 9], 36);
+        memcpy(a.t, &s->tangents[(size_t)id * 9], 36);
+        memcpy(a.uv, &s->uvs[(size_t)id * 6], 24);
+        a.material = s->material_id[id];
+        a.pad[0] = a.pad[1] = a.pad[2] = 0;
+    }
+    if ((rc = upload(s->d_nodes, bvh.nodes.data(), g.nodes_f4, s->stream)) != ER_OK) return rc;
+    memset(&isect[n], 0, sizeof(ErTriIsect));
+    // wide nodes and triangle records share ONE buffer: the wide traversal addresses both with a 32-bit
+    // offset in 16-byte units
+    B.geom.assign(g.geom_f4, make_float4(0, 0, 0, 0));
+    for (size_t k = 0; k < bvh.nodes8.size(); k++) memcpy(B.geom.data() + k * ER_NODE8_PIECES, &bvh.nodes8[k], sizeof(ErNode8));
+    memcpy(B.geom.data() + n8_pieces, isect.data(), (n + 1) * sizeof(ErTriIsect));
+    if ((rc = upload(s->d_nodes8, B.geom.data(), B.geom.size(), s->stream)) != ER_OK) return rc;
+    return upload(s->d_attr, attr.data(), g.attr_f4, s->stream);
+}
+
+// stage 2: the acceleration structure, by the device build or the host's binned-SAH build.  Either builder fills ONE description, `g`
+// (after a host build its three pointers stay null: the scene owns the buffers either way), ONE block of checks runs on it, and
+// s->accel.builder says who built.  `built_ev` is recorded when the tree is there and the uploads begin.
+int begin_accel(ErScene* s, BeginStaging& B, hipEvent_t built_ev, ErGpuBvhDevice& g) {
+    const uint32_t flags = s->params.flags;
+    const size_t n = s->tri_count;
+    bool built = false;
     // Which builder: the device build (er_gpu_build.hip: the host builder's binned SAH, level by level on the GPU -- the same tree in a
     // fraction of the time) unless the scene is small enough for the host to be done before the device has started, or the caller says so.
-    const bool force_dev = (p->flags & ER_FLAG_GPU_BUILD) || getenv("ER_GPU_BUILD");
-    const bool force_host = !force_dev && ((p->flags & ER_FLAG_HOST_BUILD) || getenv("ER_HOST_BUILD"));
+    const bool force_dev = (flags & ER_FLAG_GPU_BUILD) || getenv("ER_GPU_BUILD");
+    const bool force_host = !force_dev && ((flags & ER_FLAG_HOST_BUILD) || getenv("ER_HOST_BUILD"));
     uint32_t min_tris = ER_GPU_BUILD_MIN_TRIS;
     if (const char* e = getenv("ER_GPU_BUILD_MIN_TRIS")) min_tris = (uint32_t)std::max(0, atoi(e));
     if (!force_host && (force_dev || s->tri_count >= min_tris) && s->tri_count > ER_BVH_LEAF_MAX) {
         // whole structure on the device: tree, wide-node collapse, slot order, triangle records
         std::string why;
         ErGpuSceneArrays arrays{s->vertices.data(), s->normals.data(), s->tangents.data(), s->uvs.data(), s->tangent_sign.data(), s->material_id.data()};
-        ErGpuBvhDevice g;
         int brc = er_gpu_build_device(arrays, s->tri_count, s->device, &g, why);
         if (brc < 0 && force_dev) return fail(brc == -2 ? ER_ERR_OOM : ER_ERR_HIP, "er_render_begin: device BVH build: " + why);
         // What a default device build that did not deliver means: a DECLINE (> 0: too few triangles, a tree deeper than the
@@ -260,57 +260,37 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
             s->d_nodes.p = g.nodes; s->d_nodes.n = g.nodes_f4;
             s->d_nodes8.p = g.geom; s->d_nodes8.n = g.geom_f4;
             s->d_attr.p = g.attr; s->d_attr.n = g.attr_f4;
-            if (g.geom_f4 >= (1ull << 30)) return fail(ER_ERR_INVALID_ARG, "er_render_begin: geometry exceeds the 16 GB addressable by the wide traversal");
-            n8_pieces = g.n8_pieces;
-            bvh2_nodes = (uint32_t)(g.nodes_f4 / 4); wide_nodes = g.nodes8_count; wide_depth = g.max_depth8; leaf_count = g.leaf_count;
-            for (int a = 0; a < 3; a++) { bvh_lo[a] = g.lo[a]; bvh_hi[a] = g.hi[a]; }
-            lift_bound = g.lift_bound;
-            build_ms = g.build_ms;
             built = true;
-        }   // brc > 0: the device builder declined (tree too deep for the traversal stacks); brc < 0 without the flag: it failed -- host build
+        } else g = ErGpuBvhDevice{};
+        // brc > 0: the device builder declined (tree too deep for the traversal stacks); brc < 0 without the flag: it failed -- host build
     }
-    if (built) HIP_TRY(hipEventRecord(u0, s->stream));
     if (!built) {
         host_reserve((uint64_t)n * (sizeof(ErTriIsect) * 2 + sizeof(ErTriAttr) + 2 * sizeof(ErNode)));
-        er_build_bvh(s->vertices.data(), s->normals.data(), s->tri_count, 0, &bvh);
-        HIP_TRY(hipEventRecord(u0, s->stream));
-        if (bvh.max_depth > ER_BVH_MAX_DEPTH) return fail(ER_ERR_STATE, "er_render_begin: BVH deeper than the traversal stack");
-        if (bvh.max_depth8 > ER_STACK8) return fail(ER_ERR_STATE, "er_render_begin: wide BVH deeper than the traversal stack (ER_STACK8)");
-        isect.resize(n + 1);      // +1: the wide traversal fetches triangles in pairs
-        attr.resize(n);
-        for (size_t slot = 0; slot < n; slot++) {
-            uint32_t id = bvh.slot_to_tri[slot];
-            const float* v = &s->vertices[(size_t)id * 9];
-            ErTriIsect& r = isect[slot];
-            memcpy(r.v0, v, 12); memcpy(r.v1, v + 3, 12); memcpy(r.v2, v + 6, 12);
-            r.tri_id = (int32_t)id;
-            r.lift = bvh.tri_lift[id];
-            r.sign = s->tangent_sign[id];
-            ErTriAttr& a = attr[slot];
-            memcpy(a.n, &s->normals[(size_t)id * 9], 36);
-            memcpy(a.t, &s->tangents[(size_t)id * 9], 36);
-            memcpy(a.uv, &s->uvs[(size_t)id * 6], 24);
-            a.material = s->material_id[id];
-            a.pad[0] = a.pad[1] = a.pad[2] = 0;
-        }
-        if ((rc = upload(s->d_nodes, bvh.nodes.data(), bvh.nodes.size() * 4, s->stream)) != ER_OK) return rc;
-        memset(&isect[n], 0, sizeof(ErTriIsect));
-        // wide nodes and triangle records share ONE buffer: the wide traversal addresses both with a 32-bit
-        // offset in 16-byte units
-        n8_pieces = bvh.nodes8.size() * ER_NODE8_PIECES + 8;   // + padding: a step fetches 96 B from a node's start
-        geom.assign(n8_pieces + (n + 1) * 3, make_float4(0, 0, 0, 0));
-        for (size_t k = 0; k < bvh.nodes8.size(); k++) memcpy(geom.data() + k * ER_NODE8_PIECES, &bvh.nodes8[k], sizeof(ErNode8));
-        memcpy(geom.data() + n8_pieces, isect.data(), (n + 1) * sizeof(ErTriIsect));
-        if (geom.size() >= (1ull << 30)) return fail(ER_ERR_INVALID_ARG, "er_render_begin: geometry exceeds the 16 GB addressable by the wide traversal");
-        if ((rc = upload(s->d_nodes8, geom.data(), geom.size(), s->stream)) != ER_OK) return rc;
-        if ((rc = upload(s->d_attr, attr.data(), n * ER_ATTR_PIECES, s->stream)) != ER_OK) return rc;
-        bvh2_nodes = (uint32_t)bvh.nodes.size(); wide_nodes = (uint32_t)bvh.nodes8.size(); wide_depth = bvh.max_depth8; leaf_count = bvh.leaf_count;
-        for (int a = 0; a < 3; a++) { bvh_lo[a] = bvh.lo[a]; bvh_hi[a] = bvh.hi[a]; }
-        lift_bound = bvh.lift_bound;
-        build_ms = bvh.build_ms;
+        const ErBvhBuild& bvh = B.bvh;
+        er_build_bvh(s->vertices.data(), s->normals.data(), s->tri_count, 0, &B.bvh);
+        g.n8_pieces = bvh.nodes8.size() * ER_NODE8_PIECES + 8;   // + padding: a step fetches 96 B from a node's start
+        g.nodes_f4 = bvh.nodes.size() * 4; g.geom_f4 = g.n8_pieces + (n + 1) * 3; g.attr_f4 = n * ER_ATTR_PIECES;      // (n + 1: the wide traversal fetches triangles in pairs)
+        g.nodes8_count = (uint32_t)bvh.nodes8.size(); g.max_depth8 = bvh.max_depth8; g.max_depth2 = bvh.max_depth; g.leaf_count = bvh.leaf_count;
+        for (int a = 0; a < 3; a++) { g.lo[a] = bvh.lo[a]; g.hi[a] = bvh.hi[a]; }
+        g.lift_bound = bvh.lift_bound;
+        g.build_ms = bvh.build_ms;
     }
+    HIP_TRY(hipEventRecord(built_ev, s->stream));
+    // what the kernels are sized for, whoever built (the stream schedule's and the wavefront's spill regions hold ER_STACK8 levels of
+    // the wide tree per wave, the exact re-trace stacks ER_BVH_MAX_DEPTH of the binary one)
+    if (g.max_depth2 > ER_BVH_MAX_DEPTH) return fail(ER_ERR_STATE, "er_render_begin: BVH deeper than the traversal stack");
+    if (g.max_depth8 > ER_STACK8) return fail(ER_ERR_STATE, "er_render_begin: wide BVH deeper than the traversal stack (ER_STACK8)");
+    if (g.geom_f4 >= (1ull << 30)) return fail(ER_ERR_INVALID_ARG, "er_render_begin: geometry exceeds the 16 GB addressable by the wide traversal");
+    s->accel.builder = built ? 1u : 0u;
+    return built ? ER_OK : accel_upload_host(s, B, g);
+}
+
+// stage 3: materials, their precomputed constants, point lights
+int begin_materials(ErScene* s, BeginStaging& B) {
+    int rc;
     if ((rc = upload(s->d_materials, s->materials.data(), s->materials.size(), s->stream)) != ER_OK) return rc;
-    std::vector<float4> mat_pre(s->materials.size());
+    std::vector<float4>& mat_pre = B.mat_pre;
+    mat_pre.resize(s->materials.size());
     for (size_t i = 0; i < s->materials.size(); i++) {      // DevScene::mat_pre: the per-material constants of generate_hit_data and GTR1
         const ErMaterial& m = s->materials[i];
         const float a = 0.1f + m.clearcoat_gloss * (0.001f - 0.1f);      // lerpf(0.1f, 0.001f, clearcoatGloss), src/Math.hpp:38-41
@@ -319,10 +299,16 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     }
     if (getenv("ER_MAT_PRE_ON_DEVICE")) for (auto& v : mat_pre) v.w = 0.0f;      // (A/B and test knob: GTR1's logarithm on the device)
     if ((rc = upload(s->d_mat_pre, mat_pre.data(), mat_pre.size(), s->stream)) != ER_OK) return rc;
-    if ((rc = upload(s->d_lights, s->point_lights.data(), s->point_lights.size(), s->stream)) != ER_OK) return rc;
-    // point-light queries double the shadow records and the shadow queues of the wavefront schedule (er_wavefront.h)
-    const bool lights_on = (p->flags & ER_FLAG_POINT_LIGHTS) != 0 && !s->point_lights.empty();
+    return upload(s->d_lights, s->point_lights.data(), s->point_lights.size(), s->stream);
+}
 
+// stage 4: the texture pool.  Needs only the host scene; leaves the pool, the table, the fused records, the HDRI's CDF and its guide
+// on the device and the per-texture modes in s->tex_mode.
+int begin_textures(ErScene* s, BeginStaging& B, TexResult& out) {
+    int rc;
+    std::vector<DevTex>& table = B.table;
+    std::vector<float>& pool = B.pool;
+    std::vector<DevFused>& fused = B.fused;
     // textures: one float pool + a table
     // A texture that materials use ONLY for scalar channels -- opacity, roughness, metallic, transmission take `.x` of the fetched value
     // (src/kernel.cpp:100-150) -- is kept on the device with its first channel alone: a one-channel fetch returns that value in .x
@@ -340,8 +326,7 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     }
     const char* compact_knob = getenv("ER_TEX_COMPACT");      // (A/B and test knob: 0 = every texture as it came)
     const bool compact = !(compact_knob && atoi(compact_knob) == 0);
-    std::vector<DevTex> table(s->textures.size());
-    std::vector<float> pool;
+    table.resize(s->textures.size());
     const bool pow_on_host = !getenv("ER_MAT_PRE_ON_DEVICE");
     // mode per texture: 0 as it came, 1 first channel alone, 2 first channel alone to the power 2.2; the one-channel copies are made by a
     // few threads (C5: 8.4 M er_pow, ~0.2 s on one core) and appended in order
@@ -402,7 +387,7 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     // five floats (DevFused, er_device.h): one fetch, one cache line and one coordinate computation per hit instead of three.  The
     // texel values are what Texture::getValueFromCoordinates returns for each (src/Texture.cpp:172-200); unfiltered, roughness and
     // metallic are stored to the power 2.2 as above.  The textures themselves stay where they are for every other use.
-    std::vector<DevFused> fused(std::max<size_t>(1, s->materials.size()), DevFused{0, 0, 0, 0});
+    fused.assign(std::max<size_t>(1, s->materials.size()), DevFused{0, 0, 0, 0});
     const char* fuse_knob = getenv("ER_TEX_FUSE");      // (A/B knob; ER_TEX_COMPACT=0 = "every texture as it came" switches this off as well)
     if (compact && !(fuse_knob && atoi(fuse_knob) == 0)) {
         for (size_t m = 0; m < s->materials.size(); m++) {
@@ -437,217 +422,160 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     s->fused_any = false;
     for (const DevFused& f : fused) s->fused_any = s->fused_any || f.width > 0;
     if ((rc = upload(s->d_mat_fused, fused.data(), fused.size(), s->stream)) != ER_OK) return rc;
-    DevTex hd{s->hdri_tex.width, s->hdri_tex.height, s->hdri_tex.channels, s->hdri_tex.filter, (uint32_t)pool.size()};
+    out.hdri = DevTex{s->hdri_tex.width, s->hdri_tex.height, s->hdri_tex.channels, s->hdri_tex.filter, (uint32_t)pool.size()};
     pool.insert(pool.end(), s->hdri_tex.data.begin(), s->hdri_tex.data.end());
     if (pool.size() >= (1ull << 32)) return fail(ER_ERR_INVALID_ARG, "er_render_begin: texture pool exceeds 2^32 floats");
     if ((rc = upload(s->d_textures, table.data(), table.size(), s->stream)) != ER_OK) return rc;
     if ((rc = upload(s->d_tex_pool, pool.data(), pool.size(), s->stream)) != ER_OK) return rc;
     if ((rc = upload(s->d_cdf, s->hdri_cdf.data(), s->hdri_cdf.size(), s->stream)) != ER_OK) return rc;
-    std::vector<uint32_t> guide;
-    int buckets = er_build_cdf_guide(s->hdri_cdf.data(), s->hdri_tex.width * s->hdri_tex.height, guide);
-    if ((rc = upload(s->d_guide, guide.data(), guide.size(), s->stream)) != ER_OK) return rc;
-    // ER_FLAG_MESH_LIGHTS: the emitter table, built on the device from the placed triangle records (er_lights.hip).  An empty table
-    // leaves the render as it would be without the flag.
-    if (p->flags & ER_FLAG_MESH_LIGHTS) {
-        std::vector<int32_t> etex;
-        for (const ErMaterial& m : s->materials)
-            if (m.emission_tex >= 0 && (size_t)m.emission_tex < s->textures.size()) etex.push_back(m.emission_tex);
-        std::sort(etex.begin(), etex.end());
-        etex.erase(std::unique(etex.begin(), etex.end()), etex.end());
-        ScopedDevBuf<int32_t> d_etex;
-        if ((rc = upload(d_etex, etex.data(), etex.size(), s->stream)) != ER_OK) return rc;
-        float* tab = nullptr;
-        HIP_TRY(er_lights_build(s->d_nodes8.p + n8_pieces, s->d_attr.p, s->tri_count, s->d_materials.p, s->d_textures.p, s->d_tex_pool.p, d_etex.p,
-                                (uint32_t)etex.size(), (uint32_t)s->textures.size(), &tab, &s->light_emitters, &s->light_total, s->stream));
-        s->d_light_tab.p = tab;
-        s->d_light_tab.n = tab ? (size_t)s->tri_count + 2 * (size_t)s->light_emitters : 0;
-        if (lights_on && s->light_emitters > 0)
-            return fail(ER_ERR_INVALID_ARG, "er_render_begin: ER_FLAG_POINT_LIGHTS and ER_FLAG_MESH_LIGHTS on a scene with both point lights and "
-                                            "emissive triangles: both need the one light-query record per slot");
-    }
-    const bool mesh_on = s->light_emitters > 0;
-    // the point-light or the emitter query: a second shadow record per slot
-    const bool query_on = lights_on || mesh_on;
+    out.buckets = er_build_cdf_guide(s->hdri_cdf.data(), s->hdri_tex.width * s->hdri_tex.height, B.guide);
+    return upload(s->d_guide, B.guide.data(), B.guide.size(), s->stream);
+}
 
-    size_t npx = (size_t)s->x_res * s->y_res;
+// stage 5, ER_FLAG_MESH_LIGHTS: the emitter table, built on the device from the placed triangle records (er_lights.hip).  An empty
+// table leaves the render as it would be without the flag.
+int begin_emitters(ErScene* s, BeginStaging& B, size_t n8_pieces, bool point_lights_on) {
+    if (!(s->params.flags & ER_FLAG_MESH_LIGHTS)) return ER_OK;
+    int rc;
+    std::vector<int32_t>& etex = B.etex;
+    for (const ErMaterial& m : s->materials)
+        if (m.emission_tex >= 0 && (size_t)m.emission_tex < s->textures.size()) etex.push_back(m.emission_tex);
+    std::sort(etex.begin(), etex.end());
+    etex.erase(std::unique(etex.begin(), etex.end()), etex.end());
+    ScopedDevBuf<int32_t> d_etex;
+    if ((rc = upload(d_etex, etex.data(), etex.size(), s->stream)) != ER_OK) return rc;
+    float* tab = nullptr;
+    HIP_TRY(er_lights_build(s->d_nodes8.p + n8_pieces, s->d_attr.p, s->tri_count, s->d_materials.p, s->d_textures.p, s->d_tex_pool.p, d_etex.p,
+                            (uint32_t)etex.size(), (uint32_t)s->textures.size(), &tab, &s->light_emitters, &s->light_total, s->stream));
+    s->d_light_tab.p = tab;
+    s->d_light_tab.n = tab ? (size_t)s->tri_count + 2 * (size_t)s->light_emitters : 0;
+    if (point_lights_on && s->light_emitters > 0)
+        return fail(ER_ERR_INVALID_ARG, "er_render_begin: ER_FLAG_POINT_LIGHTS and ER_FLAG_MESH_LIGHTS on a scene with both point lights and "
+                                        "emissive triangles: both need the one light-query record per slot");
+    return ER_OK;
+}
+
+// stage 6: the planes, this rank's tiles, the counters ...
+int begin_planes(ErScene* s, BeginStaging& B) {
+    int rc;
+    const size_t npx = (size_t)s->x_res * s->y_res;
     if ((rc = upload(s->d_passes, nullptr, npx * ER_PASS_COUNT, s->stream)) != ER_OK) return rc;
     if ((rc = upload(s->d_samples, nullptr, npx, s->stream)) != ER_OK) return rc;
     if ((rc = upload(s->d_rng, nullptr, npx, s->stream)) != ER_OK) return rc;
-    std::vector<uint32_t> owned = s->tiles_of(s->params.rank, world);
-    if ((rc = upload(s->d_owned, owned.data(), owned.size(), s->stream)) != ER_OK) return rc;
+    B.owned = s->tiles_of(s->params.rank, s->params.world);
+    if ((rc = upload(s->d_owned, B.owned.data(), B.owned.size(), s->stream)) != ER_OK) return rc;
     if ((rc = upload(s->d_counters, nullptr, 1, s->stream)) != ER_OK) return rc;
     HIP_TRY(hipMemsetAsync(s->d_counters.p, 0, sizeof(DevCounters), s->stream));
-    // schedule: forced by a flag, else the streaming schedule unless this rank's share is beyond its pixel rings (see eleven_hip.h)
-    {
-        uint32_t forced = p->flags & (ER_FLAG_MEGAKERNEL | ER_FLAG_FUSED | ER_FLAG_WAVEFRONT | ER_FLAG_STREAM);
-        // (ER_FLAG_FUSED named round 1's lane-asynchronous single kernel, which the streaming schedule has overtaken at every frame size --
-        // C1 at 256 x 256: 1 186 against 849 Msamples/s, profiles/r05_schedules_small_frames.log -- and which round 5 removed: the flag
-        // is still accepted and means the streaming schedule)
-        if (forced == ER_FLAG_FUSED) forced = ER_FLAG_STREAM;
-        uint32_t sched = forced;
-        if (forced == 0) {
-            int cus = 1;
-            HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
-            cus = std::max(1, cus);
-            // beyond the streaming schedule's pixel rings -> wavefront.  Decided on the REAL deal of tiles to workgroups, not on an
-            // estimate of its largest share: the XCD-aware deal hands out whole super-tiles and can be less balanced than
-            // ceil(tiles / CUs) (near the limit the estimate chose ER_FLAG_STREAM and er_render_begin then failed
-            // with INVALID_ARG instead of taking the other schedule)
-            std::vector<uint32_t> deal;
-            const uint32_t most = er_stream_deal_tiles(owned.data(), (uint32_t)owned.size(), (s->x_res + ER_TILE - 1) / ER_TILE, (uint32_t)cus,
-                                                       stream_xcd_aware(owned.size(), (uint32_t)cus), deal);
-            // (and the streaming schedule carries a pixel as px | py << 16)
-            sched = ((size_t)most * 64u > ER_STREAM_MAX_RING || s->x_res > 65535u || s->y_res > 65535u) ? ER_FLAG_WAVEFRONT : ER_FLAG_STREAM;
-        }
-        else if (forced & (forced - 1)) return fail(ER_ERR_INVALID_ARG, "er_render_begin: more than one schedule flag");
-        s->params.flags = (s->params.flags & ~(uint32_t)(ER_FLAG_MEGAKERNEL | ER_FLAG_FUSED | ER_FLAG_WAVEFRONT | ER_FLAG_STREAM)) | sched;
-    }
-    if (s->params.flags & ER_FLAG_STREAM) {
-        // streaming schedule: one workgroup per CU with ER_STREAM_SLOTS slots of the wavefront schedule's records each
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, s->device));
-        s->stream_blocks = (uint32_t)prop.multiProcessorCount;
-        stream_choose_form(s, owned.size(), query_on, p->flags);
-        s->stream_tracers_start = s->stream_tracers; s->stream_low_streak = 0; s->stream_up_budget = 1; s->stream_readings = 0;
-        const size_t slots = (size_t)s->stream_blocks * ER_STREAM_SLOTS;
-        if ((rc = upload(s->d_wf4, nullptr, slots * er_stream_record_bytes(query_on) / sizeof(float4), s->stream)) != ER_OK) return rc;
-        if ((rc = upload(s->d_wf1, nullptr, 32, s->stream)) != ER_OK) return rc;       // [1] status word, [2..5] the tracers' lane occupancy, [6..23] start / end per XCD, [24..26] speculative samples started / right / wrong
-        if ((rc = upload(s->d_spill, nullptr, er_stream_spill_entries(s->stream_blocks), s->stream)) != ER_OK) return rc;
-        s->stream_ctl = s->d_wf1.p;
-        s->stream_lights = query_on;
-        HIP_TRY(hipMemsetAsync(s->stream_ctl, 0, 32 * sizeof(uint32_t), s->stream));
-        s->stream_spec[0] = s->stream_spec[1] = s->stream_spec[2] = 0;
-        // the workgroups' pixel rings: (pixel, samples left) entries, one per pixel of the workgroup's share
-        // (capacity rounded up to a power of two: positions are monotonic 32-bit counters and may wrap)
-        // (no minimum beyond one tile: a producer that comes round to a cell whose entry has not been read yet waits for its
-        // reader, er_ring.h -- round 2 relied on "a lap of >= 4096 cells takes longer than a read")
-        std::vector<uint32_t> deal;
-        const bool xcd_aware = stream_xcd_aware(owned.size(), s->stream_blocks);
-        const uint32_t tiles_x = (s->x_res + ER_TILE - 1) / ER_TILE;
-        uint32_t most = er_stream_deal_tiles(owned.data(), (uint32_t)owned.size(), tiles_x, s->stream_blocks, xcd_aware, deal);
-        s->stream_deal_off = 0; s->stream_deal_n = (uint32_t)deal.size();
-        s->stream_deal_alt_off = 0; s->stream_deal_alt_n = 0;
-        s->stream_xcd_spread = -1.0;
-        // Larger screen regions per XCD are faster where a frame's cost is even and slower where it is not (er_stream.h), and only the run
-        // can tell which.  With the knob unset a render STARTS on the default deal -- it spreads any frame's cost over the XCDs -- and keeps
-        // the deal of ER_STREAM_SUPER_TILE_LARGE beside it in d_deal; during the first call the kernel adds every finished path's length to
-        // its tile's sum (DevScene::tile_cost: counted work, not a measured time), and er_stream_adapt takes the large regions, for good,
-        // if under THAT deal the XCDs' shares of the counted work are within ER_STREAM_COST_SPREAD_MAX of each other.  (Round 4 started
-        // on the large deal and fell back on the XCDs' measured finish times: an uneven frame paid 8-18 % for its first call, and the
-        // decision -- and the test of it -- hung on clocks.)
-        const char* adapt_knob = getenv("ER_STREAM_ADAPT");
-        s->stream_deal_pending = false;
-        s->stream_deal_large.clear();
-        s->d_tile_cost.release();
-        if (xcd_aware && s->stream_blocks % 8u == 0u && owned.size() * 64 / s->stream_blocks >= ER_STREAM_SLOTS * 3u / 2u && !(p->flags & ER_FLAG_COUNTERS) &&      // (a half / a quarter of a 1080p frame: +1.2 % / +0.7 %)
-            !getenv("ER_STREAM_SUPER_TILE") && !(adapt_knob && atoi(adapt_knob) == 0)) {
-            std::vector<uint32_t> large;
-            const uint32_t most_large = er_stream_deal_tiles(owned.data(), (uint32_t)owned.size(), tiles_x, s->stream_blocks, xcd_aware, large, ER_STREAM_SUPER_TILE_LARGE);
-            if ((size_t)most_large * 64u <= ER_STREAM_MAX_RING) {      // (levelled, the two deals have the same largest share; never let the optional one fail the call)
-                s->stream_deal_alt_off = (uint32_t)deal.size(); s->stream_deal_alt_n = (uint32_t)large.size();
-                deal.insert(deal.end(), large.begin(), large.end());
-                most = std::max(most, most_large);
-                s->stream_deal_large.swap(large);
-                const size_t n_tiles = (size_t)tiles_x * ((s->y_res + ER_TILE - 1) / ER_TILE);
-                if ((rc = upload(s->d_tile_cost, nullptr, n_tiles, s->stream)) != ER_OK) return rc;
-                HIP_TRY(hipMemsetAsync(s->d_tile_cost.p, 0, n_tiles * sizeof(uint32_t), s->stream));
-                s->stream_deal_pending = true;
-            }
-        }
-        if ((rc = upload(s->d_px_draws, nullptr, npx, s->stream)) != ER_OK) return rc;
-        HIP_TRY(hipMemsetAsync(s->d_px_draws.p, 0, npx * sizeof(uint32_t), s->stream));
-        if ((rc = upload(s->d_deal, deal.data(), deal.size(), s->stream)) != ER_OK) return rc;
-        HIP_TRY(hipStreamSynchronize(s->stream));          // (`deal` goes out of scope)
-        if (s->x_res > 65535u || s->y_res > 65535u)
-            return fail(ER_ERR_INVALID_ARG, "er_render_begin: ER_FLAG_STREAM carries a pixel as x | y << 16: frames up to 65535 x 65535; use ER_FLAG_WAVEFRONT (the automatic choice does)");
-        s->stream_ring_cap = 64u;
-        while (s->stream_ring_cap < most * 64u) s->stream_ring_cap <<= 1;
-        if (s->stream_ring_cap > ER_STREAM_MAX_RING)
-            return fail(ER_ERR_INVALID_ARG, "er_render_begin: ER_FLAG_STREAM serves at most " + std::to_string((size_t)ER_STREAM_MAX_RING * s->stream_blocks) +
-                                                " owned pixels per rank; use ER_FLAG_WAVEFRONT (the automatic choice does)");
-        if ((rc = upload(s->d_ticket, nullptr, (size_t)s->stream_blocks * (size_t)s->stream_ring_cap * 2, s->stream)) != ER_OK) return rc;
-        s->wf.clear();
-    } else if (s->params.flags & ER_FLAG_WAVEFRONT) {
-        // wavefront path state: one slot per owned pixel lane.
-        // SLOT POOLS: the owned tiles are dealt round-robin to `pools` independent path pools, each with its own
-        // queues and counters and its own HIP stream.  A ray is a sequential chain of dependent fetches, so every
-        // trace launch ends in a tail in which the last long rays keep a few lanes busy while the chip idles
-        // (measured: 29 % of all lane slots fall after the queue has run dry, at 19 % lane occupancy); the launches
-        // of one pool fill the tails of the others.  Pools never exchange data (disjoint pixels), so the planes
-        // do not depend on their number.  Measured on C2: 1 pool 901, 2 pools 959, 3 pools 969, 4 pools 947.
-        uint32_t pools = 3;
-        if (const char* e = getenv("ER_WF_POOLS")) pools = (uint32_t)std::min(8, std::max(1, atoi(e)));   // tuning knob
-        pools = std::min<uint32_t>(pools, std::max<uint32_t>(1u, (uint32_t)owned.size()));
-        const size_t pool_tiles = (owned.size() + pools - 1) / pools;
-        const size_t qcap = pool_tiles * 64;          // queue capacity of one pool
-        size_t slots = owned.size() * 64;
-        const size_t sh = query_on ? 2 : 1;           // shadow records per slot: [slot] HDRI query, [slot + slots] point light / emitter
-        const size_t qs_cap = qcap * sh;              // shadow-queue capacity of one pool
-        const size_t q_words = 2 * qcap + 2 * qs_cap; // two closest + two shadow queues per pool
-        if ((rc = upload(s->d_wf4, nullptr, slots * (7 + 4 * sh), s->stream)) != ER_OK) return rc;
-        if ((rc = upload(s->d_wf1, nullptr, slots * (3 + 3 * sh) + q_words * pools + (size_t)WF_COUNTS * pools, s->stream)) != ER_OK) return rc;
-        WfState W{};
-        float4* f = s->d_wf4.p;
-        W.ray_o = f; W.ray_d = f + slots; W.light = f + 2 * slots; W.reduc = f + 3 * slots;
-        W.aov_n = f + 4 * slots; W.aov_t = f + 5 * slots; W.aov_b = f + 6 * slots;
-        W.sh_o = f + 7 * slots; W.sh_d = W.sh_o + sh * slots; W.c_vis = W.sh_d + sh * slots; W.c_occ = W.c_vis + sh * slots;
-        uint32_t* u = s->d_wf1.p;
-        W.hit = (int*)u; W.left = u + slots; W.hit2 = (int*)(u + 2 * slots);
-        W.occluded = (int*)(u + 3 * slots); W.occ_a = W.occluded + sh * slots; W.occ_b = W.occ_a + sh * slots;
-        uint32_t* qbase = u + (3 + 3 * sh) * slots;
-        uint32_t* cbase = qbase + q_words * pools;
-        W.pools = pools;
-        W.slots = (uint32_t)slots;
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, s->device));
-        uint32_t cus = (uint32_t)prop.multiProcessorCount;
-        // persistent waves per CU, tuned together with the pools (the launches of different pools share the CUs):
-        // trace 8/10/12/14/16 -> 1016/1046/1043/1022/1042 Msamples/s at shade 5; shade 4/5/6/7 -> 1019/1051/1012/987
-        s->trace_blocks = cus * 12;
-        s->shade_blocks = cus * 5;
-        if (const char* e = getenv("ER_TRACE_WAVES_PER_CU")) s->trace_blocks = cus * (uint32_t)std::max(1, atoi(e));   // tuning knob
-        if (const char* e = getenv("ER_SHADE_WAVES_PER_CU")) s->shade_blocks = cus * (uint32_t)std::max(1, atoi(e));
-        // (uint2 entries: the trace waves' stack levels beyond the LDS ones, then the shade waves' exact re-trace stacks, two ints per entry)
-        const size_t trace_spill = (size_t)s->trace_blocks * ER_STACK8 * 64;
-        const size_t spill_per_pool = trace_spill + (size_t)s->shade_blocks * ER_BVH_MAX_DEPTH * 32;
-        if ((rc = upload(s->d_spill, nullptr, spill_per_pool * pools, s->stream)) != ER_OK) return rc;
-        s->wf.clear();
-        for (uint32_t p2 = 0; p2 < pools; p2++) {
-            W.pool = p2;
-            uint32_t* q = qbase + (size_t)p2 * q_words;
-            W.q[0] = q; W.q[1] = q + qcap; W.qs[0] = q + 2 * qcap; W.qs[1] = q + 2 * qcap + qs_cap;
-            W.counts = cbase + (size_t)p2 * WF_COUNTS;
-            W.spill = s->d_spill.p + (size_t)p2 * spill_per_pool;
-            W.shade_stack = (int*)(W.spill + trace_spill);
-            s->wf.push_back(W);
-        }
-        for (uint32_t p2 = 1; p2 < pools; p2++) {
-            hipStream_t st;
-            HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-            s->pool_streams.push_back(st);
-        }
-        for (uint32_t p2 = 0; p2 < pools; p2++) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            s->pool_events.push_back(e);
-        }
-    }
-    HIP_TRY(hipEventRecord(u1, s->stream));
+    return ER_OK;
+}
 
+// ... and the schedule (into s->params.flags): forced by a flag, else the streaming schedule unless this rank's share is beyond its
+// pixel rings (see eleven_hip.h).  B.deal is made here for the streaming schedule to start with.
+int begin_choose_schedule(ErScene* s, BeginStaging& B, uint32_t cus) {
+    const uint32_t all = ER_FLAG_MEGAKERNEL | ER_FLAG_FUSED | ER_FLAG_WAVEFRONT | ER_FLAG_STREAM;
+    uint32_t forced = s->params.flags & all;
+    // (ER_FLAG_FUSED named round 1's lane-asynchronous single kernel, which the streaming schedule has overtaken at every frame size --
+    // C1 at 256 x 256: 1 186 against 849 Msamples/s, profiles/r05_schedules_small_frames.log -- and which round 5 removed: the flag
+    // is still accepted and means the streaming schedule)
+    if (forced == ER_FLAG_FUSED) forced = ER_FLAG_STREAM;
+    if (forced & (forced - 1)) return fail(ER_ERR_INVALID_ARG, "er_render_begin: more than one schedule flag");
+    uint32_t sched = forced;
+    if (forced == 0 || forced == ER_FLAG_STREAM) B.deal = stream_deal_owned(B.owned, s->tiles_x(), cus);
+    if (forced == 0) {
+        // beyond the streaming schedule's pixel rings -> wavefront.  Decided on the REAL deal of tiles to workgroups, not on an
+        // estimate of its largest share: the XCD-aware deal hands out whole super-tiles and can be less balanced than
+        // ceil(tiles / CUs) (near the limit the estimate chose ER_FLAG_STREAM and er_render_begin then failed
+        // with INVALID_ARG instead of taking the other schedule)
+        // (and the streaming schedule carries a pixel as px | py << 16)
+        sched = ((size_t)B.deal.most * 64u > ER_STREAM_MAX_RING || s->x_res > 65535u || s->y_res > 65535u) ? ER_FLAG_WAVEFRONT : ER_FLAG_STREAM;
+    }
+    s->params.flags = (s->params.flags & ~all) | sched;
+    return ER_OK;
+}
+
+// stage 7, ER_FLAG_WAVEFRONT (the streaming schedule's: stream_begin, er_stream_host.cpp)
+int begin_wavefront(ErScene* s, const std::vector<uint32_t>& owned, uint32_t cus, bool query_on) {
+    int rc;
+    // wavefront path state: one slot per owned pixel lane.
+    // SLOT POOLS: the owned tiles are dealt round-robin to `pools` independent path pools, each with its own
+    // queues and counters and its own HIP stream.  A ray is a sequential chain of dependent fetches, so every
+    // trace launch ends in a tail in which the last long rays keep a few lanes busy while the chip idles
+    // (measured: 29 % of all lane slots fall after the queue has run dry, at 19 % lane occupancy); the launches
+    // of one pool fill the tails of the others.  Pools never exchange data (disjoint pixels), so the planes
+    // do not depend on their number.  Measured on C2: 1 pool 901, 2 pools 959, 3 pools 969, 4 pools 947.
+    uint32_t pools = 3;
+    if (const char* e = getenv("ER_WF_POOLS")) pools = (uint32_t)std::min(8, std::max(1, atoi(e)));   // tuning knob
+    pools = std::min<uint32_t>(pools, std::max<uint32_t>(1u, (uint32_t)owned.size()));
+    const size_t pool_tiles = (owned.size() + pools - 1) / pools;
+    const size_t qcap = pool_tiles * 64;          // queue capacity of one pool
+    size_t slots = owned.size() * 64;
+    const size_t sh = query_on ? 2 : 1;           // shadow records per slot: [slot] HDRI query, [slot + slots] point light / emitter
+    const size_t qs_cap = qcap * sh;              // shadow-queue capacity of one pool
+    const size_t q_words = 2 * qcap + 2 * qs_cap; // two closest + two shadow queues per pool
+    if ((rc = upload(s->d_wf4, nullptr, slots * (7 + 4 * sh), s->stream)) != ER_OK) return rc;
+    if ((rc = upload(s->d_wf1, nullptr, slots * (3 + 3 * sh) + q_words * pools + (size_t)WF_COUNTS * pools, s->stream)) != ER_OK) return rc;
+    WfState W{};
+    float4* f = s->d_wf4.p;
+    W.ray_o = f; W.ray_d = f + slots; W.light = f + 2 * slots; W.reduc = f + 3 * slots;
+    W.aov_n = f + 4 * slots; W.aov_t = f + 5 * slots; W.aov_b = f + 6 * slots;
+    W.sh_o = f + 7 * slots; W.sh_d = W.sh_o + sh * slots; W.c_vis = W.sh_d + sh * slots; W.c_occ = W.c_vis + sh * slots;
+    uint32_t* u = s->d_wf1.p;
+    W.hit = (int*)u; W.left = u + slots; W.hit2 = (int*)(u + 2 * slots);
+    W.occluded = (int*)(u + 3 * slots); W.occ_a = W.occluded + sh * slots; W.occ_b = W.occ_a + sh * slots;
+    uint32_t* qbase = u + (3 + 3 * sh) * slots;
+    uint32_t* cbase = qbase + q_words * pools;
+    W.pools = pools;
+    W.slots = (uint32_t)slots;
+    // persistent waves per CU, tuned together with the pools (the launches of different pools share the CUs):
+    // trace 8/10/12/14/16 -> 1016/1046/1043/1022/1042 Msamples/s at shade 5; shade 4/5/6/7 -> 1019/1051/1012/987
+    s->trace_blocks = cus * 12;
+    s->shade_blocks = cus * 5;
+    if (const char* e = getenv("ER_TRACE_WAVES_PER_CU")) s->trace_blocks = cus * (uint32_t)std::max(1, atoi(e));   // tuning knob
+    if (const char* e = getenv("ER_SHADE_WAVES_PER_CU")) s->shade_blocks = cus * (uint32_t)std::max(1, atoi(e));
+    // (uint2 entries: the trace waves' stack levels beyond the LDS ones, then the shade waves' exact re-trace stacks, two ints per entry)
+    const size_t trace_spill = (size_t)s->trace_blocks * ER_STACK8 * 64;
+    const size_t spill_per_pool = trace_spill + (size_t)s->shade_blocks * ER_BVH_MAX_DEPTH * 32;
+    if ((rc = upload(s->d_spill, nullptr, spill_per_pool * pools, s->stream)) != ER_OK) return rc;
+    s->wf.clear();
+    for (uint32_t p2 = 0; p2 < pools; p2++) {
+        W.pool = p2;
+        uint32_t* q = qbase + (size_t)p2 * q_words;
+        W.q[0] = q; W.q[1] = q + qcap; W.qs[0] = q + 2 * qcap; W.qs[1] = q + 2 * qcap + qs_cap;
+        W.counts = cbase + (size_t)p2 * WF_COUNTS;
+        W.spill = s->d_spill.p + (size_t)p2 * spill_per_pool;
+        W.shade_stack = (int*)(W.spill + trace_spill);
+        s->wf.push_back(W);
+    }
+    for (uint32_t p2 = 1; p2 < pools; p2++) {
+        hipStream_t st;
+        HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        s->pool_streams.push_back(st);
+    }
+    for (uint32_t p2 = 0; p2 < pools; p2++) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        s->pool_events.push_back(e);
+    }
+    return ER_OK;
+}
+
+// stage 8: the scene descriptor, on the host and on the device
+int begin_descriptor(ErScene* s, const ErGpuBvhDevice& g, const TexResult& tex, uint32_t owned_tiles) {
+    const float lift_bound = g.lift_bound;
     float scene_scale = 0;
-    for (int a = 0; a < 3; a++) scene_scale = std::max(scene_scale, std::max(std::fabs(bvh_lo[a]), std::fabs(bvh_hi[a])));
+    for (int a = 0; a < 3; a++) scene_scale = std::max(scene_scale, std::max(std::fabs(g.lo[a]), std::fabs(g.hi[a])));
     scene_scale = std::max(scene_scale, std::max(std::fabs(s->camera.position.x), std::max(std::fabs(s->camera.position.y), std::fabs(s->camera.position.z))));
 
     DevScene& D = s->dev;
     memset(&D, 0, sizeof(D));
     D.nodes = s->d_nodes.p;
     D.nodes8 = s->d_nodes8.p;
-    D.tri_isect = s->d_nodes8.p + n8_pieces;
-    D.tri_base_pieces = (uint32_t)n8_pieces;
+    D.tri_isect = s->d_nodes8.p + g.n8_pieces;
+    D.tri_base_pieces = (uint32_t)g.n8_pieces;
     D.tri_attr = s->d_attr.p;
     D.tri_count = s->tri_count;
-    D.node_count = bvh2_nodes;
-    D.node8_count = wide_nodes;
+    D.node_count = (uint32_t)(g.nodes_f4 / 4);
+    D.node8_count = g.nodes8_count;
     D.prune_margin = lift_bound + 1e-5f * scene_scale;
     D.max_lift = lift_bound;
     D.scene_scale = scene_scale;
@@ -657,20 +585,20 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     D.tex_pool = s->d_tex_pool.p;
     D.mat_fused = s->d_mat_fused.p;
     D.fused_any = s->fused_any ? 1u : 0u;
-    D.hdri_tex = hd;
+    D.hdri_tex = tex.hdri;
     D.hdri_cdf = s->d_cdf.p;
     D.hdri_guide = s->d_guide.p;
-    D.hdri_buckets = buckets;
+    D.hdri_buckets = tex.buckets;
     D.hdri_radiance_sum = s->hdri_radiance_sum;
     D.cam = s->camera;
     D.x_res = s->x_res;
     D.y_res = s->y_res;
-    D.tiles_x = (s->x_res + ER_TILE - 1) / ER_TILE;
-    D.tiles_y = (s->y_res + ER_TILE - 1) / ER_TILE;
+    D.tiles_x = s->tiles_x();
+    D.tiles_y = s->tiles_y();
     D.max_bounces = s->params.max_bounces;
     {   // power-of-two sides everywhere: texture coordinates wrap with a mask instead of a signed division (er_device.h wrap_abs)
         auto pow2 = [](int32_t v) { return v > 0 && (v & (v - 1)) == 0; };
-        bool all = pow2(hd.width) && pow2(hd.height);
+        bool all = pow2(tex.hdri.width) && pow2(tex.hdri.height);
         for (const HostTex& t : s->textures) all = all && pow2(t.width) && pow2(t.height);
         D.tex_pow2 = all ? 1u : 0u;
         if (const char* e = getenv("ER_TEX_POW2")) D.tex_pow2 = (atoi(e) != 0 && all) ? 1u : 0u;      // A/B knob: 0 = always the division
@@ -678,7 +606,7 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     D.ext_flags = s->params.flags & (ER_FLAG_POINT_LIGHTS | ER_FLAG_MIS);
     D.lights = s->d_lights.p;
     D.light_count = (uint32_t)s->point_lights.size();
-    if (mesh_on) {      // (the words of the point lights, which this render does not sample: er_device.h)
+    if (s->light_emitters > 0) {      // (the words of the point lights, which this render does not sample: er_device.h)
         D.ext_flags = (D.ext_flags & ~(uint32_t)ER_FLAG_POINT_LIGHTS) | ER_FLAG_MESH_LIGHTS;
         D.mesh_lights = s->d_light_tab.p;
         D.emitter_count = s->light_emitters;
@@ -687,138 +615,147 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     D.samples = s->d_samples.p;
     D.rng = s->d_rng.p;
     D.owned_tiles = s->d_owned.p;
-    D.owned_tile_count = (uint32_t)owned.size();
+    D.owned_tile_count = owned_tiles;
     D.counters = s->d_counters.p;
-    D.tile_cost = ((s->params.flags & ER_FLAG_STREAM) && s->stream_deal_pending) ? s->d_tile_cost.p : nullptr;
-    D.px_draws = (s->params.flags & ER_FLAG_STREAM) ? s->d_px_draws.p : nullptr;
+    D.tile_cost = ((s->params.flags & ER_FLAG_STREAM) && s->st.deal_pending) ? s->st.d_tile_cost.p : nullptr;
+    D.px_draws = (s->params.flags & ER_FLAG_STREAM) ? s->st.d_px_draws.p : nullptr;
     {   // the camera's rotation sines / cosines, once, with the functions the device would call (er_math.h: one implementation for both sides)
         const erd::CamTrig t = erd::camera_trig(D.cam);
         D.cam_cx = t.cx; D.cam_sx = t.sx; D.cam_cy = t.cy; D.cam_sy = t.sy; D.cam_cz = t.cz; D.cam_sz = t.sz;
         D.cam_trig_valid = getenv("ER_CAM_TRIG_ON_DEVICE") ? 0u : 1u;      // (A/B and test knob: 1 = use the host's values)
     }
-    if ((rc = upload(s->d_dev, &D, 1, s->stream)) != ER_OK) return rc;
+    return upload(s->d_dev, &D, 1, s->stream);
+}
 
-    er_launch_setup(D, s->stream);
+}  // namespace
+
+static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
+    if (!s || !p) return fail(ER_ERR_INVALID_ARG, "er_render_begin: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    int rc;
+    ErDeviceInfo info;
+    if ((rc = begin_check(p, info)) != ER_OK) return rc;
+    if ((rc = begin_open(s, p)) != ER_OK) return rc;
+    const uint32_t cus = std::max(1u, info.compute_units);
+    EventPair ev;                       // (upload time: from the tree being there to the last upload enqueued) destroyed on every return path
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+    BeginStaging B;                     // outlives the hipStreamSynchronize below
+    ErGpuBvhDevice g;
+    TexResult tex;
+    if ((rc = begin_accel(s, B, ev.a, g)) != ER_OK) return rc;
+    if ((rc = begin_materials(s, B)) != ER_OK) return rc;
+    // point-light queries double the shadow records and the shadow queues of the wavefront schedule (er_wavefront.h)
+    const bool lights_on = (p->flags & ER_FLAG_POINT_LIGHTS) != 0 && !s->point_lights.empty();
+    if ((rc = begin_textures(s, B, tex)) != ER_OK) return rc;
+    if ((rc = begin_emitters(s, B, g.n8_pieces, lights_on)) != ER_OK) return rc;
+    // the point-light or the emitter query: a second shadow record per slot
+    const bool query_on = lights_on || s->light_emitters > 0;
+    if ((rc = begin_planes(s, B)) != ER_OK) return rc;
+    if ((rc = begin_choose_schedule(s, B, cus)) != ER_OK) return rc;
+    if (s->params.flags & ER_FLAG_STREAM) rc = stream_begin(s, B.owned, B.deal, cus, query_on);
+    else if (s->params.flags & ER_FLAG_WAVEFRONT) rc = begin_wavefront(s, B.owned, cus, query_on);
+    if (rc != ER_OK) return rc;
+    HIP_TRY(hipEventRecord(ev.b, s->stream));
+    if ((rc = begin_descriptor(s, g, tex, (uint32_t)B.owned.size())) != ER_OK) return rc;
+
+    er_launch_setup(s->dev, s->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s->stream));
     float up_ms = 0;
-    (void)hipEventElapsedTime(&up_ms, u0, u1);
+    (void)hipEventElapsedTime(&up_ms, ev.a, ev.b);
 
-    s->accel.node_count = wide_nodes;
+    s->accel.node_count = g.nodes8_count;
     s->accel.node_bytes = sizeof(ErNode8);
-    s->accel.max_depth = wide_depth;
-    s->accel.leaf_count = leaf_count;
+    s->accel.max_depth = g.max_depth8;
+    s->accel.leaf_count = g.leaf_count;
     s->accel.tri_record_bytes = sizeof(ErTriIsect);
-    s->accel.build_ms = (float)build_ms;
+    s->accel.build_ms = (float)g.build_ms;
     s->accel.upload_ms = up_ms;
-    s->accel.lift_bound = lift_bound;
-    s->accel.builder = built ? 1u : 0u;
+    s->accel.lift_bound = g.lift_bound;
     s->begun = true;
     return ER_OK;
 }
 
-static void er_stream_adapt(ErScene* s);
-
-// n more samples to every active tile (all owned tiles unless an adaptive render has stopped some), enqueued on the scene's stream;
-// the caller holds s->mtx.  The streaming kernel is handed the active tiles through its deal (d_deal), the wavefront and megakernel
-// schedules through the tile list of the scene descriptor they are launched with.
-static int enqueue_samples(ErScene* s, uint32_t n) {
-    const DevScene& D = s->ad_on ? s->ad_dev : s->dev;
-    const bool count = (s->params.flags & ER_FLAG_COUNTERS) != 0;
-    const bool single = (s->params.flags & (ER_FLAG_MEGAKERNEL | ER_FLAG_STREAM)) != 0;
-    if (single && (s->params.flags & ER_FLAG_PROFILE) && n > 0) {
-        while (s->prof_events.size() < s->prof_used + 3) {
+// n more samples of the wavefront schedule: trace and shade launches of every slot pool, on the pools' streams
+static int wavefront_enqueue(ErScene* s, const DevScene& D, uint32_t n, bool count) {
+    // a path takes at most max_bounces ray steps plus one finalize-only step
+    const uint32_t iters = n * (s->params.max_bounces + 1);
+    const uint32_t pools = (uint32_t)s->wf.size();
+    const bool prof = (s->params.flags & ER_FLAG_PROFILE) != 0;
+    if (prof) {
+        const size_t need = s->prof_used / 3 + (size_t)iters * pools;      // launches profiled since the last er_wait
+        while (s->prof_events.size() < 3 * need) {
             hipEvent_t e;
             HIP_TRY(hipEventCreate(&e));
             s->prof_events.push_back(e);
         }
-        HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], s->stream));
-    }
-    if (s->params.flags & ER_FLAG_STREAM) {
-        auto launch = [&](uint32_t k) -> int {
-            HIP_TRY(hipMemsetAsync(s->stream_ctl + 2, 0, 30 * sizeof(uint32_t), s->stream));      // the call's lane-occupancy counts, its end per XCD, its speculation counts ...
-            HIP_TRY(hipMemsetAsync(s->stream_ctl + 6, 0xFF, 2 * sizeof(uint32_t), s->stream));    // ... and its start (a minimum)
-            if (k > 0) s->stream_launches++;
-            er_launch_stream(s->dev, s->d_dev.p, s->d_wf4.p, s->stream_blocks * ER_STREAM_SLOTS, s->stream_lights, s->d_spill.p, s->d_deal.p + s->stream_deal_off, s->stream_deal_n, s->d_ticket.p, s->stream_ring_cap, s->stream_ctl + 1, k, count,
-                             s->stream_blocks, s->stream_tracers, s->stream_waves, s->stream_spec_form, s->stream_keep, s->stream);
-            return ER_OK;
-        };
-        // Round 6: a render that is ONE call must get the deal its frame deserves too.  While the deal is undecided, the first call's
-        // first sample is a launch of its own: the kernel counts that pass's path lengths per tile (a count of work, the same on every
-        // run), the library decides -- and stops the counting -- and the other n - 1 samples run on the deal decided.  Until round 6 the
-        // decision came after the first CALL, so a host that issued one er_render_samples(256) never left the default deal (C2 -1.5 ... -4 %,
-        // C4 -3 ... -5.7 %) and `bench.py --warmup 0` measured another kernel configuration than `--warmup 5`.  Cost: one more launch per
-        // render (~0.8 ms) and a host wait of one sample pass inside this call, once; the image does not depend on the deal.
-        static const bool split_first = [] { const char* e = getenv("ER_STREAM_SPLIT_FIRST"); return !(e && atoi(e) == 0); }();      // (A/B knob)
-        if (s->stream_deal_pending && n >= 2u && split_first) {
-            int rc = launch(1u);
-            if (rc != ER_OK) return rc;
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(s->stream));
-            if ((rc = er_scene_stream_status(s, "er_render_samples")) != ER_OK) return rc;
-            s->stream_probe_launch = true;      // (a one-pass launch is no reading of the tracer lanes' occupancy: only the deal is decided on it)
-            er_stream_adapt(s);
-            s->stream_probe_launch = false;
-            n -= 1u;
+        if (s->d_ray_log.n < need) {
+            // grow, keeping what earlier calls of this timing window logged (they are still in flight or done)
+            DevBuf<uint32_t> bigger;
+            int rc2 = upload(bigger, nullptr, need * 2, s->stream);
+            if (rc2 != ER_OK) return rc2;
+            if (s->d_ray_log.p && s->prof_used) {
+                HIP_TRY(hipStreamSynchronize(s->stream));
+                HIP_TRY(hipMemcpy(bigger.p, s->d_ray_log.p, (s->prof_used / 3) * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+            }
+            s->d_ray_log.release();
+            s->d_ray_log = bigger;
         }
-        int rc = launch(n);
-        if (rc != ER_OK) return rc;
-    } else if (s->params.flags & ER_FLAG_MEGAKERNEL) {
-        er_launch_render(D, n, count, s->stream);
     }
-    if (single && (s->params.flags & ER_FLAG_PROFILE) && n > 0) {
-        HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], s->stream));
-        HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], s->stream));   // (trace, shade) triple: shade = 0
+    // fork: the pool streams start after everything already enqueued on the scene's stream
+    if (pools > 1) {
+        HIP_TRY(hipEventRecord(s->pool_events[0], s->stream));
+        for (uint32_t p = 1; p < pools; p++) HIP_TRY(hipStreamWaitEvent(s->pool_streams[p - 1], s->pool_events[0], 0));
     }
-    if (!single && n > 0) {
-        // a path takes at most max_bounces ray steps plus one finalize-only step
-        const uint32_t iters = n * (s->params.max_bounces + 1);
-        const uint32_t pools = (uint32_t)s->wf.size();
-        const bool prof = (s->params.flags & ER_FLAG_PROFILE) != 0;
+    auto pool_stream = [&](uint32_t p) { return p == 0 ? s->stream : s->pool_streams[p - 1]; };
+    for (uint32_t p = 0; p < pools; p++) er_launch_wf_begin(D, s->wf[p], n, pool_stream(p));
+    for (uint32_t it = 0; it < iters; it++) {
+        for (uint32_t p = 0; p < pools; p++) {
+            hipStream_t st = pool_stream(p);
+            uint32_t* ray_log = prof ? s->d_ray_log.p + s->prof_used / 3 : nullptr;
+            if (prof) HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], st));
+            er_launch_wf_trace(D, s->wf[p], it & 1, count, s->trace_blocks, ray_log, st);
+            if (prof) HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], st));
+            er_launch_wf_shade(D, s->wf[p], it & 1, count, s->shade_blocks, st);
+            if (prof) HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], st));
+        }
+    }
+    // join: the scene's stream continues once every pool has drained
+    for (uint32_t p = 1; p < pools; p++) {
+        HIP_TRY(hipEventRecord(s->pool_events[p], s->pool_streams[p - 1]));
+        HIP_TRY(hipStreamWaitEvent(s->stream, s->pool_events[p], 0));
+    }
+    return ER_OK;
+}
+
+// n more samples to every active tile (all owned tiles unless an adaptive render has stopped some), enqueued on the scene's stream;
+// the caller holds s->mtx.  The streaming kernel is handed the active tiles through its deal (StreamHost::d_deal), the wavefront and
+// megakernel schedules through the tile list of the scene descriptor they are launched with.
+static int enqueue_samples(ErScene* s, uint32_t n) {
+    const DevScene& D = s->ad_on ? s->ad_dev : s->dev;
+    const bool count = (s->params.flags & ER_FLAG_COUNTERS) != 0;
+    int rc = ER_OK;
+    if (!(s->params.flags & (ER_FLAG_MEGAKERNEL | ER_FLAG_STREAM))) {
+        if (n > 0) rc = wavefront_enqueue(s, D, n, count);
+    } else {
+        const bool prof = (s->params.flags & ER_FLAG_PROFILE) && n > 0;
         if (prof) {
-            const size_t need = s->prof_used / 3 + (size_t)iters * pools;      // launches profiled since the last er_wait
-            while (s->prof_events.size() < 3 * need) {
+            while (s->prof_events.size() < s->prof_used + 3) {
                 hipEvent_t e;
                 HIP_TRY(hipEventCreate(&e));
                 s->prof_events.push_back(e);
             }
-            if (s->d_ray_log.n < need) {
-                // grow, keeping what earlier calls of this timing window logged (they are still in flight or done)
-                DevBuf<uint32_t> bigger;
-                int rc2 = upload(bigger, nullptr, need * 2, s->stream);
-                if (rc2 != ER_OK) return rc2;
-                if (s->d_ray_log.p && s->prof_used) {
-                    HIP_TRY(hipStreamSynchronize(s->stream));
-                    HIP_TRY(hipMemcpy(bigger.p, s->d_ray_log.p, (s->prof_used / 3) * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-                }
-                s->d_ray_log.release();
-                s->d_ray_log = bigger;
-            }
+            HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], s->stream));
         }
-        // fork: the pool streams start after everything already enqueued on the scene's stream
-        if (pools > 1) {
-            HIP_TRY(hipEventRecord(s->pool_events[0], s->stream));
-            for (uint32_t p = 1; p < pools; p++) HIP_TRY(hipStreamWaitEvent(s->pool_streams[p - 1], s->pool_events[0], 0));
-        }
-        auto pool_stream = [&](uint32_t p) { return p == 0 ? s->stream : s->pool_streams[p - 1]; };
-        for (uint32_t p = 0; p < pools; p++) er_launch_wf_begin(D, s->wf[p], n, pool_stream(p));
-        for (uint32_t it = 0; it < iters; it++) {
-            for (uint32_t p = 0; p < pools; p++) {
-                hipStream_t st = pool_stream(p);
-                uint32_t* ray_log = prof ? s->d_ray_log.p + s->prof_used / 3 : nullptr;
-                if (prof) HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], st));
-                er_launch_wf_trace(D, s->wf[p], it & 1, count, s->trace_blocks, ray_log, st);
-                if (prof) HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], st));
-                er_launch_wf_shade(D, s->wf[p], it & 1, count, s->shade_blocks, st);
-                if (prof) HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], st));
-            }
-        }
-        // join: the scene's stream continues once every pool has drained
-        for (uint32_t p = 1; p < pools; p++) {
-            HIP_TRY(hipEventRecord(s->pool_events[p], s->pool_streams[p - 1]));
-            HIP_TRY(hipStreamWaitEvent(s->stream, s->pool_events[p], 0));
+        if (s->params.flags & ER_FLAG_STREAM) rc = stream_enqueue(s, n);
+        else er_launch_render(D, n, count, s->stream);
+        if (rc == ER_OK && prof) {
+            HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], s->stream));
+            HIP_TRY(hipEventRecord(s->prof_events[s->prof_used++], s->stream));   // (trace, shade) triple: shade = 0
         }
     }
+    if (rc != ER_OK) return rc;
     HIP_TRY(hipGetLastError());
     return ER_OK;
 }
@@ -842,102 +779,6 @@ static int er_render_samples_async_impl(ErScene* s, uint32_t n) {
     return enqueue_samples(s, n);
 }
 
-// The streaming kernel's waves give up instead of spinning forever if their workgroup makes no progress (er_stream.hip) and
-// say so in a status word.  Called with the scene's stream idle (after a wait or a read-back): an unfinished call must not pass
-// for a finished one.  The word stays set until the next er_render_begin.
-int er_scene_stream_status(ErScene* s, const char* who) {
-    if (!(s->params.flags & ER_FLAG_STREAM) || !s->stream_ctl) return ER_OK;
-    uint32_t st[32] = {0};
-    HIP_TRY(hipMemcpy(st, s->stream_ctl, sizeof(st), hipMemcpyDeviceToHost));
-    if (s->stream_spec_seen != s->stream_launches) {      // (once per launch: a read-back after the same launch finds the same words)
-        s->stream_spec_seen = s->stream_launches;
-        for (int k = 0; k < 3; k++) s->stream_spec[k] += st[24 + k];
-    }
-    if (st[1] != 0)
-        return fail(ER_ERR_STATE, std::string(who) + ": the streaming schedule stopped without finishing (watchdog status " + std::to_string(st[1]) + "); the planes are incomplete");
-    const unsigned long long iters = (unsigned long long)st[2] | ((unsigned long long)st[3] << 32), busy = (unsigned long long)st[4] | ((unsigned long long)st[5] << 32);
-    s->stream_busy = iters ? (double)busy / (64.0 * (double)iters) : 0.0;
-    // how far apart the XCDs finished, as a share of the launch (100 MHz ticks; a launch under 2 ms says nothing: start-up and tail)
-    auto u64 = [&](int i) { return (unsigned long long)st[i] | ((unsigned long long)st[i + 1] << 32); };
-    const unsigned long long t0 = u64(6);
-    unsigned long long lo = ~0ull, hi = 0;
-    for (int x = 0; x < 8; x++) { const unsigned long long e = u64(8 + 2 * x); lo = std::min(lo, e); hi = std::max(hi, e); }
-    s->stream_xcd_spread = (t0 != ~0ull && lo > t0 && hi - t0 >= 200000ull) ? (double)(hi - lo) / (double)(hi - t0) : -1.0;
-    s->stream_launch_ms = (t0 != ~0ull && hi > t0) ? (double)(hi - t0) * 1e-5 : 0.0;
-    return ER_OK;
-}
-
-// The two roles of the streaming kernel feed each other, and which one is short depends on the scene: how long a ray's traversal is
-// against how long its shading step is.  What the tracers' lanes say after a call (counted by the kernel itself, two scalar
-// operations per iteration): clearly not full = the shader waves cannot produce rays fast enough, and one tracer wave becomes a
-// shader wave for the next call.  Measured with the product kernel (profiles/r04_sweep_split_after_shader_diet.log): C2 0.89-0.90 full
-// at 13 + 3 (its best split); C4 0.81-0.85 at 13 + 3 and 0.92 at 12 + 4 (its best); C5 with lights 0.75 at 13 + 3, 0.90 at 12 + 4 (its
-// best).  Lanes that ARE full say little (C4 looks alike at 12 + 4 and 11 + 5), so the split moves down: one wave after TWO
-// consecutive calls whose lanes were under 0.85 full, down to 10 + 6 (7 + 5 of 12 waves).  A call shorter than ER_STREAM_ADAPT_MIN_MS
-// of device time is not a reading at all (its lanes are mostly ramp-up and tail: a 1-spp preview would otherwise walk the split
-// down for good), and ONE step back up is allowed per render when a later call reads above 0.93 (a demotion caused by two
-// unrepresentative calls is undone; a second demotion after that stays).  The image does not depend on the split.
-static void er_stream_adapt(ErScene* s) {
-    const bool verbose = getenv("ER_STREAM_VERBOSE") != nullptr;      // (read per call: a test turns it on for one render)
-    if (s->stream_adapted == s->stream_launches) return;              // (a second er_wait after the same launch: its measurements have been used)
-    s->stream_adapted = s->stream_launches;
-    if (verbose && (s->params.flags & ER_FLAG_STREAM) && !s->stream_adapt) fprintf(stderr, "[er_stream] tracer lanes %.3f full at %u + %u waves (fixed split)\n", s->stream_busy, s->stream_tracers, s->stream_waves - s->stream_tracers);
-    // the deal: large screen regions per XCD if the XCDs' shares of the COUNTED work of the first call are alike under them (er_stream.h,
-    // er_render_begin).  Decided once, from counts: the same decision on every run of the same frame.
-    if ((s->params.flags & ER_FLAG_STREAM) && s->stream_deal_pending) {
-        s->stream_deal_pending = false;
-        std::vector<uint32_t> cost(s->d_tile_cost.n);
-        if (hipMemcpy(cost.data(), s->d_tile_cost.p, cost.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess) {
-            double x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            const std::vector<uint32_t>& L = s->stream_deal_large;
-            for (size_t i = 0; i < L.size(); i++)
-                if (L[i] != 0xFFFFFFFFu && L[i] < cost.size()) x[(i % s->stream_blocks) % 8u] += (double)cost[L[i]];      // entry b + k * blocks belongs to workgroup b, XCD b % 8
-            double lo = x[0], hi = x[0], sum = 0;
-            for (double v : x) { lo = std::min(lo, v); hi = std::max(hi, v); sum += v; }
-            const double spread = sum > 0 ? (hi - lo) / (sum / 8.0) : 0.0;
-            const char* lim_env = getenv("ER_STREAM_COST_SPREAD_MAX");      // (test knob, read per decision: 0 keeps the default deal, a large value takes the large one)
-            const double limit = lim_env ? atof(lim_env) : (double)ER_STREAM_COST_SPREAD_MAX;
-            const bool take = sum > 0 && spread <= limit;
-            s->stream_cost_spread = spread;
-            if (verbose) fprintf(stderr, "[er_stream] counted work of the XCDs' shares on super-tiles of %u: %.4f of the mean apart (limit %.4f) -> %s\n", (unsigned)ER_STREAM_SUPER_TILE_LARGE, spread,
-                                 limit, take ? "large regions" : "the default deal stays");
-            if (take) { s->stream_deal_off = s->stream_deal_alt_off; s->stream_deal_n = s->stream_deal_alt_n; }
-        }
-        // the kernel stops counting: the scene descriptor it reads loses the pointer (ordered on the stream before the next launch)
-        s->dev.tile_cost = nullptr;
-        (void)hipMemcpyAsync(s->d_dev.p, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice, s->stream);
-        (void)hipStreamSynchronize(s->stream);
-        s->stream_deal_large.clear(); s->stream_deal_large.shrink_to_fit();
-    }
-    if (verbose && (s->params.flags & ER_FLAG_STREAM) && s->stream_xcd_spread >= 0.0)
-        fprintf(stderr, "[er_stream] XCDs finished %.3f of the launch apart (a measured time: printed, nothing is decided on it)\n", s->stream_xcd_spread);
-    if (!s->stream_adapt || !(s->params.flags & ER_FLAG_STREAM) || s->stream_busy <= 0.0 || s->stream_probe_launch) return;
-    const uint32_t lo = s->stream_waves == 12 ? 7u : 10u;
-    const uint32_t before = s->stream_tracers;
-    // (ER_STREAM_FORCE_BUSY: test knob -- the reading the mechanism is driven with instead of the measured one, whatever the launch's length;
-    // the occupancy itself depends on clocks and may not be asserted on)
-    // (a comma-separated list gives the k-th reading of the render its k-th value, the last one from then on)
-    const char* forced = getenv("ER_STREAM_FORCE_BUSY");
-    double busy = s->stream_busy;
-    if (forced) {
-        const char* q = forced;
-        for (uint32_t k = 0; k < s->stream_readings; k++) { const char* c = strchr(q, ','); if (!c) break; q = c + 1; }
-        busy = atof(q);
-    }
-    s->stream_readings++;
-    if (!forced && s->stream_launch_ms < ER_STREAM_ADAPT_MIN_MS) {
-        if (verbose) fprintf(stderr, "[er_stream] tracer lanes %.3f full in a launch of %.2f ms: too short to be a reading\n", s->stream_busy, s->stream_launch_ms);
-        return;
-    }
-    if (busy < 0.85) {
-        if (++s->stream_low_streak >= 2u && s->stream_tracers > lo) { s->stream_tracers--; s->stream_low_streak = 0; }
-    } else {
-        s->stream_low_streak = 0;
-        if (busy > 0.93 && s->stream_up_budget > 0u && s->stream_tracers < s->stream_tracers_start) { s->stream_tracers++; s->stream_up_budget--; }
-    }
-    if (verbose) fprintf(stderr, "[er_stream] tracer lanes %.3f full%s at %u + %u waves -> %u + %u\n", busy, forced ? " (forced reading)" : "", before, s->stream_waves - before, s->stream_tracers, s->stream_waves - s->stream_tracers);
-}
-
 static int er_wait_impl(ErScene* s, float* elapsed_ms) {
     if (!s) return fail(ER_ERR_INVALID_ARG, "er_wait: NULL scene");
     std::lock_guard<std::mutex> lk(s->mtx);
@@ -954,7 +795,7 @@ static int er_wait_impl(ErScene* s, float* elapsed_ms) {
     }
     if (elapsed_ms) *elapsed_ms = ms;
     { int rc = er_scene_stream_status(s, "er_wait"); if (rc != ER_OK) { s->prof_used = 0; return rc; } }   // (the profiling window ends with the call either way)
-    er_stream_adapt(s);
+    stream_adapt(s);
     s->profile = ErProfile{};
     s->profile.schedule = s->params.flags & (ER_FLAG_MEGAKERNEL | ER_FLAG_WAVEFRONT | ER_FLAG_STREAM);
     s->profile.concurrency = (s->params.flags & ER_FLAG_WAVEFRONT) ? (uint32_t)std::max<size_t>(1, s->wf.size()) : 1u;
@@ -1017,7 +858,7 @@ static int er_samples_done_impl(ErScene* s, uint32_t* out) {
     if (s->begun && s->params.world > 1) {
         std::vector<uint32_t> t = s->tiles_of(s->params.rank, s->params.world);
         if (!t.empty()) {
-            uint32_t tiles_x = (s->x_res + ER_TILE - 1) / ER_TILE;
+            const uint32_t tiles_x = s->tiles_x();
             first = (t[0] / tiles_x) * ER_TILE * s->x_res + (t[0] % tiles_x) * ER_TILE;
         }
     }
@@ -1229,10 +1070,10 @@ static int er_accel_info_impl(ErScene* s, ErAccelInfo* out) {
 // ---- adaptive sampling (include/eleven_hip.h er_adaptive_set; the test and the compaction: er_adaptive.hip) ----
 // The active tiles live on the device as a list in the layout of er_adaptive.h (two buffers: a test reads one and compacts the kept
 // tiles into the other); the host keeps a copy, read back with the test's result in one copy, because the streaming schedule's deal
-// is made on the host.  Pack, unpack, gather, denoise and er_samples_done keep working on the whole owned share (s->dev).
+// is made on the host (stream_redeal, er_stream_host.cpp).  Pack, unpack, gather, denoise and er_samples_done keep working on the whole owned share (s->dev).
 
 static uint32_t tile_pixels(const ErScene* s, uint32_t tile) {      // pixels of a tile inside the frame
-    const uint32_t tiles_x = (s->x_res + ER_TILE - 1) / ER_TILE, tx = tile % tiles_x, ty = tile / tiles_x;
+    const uint32_t tiles_x = s->tiles_x(), tx = tile % tiles_x, ty = tile / tiles_x;
     return std::min<uint32_t>(ER_TILE, s->x_res - tx * ER_TILE) * std::min<uint32_t>(ER_TILE, s->y_res - ty * ER_TILE);
 }
 
@@ -1246,31 +1087,7 @@ static int adaptive_apply_list(ErScene* s, bool redeal) {
     s->ad_active_px = 0;
     for (uint32_t t : s->ad_active) s->ad_active_px += tile_pixels(s, t);
     if (!redeal || !(s->params.flags & ER_FLAG_STREAM) || s->ad_active.empty()) return ER_OK;
-    // (a decision between the two deals still pending -- calls of one sample each until now -- is dropped: the default deal stays; the
-    // large regions, if already taken, stay taken for the new share)
-    const bool large = !s->stream_deal_pending && s->stream_deal_alt_n > 0 && s->stream_deal_off == s->stream_deal_alt_off;
-    if (s->stream_deal_pending) {
-        s->stream_deal_pending = false;
-        s->dev.tile_cost = s->ad_dev.tile_cost = nullptr;
-        HIP_TRY(hipMemcpyAsync(s->d_dev.p, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice, s->stream));
-        s->stream_deal_large.clear();
-    }
-    const uint32_t count = (uint32_t)s->ad_active.size(), tiles_x = (s->x_res + ER_TILE - 1) / ER_TILE;
-    std::vector<uint32_t> deal;
-    uint32_t most = er_stream_deal_tiles(s->ad_active.data(), count, tiles_x, s->stream_blocks, stream_xcd_aware(count, s->stream_blocks), deal,
-                                         large ? ER_STREAM_SUPER_TILE_LARGE : 0u);
-    // (whole super-tiles can leave one workgroup more tiles of a small share than it had of the owned one; the round-robin deal never
-    // does: ceil(count / blocks) <= ceil(owned / blocks) <= the owned share's largest, which the rings were sized for)
-    if ((size_t)most * 64u > s->stream_ring_cap) most = er_stream_deal_tiles(s->ad_active.data(), count, tiles_x, s->stream_blocks, false, deal);
-    if ((size_t)most * 64u > s->stream_ring_cap) return fail(ER_ERR_STATE, "er_render_samples: the active tiles do not fit the pixel rings");
-    int rc;
-    if ((rc = upload(s->d_deal, deal.data(), deal.size(), s->stream)) != ER_OK) return rc;
-    s->stream_deal_off = 0; s->stream_deal_n = (uint32_t)deal.size();
-    s->stream_deal_alt_off = 0; s->stream_deal_alt_n = 0;
-    stream_choose_form(s, count, s->stream_lights, s->params.flags);
-    s->stream_tracers_start = s->stream_tracers; s->stream_low_streak = 0; s->stream_up_budget = 1;
-    HIP_TRY(hipStreamSynchronize(s->stream));      // (`deal` goes out of scope)
-    return ER_OK;
+    return stream_redeal(s);
 }
 
 // The test at s->ad_next samples: error plane, compaction, one read-back of the new list (the host waits for it here).
@@ -1348,7 +1165,6 @@ static int er_adaptive_set_impl(ErScene* s, const ErAdaptiveParams* p) {
     if ((rc = upload(s->d_ad_err, err.data(), err.size(), s->stream)) != ER_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s->stream));      // (`list` and `err` go out of scope)
     s->ad_threshold = q.threshold;
-    s->ad_min = q.min_samples;
     s->ad_interval = q.interval;
     s->ad_next = q.min_samples;
     s->ad_tests = 0;

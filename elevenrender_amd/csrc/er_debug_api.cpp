@@ -4,7 +4,6 @@
 // and exercise the boundary's failure paths.
 #include "er_scene.h"
 #include "er_debug.h"
-#include "er_stream.h"
 
 using namespace erh;
 
@@ -48,6 +47,13 @@ static int er_debug_stream_deal_impl(const uint32_t* owned, uint32_t count, uint
     *most = er_stream_deal_tiles(owned, count, tiles_x, blocks, xcd_aware != 0, deal, edge);
     if (deal.size() > out_cap || (deal.size() && !out)) return fail(ER_ERR_INVALID_ARG, "er_debug_stream_deal: out holds fewer than blocks * most entries");
     for (size_t i = 0; i < deal.size(); i++) out[i] = deal[i];
+    return ER_OK;
+}
+
+static int er_debug_stream_form_impl(uint32_t tiles, uint32_t blocks, int light_query, uint32_t tri_count, uint32_t flags, ErStreamForm* out) {
+    if (!out || !blocks) return fail(ER_ERR_INVALID_ARG, "er_debug_stream_form: bad argument");
+    const StreamForm f = stream_choose_form(tiles, blocks, light_query != 0, tri_count, flags);
+    *out = ErStreamForm{f.waves, f.tracers, f.adapt ? 1u : 0u, f.keep ? 1u : 0u, f.spec ? 1u : 0u, 0u};
     return ER_OK;
 }
 
@@ -290,26 +296,20 @@ static int er_debug_stream_info_impl(ErScene* s, ErStreamInfo* out) {
     memset(out, 0, sizeof(*out));
     out->cost_spread = -1.0;
     if (!s->begun || !(s->params.flags & ER_FLAG_STREAM)) return ER_OK;
-    out->waves = s->stream_waves; out->tracers = s->stream_tracers;
-    out->large_regions = (s->stream_deal_alt_n != 0u && s->stream_deal_off == s->stream_deal_alt_off && s->stream_deal_n == s->stream_deal_alt_n) ? 1u : 0u;
-    out->deal_pending = s->stream_deal_pending ? 1u : 0u;
-    out->launches = (uint32_t)s->stream_launches;
-    out->pixels_per_cu = (uint32_t)((size_t)s->dev.owned_tile_count * 64 / std::max<uint32_t>(1u, s->stream_blocks));
-    out->lanes_busy = s->stream_busy; out->launch_ms = s->stream_launch_ms; out->cost_spread = s->stream_cost_spread;
-    out->spec_started = s->stream_spec[0]; out->spec_right = s->stream_spec[1]; out->spec_wrong = s->stream_spec[2];
-    // (er_launch_stream's choice: the speculative form only for scenes it starts speculative samples in, the keep form at 16 waves)
-    const bool spec_scene = s->dev.max_bounces <= 1000u && s->tri_count >= ER_STREAM_SPEC_MIN_TRIS;
-    out->form = (s->stream_spec_form && spec_scene) ? 2u : ((s->stream_keep && s->stream_waves == 16u) ? 1u : 0u);
+    stream_fill_info(s, out);
     return ER_OK;
 }
 
 extern "C" {
-void er_debug_set_gpu_build_failure(int kind) { er_debug_gpu_build_failure.store(kind < 0 || kind > 2 ? 0 : kind); }
+void er_debug_set_gpu_build_failure(int kind) { er_debug_gpu_build_failure.store(kind < 0 || kind > 3 ? 0 : kind); }
 int er_debug_stream_info(ErScene* s, ErStreamInfo* out) { return guarded("er_debug_stream_info", [&]() -> int { return er_debug_stream_info_impl(s, out); }); }
 int er_debug_closest_hit(ErScene* s, const float* origins, const float* dirs, uint32_t n, int32_t* tri_ids, float* positions, float* distances) { return guarded("er_debug_closest_hit", [&]() -> int { return er_debug_closest_hit_impl(s, origins, dirs, n, tri_ids, positions, distances); }); }
 int er_debug_cdf_search(const float* cdf, int length, const float* values, int32_t* out, int count) { return guarded("er_debug_cdf_search", [&]() -> int { return er_debug_cdf_search_impl(cdf, length, values, out, count); }); }
 int er_debug_stream_deal(const uint32_t* owned, uint32_t count, uint32_t tiles_x, uint32_t blocks, int xcd_aware, uint32_t edge, uint32_t* out, uint32_t out_cap, uint32_t* most) {
     return guarded("er_debug_stream_deal", [&]() -> int { return er_debug_stream_deal_impl(owned, count, tiles_x, blocks, xcd_aware, edge, out, out_cap, most); });
+}
+int er_debug_stream_form(uint32_t tiles, uint32_t blocks, int light_query, uint32_t tri_count, uint32_t flags, ErStreamForm* out) {
+    return guarded("er_debug_stream_form", [&]() -> int { return er_debug_stream_form_impl(tiles, blocks, light_query, tri_count, flags, out); });
 }
 int er_debug_bvh_check(const float* vertices, const float* normals, uint32_t tri_count, int threads, ErBvhCheck* out) { return guarded("er_debug_bvh_check", [&]() -> int { return er_debug_bvh_check_impl(vertices, normals, tri_count, threads, out); }); }
 int er_debug_trace_rays(ErScene* s, const float* origins, const float* dirs, uint32_t n, const int32_t* self_slots, const float* limits, int32_t* tri_ids,

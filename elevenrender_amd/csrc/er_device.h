@@ -98,7 +98,7 @@ struct DevScene {
     const uint32_t* owned_tiles;
     uint32_t owned_tile_count;
     DevCounters* counters;
-    // streaming schedule, while the deal of tiles to the XCDs is undecided (er_api.cpp er_stream_adapt): per tile of the frame, the sum
+    // streaming schedule, while the deal of tiles to the XCDs is undecided (er_stream_host.cpp stream_adapt): per tile of the frame, the sum
     // of the path lengths of its finished samples -- WORK counted by the kernel, the same on every run of the same frame; NULL = do not count
     uint32_t* tile_cost;
     // streaming schedule, 12-wave form (er_stream.hip, speculative sample pipelining): per pixel, the draw count its samples are guessed to

@@ -34,6 +34,6 @@ struct ErGpuBvhDevice {
     double build_ms = 0;
 };
 // Test hook (include/eleven_hip_debug.h er_debug_set_gpu_build_failure): 0 = none; 1 = device builds fail as a fault inside the builder
-// would; 2 = as a device out-of-memory would.  (Until round 6 an environment variable read on the production path.)
+// would; 2 = as a device out-of-memory would; 3 = they deliver but report a wide tree of ER_STACK8 + 1 levels.  (Until round 6 an environment variable read on the production path.)
 inline std::atomic<int> er_debug_gpu_build_failure{0};
 int er_gpu_build_device(const ErGpuSceneArrays& arrays, uint32_t n, int device, ErGpuBvhDevice* out, std::string& err);

@@ -797,7 +797,7 @@ hipError_t er_probe_gpu_build(const char** which) {   // see er_kernels.h
 int er_gpu_build_device(const ErGpuSceneArrays& a, uint32_t n, int device, ErGpuBvhDevice* out, std::string& err) {
     auto t0 = std::chrono::steady_clock::now();
     if (n <= ER_BVH_LEAF_MAX) { err = "too few triangles for the device builder"; return 1; }
-    if (const int dbg = er_debug_gpu_build_failure.load()) {      // (test hook er_debug_set_gpu_build_failure: the caller's handling of a failed build)
+    if (const int dbg = er_debug_gpu_build_failure.load(); dbg == 1 || dbg == 2) {      // (test hook er_debug_set_gpu_build_failure: the caller's handling of a failed build)
         err = dbg == 2 ? "simulated failure: out of device memory" : "simulated failure: a fault inside the builder";
         return dbg == 2 ? -2 : -1;
     }
@@ -889,7 +889,7 @@ int er_gpu_build_device(const ErGpuSceneArrays& a, uint32_t n, int device, ErGpu
     out->lift_bound = B.lift_bound();
     out->leaf_count = B.g[9];
     out->max_depth2 = B.g[8] + 1;
-    out->max_depth8 = depth8;
+    out->max_depth8 = er_debug_gpu_build_failure.load() == 3 ? ER_STACK8 + 1u : depth8;      // (test hook, kind 3)
     out->nodes8_count = nodes8_count;
     out->n8_pieces = n8_pieces;
     out->geom_f4 = geom_f4;

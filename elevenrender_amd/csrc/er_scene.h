@@ -1,6 +1,6 @@
 // er_scene.h -- host-side state behind the opaque ErScene handle of include/eleven_hip.h, and the small helpers the
-// translation units of the boundary share (er_api.cpp: the drop-in entry points; er_debug_api.cpp: inspection hooks of
-// include/eleven_hip_debug.h; er_collective.cpp: the RCCL framebuffer combine).
+// translation units of the boundary share (er_api.cpp: the drop-in entry points; er_stream_host.cpp: the streaming schedule's host
+// side; er_debug_api.cpp: inspection hooks of include/eleven_hip_debug.h; er_collective.cpp: the RCCL framebuffer combine).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,11 +19,13 @@
 
 #include "../../include/eleven_hip.h"
 #include "er_bvh.h"
+#include "er_devbuf.h"
 #include "er_device.h"
 #include "er_gpu_build.h"
 #include "er_kernels.h"
 #include "er_wavefront.h"
 #include "er_stream.h"
+#include "er_stream_host.h"
 #include "er_adaptive.h"
 #include "er_lights.h"
 
@@ -122,26 +124,6 @@ inline void host_generate_cdf(const HostTex& t, std::vector<float>& cdf, float& 
         }
 }
 
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-template <class T>
-struct ScopedDevBuf : DevBuf<T> {   // a temporary: freed on every way out of the function
-    ScopedDevBuf() = default;
-    ScopedDevBuf(const ScopedDevBuf&) = delete;
-    ScopedDevBuf& operator=(const ScopedDevBuf&) = delete;
-    ~ScopedDevBuf() { this->release(); }
-};
-
-
 }  // namespace erh
 
 using erh::DevBuf;
@@ -170,7 +152,7 @@ struct ErScene {
     bool timing_open = false;
     DevScene dev{};
     ErAccelInfo accel{};
-    DevBuf<float4> d_nodes, d_nodes8, d_isect, d_attr, d_passes;
+    DevBuf<float4> d_nodes, d_nodes8, d_attr, d_passes;
     DevBuf<float4> d_plane;      // staging: one pass gathered as a plane for er_read_pass
     DevBuf<ErMaterial> d_materials;
     DevBuf<float4> d_mat_pre;    // DevScene::mat_pre
@@ -189,33 +171,14 @@ struct ErScene {
     DevBuf<float4> d_wf4;        // 11 float4 arrays of the wavefront state, back to back
     DevBuf<uint32_t> d_wf1;      // hit, left, occluded, 4 queues, counts
     DevBuf<uint2> d_spill;
-    DevBuf<uint32_t> d_guide, d_ticket, d_deal;      // d_deal: the streaming schedule's deal of tiles to workgroups (er_stream_deal_tiles)
-    uint32_t stream_blocks = 0, stream_tracers = 0, stream_waves = 16, stream_ring_cap = 0;     // streaming schedule (er_stream.hip): workgroups; tracer waves of the 16
-    bool stream_lights = false;                         //   slot records carry the point-light query's line
-    uint32_t* stream_ctl = nullptr;                     //   [0] pixel ticket, [1] status word, [2..3] tracer iterations, [4..5] busy tracer lanes of the last call, [6..7] its start, [8..23] its end per XCD (100 MHz)
-    bool stream_adapt = false;                          //   move a wave between the roles by how full the tracer lanes were (er_stream_adapt)
-    double stream_busy = 0.0;                           //   tracer lanes that held a ray, last completed call
-    double stream_launch_ms = 0.0;                      //   device time of that call's launch (start stamp to the last XCD's end stamp)
-    uint32_t stream_low_streak = 0, stream_up_budget = 1, stream_tracers_start = 0, stream_readings = 0;   //   er_stream_adapt: consecutive low readings; steps back up left; the split the render began with
-    uint32_t stream_deal_off = 0, stream_deal_n = 0;    //   the deal in use inside d_deal (entries): the one of large super-tiles first, the default edge's after it
-    uint32_t stream_deal_alt_off = 0, stream_deal_alt_n = 0;   //   the deal of large screen regions beside it (0 entries: none)
-    uint64_t stream_spec[3] = {0, 0, 0}, stream_spec_seen = 0;   //   speculative samples started / whose guess was right / wrong, summed over the render's completed launches (small shares: er_stream.hip ST_PRED_BIT)
-    bool stream_spec_form = false;                      //   launch the kernel's form with speculative samples (small shares)
-    bool stream_keep = false;                           //   a pixel that is behind its workgroup's most advanced one keeps its slot (er_stream.hip s_front)
-    bool stream_probe_launch = false;                   //   the launch just completed was the first sample of a render's first call, run alone to decide the deal (er_render_samples)
-    bool stream_deal_pending = false;                   //   the first completed call decides between the two (er_stream_adapt), from ...
-    DevBuf<uint32_t> d_px_draws;                         //   ... DevScene::px_draws
-    DevBuf<uint32_t> d_tile_cost;                       //   ... DevScene::tile_cost: per tile of the frame, the summed path lengths of its finished samples
-    std::vector<uint32_t> stream_deal_large;            //   host copy of the large deal until then (which XCD gets which tile under it)
-    double stream_cost_spread = -1.0;                   //   (max - min) / mean of the XCDs' counted work under the large deal; < 0: not decided yet
-    double stream_xcd_spread = 0.0;                     //   (latest - earliest XCD) / launch duration of the last completed call; < 0: not measured
-    uint64_t stream_launches = 0, stream_adapted = 0;   //   launches enqueued / the launch whose measurements er_stream_adapt has already used
+    DevBuf<uint32_t> d_guide;
+    StreamHost st;               // the streaming schedule's host state (er_stream_host.h); its records, control words and spill live in d_wf4, d_wf1, d_spill
     // adaptive sampling (er_adaptive_set, er_api.cpp): the active tiles as a device list in the layout of er_adaptive.h, two buffers
     // that the test's compaction writes in turn; ad_dev = `dev` with owned_tiles pointing at the active list (wavefront, megakernel)
     uint32_t rendered = 0;                // samples given to every active tile since er_render_begin (adaptive or not)
     bool ad_on = false;
     float ad_threshold = 0;
-    uint32_t ad_min = 0, ad_interval = 0, ad_next = 0, ad_tests = 0, ad_cur = 0;   // ad_cur: which of d_ad_list holds the active list
+    uint32_t ad_interval = 0, ad_next = 0, ad_tests = 0, ad_cur = 0;   // ad_cur: which of d_ad_list holds the active list
     bool ad_snapped = false;              // the snapshot for the next test has been taken
     float ad_max_error = -1.0f;
     uint64_t ad_pixel_samples = 0, ad_active_px = 0;    // samples given to owned pixels; in-frame pixels of the active tiles
@@ -244,18 +207,21 @@ struct ErScene {
     std::set<uint32_t> unpacked[ER_PASS_COUNT];
     std::mutex mtx;
 
+    uint32_t tiles_x() const { return (x_res + ER_TILE - 1) / ER_TILE; }      // the frame in tiles of ER_TILE x ER_TILE pixels
+    uint32_t tiles_y() const { return (y_res + ER_TILE - 1) / ER_TILE; }
     std::vector<uint32_t> tiles_of(uint32_t rank, uint32_t world) const {
         std::vector<uint32_t> t;
-        uint32_t tiles_x = (x_res + ER_TILE - 1) / ER_TILE, tiles_y = (y_res + ER_TILE - 1) / ER_TILE;
-        for (uint32_t ty = 0; ty < tiles_y; ty++)
-            for (uint32_t tx = 0; tx < tiles_x; tx++)
-                if ((tx + ty) % world == rank) t.push_back(ty * tiles_x + tx);
+        const uint32_t nx = tiles_x(), ny = tiles_y();
+        for (uint32_t ty = 0; ty < ny; ty++)
+            for (uint32_t tx = 0; tx < nx; tx++)
+                if ((tx + ty) % world == rank) t.push_back(ty * nx + tx);
         return t;
     }
     void release_device() {
-        d_nodes.release(); d_nodes8.release(); d_isect.release(); d_attr.release(); d_passes.release(); d_plane.release(); d_materials.release();
+        d_nodes.release(); d_nodes8.release(); d_attr.release(); d_passes.release(); d_plane.release(); d_materials.release();
         d_textures.release(); d_tex_pool.release(); d_lights.release(); d_cdf.release(); d_samples.release(); d_rng.release();
-        d_owned.release(); d_counters.release(); d_wf4.release(); d_wf1.release(); d_spill.release(); d_guide.release(); d_ticket.release(); d_deal.release(); d_ray_log.release(); d_mat_fused.release(); d_mat_pre.release(); d_dev.release(); d_tile_cost.release(); d_px_draws.release();
+        d_owned.release(); d_counters.release(); d_wf4.release(); d_wf1.release(); d_spill.release(); d_guide.release(); d_ray_log.release(); d_mat_fused.release(); d_mat_pre.release(); d_dev.release();
+        st.release();
         d_ad_list[0].release(); d_ad_list[1].release(); d_ad_keep.release(); d_ad_snap.release(); d_ad_err.release();
         d_light_tab.release(); light_emitters = 0; light_total = 0.0f;
         ad_on = false; rendered = 0;
@@ -282,7 +248,7 @@ struct ErScene {
     }
 };
 
-// ER_OK unless the streaming schedule's watchdog ended a call early (er_api.cpp); call with the scene's stream idle and its
+// ER_OK unless the streaming schedule's watchdog ended a call early (er_stream_host.cpp); call with the scene's stream idle and its
 // mutex held.  Every entry point that hands planes out (read-backs, snapshot, gather, pack, denoise) ends with it.
 extern "C" __attribute__((visibility("hidden"))) int er_scene_stream_status(ErScene* s, const char* who);   // (library-internal)
 

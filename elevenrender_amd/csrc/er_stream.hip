@@ -37,8 +37,6 @@
 // ~0.2 s, or whose ring wait outlasts ER_RING_GUARD polls, raises the status word and ends the workgroup (it cannot hang).
 #include <algorithm>
 #include <cstdlib>
-#include <map>
-#include <vector>
 #include "er_device.h"
 #include "er_kernels.h"
 #include "er_wavefront.h"
@@ -138,7 +136,7 @@ static_assert((1u << ST_RQ_LOG2) >= 3u * ER_STREAM_SLOTS, "the ray ring must hol
 // Waves per CU = a template argument of the kernel (its launch bound decides the register budget): 16 waves of 128 registers -- four per
 // SIMD, the shader step spills 111 of them -- or 12 waves of 168 registers (34 spilled), which is faster when a workgroup owns so few
 // pixels that the tracer lanes cannot be filled anyway (one GPU's eighth of a 1080p frame: 1.26 instead of 1.34 ms per pass,
-// profiles/r04_sweep_sim_world8.log); er_api.cpp chooses by owned pixels per CU.
+// profiles/r04_sweep_sim_world8.log); er_stream_host.cpp chooses by owned pixels per CU.
 // north_star: "top BVH levels staged in LDS".  Every workgroup keeps the first wide nodes in LDS (the tree is stored
 // breadth-first: 585 = levels 0-3, 47 KB) and the tracer lanes whose node is one of them read it with ds_read_b128 instead of
 // five global loads: 9 of a ray's 21 node visits on C2.  Measured on C2 with the first tracer: 0 nodes 1240, 73 -> 1274,
@@ -167,7 +165,7 @@ enum { C_LIVE = 0, C_DONE, C_INIT, C_WORDS };
 #define ST_ERR_SHADE 8u
 #define ST_ERR_RAY 16u
 #define ST_ERR_CTX 32u
-// the pixel ring's "previous entry has been read" bits (er_ring.h): one per cell, so ring_cap <= ER_STREAM_MAX_RING (er_api.cpp checks)
+// the pixel ring's "previous entry has been read" bits (er_ring.h): one per cell, so ring_cap <= ER_STREAM_MAX_RING (er_stream_host.cpp checks)
 #define ST_PXBITS_WORDS (ER_STREAM_MAX_RING / 32u)
 
 __device__ __forceinline__ unsigned st_wave_sum(unsigned v) {
@@ -298,7 +296,7 @@ struct StState {
 #define ST_LONG_SHIFT 23             // ... the mean length of its paths, iterations x 16 (0 .. 511)
 enum { SP_NONE = 0, SP_PENDING = 1, SP_PARKED = 2, SP_VALID = 3, SP_INVALID = 4 };      // StState::spec_word of a speculative slot
 
-// pixel k of workgroup b's share: entry b + (k / 64) * workgroups of the deal (er_stream_deal_tiles below), lane k % 64
+// pixel k of workgroup b's share: entry b + (k / 64) * workgroups of the deal (er_stream_deal_tiles, er_stream_host.cpp), lane k % 64
 // (false: no tile there, or outside the image)
 __device__ __forceinline__ bool st_pixel_of(const DevScene& S, const uint32_t* deal, uint32_t deal_count, uint32_t b, uint32_t nb, uint32_t k, uint32_t& px,
                                             uint32_t& py) {
@@ -311,7 +309,7 @@ __device__ __forceinline__ bool st_pixel_of(const DevScene& S, const uint32_t* d
     return px < S.x_res && py < S.y_res;
 }
 
-// A pixel travels through the slots and the pixel ring as px | py << 16 (both < 65 536: er_api.cpp checks), so that nobody divides by
+// A pixel travels through the slots and the pixel ring as px | py << 16 (both < 65 536: er_stream_host.cpp checks), so that nobody divides by
 // the run-time width to get its coordinates back; its index in the planes is py * x_res + px.
 #define ST_PXY(px, py) ((uint32_t)(px) | ((uint32_t)(py) << 16))
 __device__ __forceinline__ uint32_t st_pixel_index(const DevScene& S, uint32_t pxy) { return (pxy >> 16) * S.x_res + (pxy & 0xFFFFu); }
@@ -366,13 +364,13 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
     // The scene descriptor lives in constant memory and is read with scalar loads where it is used.  As a by-value kernel argument its
     // ~60 dwords stayed in SGPRs for the whole kernel and the shading step moved 585 scalar spills to and from VGPR lanes (round 4).
     const DevScene& S = *(const DevScene*)Sp;
-    // when the launch began and when each XCD's last wave left (status[5..6], status[7 + 2 x ..]; 100 MHz): how evenly the deal spread
-    // the frame's COST over the XCDs is something only the run can tell (er_api.cpp er_stream_adapt)
-    if (threadIdx.x == 0) atomicMin((unsigned long long*)(status + 5), (unsigned long long)wall_clock64());
+    // when the launch began and when each XCD's last wave left (ER_SC_START, ER_SC_END + 2 x; 100 MHz): how evenly the deal spread
+    // the frame's COST over the XCDs is something only the run can tell (er_stream_host.cpp stream_adapt)
+    if (threadIdx.x == 0) atomicMin((unsigned long long*)(status + ER_SC_START), (unsigned long long)wall_clock64());
     constexpr uint32_t RQ_LOG2 = ST_RQ_LOG2, SLOTS = ER_STREAM_SLOTS, TOP_NODES = ER_STREAM_TOP_NODES;
     // The kernel's FORM is a template argument: 0 -- the instances that render whole frames, the code they were in round 5; 1 -- with the rule that
     // a pixel which is behind keeps its slot (s_front), for shares of a few pixels per slot; 2 -- that and speculative sample pipelining (comment at
-    // ST_DRAWS_MASK), for shares in which slots fall free.  er_launch_stream picks by owned pixels per CU (er_api.cpp).
+    // ST_DRAWS_MASK), for shares in which slots fall free.  er_launch_stream picks by owned pixels per CU (er_stream_host.cpp stream_choose_form, er_stream_launch_form below).
     constexpr bool SPEC = FORM == 2;
     constexpr bool KEEP = FORM >= 1;
     bool spec_on = false;
@@ -485,7 +483,7 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
             uint32_t lsk = 0;      // the ray in hand: its ray-ring payload, local slot | kind << 11 (ONE register across the traversal; the
                                    // record index g0 + slot (+ W.slots for a point-light query) is recomputed where it is needed)
             uint32_t idle = 0, progress = 0;
-            uint32_t a_iter = 0, a_busy = 0;      // iterations of this wave's loop and the lanes that held a ray in them (-> status[1..4])
+            uint32_t a_iter = 0, a_busy = 0;      // iterations of this wave's loop and the lanes that held a ray in them (-> ER_SC_ITERS, ER_SC_BUSY)
             ER_SP(uint32_t spA = 0; uint32_t spB = 0; uint32_t spC = 0; uint32_t sAB = 0; uint32_t sBC = 0; uint32_t sCD = 0; uint32_t sN = 0;)      // (per lane, flushed once at the end)
 #ifdef ER_TRACER_PROBE
             uint32_t trp[7] = {0, 0, 0, 0, 0, 0, 0}, trp_pub = 0, trp_take = 0;
@@ -665,10 +663,10 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
 #endif
             ER_SP({ unsigned long long* spc = (unsigned long long*)&S.counters->node_visits; sp_add(spc + 0, sAB); sp_add(spc + 1, sBC); sp_add(spc + 2, sCD); sp_add(spc + 5, sN); })
             // how full the tracer lanes were: the host reads it after the call and moves one wave between the two roles for the next
-            // call when the tracers starve or the shaders idle (er_api.cpp, er_stream_adapt)
+            // call when the tracers starve or the shaders idle (er_stream_host.cpp, stream_adapt)
             if (lane == 0) {
-                atomicAdd((unsigned long long*)(status + 1), (unsigned long long)a_iter);
-                atomicAdd((unsigned long long*)(status + 3), (unsigned long long)a_busy);
+                atomicAdd((unsigned long long*)(status + ER_SC_ITERS), (unsigned long long)a_iter);
+                atomicAdd((unsigned long long*)(status + ER_SC_BUSY), (unsigned long long)a_busy);
             }
         }
     }
@@ -1191,14 +1189,14 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
     if (SPEC) {
         if (lane == 0) {
             const unsigned q0 = atomicExch(&s_spec[0], 0u), q1 = atomicExch(&s_spec[1], 0u), q2 = atomicExch(&s_spec[2], 0u);
-            if (q0 | q1 | q2) { atomicAdd(status + 23, q0); atomicAdd(status + 24, q1); atomicAdd(status + 25, q2); }
+            if (q0 | q1 | q2) { atomicAdd(status + ER_SC_SPEC, q0); atomicAdd(status + ER_SC_SPEC + 1, q1); atomicAdd(status + ER_SC_SPEC + 2, q2); }
         }
     }
     unsigned t0 = st_wave_sum(c_paths), t1 = st_wave_sum(c_bounce), t2 = st_wave_sum(c_rays), t3 = st_wave_sum(c_shaded), t4 = st_wave_sum(c_hdri);
     unsigned t5 = 0, t6 = 0, t7 = 0;
     if (COUNT) { t5 = st_wave_sum(c_nodes); t6 = st_wave_sum(c_tris); t7 = st_wave_sum(c_texels); }
     if (lane == 0) {
-        atomicMax((unsigned long long*)(status + 7 + 2 * (blockIdx.x & 7u)), (unsigned long long)wall_clock64());
+        atomicMax((unsigned long long*)(status + ER_SC_END + 2 * (blockIdx.x & 7u)), (unsigned long long)wall_clock64());
         if (t0) atomicAdd(&S.counters->paths, (unsigned long long)t0);
         if (t1) atomicAdd(&S.counters->bounce_samples, (unsigned long long)t1);
         if (t2) atomicAdd(&S.counters->rays, (unsigned long long)t2);
@@ -1218,7 +1216,7 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
 
 // The instances with the emitter samples of ER_FLAG_MESH_LIGHTS (MESH = true) are compiled in a translation unit of their own,
 // er_stream_mesh.hip, which includes this file with ER_STREAM_MESH_TU defined: there the launcher below is er_launch_stream_mesh and
-// picks only those instances, and the other host functions are left to this one.  Each unit's device assembly gets its own split-wait
+// picks only those instances, and the other host functions are left to this one (the deal of tiles and everything else that needs no kernel: er_stream_host.cpp).  Each unit's device assembly gets its own split-wait
 // check (Makefile), and this one holds the 40 instances without the extension.
 #ifndef ER_STREAM_MESH_TU
 hipError_t er_probe_stream(const char** which) {
@@ -1229,58 +1227,39 @@ hipError_t er_probe_stream(const char** which) {
     return e != hipSuccess ? e : hipFuncGetAttributes(&a, (const void*)er_stream_kernel<false, false, false, 768u, true, 2>);
 }
 
-// Which workgroup renders which tiles.  Workgroups b and b + 8 run on the same XCD and share its 4 MB L2 (observed dispatch
-// order, MI355X_MICROARCH.md; used for speed only -- any deal gives the same pixels), so the frame is cut into super-tiles of
-// edge x edge tiles (8: 64 x 64 pixels; er_render_begin also makes the deal of 16, er_stream.h), every super-tile goes to ONE XCD (the
-// one with the fewest tiles so far), the XCDs are then levelled tile by tile, and inside an XCD the
-// tiles are dealt round-robin to its workgroups: the camera rays and first bounces that an L2 serves then come from a few
-// compact screen regions instead of from every eighth tile of the whole frame.  out[b + k * blocks] = the k-th tile of
-// workgroup b, 0xFFFFFFFF = none; returns the largest number of tiles any workgroup got.
-uint32_t er_stream_deal_tiles(const uint32_t* owned, uint32_t count, uint32_t tiles_x, uint32_t blocks, bool xcd_aware, std::vector<uint32_t>& out, uint32_t edge) {
-    if (edge == 0u) {
-        const char* e = getenv("ER_STREAM_SUPER_TILE");      // (A/B knob)
-        const int v = e ? atoi(e) : 0;
-        edge = v >= 1 ? (uint32_t)v : ER_STREAM_SUPER_TILE_DEFAULT;
-    }
-    const uint32_t X = (xcd_aware && blocks % 8u == 0u) ? 8u : 1u, per = blocks / X, S8 = edge;
-    const uint32_t super_x = (tiles_x + S8 - 1u) / S8;
-    std::map<uint32_t, std::vector<uint32_t>> by_super;      // row-major super-tile order; tiles inside keep their row-major order
-    for (uint32_t i = 0; i < count; i++) {
-        const uint32_t tx = owned[i] % tiles_x, ty = owned[i] / tiles_x;
-        by_super[X == 1u ? 0u : (ty / S8) * super_x + tx / S8].push_back(owned[i]);
-    }
-    std::vector<std::vector<uint32_t>> seq(X);
-    for (auto& kv : by_super) {
-        uint32_t best = 0;
-        for (uint32_t x = 1; x < X; x++) if (seq[x].size() < seq[best].size()) best = x;
-        seq[best].insert(seq[best].end(), kv.second.begin(), kv.second.end());
-    }
-    // Whole super-tiles leave the XCDs up to one super-tile apart (1.6 % of an XCD's share of a 1080p frame at the default edge, 6 % at
-    // 16) and a launch lasts as long as its fullest XCD: level them tile by tile -- the tail of the fullest XCD's last super-tile goes
-    // to the emptiest one -- until no two differ by more than a tile (tests/test_abi_cpu.py; within noise on the soup frames,
-    // profiles/r04_sweep_super_tile.log: what a larger super-tile loses on a frame of uneven cost is the CONTENT of its XCDs' shares).
-    const char* lv = getenv("ER_STREAM_LEVEL_XCDS");      // (A/B knob)
-    for (; !(lv && atoi(lv) == 0);) {
-        uint32_t hi = 0, lo = 0;
-        for (uint32_t x = 1; x < X; x++) {
-            if (seq[x].size() > seq[hi].size()) hi = x;
-            if (seq[x].size() < seq[lo].size()) lo = x;
-        }
-        const size_t diff = seq[hi].size() - seq[lo].size();
-        if (diff <= 1u) break;
-        const size_t n = diff / 2u;
-        seq[lo].insert(seq[lo].end(), seq[hi].end() - (ptrdiff_t)n, seq[hi].end());
-        seq[hi].resize(seq[hi].size() - n);
-    }
-    uint32_t maxk = 0;
-    for (uint32_t x = 0; x < X; x++) maxk = std::max<uint32_t>(maxk, (uint32_t)((seq[x].size() + per - 1u) / per));
-    out.assign((size_t)blocks * maxk, 0xFFFFFFFFu);
-    for (uint32_t x = 0; x < X; x++)
-        for (size_t sidx = 0; sidx < seq[x].size(); sidx++) {
-            const uint32_t j = (uint32_t)(sidx % per), k = (uint32_t)(sidx / per), b = j * X + x;      // b % X == x: the XCD
-            out[(size_t)b + (size_t)k * blocks] = seq[x][sidx];
-        }
-    return maxk;
+// The form a launch uses, from what the share asks for (spec, keep: er_stream_host.cpp stream_choose_form), the scene and the knobs.
+ErStreamLaunchForm er_stream_launch_form(uint32_t max_bounces, uint32_t tri_count, uint32_t waves, bool spec, bool keep) {
+    // speculative sample pipelining.  ER_STREAM_SPEC: 0 = off, 1 .. 7 = the confidence a pixel's guessed draw count needs (A/B knob)
+    static const uint32_t spec_flag = [] {
+        const char* e = getenv("ER_STREAM_SPEC");
+        const char* b = getenv("ER_STREAM_SPEC_SLACK");      // polls a shader wave must have waited before a step that starts speculative samples (knob; 0 = no condition)
+        int v = e ? atoi(e) : 2, bl = b ? atoi(b) : 1;
+        return ((uint32_t)(v < 0 ? 0 : (v > 7 ? 7 : v)) << 8) | ((uint32_t)(bl < 0 ? 0 : (bl > 255 ? 255 : bl)) << 12);
+    }();
+    // ER_STREAM_SPEC_LONG: sixteenths of max_bounces; a pixel whose paths are longer than that on average starts a speculative successor with every sample (0 = off)
+    static const uint32_t spec_long16 = [] {
+        const char* e = getenv("ER_STREAM_SPEC_LONG");
+        int v = e ? atoi(e) : ER_STREAM_SPEC_LONG_DEFAULT;
+        return (uint32_t)(v < 0 ? 0 : (v > 16 ? 16 : v));
+    }();
+    // ER_STREAM_SPEC_KEEP: 1 + the samples a pixel may be behind before it keeps its slot (0 = off, 1 .. 7)
+    static const uint32_t spec_keep = [] {
+        const char* e = getenv("ER_STREAM_SPEC_KEEP");
+        int v = e ? atoi(e) : ER_STREAM_SPEC_KEEP_DEFAULT;
+        return (uint32_t)(v < 0 ? 0 : (v > 7 ? 7 : v));
+    }();
+    waves = waves == 12u ? 12u : 16u;
+    // (a slot's tally keeps its iterations in ten bits; and a scene of a few triangles -- C1's 12-triangle box, 256 pixels per CU -- runs 5-9 % SLOWER two
+    // samples deep, right guesses and all: its rays are three traversal steps long and there is nothing to overlap, profiles/r06_ab_speculative_samples.log)
+    // (iterations x 16; the field holds up to 511: longer paths, no such pixels.  12-wave form only: 1/16 share of the C2 frame - 5 %, 1/8 - 0 ... 2 %; the 16-wave form's 1/4 share + 0.6 %)
+    const uint32_t long_thr = waves == 12u ? max_bounces * spec_long16 : 0u;
+    const uint32_t spec_now = (max_bounces <= 1000u && tri_count >= ER_STREAM_SPEC_MIN_TRIS) ? (spec_flag | ((long_thr > 511u ? 0u : long_thr) << 20) | (((waves == 16u && keep) ? spec_keep : 0u) << 29)) : 0u;      // (the 16-wave form, whose pixels outnumber its slots: 1/4 share - 3.7 ... 5 %, 1/6 - 1 %; the 12-wave form's 1/8 ... 1/16 shares +- 0 ... + 1 %)
+    // (the kernel's last argument, one word: bits 0-7 the finishing batch's minimum; forms 1 and 2: bits 29-31 the keep rule's slack + 1; form 2: bits 8-10 the
+    // confidence a guess needs, 12-19 the idle polls a shader wave must have behind it before it starts speculative samples, 20-28 the long pixels' mean path x 16)
+    const uint32_t keep_plain = (keep && waves == 16u) ? (spec_keep << 29) : 0u;
+    if (spec && spec_now) return {2u, waves, spec_now};
+    if (keep_plain) return {1u, waves, keep_plain};      // (16 waves only: the 12-wave instances are plain or speculative)
+    return {0u, waves, 0u};
 }
 
 #endif  // ER_STREAM_MESH_TU
@@ -1290,11 +1269,11 @@ uint32_t er_stream_deal_tiles(const uint32_t* owned, uint32_t count, uint32_t ti
 #else
 #define ER_STREAM_LAUNCH er_launch_stream
 #endif
-void ER_STREAM_LAUNCH(const DevScene& S, const DevScene* S_dev, void* records, uint32_t slots, bool lights, void* spill, const uint32_t* deal, uint32_t deal_count, void* ring,
-                      uint32_t ring_cap, uint32_t* status, uint32_t n_samples, bool count, uint32_t blocks, uint32_t tracers, uint32_t waves, bool spec, bool keep, hipStream_t stream) {
+void ER_STREAM_LAUNCH(const ErStreamLaunch& L) {
+    const DevScene& S = *L.S;
 #ifndef ER_STREAM_MESH_TU
     if (er_mesh_active(S)) {
-        er_launch_stream_mesh(S, S_dev, records, slots, lights, spill, deal, deal_count, ring, ring_cap, status, n_samples, count, blocks, tracers, waves, spec, keep, stream);
+        er_launch_stream_mesh(L);
         return;
     }
 #endif
@@ -1318,36 +1297,12 @@ void ER_STREAM_LAUNCH(const DevScene& S, const DevScene* S_dev, void* records, u
         int v = e ? atoi(e) : 64;      // (a finishing step runs as soon as it is full)
         return (uint32_t)(v < 1 ? 1 : (v > 64 ? 64 : v));
     }();
-    // speculative sample pipelining (12-wave form).  ER_STREAM_SPEC: 0 = off, 1 .. 7 = the confidence a pixel's guessed draw count needs (A/B knob)
-    static const uint32_t spec_flag = [] {
-        const char* e = getenv("ER_STREAM_SPEC");
-        const char* b = getenv("ER_STREAM_SPEC_SLACK");      // polls a shader wave must have waited before a step that starts speculative samples (knob; 0 = no condition)
-        int v = e ? atoi(e) : 2, bl = b ? atoi(b) : 1;
-        return ((uint32_t)(v < 0 ? 0 : (v > 7 ? 7 : v)) << 8) | ((uint32_t)(bl < 0 ? 0 : (bl > 255 ? 255 : bl)) << 12);
-    }();
-    // ER_STREAM_SPEC_LONG: sixteenths of max_bounces; a pixel whose paths are longer than that on average starts a speculative successor with every sample (0 = off)
-    static const uint32_t spec_long16 = [] {
-        const char* e = getenv("ER_STREAM_SPEC_LONG");
-        int v = e ? atoi(e) : ER_STREAM_SPEC_LONG_DEFAULT;
-        return (uint32_t)(v < 0 ? 0 : (v > 16 ? 16 : v));
-    }();
-    // ER_STREAM_SPEC_KEEP: 1 + the samples a pixel may be behind before it keeps its slot (0 = off, 1 .. 7)
-    static const uint32_t spec_keep = [] {
-        const char* e = getenv("ER_STREAM_SPEC_KEEP");
-        int v = e ? atoi(e) : ER_STREAM_SPEC_KEEP_DEFAULT;
-        return (uint32_t)(v < 0 ? 0 : (v > 7 ? 7 : v));
-    }();
-    if (S.owned_tile_count == 0 || n_samples == 0) return;
-    // (a slot's tally keeps its iterations in ten bits; and a scene of a few triangles -- C1's 12-triangle box, 256 pixels per CU -- runs 5-9 % SLOWER two
-    // samples deep, right guesses and all: its rays are three traversal steps long and there is nothing to overlap, profiles/r06_ab_speculative_samples.log)
-    // (iterations x 16; the field holds up to 511: longer paths, no such pixels.  12-wave form only: 1/16 share of the C2 frame - 5 %, 1/8 - 0 ... 2 %; the 16-wave form's 1/4 share + 0.6 %)
-    const uint32_t long_thr = waves == 12u ? S.max_bounces * spec_long16 : 0u;
-    const uint32_t spec_now = (S.max_bounces <= 1000u && S.tri_count >= ER_STREAM_SPEC_MIN_TRIS) ? (spec_flag | ((long_thr > 511u ? 0u : long_thr) << 20) | (((waves == 16u && keep) ? spec_keep : 0u) << 29)) : 0u;      // (the 16-wave form, whose pixels outnumber its slots: 1/4 share - 3.7 ... 5 %, 1/6 - 1 %; the 12-wave form's 1/8 ... 1/16 shares +- 0 ... + 1 %)
-    // (the kernel's last argument, one word: bits 0-7 the finishing batch's minimum; forms 1 and 2: bits 29-31 the keep rule's slack + 1; form 2: bits 8-10 the
-    // confidence a guess needs, 12-19 the idle polls a shader wave must have behind it before it starts speculative samples, 20-28 the long pixels' mean path x 16)
-    const uint32_t keep_plain = (keep && waves == 16u) ? (spec_keep << 29) : 0u;
+    if (S.owned_tile_count == 0 || L.n_samples == 0) return;
+    const ErStreamLaunchForm form = er_stream_launch_form(S.max_bounces, S.tri_count, L.waves, L.spec, L.keep);
+    const uint32_t waves = form.waves, last = fin_min | form.bits;
+    const bool count = L.count;
+    uint32_t tracers = L.tracers;
     if (tracers > ST_MAX_TRACERS) tracers = ST_MAX_TRACERS;      // (the LDS traversal stacks are sized for that many; at least 3 shader waves stay)
-    waves = waves == 12u ? 12u : 16u;
     if (tracers > waves - 1u) tracers = waves - 1u;      // at least one shader wave
     if (tracers < 1u) tracers = 1u;
     // (FUSE: an instance without the fused-texel path for scenes in which no material is fused, er_device.h generate_hit_data)
@@ -1375,16 +1330,18 @@ void ER_STREAM_LAUNCH(const DevScene& S, const DevScene* S_dev, void* records, u
     auto k12 = ST_PICK(768u, 0);
 #undef ST_PICK
     StState st;
-    st.base = (char*)records;
-    st.spill = (uint2*)spill;
-    st.slots = slots;
-    st.stride = er_stream_record_bytes(lights);
-    const DevScene __attribute__((address_space(4)))* dS = (const DevScene __attribute__((address_space(4)))*)S_dev;
-    if (waves == 12u && spec && spec_now) hipLaunchKernelGGL(k12s, dim3(blocks), dim3(768), 0, stream, dS, st, deal, deal_count, (uint2*)ring, ring_cap, status, n_samples, tracers, refill_min, batch_min, fin_min | spec_now);
-    else if (waves == 12u) hipLaunchKernelGGL(k12, dim3(blocks), dim3(768), 0, stream, dS, st, deal, deal_count, (uint2*)ring, ring_cap, status, n_samples, tracers, refill_min, batch_min, fin_min);
-    else if (spec && spec_now) hipLaunchKernelGGL(k16s, dim3(blocks), dim3(1024), 0, stream, dS, st, deal, deal_count, (uint2*)ring, ring_cap, status, n_samples, tracers, refill_min, batch_min, fin_min | spec_now);
-    else if (keep_plain) hipLaunchKernelGGL(k16k, dim3(blocks), dim3(1024), 0, stream, dS, st, deal, deal_count, (uint2*)ring, ring_cap, status, n_samples, tracers, refill_min, batch_min, fin_min | keep_plain);
-    else hipLaunchKernelGGL(k16, dim3(blocks), dim3(1024), 0, stream, dS, st, deal, deal_count, (uint2*)ring, ring_cap, status, n_samples, tracers, refill_min, batch_min, fin_min);
+    st.base = (char*)L.records;
+    st.spill = (uint2*)L.spill;
+    st.slots = L.slots;
+    st.stride = er_stream_record_bytes(L.lights);
+    const DevScene __attribute__((address_space(4)))* dS = (const DevScene __attribute__((address_space(4)))*)L.S_dev;
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(waves * 64u), 0, L.stream, dS, st, L.deal, L.deal_count, (uint2*)L.ring, L.ring_cap, L.status, L.n_samples, tracers, refill_min, batch_min, last);
+    };
+    if (waves == 12u) { if (form.form == 2u) go(k12s); else go(k12); }
+    else if (form.form == 2u) go(k16s);
+    else if (form.form == 1u) go(k16k);
+    else go(k16);
 }
 
 #undef ER_STREAM_LAUNCH

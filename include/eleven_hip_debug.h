@@ -106,7 +106,7 @@ int er_debug_eval(struct ErScene* scene, int kind, const float* in, uint32_t n, 
 struct ErComm;
 int er_debug_comm_create_local(uint32_t world, struct ErComm** out);
 
-/* What the streaming schedule ran the last completed call with, and what it read from it (er_api.cpp er_stream_adapt): for bench.py's
+/* What the streaming schedule ran the last completed call with, and what it read from it (er_stream_host.cpp stream_adapt): for bench.py's
  * `projected` block and the tests.  Valid after er_wait / a read-back; all zero for the other schedules. */
 typedef struct ErStreamInfo {
     uint32_t waves, tracers;       /* waves per workgroup (16 or 12) and how many of them trace */
@@ -141,6 +141,17 @@ int er_debug_comm_loopback(struct ErComm* c, uint64_t bytes, double* ms);
 int er_debug_stream_deal(const uint32_t* owned, uint32_t count, uint32_t tiles_x, uint32_t blocks, int xcd_aware, uint32_t edge, uint32_t* out, uint32_t out_cap,
                          uint32_t* most);
 
+/* The streaming kernel's form for a share of `tiles` tiles on `blocks` workgroups, as er_render_begin and an adaptive re-deal choose
+ * it (host code, no device needed; the A/B knobs of the environment are honoured): light_query = the slots carry a point-light or
+ * emitter query; flags: the render's (ER_FLAG_COUNTERS matters). */
+typedef struct ErStreamForm {
+    uint32_t waves, tracers;       /* waves per workgroup (16 or 12) and how many of them trace at the start */
+    uint32_t adapt;                /* 1: the split follows the tracer lanes' occupancy */
+    uint32_t keep, spec;           /* 1: the share asks for the keep rule / for speculative samples */
+    uint32_t reserved;
+} ErStreamForm;
+int er_debug_stream_form(uint32_t tiles, uint32_t blocks, int light_query, uint32_t tri_count, uint32_t flags, ErStreamForm* out);
+
 /* Test hook for the out-of-memory path of the boundary: while `bytes` is non-zero, any single large host allocation the
  * library announces (scene copy in er_scene_create, build staging in er_render_begin) larger than `bytes` fails as
  * std::bad_alloc would, which the entry point must turn into ER_ERR_OOM (no exception crosses the C ABI).  0 = off. */
@@ -148,7 +159,8 @@ void er_debug_set_host_alloc_limit(uint64_t bytes);
 
 /* Test hook for er_render_begin's handling of a device BVH build that does not deliver: 0 = off; 1 = every device build fails as a
  * fault inside the builder would (default builder: one line on stderr and the host builder takes over; ER_FLAG_GPU_BUILD: ER_ERR_HIP);
- * 2 = as running out of device memory would (default builder: silent host fallback; ER_FLAG_GPU_BUILD: ER_ERR_OOM). */
+ * 2 = as running out of device memory would (default builder: silent host fallback; ER_FLAG_GPU_BUILD: ER_ERR_OOM); 3 = every device
+ * build delivers but reports a wide tree of ER_STACK8 + 1 levels (either way ER_ERR_STATE: the host builder makes the same tree). */
 void er_debug_set_gpu_build_failure(int kind);
 
 #ifdef __cplusplus

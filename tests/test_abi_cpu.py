@@ -231,10 +231,53 @@ def stream_deal(owned, tiles_x, blocks=256, xcd_aware=1, edge=0):
     return out.reshape(most.value, blocks)          # [k, b] = the k-th tile of workgroup b
 
 
+STREAM_FORM_KNOBS = ("ER_STREAM_SPEC_FORM", "ER_STREAM_KEEP", "ER_STREAM_WAVES", "ER_STREAM_TRACERS", "ER_STREAM_ADAPT")
+
+
+def stream_form(tiles, blocks=256, light_query=0, tri_count=100000, flags=0):
+    lib = abi.load()
+    f = abi.ErStreamForm()
+    assert lib.er_debug_stream_form(tiles, blocks, light_query, tri_count, flags, C.byref(f)) == abi.ER_OK
+    return f.waves, f.tracers, bool(f.adapt), bool(f.keep), bool(f.spec)
+
+
+def test_stream_form_follows_the_owned_pixels_per_cu(monkeypatch):
+    """The streaming kernel's form for a share (er_stream_host.cpp stream_choose_form; host code, a pure function of the share, the
+    workgroups, the light query, the triangle count and the flags): the table of er_stream.h and DESIGN.md section 5, on 256 workgroups,
+    where a share of t tiles is t / 4 pixels per CU.  The boundaries belong to the small side (`<=`)."""
+    for k in STREAM_FORM_KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    # the shares of a 1080p frame (32 400 tiles): whole, 1/2, 1/4, 1/8, 1/16
+    want = {1: (16, 13, False, False), 2: (16, 13, True, False), 4: (16, 13, True, True), 8: (12, 10, True, True), 16: (12, 9, True, True)}
+    for world, (waves, tracers, keep, spec) in want.items():
+        w, t, adapt, k, s = stream_form(32400 // world)
+        assert (w, t, k, s) == (waves, tracers, keep, spec), (world, w, t, k, s)
+        assert adapt == (32400 // world * 64 // 256 >= 4096), world
+    # a light query or a scene beyond 4 000 000 triangles: 12 tracers of 16 instead of 13; the 12-wave forms keep their split
+    assert stream_form(32400, light_query=1)[:2] == (16, 12)
+    assert stream_form(32400, tri_count=4000001)[:2] == (16, 12)
+    assert stream_form(32400, tri_count=4000000)[:2] == (16, 13)
+    assert stream_form(32400 // 8, light_query=1)[:2] == (12, 10)
+    assert stream_form(32400 // 16, tri_count=4000001)[:2] == (12, 9)
+    # adapt: from 4 096 pixels per CU (4 x ER_STREAM_SLOTS) up, and never in the instrumented kernel of ER_FLAG_COUNTERS
+    px = lambda p: stream_form(4 * p)      # p pixels per CU on 256 workgroups
+    assert px(4096)[2] and not px(4095)[2]
+    assert not stream_form(4 * 4096, flags=abi.FLAG_COUNTERS)[2] and not stream_form(32400, flags=abi.FLAG_COUNTERS)[2]
+    assert stream_form(32400, flags=abi.FLAG_COUNTERS)[:2] == (16, 13)
+    # ER_STREAM_KEEP_SHARE 6 000, ER_STREAM_SPEC_SHARE 2 304, ER_STREAM_SMALL_SHARE 1 152, ER_STREAM_TEN_TRACERS_SHARE 704
+    assert px(6000)[3] and not px(6001)[3]
+    assert px(2304)[4] and not px(2305)[4]
+    assert px(1152)[:2] == (12, 10) and px(1153)[:2] == (16, 13)
+    assert px(704)[:2] == (12, 9) and px(705)[:2] == (12, 10)
+    # the pixels per CU are tiles x 64 / workgroups, rounded down
+    assert stream_form(4 * 1152 + 3)[0] == 12 and stream_form(1152 * 2, blocks=128)[0] == 12 and stream_form(1153 * 2, blocks=128)[0] == 16
+    assert abi.load().er_debug_stream_form(100, 0, 0, 1, 0, C.byref(abi.ErStreamForm())) == abi.ER_ERR_INVALID_ARG
+
+
 @pytest.mark.parametrize("edge", [0, 1, 8, 16, 32, 100])
 @pytest.mark.parametrize("frame", [(240, 135, 1, 0), (480, 270, 1, 0), (240, 135, 8, 3), (37, 5, 1, 0), (240, 135, 128, 37)])
 def test_stream_deal_is_a_levelled_partition_of_the_owned_tiles(frame, edge):
-    """The streaming schedule's deal of tiles to workgroups (er_stream.hip er_stream_deal_tiles; host code): every owned tile goes to
+    """The streaming schedule's deal of tiles to workgroups (er_stream_host.cpp er_stream_deal_tiles; host code): every owned tile goes to
     exactly one workgroup, the eight XCDs (workgroups b, b + 8, ...) get tile counts that differ by at most one whatever the
     super-tile edge (round 4: whole super-tiles had left them up to one super-tile apart, and a launch lasts as long as its fullest
     XCD), and the workgroups of an XCD differ by at most one tile."""

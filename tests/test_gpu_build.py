@@ -113,7 +113,9 @@ def test_a_failed_default_device_build_falls_back_to_the_host_build(capfd):
     """The device builder is the default from 20 000 triangles up; if it does not deliver (simulated: er_debug_set_gpu_build_failure) the
     call still does -- the host builder takes over and the image is the same -- SILENTLY when the device was out of memory, with one
     line on stderr when the builder itself failed (a builder fault must not pass for an OOM); if the caller had forced the
-    device build its failure is the call's: ER_ERR_HIP / ER_ERR_OOM with the reason."""
+    device build its failure is the call's: ER_ERR_HIP / ER_ERR_OOM with the reason.  A device build that DELIVERS a wide tree deeper than the
+    traversal stacks (kind 3: ER_STACK8 + 1 levels) is refused like a host-built one, with or without the flag: ER_ERR_STATE, and no
+    fall-back -- the host builder makes the same tree."""
     lib = abi.load()
     sc = scenes.soup(30000, 120, 88, seed=8, hdri_size=(128, 64))
     ref = gpu_render(sc, 3, max_bounces=8)
@@ -132,6 +134,13 @@ def test_a_failed_default_device_build_falls_back_to_the_host_build(capfd):
             with pytest.raises(abi.ErError) as e:
                 rm.start_rendering(sc)
             assert e.value.code == code and "simulated failure" in str(e.value)
+            rm.close()
+        lib.er_debug_set_gpu_build_failure(3)
+        for flags in (0, abi.FLAG_GPU_BUILD):
+            rm = render.RenderingManager(render.RenderParameters(max_bounces=8, flags=flags))
+            with pytest.raises(abi.ErError) as e:
+                rm.start_rendering(sc)
+            assert e.value.code == abi.ER_ERR_STATE and "ER_STACK8" in str(e.value), str(e.value)
             rm.close()
     finally:
         lib.er_debug_set_gpu_build_failure(0)

@@ -467,8 +467,8 @@ def test_two_threads_reading_two_passes_of_one_scene_each_get_their_own():
 
 
 def test_adaptive_tracer_shader_split_does_not_change_the_image(monkeypatch, capfd):
-    """After a completed call the library may turn one tracer wave of the streaming kernel into a shader wave (er_stream_adapt in
-    csrc/er_api.cpp: two consecutive calls whose tracer lanes were under 0.85 full).  Whatever it decides, the planes are those of a
+    """After a completed call the library may turn one tracer wave of the streaming kernel into a shader wave (stream_adapt in
+    csrc/er_stream_host.cpp: two consecutive calls whose tracer lanes were under 0.85 full).  Whatever it decides, the planes are those of a
     fixed split: a frame of 1.06 M pixels in three calls with the adaptation on == the same calls at a fixed 12 + 4 and at a fixed
     10 + 6.  The lane occupancy itself is a measurement that depends on clocks, so nothing is asserted on it: the mechanism is DRIVEN
     with a forced reading (ER_STREAM_FORCE_BUSY=0.70) and the sequence of splits it must produce is exact -- no change after the first
@@ -569,7 +569,7 @@ def test_deal_is_decided_by_counted_work_and_the_image_does_not_change(monkeypat
     """The streaming schedule starts a render on the default deal of 8 x 8-tile screen regions per XCD and keeps a deal of 16 x 16-tile
     regions (better L2 locality on frames of even cost) beside it.  During the first call the kernel adds every finished path's length to
     its tile's sum, and after it the library takes the large regions iff the XCDs' shares of that COUNTED work under them are within
-    ER_STREAM_COST_SPREAD_MAX of each other (csrc/er_api.cpp er_stream_adapt, csrc/er_stream.h): a decision made from counts -- the
+    ER_STREAM_COST_SPREAD_MAX of each other (csrc/er_stream_host.cpp stream_adapt, csrc/er_stream.h): a decision made from counts -- the
     same on every run of the same frame, unlike round 4's, which hung on the XCDs' measured finish times.  A soup seen from far away --
     geometry in the middle of the frame, sky around it -- is a frame of uneven cost: the verbose line must say that the default deal
     stays, with the same figure on a second run; with the limit raised the large regions are taken after the first call; and the planes
@@ -721,7 +721,7 @@ def test_pixels_behind_keep_their_slots_and_the_image_does_not_change(ext, monke
 
 
 def test_a_share_of_a_1080p_frame_gets_the_form_made_for_its_size():
-    """Round 6 (csrc/er_api.cpp, er_stream.h): the streaming kernel has three forms and two wave counts, picked by a rank's owned pixels per CU --
+    """Round 6 (csrc/er_stream_host.cpp, er_stream.h): the streaming kernel has three forms and two wave counts, picked by a rank's owned pixels per CU --
     the whole frame (8 100): form 0, 16 waves, 13 tracers (round 5's code); a half (4 050): form 1 (pixels that are behind keep their slots); a
     quarter (2 025): form 2 (that and speculative samples), 16 waves; an eighth (1 012): form 2 in 12 waves, 10 of them tracers; a sixteenth
     (506): 9 tracers.  A scene of fewer than 1 000 triangles starts no speculative samples whatever its share."""
