@@ -1,6 +1,6 @@
 // er_oracle.cpp -- CPU restatement of ElevenRender's per-sample path (renderingKernel and
 // everything it calls), written from reading the reference source.  TEST INFRASTRUCTURE ONLY;
-// PARITY UNPINNED (see er_oracle.h).  Every function cites the reference lines it follows
+// pinned to the reference's own code by tests/golden/reference_*.npz (see er_oracle.h).  Every function cites the reference lines it follows
 // (paths relative to the reference tree).
 //
 // Arithmetic rules kept from the reference: IEEE binary32 throughout, no FMA contraction

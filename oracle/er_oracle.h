@@ -4,12 +4,15 @@
  * include, link or call this.  Only tests/, __graft_entry__.smoke() and bench.py's
  * cpu_baseline leg load it -- as the checker / CPU baseline, never as the thing shipped.
  *
- * PARITY UNPINNED: the reference (101001000/ElevenRender) has no tests, golden vectors or
- * fixtures for this path, and its sources cannot be compiled in this image (they need a
- * SYCL toolchain + Boost; stand-in headers are not allowed).  This oracle is therefore a
- * line-by-line restatement of the reference algorithm from reading its source, pinned only
- * by published known-answer values of the public algorithms it uses (Jenkins OAAT,
- * Marsaglia xorshift32) and by analytic properties; see DESIGN.md "Oracle".
+ * The reference (101001000/ElevenRender) has no tests, golden vectors or fixtures for this
+ * path.  This oracle is a line-by-line restatement of the reference algorithm from reading
+ * its source.  On the default path (flags 0) it is PINNED to the reference's own code: the
+ * reference's per-sample sources, compiled on the host (`make ref`, ref_driver.cpp, stand-in
+ * third-party headers in ref_shim/), recorded tests/golden/reference_*.npz, and
+ * tests/test_reference_kat_cpu.py requires every function-level entry point below and whole
+ * renders of two scenes to equal them bit for bit in both math modes.  PARITY UNPINNED
+ * remains: the build-defined extensions (flags), SYCL device math versus libm, scene and
+ * texture loading; see DESIGN.md "Oracle".
  */
 #ifndef ER_ORACLE_H
 #define ER_ORACLE_H

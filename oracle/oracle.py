@@ -1,7 +1,7 @@
 """ctypes binding of the CPU oracle (oracle/liberoracle.so).
 
 TEST INFRASTRUCTURE ONLY -- imported by tests/, __graft_entry__.smoke() and bench.py's
-cpu_baseline leg; never by the product package.  PARITY UNPINNED, see er_oracle.h.
+cpu_baseline leg; never by the product package.  Pinned to the reference's own code on the default path, see er_oracle.h.
 """
 import ctypes as C
 import os

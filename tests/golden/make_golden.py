@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Regenerates tests/golden/*.npz from the CPU oracle (er_math mode).
 
-These are REGRESSION vectors of this repository's oracle, not reference outputs: the
-reference cannot be built or run in this image (DESIGN.md "Oracle"), and it ships no
-vectors of its own.  Each file stores the complete inputs next to the expected outputs,
+These are REGRESSION vectors of this repository's oracle, not reference outputs (those are
+reference_*.npz, recorded by make_golden_reference.py from the reference's own code:
+DESIGN.md "Oracle").  Each file stores the complete inputs next to the expected outputs,
 so the tests never depend on regenerating inputs bit for bit.
 Usage: python tests/golden/make_golden.py
 """

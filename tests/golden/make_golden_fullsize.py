@@ -3,8 +3,8 @@
 all 10 M triangles) of 8 whole rows of BASELINE config 4 at 3840x2160, 2 spp, 8 bounces -- the window that
 tests/test_gpu_fullsize_oracle.py compares the HIP path with on the GPU box.
 
-A regression vector of this repository's oracle, not a reference output (the reference cannot be built here and ships no
-vectors: DESIGN.md 1, parity unpinned).  The scene is NOT stored (1.4 GB of arrays); its generator is committed
+A regression vector of this repository's oracle, not a reference output (the reference's own vectors are reference_*.npz, at
+32 x 32: DESIGN.md 1).  The scene is NOT stored (1.4 GB of arrays); its generator is committed
 (elevenrender_amd/scenes.py blob_instances) and the file carries the sha256 of the arrays it was made for.
 Usage: python tests/golden/make_golden_fullsize.py      (about a minute: one 16 s reference-style build + 8 rows)
 """

@@ -9,8 +9,9 @@ GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MAT_FIELDS = [(n, t) for n, t in abi.ErMaterial._fields_]
 
 
-def load(name):
-    z = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
+def scene_from(z, prefix=""):
+    """The SceneData stored in an opened .npz under the array names of make_golden.py's dump(), each with `prefix` in front."""
+    z = _Prefixed(z, prefix) if prefix else z
     mats = []
     for row in z["materials"]:
         m = abi.ErMaterial()
@@ -39,4 +40,21 @@ def load(name):
     x_res, y_res, spp, max_bounces = (int(v) for v in z["res"])
     sc = abi.SceneData(z["vertices"], z["normals"], z["tangents"], z["uvs"], z["tangent_sign"], z["material_id"], mats,
                        textures=textures, hdri=(z["hdri"], hw, hh, hch, hflt), camera=cam, x_res=x_res, y_res=y_res)
+    return sc, spp, max_bounces
+
+
+class _Prefixed:
+    def __init__(self, z, prefix):
+        self.z, self.prefix = z, prefix
+
+    def __getitem__(self, k):
+        return self.z[self.prefix + k]
+
+    def __contains__(self, k):
+        return (self.prefix + k) in self.z
+
+
+def load(name):
+    z = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
+    sc, spp, max_bounces = scene_from(z)
     return sc, spp, max_bounces, z

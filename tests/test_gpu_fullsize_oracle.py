@@ -12,7 +12,7 @@ product's own tree, its LDS-resident top levels and its pixel rings have their r
       samples -- equal to the oracle's over exactly those pixels.
 
 C4 also checks the window against tests/golden/c4_fullsize_rows.npz, generated in the build container by
-tests/golden/make_golden_fullsize.py (the oracle's output: parity unpinned like every vector here).
+tests/golden/make_golden_fullsize.py (the oracle's output, not the reference's: DESIGN.md 1).
 """
 import os
 

@@ -8,7 +8,7 @@ atan2f/powf/logf, i.e. what a CPU build of the reference computes -- under the i
 
 A 1-ulp difference in one transcendental can send a path into another HDRI texel or past a triangle edge, after which that
 pixel's sample is a different (equally valid) sample: such pixels are the < 0.5 % the tolerance allows, and the deeper the paths
-the more of them there are.  Parity stays "unpinned" (the reference holds no vectors); what this adds is independence from the
+the more of them there are.  (The reference's own vectors are in tests/test_gpu_reference_kat.py, at fixture size.)  What this adds is independence from the
 shared header on every scene family of the suite, not only on the 128x128 Cornell frame.
 """
 import numpy as np

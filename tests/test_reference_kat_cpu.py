@@ -1,0 +1,238 @@
+"""The oracle against vectors recorded from the REFERENCE's own code (tests/golden/reference_*.npz, written by
+tests/golden/make_golden_reference.py from oracle/_ref/ref_libm and ref_er -- the reference's sources compiled on the host).
+
+oracle/er_oracle.cpp is a restatement of the reference from reading it; these tests pin what a restatement gets wrong silently:
+operation order, a double literal in a float expression, the order of RNG draws, the side of a `<` a tie falls on.  Every
+function-level entry point in MATH_LIBM equals `*_libm` and in MATH_ER equals `*_er`, bit for bit (NaN matching NaN), and so do
+whole renders of the two golden scenes: every plane, the sample counts and the RNG states.  No tolerances: ref_er is the
+reference's algorithm with er_math.h's six functions plugged in underneath, which is what MATH_ER claims to be."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+from elevenrender_amd import abi
+from golden_util import GOLDEN_DIR, load, scene_from
+
+import sys
+sys.path.insert(0, GOLDEN_DIR)
+import make_golden_reference as gen  # noqa: E402
+
+MODES = ["libm", "er"]
+_FP = C.POINTER(C.c_float)
+
+
+def fp(a):
+    return a.ctypes.data_as(_FP)
+
+
+def same(a, b):
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+
+
+def first_bad(ok):
+    return np.argwhere(~np.asarray(ok))[:5].tolist()
+
+
+@pytest.fixture(scope="module")
+def fx():
+    z = np.load(os.path.join(GOLDEN_DIR, "reference_functions.npz"), allow_pickle=False)
+    return {k: z[k] for k in z.files}
+
+
+@pytest.fixture(scope="module")
+def rig(fx):
+    sc, _, _ = scene_from(fx, "rig_")
+    return sc
+
+
+def mode_of(oracle_mod, m):
+    return oracle_mod.MATH_LIBM if m == "libm" else oracle_mod.MATH_ER
+
+
+def test_fixtures_hold_numbers_only():
+    for name in gen.FIXTURES:
+        path = os.path.join(GOLDEN_DIR, name + ".npz")
+        assert os.path.getsize(path) < gen.MAX_BYTES
+        z = np.load(path, allow_pickle=False)
+        for k in z.files:
+            assert z[k].dtype.kind in "fiu", (name, k, z[k].dtype)
+            if not k.startswith(("rig_", "pass_", "samples_", "rng_", "spp", "max_bounces")) and not k.endswith(("_libm", "_er")):
+                assert k in ("rng_idx", "cam_items", "trihit_items", "disney_items", "disney_rs", "sph_p", "rev_uv", "texfetch_items",
+                             "hdri_search_vals", "hdri_pdf_xy", "closest_o", "closest_d", "graze_o", "graze_d", "graze_index"), k
+
+
+def test_rng_streams(oracle_mod, fx):
+    L = oracle_mod.lib()
+    for m in MODES:     # (no transcendental in the generator: both recordings have to be the one stream)
+        for k, i in enumerate(fx["rng_idx"]):
+            st, va = np.zeros(16, np.uint32), np.zeros(16, np.float32)
+            L.oracle_rng_stream(int(i), 16, st.ctypes.data_as(C.POINTER(C.c_uint32)), fp(va))
+            assert (st == fx["rng_states_" + m][k]).all(), (m, i)
+            assert same(va, fx["rng_values_" + m][k]).all(), (m, i)
+
+
+@pytest.mark.parametrize("m", MODES)
+def test_camera_rays(oracle_mod, fx, rig, m):
+    L = oracle_mod.lib()
+    items = fx["cam_items"]
+    got = np.zeros((len(items), 6), np.float32)
+    for k, it in enumerate(items):
+        o, d = (C.c_float * 3)(), (C.c_float * 3)()
+        L.oracle_camera_ray(C.byref(rig.camera), rig.x_res, rig.y_res, int(it[0]), int(it[1]), (C.c_float * 5)(*it[2:].tolist()),
+                            mode_of(oracle_mod, m), o, d)
+        got[k] = list(o) + list(d)
+    ok = same(got, fx["cam_rays_" + m]).all(1)
+    assert ok.all(), first_bad(ok)
+
+
+def test_tri_hit_records(oracle_mod, fx, rig):
+    L = oracle_mod.lib()
+    items = fx["trihit_items"]
+    tri = items[:, 0].copy().view(np.int32)
+    V, N, T, U = rig.vertices.reshape(-1, 9), rig.normals.reshape(-1, 9), rig.tangents.reshape(-1, 9), rig.uvs.reshape(-1, 6)
+    okf = np.zeros(len(items), np.int32)
+    rec = np.zeros((len(items), 17), np.float32)
+    for k in range(len(items)):
+        t = int(tri[k])
+        okf[k] = L.oracle_tri_hit(fp(np.ascontiguousarray(V[t])), fp(np.ascontiguousarray(N[t])), fp(np.ascontiguousarray(T[t])),
+                                  fp(np.ascontiguousarray(U[t])), float(rig.tangent_sign[t]), fp(np.ascontiguousarray(items[k, 1:4])),
+                                  fp(np.ascontiguousarray(items[k, 4:7])), fp(rec[k]))
+    for m in MODES:
+        assert (okf == fx["trihit_ok_" + m]).all(), (m, first_bad(okf == fx["trihit_ok_" + m]))
+        hit = okf == 1
+        ok = same(rec[hit], fx["trihit_rec_" + m][hit]).all(1)
+        assert ok.all(), (m, first_bad(ok))
+    assert len(items) // 2 < hit.sum() < len(items)        # hits and misses both
+
+
+@pytest.mark.parametrize("m", MODES)
+def test_closest_hit_of_throw_ray(oracle_mod, fx, m):
+    sc, _, _, _ = load(gen.TRACE_SCENE)
+    o = oracle_mod.Oracle(sc, math_mode=mode_of(oracle_mod, m))
+    tri, pos = o.closest_hit(fx["closest_o"], fx["closest_d"])
+    gtri, gpos = o.closest_hit(fx["graze_o"], fx["graze_d"])
+    o.close()
+    assert (tri == fx["closest_tri_" + m]).all(), first_bad(tri == fx["closest_tri_" + m])
+    ok = same(pos, fx["closest_pos_" + m]).all(1)
+    assert ok.all(), first_bad(ok)
+    assert 0.3 < (tri >= 0).mean() < 1.0
+    # the box-corner rays: the reference's tree drops the nearest triangle there, and so must its restatement
+    assert len(gtri) > 0 and (fx["graze_tri_" + m] != fx["graze_alltri_" + m]).all()
+    assert (gtri == fx["graze_tri_" + m]).all() and same(gpos, fx["graze_pos_" + m]).all()
+
+
+@pytest.mark.parametrize("m", MODES)
+def test_brute_force_traversal_gives_the_hit_the_reference_tree_drops(oracle_mod, fx, m):
+    """TRAV_BRUTE is the reference's Tri::hit over every triangle: on the box-corner rays it finds what the tree dropped, elsewhere the same."""
+    sc, _, _, _ = load(gen.TRACE_SCENE)
+    o = oracle_mod.Oracle(sc, math_mode=mode_of(oracle_mod, m), traversal=oracle_mod.TRAV_BRUTE)
+    tri, pos = o.closest_hit(fx["closest_o"], fx["closest_d"])
+    gtri, gpos = o.closest_hit(fx["graze_o"], fx["graze_d"])
+    o.close()
+    assert (tri == fx["closest_tri_" + m]).all() and same(pos, fx["closest_pos_" + m]).all()
+    assert (gtri == fx["graze_alltri_" + m]).all() and same(gpos, fx["graze_allpos_" + m]).all()
+
+
+@pytest.mark.parametrize("m", MODES)
+def test_disney_eval_pdf_sample(oracle_mod, fx, m):
+    L = oracle_mod.lib()
+    mode = mode_of(oracle_mod, m)
+    it, rs = fx["disney_items"], fx["disney_rs"]
+    n = len(it)
+    ev, pd, sm = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
+    for k in range(n):
+        row = np.ascontiguousarray(it[k])
+        hd, V, N, Lv = fp(row[:20].copy()), fp(row[20:23].copy()), fp(row[23:26].copy()), fp(row[26:29].copy())
+        L.oracle_disney_eval(hd, V, N, Lv, mode, fp(ev[k]))
+        pd[k] = L.oracle_disney_pdf(hd, V, N, Lv, mode)
+        L.oracle_disney_sample(hd, V, N, float(rs[k, 0]), float(rs[k, 1]), float(rs[k, 2]), mode, fp(sm[k]))
+    for name, got in (("disney_eval_", ev), ("disney_pdf_", pd), ("disney_sample_", sm)):
+        ok = same(got, fx[name + m])
+        assert ok.all(), (name, first_bad(ok))
+    assert (pd[::7] == 1.0).all() and (ev[::7] == 0.0).all()      # L below the horizon
+
+
+@pytest.mark.parametrize("m", MODES)
+def test_spherical_mappings(oracle_mod, fx, m):
+    L = oracle_mod.lib()
+    mode = mode_of(oracle_mod, m)
+    p, uvs = fx["sph_p"], fx["rev_uv"]
+    uv = np.zeros((len(p), 2), np.float32)
+    for k in range(len(p)):
+        u, v = C.c_float(), C.c_float()
+        L.oracle_spherical_mapping(fp(np.ascontiguousarray(p[k])), mode, C.byref(u), C.byref(v))
+        uv[k] = u.value, v.value
+    ok = same(uv, fx["sph_uv_" + m]).all(1)
+    assert ok.all(), first_bad(ok)
+    rev = np.zeros((len(uvs), 3), np.float32)
+    for k in range(len(uvs)):
+        L.oracle_reverse_spherical_mapping(float(uvs[k, 0]), float(uvs[k, 1]), mode, fp(rev[k]))
+    ok = same(rev, fx["rev_p_" + m]).all(1)
+    assert ok.all(), first_bad(ok)
+
+
+def _tex(rig, tid):
+    data, w, h, ch, flt = rig.hdri if tid < 0 else rig.textures[tid]
+    return abi.ErTexture(w, h, ch, flt, abi._fptr(data))
+
+
+def test_texture_fetches(oracle_mod, fx, rig):
+    L = oracle_mod.lib()
+    it = fx["texfetch_items"]
+    tids = it[:, 0].copy().view(np.int32)
+    got = np.zeros((len(it), 3), np.float32)
+    for k in range(len(it)):
+        L.oracle_texture_fetch(C.byref(_tex(rig, int(tids[k]))), float(it[k, 1]), float(it[k, 2]), int(it[k, 3]), fp(got[k]))
+    assert {rig.textures[t][3] if t >= 0 else rig.hdri[3] for t in set(tids.tolist())} == {1, 2, 3}      # channel counts covered
+    for m in MODES:
+        ok = same(got, fx["texfetch_" + m]).all(1)
+        assert ok.all(), (m, first_bad(ok))
+
+
+@pytest.mark.parametrize("m", MODES)
+def test_hdri_cdf_search_pdf(oracle_mod, fx, rig, m):
+    L = oracle_mod.lib()
+    tex = _tex(rig, -1)
+    w, h = rig.hdri[1], rig.hdri[2]
+    cdf = np.zeros(w * h + 1, np.float32)
+    rsum = C.c_float()
+    L.oracle_hdri_cdf(C.byref(tex), fp(cdf), C.byref(rsum))
+    assert same(cdf, fx["hdri_cdf_" + m]).all() and same(np.float32(rsum.value), fx["hdri_rsum_" + m]).all()
+    vals = fx["hdri_search_vals"]
+    got = np.array([L.oracle_hdri_binary_search(fp(cdf), float(v), w * h) for v in vals], np.int32)
+    assert (got == fx["hdri_search_" + m]).all(), first_bad(got == fx["hdri_search_" + m])
+    xy = fx["hdri_pdf_xy"]
+    pdf = np.array([L.oracle_hdri_pdf(C.byref(tex), rsum.value, int(x), int(y), mode_of(oracle_mod, m)) for x, y in xy], np.float32)
+    ok = same(pdf, fx["hdri_pdf_" + m])
+    assert ok.all(), first_bad(ok)
+    assert not np.isfinite(fx["hdri_pdf_" + m][:4]).any()          # row 0: inf / NaN recorded, and matched
+
+
+@pytest.mark.parametrize("m", MODES)
+@pytest.mark.parametrize("name", ["cornell_32x32", "torture_300tri_32x24"])
+def test_whole_path_render(oracle_mod, name, m):
+    sc, _, _, _ = load(name + "_4spp")
+    z = np.load(os.path.join(GOLDEN_DIR, f"reference_{name}.npz"), allow_pickle=False)
+    o = oracle_mod.Oracle(sc, math_mode=mode_of(oracle_mod, m), max_bounces=int(z["max_bounces"][0]))
+    o.render(int(z["spp"][0]))
+    for pname, p in abi.PASS_NAMES.items():
+        ok = same(o.read_pass(p), z[f"pass_{pname}_{m}"]).all(-1)
+        assert ok.all(), (pname, int((~ok).sum()), first_bad(ok))
+    assert (o.read_samples() == z["samples_" + m]).all() and (o.read_rng() == z["rng_" + m]).all()
+    o.close()
+
+
+def test_fixtures_are_what_the_reference_gives_today(tmp_path):
+    """Freshness: wherever the reference has been built (oracle/_ref/), the generator run again gives the committed arrays."""
+    if not gen.available():
+        pytest.skip("oracle/_ref/ is absent: the reference's sources are not on this machine, nothing to record from")
+    gen.main(str(tmp_path))
+    for name in gen.FIXTURES:
+        a = np.load(os.path.join(GOLDEN_DIR, name + ".npz"), allow_pickle=False)
+        b = np.load(os.path.join(str(tmp_path), name + ".npz"), allow_pickle=False)
+        assert sorted(a.files) == sorted(b.files), name
+        for k in a.files:
+            assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), (name, k)
