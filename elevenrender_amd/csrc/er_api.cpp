@@ -603,6 +603,8 @@ int begin_descriptor(ErScene* s, const ErGpuBvhDevice& g, const TexResult& tex, 
         D.tex_pow2 = all ? 1u : 0u;
         if (const char* e = getenv("ER_TEX_POW2")) D.tex_pow2 = (atoi(e) != 0 && all) ? 1u : 0u;      // A/B knob: 0 = always the division
     }
+    D.trace_every_query = 0u;      // (test and A/B knob: 1 = shadow queries whose two outcomes are the same addend are traced as well, er_bounce.inc)
+    if (const char* e = getenv("ER_TRACE_EVERY_QUERY")) D.trace_every_query = atoi(e) != 0 ? 1u : 0u;
     D.ext_flags = s->params.flags & (ER_FLAG_POINT_LIGHTS | ER_FLAG_MIS);
     D.lights = s->d_lights.p;
     D.light_count = (uint32_t)s->point_lights.size();

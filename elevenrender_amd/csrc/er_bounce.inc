@@ -5,6 +5,8 @@
 //   COUNT, EXT          compile-time bools (EXT = false compiles the extensions out)
 //   ER_BOUNCE_FUSE      macro, optional (default true): a compile-time bool; false compiles the fused-texel fetch of generate_hit_data out
 //   ER_BOUNCE_MESH      macro, optional (default false): a compile-time bool; true compiles ER_FLAG_MESH_LIGHTS in (needs EXT)
+//   ER_BOUNCE_SKIP_EQUAL macro, optional (default true): a compile-time bool; false hands every shadow query to the hooks even when its
+//                       two outcomes are the same addend (the debug pixel trace: its records are compared with the oracle's, which always traces)
 //   S                   the DevScene
 //   Ray      ray        in: the ray that was traced; out: the continuation ray (unchanged when it left the scene)
 //   int      hslot      its closest hit (triangle slot), or < 0
@@ -30,7 +32,15 @@
 #ifndef ER_BOUNCE_FUSE
 #define ER_BOUNCE_FUSE true
 #endif
+#ifndef ER_BOUNCE_SKIP_EQUAL
+#define ER_BOUNCE_SKIP_EQUAL true
+#endif
 {
+    // A shadow query only selects one of two addends that are both known before it is traced.  Where the two are the same bits the verdict
+    // cannot change `light`, and the query is not issued: the addend is added at once.  The common case is a dead path -- `reduction` exactly
+    // (0, 0, 0) after a bounce whose DisneyEval was zero (a back-facing hit) -- which still has to trace its closest-hit rays (their hits
+    // decide how many numbers the sample draws) but none of its shadow rays.  DevScene::trace_every_query (a scalar load) switches the rule off.
+    const bool er_skip_equal = (ER_BOUNCE_SKIP_EQUAL) && S.trace_every_query == 0u;
     const int hw = S.hdri_tex.width, hh = S.hdri_tex.height;
     const bool er_mis = EXT && (S.ext_flags & ER_FLAG_MIS) != 0;
 #ifdef ER_BOUNCE_MESH
@@ -97,7 +107,7 @@
             float absdot = __builtin_fabsf(dot(wihdri, N));
             // The reference always traces the shadow ray (src/kernel.cpp:555-562); a hit on another triangle zeroes
             // hdriValue.  Both outcomes are computed here with the reference's expression; when the BRDF term is
-            // exactly zero they coincide and the query is skipped.
+            // exactly zero, or the two addends are the same bits for another reason, they coincide and the query is skipped.
             float er_wnee = 1.0f;
             if (er_mis) er_wnee = 1.0f / (1.0f + DisneyPdf(hd, wo, N, wihdri) / hdripdf);   // balance heuristic, NEE direction
             F3 er_em = hd.emission;
@@ -115,10 +125,10 @@
             }
             F3 c_vis = er_mis ? reduction * (er_em + (hdriValue * evalh * absdot / hdripdf) * er_wnee)
                               : reduction * (er_em + hdriValue * evalh * absdot / hdripdf);
-            if (evalh.x != 0.0f || evalh.y != 0.0f || evalh.z != 0.0f) {
+            const F3 c_occ = er_mis ? reduction * (er_em + (f3s(0) * evalh * absdot / hdripdf) * er_wnee)
+                                    : reduction * (er_em + f3s(0) * evalh * absdot / hdripdf);
+            if ((evalh.x != 0.0f || evalh.y != 0.0f || evalh.z != 0.0f) && !(er_skip_equal && same_bits(c_vis, c_occ))) {
                 // shadow query needed: occluded iff the closest hit is another triangle
-                F3 c_occ = er_mis ? reduction * (er_em + (f3s(0) * evalh * absdot / hdripdf) * er_wnee)
-                                  : reduction * (er_em + f3s(0) * evalh * absdot / hdripdf);
                 Ray sr = make_ray(hd.position + N * 0.001f, wihdri);
                 F3 v0, v1, v2;
                 float4 qa, qb, qc4;
@@ -147,8 +157,14 @@
                 // a light whose BRDF term is exactly zero (below the shading normal's horizon) is skipped: no ray, no addition
                 if (er_evall.x != 0.0f || er_evall.y != 0.0f || er_evall.z != 0.0f) {
                     const F3 er_pl = er_value * er_evall * __builtin_fabsf(dot(er_dir, N)) / er_lpdf;   // :299-300
-                    ER_BOUNCE_LIGHT_QUERY(er_lr, -1, er_limit, reduction * er_pl, reduction * f3s(0));
-                    lpending = true;
+                    const F3 er_lv = reduction * er_pl, er_lo = reduction * f3s(0);
+                    // (the same addend either way: added now, which is its place -- after the HDRI term -- only if that term is in `light` already)
+                    if (er_skip_equal && !pending && same_bits(er_lv, er_lo)) {
+                        light = light + er_lv;
+                    } else {
+                        ER_BOUNCE_LIGHT_QUERY(er_lr, -1, er_limit, er_lv, er_lo);
+                        lpending = true;
+                    }
                 }
             }
             if (er_mesh && bounce + 1u < S.max_bounces) {
@@ -181,9 +197,14 @@
                         const float er_lpdf = mesh_prob(S)[er_k] * (er_dist * er_dist) / (er_area * __builtin_fabsf(er_cosl));
                         const float er_wl = 1.0f / (1.0f + DisneyPdf(hd, wo, N, er_dir) / er_lpdf);
                         const F3 er_ml = er_le * er_evall * __builtin_fabsf(dot(er_dir, N)) / er_lpdf * er_wl;
-                        const Ray er_lr = make_ray(hd.position + er_dir * 0.001f, er_dir);
-                        ER_BOUNCE_LIGHT_QUERY(er_lr, (int)er_k, length(er_p - er_lr.o), reduction * er_ml, reduction * f3s(0));
-                        lpending = true;
+                        const F3 er_lv = reduction * er_ml, er_lo = reduction * f3s(0);
+                        if (er_skip_equal && !pending && same_bits(er_lv, er_lo)) {      // (as for a point light)
+                            light = light + er_lv;
+                        } else {
+                            const Ray er_lr = make_ray(hd.position + er_dir * 0.001f, er_dir);
+                            ER_BOUNCE_LIGHT_QUERY(er_lr, (int)er_k, length(er_p - er_lr.o), er_lv, er_lo);
+                            lpending = true;
+                        }
                     }
                 }
             }

@@ -84,6 +84,9 @@ struct DevScene {
     // camera_trig() below; cam_trig_valid = 0 makes camera_ray compute them itself (the other schedules' kernels leave it 0 or 1 alike)
     float cam_cx, cam_sx, cam_cy, cam_sy, cam_cz, cam_sz;
     uint32_t cam_trig_valid;
+    // 1 (ER_TRACE_EVERY_QUERY=1 at er_render_begin: test and A/B knob) makes the bounce step hand every shadow query to the tracers as it did
+    // before er_bounce.inc skipped those whose two outcomes are the same addend bit for bit; 0 in the product.  Wave-uniform.
+    uint32_t trace_every_query;
     // build-defined extensions (er_shade.h): ER_FLAG_POINT_LIGHTS / ER_FLAG_MIS / ER_FLAG_MESH_LIGHTS bits of the render flags.
     // The light the light-query record samples: the point lights, or -- ER_FLAG_MESH_LIGHTS set here, which er_render_begin does only
     // for a non-empty emitter table and never together with ER_FLAG_POINT_LIGHTS -- the emitter table of er_lights.h.  One pair of
@@ -133,6 +136,11 @@ ERD F3 operator*(F3 a, float s) { return f3(a.x * s, a.y * s, a.z * s); }
 ERD F3 operator*(float s, F3 a) { return f3(a.x * s, a.y * s, a.z * s); }
 ERD F3 operator/(F3 a, float s) { return f3(a.x / s, a.y / s, a.z / s); }
 ERD F3 operator*(F3 a, F3 b) { return f3(b.x * a.x, b.y * a.y, b.z * a.z); }
+// the same three words: what `==` would get wrong both ways (NaN of one payload is the same addend, +0 and -0 are not)
+ERD bool same_bits(F3 a, F3 b) {
+    return ((__builtin_bit_cast(uint32_t, a.x) ^ __builtin_bit_cast(uint32_t, b.x)) | (__builtin_bit_cast(uint32_t, a.y) ^ __builtin_bit_cast(uint32_t, b.y)) |
+            (__builtin_bit_cast(uint32_t, a.z) ^ __builtin_bit_cast(uint32_t, b.z))) == 0u;
+}
 ERD F3 addf(F3 a, float s) { return f3(a.x + s, a.y + s, a.z + s); }
 ERD float dot(F3 a, F3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 ERD F3 cross(F3 a, F3 b) {   // sign convention of src/Vector.h:173-175

@@ -91,6 +91,9 @@ StreamForm stream_choose_form(size_t tiles, uint32_t blocks, bool light_query, u
     // (textured materials started at 12 + 4 until their textures were fused / pre-powered / one-channel, er_render_begin: C5 without
     // lights now 1 712 vs 1 640 at 12 + 4; a textured scene whose shading step is still too long for 13 tracers reads < 0.85 full lanes
     // after its first call and gets 12)
+    // (swept again after er_bounce.inc stopped tracing the shadow queries of dead paths -- a shading step then yields 1.06 rays instead of
+    // 1.22 on C2 and the tracer lanes read 0.88 instead of 0.91 at 13 + 3 --: the same splits win, C2 2 026 vs 1 989 at 12 + 4, C5 without
+    // lights 1 925 vs 1 881, C5 with lights 1 771 at 12 + 4 vs 1 587, C4 1 784 vs 1 661; profiles/equal_queries_ab.log)
     const uint32_t large_tracers = (light_query || tri_count > 4000000u) ? 12u : 13u;
     f.tracers = large_tracers;
     // A workgroup that owns hardly more pixels than it has slots (an eighth of a 1080p frame: 1 012 pixels per CU) cannot fill 12 tracer
