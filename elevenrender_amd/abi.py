@@ -121,6 +121,57 @@ class ErStreamForm(C.Structure):   # include/eleven_hip_debug.h
     _fields_ = [("waves", C.c_uint32), ("tracers", C.c_uint32), ("adapt", C.c_uint32), ("keep", C.c_uint32), ("spec", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ErAccelDump(C.Structure):   # include/eleven_hip_debug.h: er_debug_read_accel / er_debug_bvh_dump
+    _fields_ = [("tri_count", C.c_uint32), ("node_count", C.c_uint32), ("node8_count", C.c_uint32), ("node8_pieces", C.c_uint32),
+                ("attr_pieces", C.c_uint32), ("max_depth", C.c_uint32), ("max_depth8", C.c_uint32), ("builder", C.c_uint32),
+                ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("lift_bound", C.c_float), ("max_lift", C.c_float)]
+
+
+# numpy mirrors of the structure's records (elevenrender_amd/csrc/er_bvh.h: ErNode, ErNode8, ErTriIsect, ErTriAttr)
+NODE_DTYPE = np.dtype([("lo0", "<f4", 3), ("hi0", "<f4", 3), ("lo1", "<f4", 3), ("hi1", "<f4", 3), ("c0", "<i4"), ("c1", "<i4"), ("pad", "<i4", 2)])
+NODE8_DTYPE = np.dtype([("p", "<f4", 3), ("e", "u1", 3), ("imask", "u1"), ("child_base", "<u4"), ("tri_base", "<u4"), ("tri_present", "<u4"),
+                        ("reserved", "<u4"), ("qlo", "u1", (3, 8)), ("qhi", "u1", (3, 8))])
+ISECT_DTYPE = np.dtype([("v0", "<f4", 3), ("tri_id", "<i4"), ("v1", "<f4", 3), ("lift", "<f4"), ("v2", "<f4", 3), ("sign", "<f4")])
+assert NODE_DTYPE.itemsize == 64 and NODE8_DTYPE.itemsize == 80 and ISECT_DTYPE.itemsize == 48
+
+
+def attr_dtype(pieces):
+    """ErTriAttr at a stride of `pieces` 16-byte pieces (ER_ATTR_PIECES: 7 packed, 8 one record per 128-byte line)."""
+    dt = np.dtype([("n", "<f4", (3, 3)), ("t", "<f4", (3, 3)), ("uv", "<f4", (3, 2)), ("material", "<i4"), ("pad", "<u4", 4 * pieces - 25)])
+    assert dt.itemsize == 16 * pieces
+    return dt
+
+
+def accel_dump_dict(info, **arrays):
+    """The Python form of an ErAccelDump and its arrays: what tests/accel_check.py takes."""
+    d = {n: int(getattr(info, n)) for n in ("tri_count", "node_count", "node8_count", "max_depth", "max_depth8", "builder")}
+    d["lo"], d["hi"] = np.array(list(info.lo), np.float32), np.array(list(info.hi), np.float32)
+    d["lift_bound"], d["max_lift"] = np.float32(info.lift_bound), np.float32(info.max_lift)
+    d.update(arrays)
+    return d
+
+
+def debug_bvh_dump(vertices, normals, threads=0):
+    """include/eleven_hip_debug.h er_debug_bvh_dump: the HOST builder's structure for [n][3][3] vertices / normals (no device needed) as
+    a dict: nodes (NODE_DTYPE), nodes8 (NODE8_DTYPE), slot_to_tri uint32[n], tri_lift float32[n] (per original triangle), lo, hi,
+    lift_bound, max_depth, max_depth8, counts."""
+    lib = load()
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3, 3)
+    nn = np.ascontiguousarray(normals, np.float32).reshape(-1, 3, 3)
+    assert v.shape == nn.shape
+    n = len(v)
+    info = ErAccelDump()
+    args = (_fptr(v), _fptr(nn), n, threads, C.byref(info))
+    check(lib.er_debug_bvh_dump(*args, None, 0, None, 0, None, 0, None, 0))
+    assert info.node8_pieces * 16 == NODE8_DTYPE.itemsize
+    nodes, nodes8 = np.zeros(info.node_count, NODE_DTYPE), np.zeros(info.node8_count, NODE8_DTYPE)
+    s2t, lift = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(lib.er_debug_bvh_dump(*args, vp(nodes), nodes.nbytes, vp(nodes8), nodes8.nbytes, s2t.ctypes.data_as(C.POINTER(C.c_uint32)), s2t.nbytes,
+                                _fptr(lift), lift.nbytes))
+    return accel_dump_dict(info, nodes=nodes, nodes8=nodes8, slot_to_tri=s2t, tri_lift=lift)
+
+
 class ErTraceRec(C.Structure):   # include/eleven_hip_debug.h; same layout as the oracle's OracleTraceRec
     _fields_ = [("bounce", C.c_int32), ("tri", C.c_int32), ("shadow_tri", C.c_int32), ("opaque", C.c_int32),
                 ("position", C.c_float * 3), ("wi", C.c_float * 3), ("light", C.c_float * 3), ("reduction", C.c_float * 3),
@@ -195,6 +246,9 @@ ABI_VERSION = 2     # include/eleven_hip.h ER_ABI_VERSION
 # older builds of the library (ELEVEN_HIP_LIB), which need not export the newest hooks.
 OPTIONAL_SYMBOLS = {
     "er_debug_stream_form": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(ErStreamForm)]),
+    "er_debug_read_accel": (C.c_int, [_P, C.POINTER(ErAccelDump), _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64]),
+    "er_debug_bvh_dump": (C.c_int, [_FP, _FP, C.c_uint32, C.c_int, C.POINTER(ErAccelDump), _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64,
+                                    _FP, C.c_uint64]),
 }
 
 

@@ -675,6 +675,8 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     s->accel.build_ms = (float)g.build_ms;
     s->accel.upload_ms = up_ms;
     s->accel.lift_bound = g.lift_bound;
+    for (int a = 0; a < 3; a++) { s->accel_lo[a] = g.lo[a]; s->accel_hi[a] = g.hi[a]; }
+    s->accel_depth2 = g.max_depth2;
     s->begun = true;
     return ER_OK;
 }

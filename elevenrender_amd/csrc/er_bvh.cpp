@@ -422,8 +422,12 @@ void er_build_bvh(const float* vertices, const float* normals, uint32_t tri_coun
             // computed position can sit a few ulp outside the exact vertex bounds
             float m = std::max(std::fabs(b.lo[a]), std::fabs(b.hi[a]));
             float pad = std::max(m * 4e-7f + 1e-37f, pad_abs);
+            // rounded OUTWARD: the rounding of the subtraction may take up to half an ulp of the coordinate back, 6 % of the
+            // absolute padding at the scene's far end; the box holds the padding in full (the differences are exact in double)
             p.lo[a] = b.lo[a] - pad;
             p.hi[a] = b.hi[a] + pad;
+            if ((double)p.lo[a] > (double)b.lo[a] - (double)pad) p.lo[a] = std::nextafterf(p.lo[a], -INFINITY);
+            if ((double)p.hi[a] < (double)b.hi[a] + (double)pad) p.hi[a] = std::nextafterf(p.hi[a], INFINITY);
             p.c[a] = (v[a] + v[3 + a] + v[6 + a]) * (1.0f / 3.0f);
         }
         p.id = i;

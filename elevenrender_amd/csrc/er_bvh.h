@@ -61,7 +61,11 @@ static_assert(sizeof(ErTriAttr) == 16 * ER_ATTR_PIECES, "attr record must be ER_
 
 // 8-wide compressed node (layout after Ylitie, Karras, Laine 2017, "Efficient incoherent ray traversal on
 // GPUs through compressed wide BVHs"): child boxes are 8-bit offsets from `p` in units of 2^e per axis,
-// quantised OUTWARD (decoded box always contains the float box), inner children are consecutive nodes from
+// quantised OUTWARD (decoded box always contains the float box -- "decoded" meaning, per axis, float(p + float(q * 2^(e - 127))):
+// the product is exact, so ONE float rounding per plane.  The builders pick q against exactly that expression and
+// tests/accel_check.py re-evaluates it for every occupied slot of every node against the padded boxes of the triangles
+// beneath.  The traversal never forms the plane: it folds the decode into one fused multiply-add per slab distance,
+// er_trav.h, whose rounding the absolute part of the builders' box padding covers), inner children are consecutive nodes from
 // child_base, leaf children's triangles are consecutive slots from tri_base.  Children sit in slots whose
 // 3-bit index encodes their position relative to the node centre, so `slot ^ octant` orders a ray's visits.
 struct ErNode8 {            // 80 bytes = five 16-byte loads

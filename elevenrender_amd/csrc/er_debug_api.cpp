@@ -132,6 +132,69 @@ static int er_debug_bvh_check_impl(const float* vertices, const float* normals, 
     return ER_OK;
 }
 
+// ---- the structure itself, copied out for tests/accel_check.py: no judgement here ----
+static int dump_put(const char* who, void* dst, uint64_t cap, const void* src, uint64_t bytes, bool from_device, hipStream_t st) {
+    if (!dst) return ER_OK;
+    if (cap < bytes) return fail(ER_ERR_INVALID_ARG, std::string(who) + ": a buffer is smaller than its array (all buffers NULL queries the sizes)");
+    if (!bytes) return ER_OK;
+    if (from_device) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+    else memcpy(dst, src, bytes);
+    return ER_OK;
+}
+
+static int er_debug_read_accel_impl(ErScene* s, ErAccelDump* info, void* nodes, uint64_t nodes_cap, void* nodes8, uint64_t nodes8_cap, void* isect, uint64_t isect_cap,
+                                    void* attr, uint64_t attr_cap) {
+    if (!s || !info) return fail(ER_ERR_INVALID_ARG, "er_debug_read_accel: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_debug_read_accel: er_render_begin has not succeeded");
+    const DevScene& D = s->dev;
+    memset(info, 0, sizeof(*info));
+    info->tri_count = s->tri_count;
+    info->node_count = D.node_count;
+    info->node8_count = D.node8_count;
+    info->node8_pieces = ER_NODE8_PIECES;
+    info->attr_pieces = ER_ATTR_PIECES;
+    info->max_depth = s->accel_depth2;
+    info->max_depth8 = s->accel.max_depth;
+    info->builder = s->accel.builder;
+    for (int a = 0; a < 3; a++) { info->lo[a] = s->accel_lo[a]; info->hi[a] = s->accel_hi[a]; }
+    info->lift_bound = s->accel.lift_bound;
+    info->max_lift = D.max_lift;
+    if (!nodes && !nodes8 && !isect && !attr) return ER_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    int rc;
+    const char* who = "er_debug_read_accel";
+    if ((rc = dump_put(who, nodes, nodes_cap, D.nodes, (uint64_t)D.node_count * sizeof(ErNode), true, s->stream)) != ER_OK) return rc;
+    if ((rc = dump_put(who, nodes8, nodes8_cap, D.nodes8, (uint64_t)D.node8_count * ER_NODE8_PIECES * 16, true, s->stream)) != ER_OK) return rc;
+    if ((rc = dump_put(who, isect, isect_cap, D.tri_isect, ((uint64_t)s->tri_count + 1) * sizeof(ErTriIsect), true, s->stream)) != ER_OK) return rc;
+    if ((rc = dump_put(who, attr, attr_cap, D.tri_attr, (uint64_t)s->tri_count * sizeof(ErTriAttr), true, s->stream)) != ER_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return ER_OK;
+}
+
+static int er_debug_bvh_dump_impl(const float* vertices, const float* normals, uint32_t tri_count, int threads, ErAccelDump* info, void* nodes, uint64_t nodes_cap,
+                                  void* nodes8, uint64_t nodes8_cap, uint32_t* slot_to_tri, uint64_t slot_cap, float* tri_lift, uint64_t lift_cap) {
+    if (!info || (tri_count && (!vertices || !normals))) return fail(ER_ERR_INVALID_ARG, "er_debug_bvh_dump: NULL argument");
+    ErBvhBuild b;
+    er_build_bvh(vertices, normals, tri_count, threads, &b);
+    memset(info, 0, sizeof(*info));
+    info->tri_count = tri_count;
+    info->node_count = (uint32_t)b.nodes.size();
+    info->node8_count = (uint32_t)b.nodes8.size();
+    info->node8_pieces = sizeof(ErNode8) / 16;
+    info->max_depth = b.max_depth;
+    info->max_depth8 = b.max_depth8;
+    for (int a = 0; a < 3; a++) { info->lo[a] = b.lo[a]; info->hi[a] = b.hi[a]; }
+    info->lift_bound = info->max_lift = b.lift_bound;
+    if (!nodes && !nodes8 && !slot_to_tri && !tri_lift) return ER_OK;
+    int rc;
+    const char* who = "er_debug_bvh_dump";
+    if ((rc = dump_put(who, nodes, nodes_cap, b.nodes.data(), (uint64_t)b.nodes.size() * sizeof(ErNode), false, nullptr)) != ER_OK) return rc;
+    if ((rc = dump_put(who, nodes8, nodes8_cap, b.nodes8.data(), (uint64_t)b.nodes8.size() * sizeof(ErNode8), false, nullptr)) != ER_OK) return rc;
+    if ((rc = dump_put(who, slot_to_tri, slot_cap, b.slot_to_tri.data(), (uint64_t)tri_count * 4, false, nullptr)) != ER_OK) return rc;
+    return dump_put(who, tri_lift, lift_cap, b.tri_lift.data(), (uint64_t)tri_count * 4, false, nullptr);
+}
+
 static int er_debug_trace_rays_impl(ErScene* s, const float* origins, const float* dirs, uint32_t n, const int32_t* self_slots, const float* limits,
                                     int32_t* tri_ids, int32_t* slots, float* positions, float* distances, int32_t* info) {
     if (!s || !origins || !dirs || !tri_ids || !slots || !positions || !distances || !info || (self_slots && !limits))
@@ -310,6 +373,13 @@ int er_debug_stream_deal(const uint32_t* owned, uint32_t count, uint32_t tiles_x
 }
 int er_debug_stream_form(uint32_t tiles, uint32_t blocks, int light_query, uint32_t tri_count, uint32_t flags, ErStreamForm* out) {
     return guarded("er_debug_stream_form", [&]() -> int { return er_debug_stream_form_impl(tiles, blocks, light_query, tri_count, flags, out); });
+}
+int er_debug_read_accel(ErScene* s, ErAccelDump* info, void* nodes, uint64_t nodes_cap, void* nodes8, uint64_t nodes8_cap, void* isect, uint64_t isect_cap, void* attr, uint64_t attr_cap) {
+    return guarded("er_debug_read_accel", [&]() -> int { return er_debug_read_accel_impl(s, info, nodes, nodes_cap, nodes8, nodes8_cap, isect, isect_cap, attr, attr_cap); });
+}
+int er_debug_bvh_dump(const float* vertices, const float* normals, uint32_t tri_count, int threads, ErAccelDump* info, void* nodes, uint64_t nodes_cap, void* nodes8, uint64_t nodes8_cap,
+                      uint32_t* slot_to_tri, uint64_t slot_cap, float* tri_lift, uint64_t lift_cap) {
+    return guarded("er_debug_bvh_dump", [&]() -> int { return er_debug_bvh_dump_impl(vertices, normals, tri_count, threads, info, nodes, nodes_cap, nodes8, nodes8_cap, slot_to_tri, slot_cap, tri_lift, lift_cap); });
 }
 int er_debug_bvh_check(const float* vertices, const float* normals, uint32_t tri_count, int threads, ErBvhCheck* out) { return guarded("er_debug_bvh_check", [&]() -> int { return er_debug_bvh_check_impl(vertices, normals, tri_count, threads, out); }); }
 int er_debug_trace_rays(ErScene* s, const float* origins, const float* dirs, uint32_t n, const int32_t* self_slots, const float* limits, int32_t* tri_ids,

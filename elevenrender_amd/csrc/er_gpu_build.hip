@@ -65,9 +65,11 @@ __global__ __launch_bounds__(256) void k_scene_bounds(const float* __restrict__ 
 
 // pass 2: padded box, lift bound (er_build_bvh's arithmetic, reference src/Tri.h:106-112)
 __global__ __launch_bounds__(256) void k_prims(const float* __restrict__ v, const float* __restrict__ nrm, uint32_t n, const unsigned* __restrict__ g,
-                                                Box3* __restrict__ boxes, float* __restrict__ lift, unsigned* __restrict__ lift_max) {
+                                                Box3* __restrict__ boxes, float* __restrict__ lift, unsigned* __restrict__ lift_max,
+                                                unsigned* __restrict__ bounds /* lo[3], hi[3] of all padded boxes, order-preserving integers */) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     float my_lift = 0;
+    float slo[3] = {INFINITY, INFINITY, INFINITY}, shi[3] = {-INFINITY, -INFINITY, -INFINITY};
     if (i < n) {
         const float pad_abs = __uint_as_float(g[0]) * 1e-6f;
         const float* p = v + (size_t)i * 9;
@@ -76,8 +78,11 @@ __global__ __launch_bounds__(256) void k_prims(const float* __restrict__ v, cons
             float lo = fminf(fminf(p[a], p[3 + a]), p[6 + a]), hi = fmaxf(fmaxf(p[a], p[3 + a]), p[6 + a]);
             float m = fmaxf(fabsf(lo), fabsf(hi));
             float pad = fmaxf(m * 4e-7f + 1e-37f, pad_abs);
-            b.lo[a] = lo - pad;
-            b.hi[a] = hi + pad;
+            float bl = lo - pad, bh = hi + pad;      // rounded outward, as er_build_bvh does
+            if ((double)bl > (double)lo - (double)pad) bl = nextafterf(bl, -INFINITY);
+            if ((double)bh < (double)hi + (double)pad) bh = nextafterf(bh, INFINITY);
+            b.lo[a] = slo[a] = bl;
+            b.hi[a] = shi[a] = bh;
         }
         boxes[i] = b;
         const float* nn = nrm + (size_t)i * 9;
@@ -97,6 +102,12 @@ __global__ __launch_bounds__(256) void k_prims(const float* __restrict__ v, cons
     }
     for (int off = 32; off >= 1; off >>= 1) my_lift = fmaxf(my_lift, __shfl_xor(my_lift, off, 64));
     if ((threadIdx.x & 63) == 0) atomicMax(lift_max, __float_as_uint(my_lift));
+    // the scene bounds are the union of the padded boxes, as er_build_bvh's (until round 7 they were read off the root's child boxes, which
+    // are a box of the builder's own choosing when every centroid coincides and the root is split by position)
+    for (int off = 32; off >= 1; off >>= 1)
+        for (int a = 0; a < 3; a++) { slo[a] = fminf(slo[a], __shfl_xor(slo[a], off, 64)); shi[a] = fmaxf(shi[a], __shfl_xor(shi[a], off, 64)); }
+    if ((threadIdx.x & 63) == 0)
+        for (int a = 0; a < 3; a++) { atomicMin(&bounds[a], f2ord(slo[a])); atomicMax(&bounds[3 + a], f2ord(shi[a])); }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -678,11 +689,11 @@ struct GpuBuild {
         GB_OK(hipMalloc(&d_g.p, 12 * 4));
         GB_OK(hipMemcpyAsync(d_v.p, vertices, (size_t)n * 36, hipMemcpyHostToDevice, st));
         GB_OK(hipMemcpyAsync(d_n.p, normals, (size_t)n * 36, hipMemcpyHostToDevice, st));
-        // [0] vmax, [7] lift max; [8] the deepest node's depth, [9] leaf count (set on the host by sah())
-        for (int k = 0; k < 12; k++) g[k] = 0;
+        // [0] vmax, [1..6] scene bounds (order-preserving integers), [7] lift max; [8] the deepest node's depth, [9] leaf count (set on the host by sah())
+        for (int k = 0; k < 12; k++) g[k] = (k >= 1 && k <= 3) ? 0xffffffffu : 0u;
         GB_OK(hipMemcpyAsync(d_g.p, g, sizeof(g), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_scene_bounds, dim3(blocks), dim3(256), 0, st, d_v.p, n, d_g.p);
-        hipLaunchKernelGGL(k_prims, dim3(blocks), dim3(256), 0, st, d_v.p, d_n.p, n, d_g.p, d_box.p, d_lift.p, d_g.p + 7);
+        hipLaunchKernelGGL(k_prims, dim3(blocks), dim3(256), 0, st, d_v.p, d_n.p, n, d_g.p, d_box.p, d_lift.p, d_g.p + 7, d_g.p + 1);
         int rc = sah(err);
         if (rc != 0) return rc;
         if (g[8] + 1 > ER_BVH_MAX_DEPTH - 1) {
@@ -733,11 +744,7 @@ struct GpuBuild {
         GB_OK(hipStreamSynchronize(st));
         SahAct root;
         root.node = 0; root.lo = 0; root.hi = n; root.depth = 0;
-        {   // (the root's box is only read if every centroid of the scene coincides: any box that holds the scene will do)
-            float vmax; memcpy(&vmax, &g[0], 4);
-            const float r = vmax * 1.00001f + 1e-30f;
-            for (int m = 0; m < 3; m++) { root.blo[m] = -r; root.bhi[m] = r; }
-        }
+        for (int m = 0; m < 3; m++) { root.blo[m] = bound(m); root.bhi[m] = bound(3 + m); }      // (only read if every centroid of the scene coincides)
         GB_OK(hipMemcpyAsync(d_act[0].p, &root, sizeof(root), hipMemcpyHostToDevice, st));
         uint32_t n_act = 1, created = 1, leaves = 0, depth = 0;
         int cur = 0;
@@ -784,6 +791,10 @@ struct GpuBuild {
         return 0;
     }
     float lift_bound() const { float lm; memcpy(&lm, &g[7], 4); return lm; }
+    float bound(int k) const {      // scene bounds, k = 0..2 lo, 3..5 hi (the host side of ord2f)
+        const unsigned u = g[1 + k], b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+        float f; memcpy(&f, &b, 4); return f;
+    }
 };
 
 }  // namespace
@@ -882,10 +893,8 @@ int er_gpu_build_device(const ErGpuSceneArrays& a, uint32_t n, int device, ErGpu
     hipLaunchKernelGGL(k_records, dim3((n + 256) / 256), dim3(256), 0, st, d_new_order.p, B.d_ids2.p, n, B.d_v.p, B.d_n.p, d_tan.p, d_uv.p, d_sign.p,
                        d_mat.p, B.d_lift.p, (ErTriIsect*)(d_geom.p + n8_pieces), (ErTriAttr*)d_attr.p, d_s2t.p);
     GB_OK(hipGetLastError());
-    ErNode rootn;
-    GB_OK(hipMemcpyAsync(&rootn, B.d_nodes.p, sizeof(ErNode), hipMemcpyDeviceToHost, st));
     GB_OK(hipStreamSynchronize(st));
-    for (int k = 0; k < 3; k++) { out->lo[k] = std::fmin(rootn.lo0[k], rootn.lo1[k]); out->hi[k] = std::fmax(rootn.hi0[k], rootn.hi1[k]); }
+    for (int k = 0; k < 3; k++) { out->lo[k] = B.bound(k); out->hi[k] = B.bound(3 + k); }
     out->lift_bound = B.lift_bound();
     out->leaf_count = B.g[9];
     out->max_depth2 = B.g[8] + 1;

@@ -152,6 +152,8 @@ struct ErScene {
     bool timing_open = false;
     DevScene dev{};
     ErAccelInfo accel{};
+    float accel_lo[3] = {0, 0, 0}, accel_hi[3] = {0, 0, 0};   // scene bounds as the builder reported them (er_debug_read_accel)
+    uint32_t accel_depth2 = 0;                                 // levels of the binary tree (the same hook)
     DevBuf<float4> d_nodes, d_nodes8, d_attr, d_passes;
     DevBuf<float4> d_plane;      // staging: one pass gathered as a plane for er_read_pass
     DevBuf<ErMaterial> d_materials;

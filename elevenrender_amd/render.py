@@ -184,6 +184,22 @@ class RenderingManager:
         abi.check(self.lib.er_accel_info(self.handle, C.byref(a)))
         return {n: getattr(a, n) for n, _ in abi.ErAccelInfo._fields_}
 
+    def debug_read_accel(self):
+        """include/eleven_hip_debug.h er_debug_read_accel: the acceleration structure as it lies in device memory, as a dict of numpy
+        structured arrays -- nodes (abi.NODE_DTYPE), nodes8 (abi.NODE8_DTYPE, the stride removed), isect (abi.ISECT_DTYPE, tri_count + 1
+        records), attr (abi.attr_dtype) -- plus lo, hi, lift_bound, max_lift, max_depth, max_depth8, builder and the counts."""
+        info = abi.ErAccelDump()
+        abi.check(self.lib.er_debug_read_accel(self.handle, C.byref(info), None, 0, None, 0, None, 0, None, 0))
+        nodes = np.zeros(info.node_count, abi.NODE_DTYPE)
+        raw8 = np.zeros((info.node8_count, info.node8_pieces * 16), np.uint8)
+        isect = np.zeros(info.tri_count + 1, abi.ISECT_DTYPE)
+        attr = np.zeros(info.tri_count, abi.attr_dtype(info.attr_pieces))
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        abi.check(self.lib.er_debug_read_accel(self.handle, C.byref(info), vp(nodes), nodes.nbytes, vp(raw8), raw8.nbytes, vp(isect), isect.nbytes,
+                                               vp(attr), attr.nbytes))
+        nodes8 = np.ascontiguousarray(raw8[:, :abi.NODE8_DTYPE.itemsize]).view(abi.NODE8_DTYPE).reshape(-1)
+        return abi.accel_dump_dict(info, nodes=nodes, nodes8=nodes8, isect=isect, attr=attr, node8_stride_tail=raw8[:, abi.NODE8_DTYPE.itemsize:])
+
     def debug_closest_hit(self, origins, dirs):
         """include/eleven_hip_debug.h: (triangle id, Hit.position, distance) of arbitrary rays through the exact routine."""
         o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)

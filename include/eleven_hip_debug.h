@@ -23,6 +23,39 @@ typedef struct ErBvhCheck {
 /* Builds the BVH for [tri_count][3][3] vertices/normals exactly as er_render_begin does and checks its invariants. */
 int er_debug_bvh_check(const float* vertices, const float* normals, uint32_t tri_count, int threads, ErBvhCheck* out);
 
+/* The acceleration structure itself, byte for byte, for a checker outside the library (tests/accel_check.py).  Both hooks below
+ * only copy: they judge nothing.  Layouts (elevenrender_amd/csrc/er_bvh.h): binary nodes ErNode, 64 bytes each, root = node 0; wide
+ * nodes ErNode8, 80 bytes at the start of every node8_pieces x 16 bytes; intersection records ErTriIsect, 48 bytes, tri_count + 1 of them
+ * (the last one is the zero record the paired triangle fetch of the wide traversal may read); attribute records ErTriAttr at the
+ * start of every attr_pieces x 16 bytes. */
+typedef struct ErAccelDump {
+    uint32_t tri_count;
+    uint32_t node_count;           /* binary nodes */
+    uint32_t node8_count;          /* wide nodes */
+    uint32_t node8_pieces;         /* stride of the wide nodes in 16-byte pieces (ER_NODE8_PIECES) */
+    uint32_t attr_pieces;          /* stride of the attribute records in 16-byte pieces (ER_ATTR_PIECES); 0: no records (er_debug_bvh_dump) */
+    uint32_t max_depth;            /* levels of inner nodes of the binary tree (what ER_BVH_MAX_DEPTH bounds) */
+    uint32_t max_depth8;           /* levels of the wide tree (what ER_STACK8 bounds; ErAccelInfo::max_depth) */
+    uint32_t builder;              /* 0 = host build, 1 = device build */
+    float lo[3], hi[3];            /* scene bounds as the builder reported them */
+    float lift_bound;              /* the builder's bound on |shadingPosition - geomPosition| over all triangles */
+    float max_lift;                /* the same bound as the kernels' scene descriptor carries it */
+} ErAccelDump;
+
+/* The structure as it lies in DEVICE memory after er_render_begin, whichever builder made it (before: ER_ERR_STATE).  `info` is always
+ * filled.  With all four buffers NULL that is all (the size query: nodes need node_count * 64 bytes, nodes8 node8_count * node8_pieces * 16,
+ * isect (tri_count + 1) * 48, attr tri_count * attr_pieces * 16); otherwise every non-NULL buffer receives its array, and a capacity
+ * (in bytes) smaller than the array is ER_ERR_INVALID_ARG.  A copy made on request: nothing is kept for it by er_render_begin. */
+struct ErScene;
+int er_debug_read_accel(struct ErScene* scene, ErAccelDump* info, void* nodes, uint64_t nodes_cap, void* nodes8, uint64_t nodes8_cap,
+                        void* isect, uint64_t isect_cap, void* attr, uint64_t attr_cap);
+
+/* The HOST builder's output for [tri_count][3][3] vertices / normals (er_build_bvh, run exactly as er_debug_bvh_check runs it; no device
+ * needed): nodes, packed wide nodes (node8_pieces = 5), slot_to_tri[tri_count] and tri_lift[tri_count] (per ORIGINAL triangle id) in place
+ * of the records.  Same protocol: all four buffers NULL = size query; capacities in bytes. */
+int er_debug_bvh_dump(const float* vertices, const float* normals, uint32_t tri_count, int threads, ErAccelDump* info, void* nodes, uint64_t nodes_cap,
+                      void* nodes8, uint64_t nodes8_cap, uint32_t* slot_to_tri, uint64_t slot_cap, float* tri_lift, uint64_t lift_cap);
+
 /* Runs the library's HDRI CDF search (elevenrender_amd/csrc/er_cdf.h, the replacement of the 21-level
  * HDRI::binarySearch, reference src/HDRI.cpp:85-98) on the host for `count` values. */
 int er_debug_cdf_search(const float* cdf, int length, const float* values, int32_t* out, int count);
