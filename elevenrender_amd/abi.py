@@ -117,6 +117,11 @@ class ErStreamInfo(C.Structure):   # include/eleven_hip_debug.h
                 ("form", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ErStreamBalance(C.Structure):   # include/eleven_hip_debug.h
+    _fields_ = [("blocks", C.c_uint32), ("most", C.c_uint32), ("levelled", C.c_uint32), ("counting", C.c_uint32), ("cost_tiles", C.c_uint32), ("cap", C.c_uint32),
+                ("launch_ticks", C.c_uint64)]
+
+
 class ErStreamForm(C.Structure):   # include/eleven_hip_debug.h
     _fields_ = [("waves", C.c_uint32), ("tracers", C.c_uint32), ("adapt", C.c_uint32), ("keep", C.c_uint32), ("spec", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -246,6 +251,10 @@ ABI_VERSION = 2     # include/eleven_hip.h ER_ABI_VERSION
 # older builds of the library (ELEVEN_HIP_LIB), which need not export the newest hooks.
 OPTIONAL_SYMBOLS = {
     "er_debug_stream_form": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(ErStreamForm)]),
+    "er_debug_stream_level": (C.c_int, [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
+                                        C.c_uint32, C.POINTER(C.c_uint32)]),
+    "er_debug_stream_balance": (C.c_int, [_P, C.POINTER(ErStreamBalance), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32),
+                                          C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]),
     "er_debug_read_accel": (C.c_int, [_P, C.POINTER(ErAccelDump), _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64]),
     "er_debug_bvh_dump": (C.c_int, [_FP, _FP, C.c_uint32, C.c_int, C.POINTER(ErAccelDump), _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64,
                                     _FP, C.c_uint64]),

@@ -619,7 +619,7 @@ int begin_descriptor(ErScene* s, const ErGpuBvhDevice& g, const TexResult& tex, 
     D.owned_tiles = s->d_owned.p;
     D.owned_tile_count = owned_tiles;
     D.counters = s->d_counters.p;
-    D.tile_cost = ((s->params.flags & ER_FLAG_STREAM) && s->st.deal_pending) ? s->st.d_tile_cost.p : nullptr;
+    D.tile_cost = ((s->params.flags & ER_FLAG_STREAM) && s->st.counting) ? s->st.d_tile_cost.p : nullptr;
     D.px_draws = (s->params.flags & ER_FLAG_STREAM) ? s->st.d_px_draws.p : nullptr;
     {   // the camera's rotation sines / cosines, once, with the functions the device would call (er_math.h: one implementation for both sides)
         const erd::CamTrig t = erd::camera_trig(D.cam);

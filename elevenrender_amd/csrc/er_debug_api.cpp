@@ -50,6 +50,44 @@ static int er_debug_stream_deal_impl(const uint32_t* owned, uint32_t count, uint
     return ER_OK;
 }
 
+static int er_debug_stream_level_impl(const uint32_t* deal, uint32_t deal_n, uint32_t tiles_x, uint32_t blocks, const uint32_t* cost, uint32_t cost_n, uint32_t cap, uint32_t* out,
+                                      uint32_t out_cap, uint32_t* most) {
+    if ((deal_n && !deal) || (cost_n && !cost) || !tiles_x || !blocks || deal_n % blocks != 0u || !cap || !most) return fail(ER_ERR_INVALID_ARG, "er_debug_stream_level: bad argument");
+    std::vector<uint32_t> lvl;
+    *most = er_stream_level_by_cost(std::vector<uint32_t>(deal, deal + deal_n), tiles_x, blocks, cost, cost_n, cap, lvl);
+    if (lvl.size() > out_cap || (lvl.size() && !out)) return fail(ER_ERR_INVALID_ARG, "er_debug_stream_level: out holds fewer than blocks * most entries");
+    for (size_t i = 0; i < lvl.size(); i++) out[i] = lvl[i];
+    return ER_OK;
+}
+
+static int er_debug_stream_balance_impl(ErScene* s, ErStreamBalance* info, uint64_t* wg_ticks, uint32_t* wg_tiles, uint64_t* wg_cost, uint32_t wg_cap, uint32_t* deal, uint32_t deal_cap,
+                                        uint32_t* tile_cost, uint32_t cost_cap) {
+    if (!s || !info) return fail(ER_ERR_INVALID_ARG, "er_debug_stream_balance: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    memset(info, 0, sizeof(*info));
+    if (!s->begun || !(s->params.flags & ER_FLAG_STREAM)) return ER_OK;
+    const StreamHost& st = s->st;
+    info->blocks = st.blocks;
+    info->most = st.blocks ? (uint32_t)(st.deal_host.size() / st.blocks) : 0u;
+    info->levelled = st.deal_levelled ? 1u : 0u;
+    info->counting = st.counting ? 1u : 0u;
+    info->cost_tiles = (uint32_t)st.cost_host.size();
+    info->cap = st.ring_cap / 64u;
+    info->launch_ticks = st.launch_end > st.launch_start ? st.launch_end - st.launch_start : 0u;
+    if (wg_cap >= st.blocks) {
+        std::vector<uint32_t> tiles; std::vector<uint64_t> cost, ticks;
+        stream_balance(s, tiles, cost, ticks);
+        for (uint32_t b = 0; b < st.blocks; b++) {
+            if (wg_ticks) wg_ticks[b] = ticks[b];
+            if (wg_tiles) wg_tiles[b] = tiles[b];
+            if (wg_cost) wg_cost[b] = cost[b];
+        }
+    }
+    if (deal && deal_cap >= st.deal_host.size()) for (size_t i = 0; i < st.deal_host.size(); i++) deal[i] = st.deal_host[i];
+    if (tile_cost && cost_cap >= st.cost_host.size()) for (size_t i = 0; i < st.cost_host.size(); i++) tile_cost[i] = st.cost_host[i];
+    return ER_OK;
+}
+
 static int er_debug_stream_form_impl(uint32_t tiles, uint32_t blocks, int light_query, uint32_t tri_count, uint32_t flags, ErStreamForm* out) {
     if (!out || !blocks) return fail(ER_ERR_INVALID_ARG, "er_debug_stream_form: bad argument");
     const StreamForm f = stream_choose_form(tiles, blocks, light_query != 0, tri_count, flags);
@@ -370,6 +408,12 @@ int er_debug_closest_hit(ErScene* s, const float* origins, const float* dirs, ui
 int er_debug_cdf_search(const float* cdf, int length, const float* values, int32_t* out, int count) { return guarded("er_debug_cdf_search", [&]() -> int { return er_debug_cdf_search_impl(cdf, length, values, out, count); }); }
 int er_debug_stream_deal(const uint32_t* owned, uint32_t count, uint32_t tiles_x, uint32_t blocks, int xcd_aware, uint32_t edge, uint32_t* out, uint32_t out_cap, uint32_t* most) {
     return guarded("er_debug_stream_deal", [&]() -> int { return er_debug_stream_deal_impl(owned, count, tiles_x, blocks, xcd_aware, edge, out, out_cap, most); });
+}
+int er_debug_stream_level(const uint32_t* deal, uint32_t deal_n, uint32_t tiles_x, uint32_t blocks, const uint32_t* cost, uint32_t cost_n, uint32_t cap, uint32_t* out, uint32_t out_cap, uint32_t* most) {
+    return guarded("er_debug_stream_level", [&]() -> int { return er_debug_stream_level_impl(deal, deal_n, tiles_x, blocks, cost, cost_n, cap, out, out_cap, most); });
+}
+int er_debug_stream_balance(ErScene* s, ErStreamBalance* info, uint64_t* wg_ticks, uint32_t* wg_tiles, uint64_t* wg_cost, uint32_t wg_cap, uint32_t* deal, uint32_t deal_cap, uint32_t* tile_cost, uint32_t cost_cap) {
+    return guarded("er_debug_stream_balance", [&]() -> int { return er_debug_stream_balance_impl(s, info, wg_ticks, wg_tiles, wg_cost, wg_cap, deal, deal_cap, tile_cost, cost_cap); });
 }
 int er_debug_stream_form(uint32_t tiles, uint32_t blocks, int light_query, uint32_t tri_count, uint32_t flags, ErStreamForm* out) {
     return guarded("er_debug_stream_form", [&]() -> int { return er_debug_stream_form_impl(tiles, blocks, light_query, tri_count, flags, out); });

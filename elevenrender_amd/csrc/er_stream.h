@@ -67,10 +67,13 @@ enum ErStreamCtl : uint32_t {
     ER_SC_START = 5,      // 64 bit: the earliest start of a workgroup, wall_clock64() ticks (100 MHz)
     ER_SC_END = 7,        // 8 x 64 bit: [+ 2 x] the latest end of a wave of XCD x = workgroup index % 8
     ER_SC_SPEC = 23,      // speculative samples started, [+ 1] whose guess was right, [+ 2] wrong
-    ER_SC_WORDS = 26      // one past the last: how many words `status` points at
+    ER_SC_WORDS = 26,     // one past the last of the words above
+    ER_SC_WG_END = 27     // blocks x 64 bit behind them (one word of padding: 8-byte aligned): [+ 2 b] the latest end of a wave of workgroup b
 };
 constexpr uint32_t ER_STREAM_CTL_LEAD = 1;      // words of the host's buffer in front of `status` (a count, not an index from it)
-static_assert((ER_STREAM_CTL_LEAD + ER_SC_ITERS) % 2u == 0u && ER_SC_BUSY % 2u == 1u && ER_SC_START % 2u == 1u && ER_SC_END % 2u == 1u, "the 64-bit control words are 8-byte aligned");
+static_assert((ER_STREAM_CTL_LEAD + ER_SC_ITERS) % 2u == 0u && ER_SC_BUSY % 2u == 1u && ER_SC_START % 2u == 1u && ER_SC_END % 2u == 1u && ER_SC_WG_END % 2u == 1u && ER_SC_WG_END >= ER_SC_WORDS,
+              "the 64-bit control words are 8-byte aligned");
+constexpr uint32_t er_stream_ctl_words(uint32_t blocks) { return ER_SC_WG_END + 2u * blocks; }      // how many words `status` points at
 
 // One launch of the streaming kernel.  S_dev: a device copy of S (the kernel reads the scene descriptor from constant memory, not
 // from its arguments).  ER_FLAG_MESH_LIGHTS (er_mesh_active): er_launch_stream hands the launch to er_launch_stream_mesh (er_stream_mesh.hip).
@@ -85,7 +88,7 @@ struct ErStreamLaunch {
     uint32_t deal_count = 0;            // ... and its size
     void* ring = nullptr;               // the workgroups' pixel rings: blocks * ring_cap uint2 entries
     uint32_t ring_cap = 0;              // a power of two >= 64 * the deal's largest share and <= ER_STREAM_MAX_RING
-    uint32_t* status = nullptr;         // ER_SC_WORDS control words (ErStreamCtl)
+    uint32_t* status = nullptr;         // er_stream_ctl_words(blocks) control words (ErStreamCtl)
     uint32_t n_samples = 0;
     bool count = false;                 // the instrumented instances of ER_FLAG_COUNTERS
     uint32_t blocks = 0;                // workgroups: one per CU
@@ -105,6 +108,10 @@ ErStreamLaunchForm er_stream_launch_form(uint32_t max_bounces, uint32_t tri_coun
 // the deal of the owned tiles to the workgroups (er_stream_host.cpp; device copy of `out` = ErStreamLaunch::deal, deal_count = out.size()); returns the most tiles of one workgroup
 // edge: side of a super-tile in 8 x 8 tiles; 0 = ER_STREAM_SUPER_TILE from the environment, else ER_STREAM_SUPER_TILE_DEFAULT
 uint32_t er_stream_deal_tiles(const uint32_t* owned, uint32_t count, uint32_t tiles_x, uint32_t blocks, bool xcd_aware, std::vector<uint32_t>& out, uint32_t edge = 0);
+// The deal `deal` (of `blocks` workgroups, as er_stream_deal_tiles made it) levelled by counted cost (er_stream_host.cpp): cost[t] = the
+// counted work of tile t of the frame (tiles beyond cost_n count 0), cap = the most tiles a workgroup may get.  Same layout; returns the
+// most tiles of one workgroup.  Pure and deterministic; a total cost of 0 gives `deal` back.
+uint32_t er_stream_level_by_cost(const std::vector<uint32_t>& deal, uint32_t tiles_x, uint32_t blocks, const uint32_t* cost, size_t cost_n, uint32_t cap, std::vector<uint32_t>& out);
 uint32_t er_stream_record_bytes(bool lights);
 size_t er_stream_spill_entries(uint32_t blocks);
 hipError_t er_probe_stream(const char** which);

@@ -1196,7 +1196,9 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
     unsigned t5 = 0, t6 = 0, t7 = 0;
     if (COUNT) { t5 = st_wave_sum(c_nodes); t6 = st_wave_sum(c_tris); t7 = st_wave_sum(c_texels); }
     if (lane == 0) {
-        atomicMax((unsigned long long*)(status + ER_SC_END + 2 * (blockIdx.x & 7u)), (unsigned long long)wall_clock64());
+        const unsigned long long t_end = (unsigned long long)wall_clock64();
+        atomicMax((unsigned long long*)(status + ER_SC_END + 2 * (blockIdx.x & 7u)), t_end);
+        atomicMax((unsigned long long*)(status + ER_SC_WG_END + 2 * blockIdx.x), t_end);      // ... and each workgroup's (er_debug_stream_balance: printed and logged, nothing is decided on it)
         if (t0) atomicAdd(&S.counters->paths, (unsigned long long)t0);
         if (t1) atomicAdd(&S.counters->bounce_samples, (unsigned long long)t1);
         if (t2) atomicAdd(&S.counters->rays, (unsigned long long)t2);

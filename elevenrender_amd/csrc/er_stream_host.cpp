@@ -64,6 +64,75 @@ uint32_t er_stream_deal_tiles(const uint32_t* owned, uint32_t count, uint32_t ti
     return maxk;
 }
 
+// The same deal levelled by COUNTED cost.  The count deal gives every workgroup the same positions of every super-tile, and a frame has
+// structure: on the C2 frame the workgroups' shares of the counted bounce-loop iterations are 0.964 ... 1.040 of their mean, the same
+// workgroups heavy in every sample (NOTEBOOK.md), and a launch lasts as long as its slowest workgroup.  Two stages, both on integers (the
+// same costs give the same bytes):
+//   the XCDs -- while the costliest exceeds the cheapest by more than twice the cost of the costliest one's LAST tile, that tile goes to
+//   the end of the cheapest one's sequence: as in the count levelling above what moves is the edge of a super-tile, the map of
+//   super-tiles to XCDs (L2 locality) otherwise stays;
+//   inside each XCD -- its tiles by (cost descending, tile ascending), each to the workgroup with the smallest summed cost that has
+//   fewer than `cap` tiles (ties: the lower workgroup), a workgroup's tiles then in ascending order.  The greedy rule leaves the largest
+//   workgroup within one tile's cost of the XCD's mean wherever the cap does not bind.
+// cap = cells of a pixel ring / 64: the rings and their tickets do not grow.  A total cost of 0, or a deal that does not fit the cap,
+// comes back as it was.  (tiles_x: the layout's, kept in the signature beside er_stream_deal_tiles'; the levelling needs no geometry.)
+uint32_t er_stream_level_by_cost(const std::vector<uint32_t>& deal, uint32_t tiles_x, uint32_t blocks, const uint32_t* cost, size_t cost_n, uint32_t cap, std::vector<uint32_t>& out) {
+    (void)tiles_x;
+    const uint32_t NONE = 0xFFFFFFFFu;
+    const uint32_t rows = blocks ? (uint32_t)(deal.size() / blocks) : 0u;
+    auto keep = [&]() { out = deal; return rows; };
+    if (!blocks || !rows || !cap) return keep();
+    const uint32_t X = blocks % 8u == 0u ? 8u : 1u, per = blocks / X;
+    auto c_of = [&](uint32_t t) -> uint64_t { return (cost && t < cost_n) ? cost[t] : 0u; };
+    // the XCDs' sequences in the order er_stream_deal_tiles dealt them: entry j + k * per of XCD x is the k-th tile of workgroup j * X + x
+    std::vector<std::vector<uint32_t>> seq(X);
+    std::vector<uint64_t> sum(X, 0);
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < rows; k++)
+        for (uint32_t j = 0; j < per; j++)
+            for (uint32_t x = 0; x < X; x++) {
+                const uint32_t t = deal[(size_t)(j * X + x) + (size_t)k * blocks];
+                if (t == NONE) continue;
+                seq[x].push_back(t); sum[x] += c_of(t); total += c_of(t);
+            }
+    if (total == 0) return keep();
+    for (uint32_t x = 0; x < X; x++) if (seq[x].size() > (size_t)per * cap) return keep();
+    for (;;) {      // (every move lowers the sum of the XCDs' squared costs: it ends)
+        uint32_t hi = 0, lo = 0;
+        for (uint32_t x = 1; x < X; x++) {
+            if (sum[x] > sum[hi]) hi = x;
+            if (sum[x] < sum[lo]) lo = x;
+        }
+        if (hi == lo || seq[hi].empty() || seq[lo].size() >= (size_t)per * cap) break;
+        const uint32_t t = seq[hi].back();
+        const uint64_t c = c_of(t);
+        if (c == 0 || sum[hi] - sum[lo] <= 2u * c) break;
+        seq[hi].pop_back(); seq[lo].push_back(t);
+        sum[hi] -= c; sum[lo] += c;
+    }
+    std::vector<std::vector<uint32_t>> mine(blocks);
+    std::vector<uint64_t> load(per);
+    uint32_t most = 0;
+    for (uint32_t x = 0; x < X; x++) {
+        std::vector<uint32_t>& q = seq[x];
+        std::sort(q.begin(), q.end(), [&](uint32_t a, uint32_t b) { const uint64_t ca = c_of(a), cb = c_of(b); return ca != cb ? ca > cb : a < b; });
+        std::fill(load.begin(), load.end(), 0);
+        for (uint32_t t : q) {
+            uint32_t best = per;
+            for (uint32_t j = 0; j < per; j++)
+                if (mine[(size_t)j * X + x].size() < cap && (best == per || load[j] < load[best])) best = j;
+            if (best == per) return keep();      // (cannot happen: the XCD holds at most per * cap tiles)
+            mine[(size_t)best * X + x].push_back(t);
+            load[best] += c_of(t);
+        }
+    }
+    for (auto& m : mine) { std::sort(m.begin(), m.end()); most = std::max<uint32_t>(most, (uint32_t)m.size()); }
+    out.assign((size_t)blocks * most, NONE);
+    for (uint32_t b = 0; b < blocks; b++)
+        for (size_t k = 0; k < mine[b].size(); k++) out[(size_t)b + k * blocks] = mine[b][k];
+    return most;
+}
+
 bool stream_xcd_aware(size_t owned_tiles, uint32_t blocks) {
     const char* xe = getenv("ER_STREAM_XCD_TILES");        // A/B knob: 0 = tiles dealt round-robin to the workgroups (round 2)
     // (a share with no more pixels than slots -- an eighth of a 1080p frame -- has nothing waiting in its pixel rings; there the
@@ -127,12 +196,14 @@ static void stream_set_form(ErScene* s, size_t tiles) {
     st.tracers_start = st.form.tracers; st.low_streak = 0; st.up_budget = 1;
 }
 
-// A decision between the two deals that is still open is closed: the kernel stops counting -- the scene descriptor it reads loses the
-// pointer (ordered on the stream before the next launch) -- and the host's copy of the large deal goes.
+// A decision between the two deals that is still open is closed and the kernel stops counting -- the scene descriptor it reads loses the
+// pointer (ordered on the stream before the next launch) -- and the host's copies of the large deal and of the deal to level go.
 static hipError_t stream_drop_pending_deal(ErScene* s) {
     s->st.deal_pending = false;
+    s->st.counting = false;
     s->dev.tile_cost = s->ad_dev.tile_cost = nullptr;
     s->st.deal_large.clear(); s->st.deal_large.shrink_to_fit();
+    s->st.deal_base.clear(); s->st.deal_base.shrink_to_fit();
     return hipMemcpyAsync(s->d_dev.p, &s->dev, sizeof(DevScene), hipMemcpyHostToDevice, s->stream);
 }
 
@@ -146,11 +217,13 @@ int stream_begin(ErScene* s, const std::vector<uint32_t>& owned, StreamDeal& dea
     st.readings = 0;
     const size_t slots = (size_t)st.blocks * ER_STREAM_SLOTS, npx = (size_t)s->x_res * s->y_res;
     if ((rc = upload(s->d_wf4, nullptr, slots * er_stream_record_bytes(light_query) / sizeof(float4), s->stream)) != ER_OK) return rc;
-    if ((rc = upload(s->d_wf1, nullptr, ER_STREAM_CTL_LEAD + ER_SC_WORDS, s->stream)) != ER_OK) return rc;       // the control words (er_stream.h ErStreamCtl)
+    const size_t ctl_words = ER_STREAM_CTL_LEAD + er_stream_ctl_words(st.blocks);
+    if ((rc = upload(s->d_wf1, nullptr, ctl_words, s->stream)) != ER_OK) return rc;       // the control words (er_stream.h ErStreamCtl)
     if ((rc = upload(s->d_spill, nullptr, er_stream_spill_entries(st.blocks), s->stream)) != ER_OK) return rc;
     st.ctl = s->d_wf1.p;
-    HIP_TRY(hipMemsetAsync(st.ctl, 0, (ER_STREAM_CTL_LEAD + ER_SC_WORDS) * sizeof(uint32_t), s->stream));
+    HIP_TRY(hipMemsetAsync(st.ctl, 0, ctl_words * sizeof(uint32_t), s->stream));
     st.spec[0] = st.spec[1] = st.spec[2] = 0;
+    st.launch_start = st.launch_end = 0; st.wg_end.clear();
     // the workgroups' pixel rings: (pixel, samples left) entries, one per pixel of the workgroup's share
     // (capacity rounded up to a power of two: positions are monotonic 32-bit counters and may wrap)
     // (no minimum beyond one tile: a producer that comes round to a cell whose entry has not been read yet waits for its
@@ -160,6 +233,10 @@ int stream_begin(ErScene* s, const std::vector<uint32_t>& owned, StreamDeal& dea
     uint32_t most = deal.most;
     st.deal_off = 0; st.deal_n = (uint32_t)deal.tiles.size();
     st.deal_alt_off = 0; st.deal_alt_n = 0;
+    st.deal_base_off = 0; st.deal_lvl_off = 0; st.deal_lvl_cap = 0; st.deal_levelled = false;
+    st.counting = false;
+    st.deal_base.clear(); st.cost_host.clear();
+    st.deal_host = deal.tiles;
     st.xcd_spread = -1.0;
     // Larger screen regions per XCD are faster where a frame's cost is even and slower where it is not (er_stream.h), and only the run
     // can tell which.  With the knob unset a render STARTS on the default deal -- it spreads any frame's cost over the XCDs -- and keeps
@@ -184,12 +261,11 @@ int stream_begin(ErScene* s, const std::vector<uint32_t>& owned, StreamDeal& dea
             const size_t n_tiles = (size_t)tiles_x * s->tiles_y();
             if ((rc = upload(st.d_tile_cost, nullptr, n_tiles, s->stream)) != ER_OK) return rc;
             HIP_TRY(hipMemsetAsync(st.d_tile_cost.p, 0, n_tiles * sizeof(uint32_t), s->stream));
-            st.deal_pending = true;
+            st.deal_pending = st.counting = true;
         }
     }
     if ((rc = upload(st.d_px_draws, nullptr, npx, s->stream)) != ER_OK) return rc;
     HIP_TRY(hipMemsetAsync(st.d_px_draws.p, 0, npx * sizeof(uint32_t), s->stream));
-    if ((rc = upload(st.d_deal, deal.tiles.data(), deal.tiles.size(), s->stream)) != ER_OK) return rc;
     if (s->x_res > 65535u || s->y_res > 65535u)
         return fail(ER_ERR_INVALID_ARG, "er_render_begin: ER_FLAG_STREAM carries a pixel as x | y << 16: frames up to 65535 x 65535; use ER_FLAG_WAVEFRONT (the automatic choice does)");
     st.ring_cap = 64u;
@@ -198,6 +274,10 @@ int stream_begin(ErScene* s, const std::vector<uint32_t>& owned, StreamDeal& dea
         return fail(ER_ERR_INVALID_ARG, "er_render_begin: ER_FLAG_STREAM serves at most " + std::to_string((size_t)ER_STREAM_MAX_RING * st.blocks) +
                                             " owned pixels per rank; use ER_FLAG_WAVEFRONT (the automatic choice does)");
     if ((rc = upload(st.d_ticket, nullptr, (size_t)st.blocks * (size_t)st.ring_cap * 2, s->stream)) != ER_OK) return rc;
+    // (behind the two deals: room for the one taken, levelled by counted cost -- at most ring_cap / 64 tiles per workgroup, stream_adapt)
+    if (st.counting) { st.deal_lvl_off = (uint32_t)deal.tiles.size(); st.deal_lvl_cap = st.blocks * (st.ring_cap / 64u); }
+    if ((rc = upload(st.d_deal, nullptr, deal.tiles.size() + st.deal_lvl_cap, s->stream)) != ER_OK) return rc;
+    if (!deal.tiles.empty()) HIP_TRY(hipMemcpyAsync(st.d_deal.p, deal.tiles.data(), deal.tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
     return ER_OK;
 }
 
@@ -205,8 +285,9 @@ int stream_redeal(ErScene* s) {
     StreamHost& st = s->st;
     // (a decision between the two deals still pending -- calls of one sample each until now -- is dropped: the default deal stays; the
     // large regions, if already taken, stay taken for the new share)
+    // (nor does a deal levelled by counted cost survive: the new share is dealt by count, and the counting stops)
     const bool large = st.large_deal_in_use();
-    if (st.deal_pending) HIP_TRY(stream_drop_pending_deal(s));
+    if (st.deal_pending || st.counting) HIP_TRY(stream_drop_pending_deal(s));
     const uint32_t count = (uint32_t)s->ad_active.size(), tiles_x = s->tiles_x();
     std::vector<uint32_t> deal;
     uint32_t most = er_stream_deal_tiles(s->ad_active.data(), count, tiles_x, st.blocks, stream_xcd_aware(count, st.blocks), deal, large ? ER_STREAM_SUPER_TILE_LARGE : 0u);
@@ -218,6 +299,8 @@ int stream_redeal(ErScene* s) {
     if ((rc = upload(st.d_deal, deal.data(), deal.size(), s->stream)) != ER_OK) return rc;
     st.deal_off = 0; st.deal_n = (uint32_t)deal.size();
     st.deal_alt_off = 0; st.deal_alt_n = 0;
+    st.deal_base_off = 0; st.deal_lvl_off = 0; st.deal_lvl_cap = 0; st.deal_levelled = false;
+    st.deal_host = deal;
     stream_set_form(s, count);
     HIP_TRY(hipStreamSynchronize(s->stream));      // (`deal` goes out of scope)
     return ER_OK;
@@ -225,7 +308,7 @@ int stream_redeal(ErScene* s) {
 
 static int stream_launch(ErScene* s, uint32_t k) {
     StreamHost& st = s->st;
-    HIP_TRY(hipMemsetAsync(st.status() + ER_SC_ITERS, 0, (ER_SC_WORDS - ER_SC_ITERS) * sizeof(uint32_t), s->stream));      // the call's lane-occupancy counts, its end per XCD, its speculation counts ...
+    HIP_TRY(hipMemsetAsync(st.status() + ER_SC_ITERS, 0, (er_stream_ctl_words(st.blocks) - ER_SC_ITERS) * sizeof(uint32_t), s->stream));      // the call's lane-occupancy counts, its end per XCD and per workgroup, its speculation counts ...
     HIP_TRY(hipMemsetAsync(st.status() + ER_SC_START, 0xFF, 2 * sizeof(uint32_t), s->stream));                            // ... and its start (a minimum)
     if (k > 0) st.launches++;
     ErStreamLaunch L;
@@ -272,8 +355,8 @@ int stream_enqueue(ErScene* s, uint32_t n) {
 int er_scene_stream_status(ErScene* s, const char* who) {
     StreamHost& st = s->st;
     if (!(s->params.flags & ER_FLAG_STREAM) || !st.ctl) return ER_OK;
-    uint32_t w[ER_SC_WORDS] = {0};
-    HIP_TRY(hipMemcpy(w, st.status(), sizeof(w), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> w(er_stream_ctl_words(st.blocks), 0u);
+    HIP_TRY(hipMemcpy(w.data(), st.status(), w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (st.spec_seen != st.launches) {      // (once per launch: a read-back after the same launch finds the same words)
         st.spec_seen = st.launches;
         for (int k = 0; k < 3; k++) st.spec[k] += w[ER_SC_SPEC + k];
@@ -289,7 +372,50 @@ int er_scene_stream_status(ErScene* s, const char* who) {
     for (uint32_t x = 0; x < 8; x++) { const unsigned long long e = u64(ER_SC_END + 2 * x); lo = std::min(lo, e); hi = std::max(hi, e); }
     st.xcd_spread = (t0 != ~0ull && lo > t0 && hi - t0 >= 200000ull) ? (double)(hi - lo) / (double)(hi - t0) : -1.0;
     st.launch_ms = (t0 != ~0ull && hi > t0) ? (double)(hi - t0) * 1e-5 : 0.0;
+    // ... and every workgroup's end (er_debug_stream_balance, ER_STREAM_VERBOSE: printed and logged, never acted on)
+    st.launch_start = (t0 != ~0ull && hi > t0) ? t0 : 0u; st.launch_end = st.launch_start ? hi : 0u;
+    st.wg_end.assign(st.blocks, 0u);
+    for (uint32_t b = 0; b < st.blocks; b++) st.wg_end[b] = u64(ER_SC_WG_END + 2 * b);
     return ER_OK;
+}
+
+// per workgroup of the deal in use: tiles, counted cost (the tile costs last read), end stamp minus launch start of the last completed launch
+void stream_balance(const ErScene* s, std::vector<uint32_t>& wg_tiles, std::vector<uint64_t>& wg_cost, std::vector<uint64_t>& wg_ticks) {
+    const StreamHost& st = s->st;
+    wg_tiles.assign(st.blocks, 0u); wg_cost.assign(st.blocks, 0u); wg_ticks.assign(st.blocks, 0u);
+    for (size_t i = 0; i < st.deal_host.size() && st.blocks; i++) {
+        const uint32_t t = st.deal_host[i];
+        if (t == 0xFFFFFFFFu) continue;
+        wg_tiles[i % st.blocks]++;
+        if (t < st.cost_host.size()) wg_cost[i % st.blocks] += st.cost_host[t];
+    }
+    for (uint32_t b = 0; b < st.blocks && b < st.wg_end.size(); b++)
+        if (st.launch_start && st.wg_end[b] > st.launch_start) wg_ticks[b] = st.wg_end[b] - st.launch_start;
+}
+
+// ER_STREAM_VERBOSE: how evenly the launch just completed ended and how evenly its deal spread the counted work -- over the workgroups that
+// own a tile.  S = (latest end - mean end) / (latest end - launch start): the idle tail, what a better deal could win at most.  Measured
+// times: printed, nothing is decided on them.
+static void stream_print_balance(const ErScene* s) {
+    const StreamHost& st = s->st;
+    std::vector<uint32_t> tiles; std::vector<uint64_t> cost, ticks;
+    stream_balance(s, tiles, cost, ticks);
+    double t_sum = 0, t_max = 0, t_min = 0, c_sum = 0, c_max = 0, c_min = 0;
+    uint32_t n = 0, n_max = 0, n_min = 0;
+    for (uint32_t b = 0; b < st.blocks; b++) {
+        if (!tiles[b] || !ticks[b]) continue;
+        const double t = (double)ticks[b], c = (double)cost[b];
+        if (!n) { t_max = t_min = t; c_max = c_min = c; n_max = n_min = tiles[b]; }
+        t_sum += t; t_max = std::max(t_max, t); t_min = std::min(t_min, t);
+        c_sum += c; c_max = std::max(c_max, c); c_min = std::min(c_min, c);
+        n_max = std::max(n_max, tiles[b]); n_min = std::min(n_min, tiles[b]);
+        n++;
+    }
+    if (!n || t_sum <= 0) return;
+    const double t_mean = t_sum / n, c_mean = c_sum / n;
+    fprintf(stderr, "[er_stream] workgroups of a launch of %.3f ms: finished max/mean %.4f min/mean %.4f, idle tail S %.4f", t_max * 1e-5, t_max / t_mean, t_min / t_mean, (t_max - t_mean) / t_max);
+    if (c_mean > 0) fprintf(stderr, "; counted cost max/mean %.4f min/mean %.4f", c_max / c_mean, c_min / c_mean);
+    fprintf(stderr, " (%s deal, %u ... %u tiles; measured times: printed, nothing is decided on them)\n", st.deal_levelled ? "cost-levelled" : "count", n_min, n_max);
 }
 
 // The two roles of the streaming kernel feed each other, and which one is short depends on the scene: how long a ray's traversal is
@@ -311,9 +437,17 @@ void stream_adapt(ErScene* s) {
     if (verbose && !st.form.adapt) fprintf(stderr, "[er_stream] tracer lanes %.3f full at %u + %u waves (fixed split)\n", st.busy, st.form.tracers, st.form.waves - st.form.tracers);
     // the deal: large screen regions per XCD if the XCDs' shares of the COUNTED work of the first call are alike under them (er_stream.h,
     // stream_begin).  Decided once, from counts: the same decision on every run of the same frame.
-    if (st.deal_pending) {
+    const bool counted = st.deal_pending || st.counting;
+    bool have_cost = false;
+    if (counted) {
         std::vector<uint32_t> cost(st.d_tile_cost.n);
-        if (hipMemcpy(cost.data(), st.d_tile_cost.p, cost.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess) {
+        have_cost = hipMemcpy(cost.data(), st.d_tile_cost.p, cost.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess;
+        if (have_cost) st.cost_host.swap(cost);
+    }
+    if (verbose) stream_print_balance(s);      // (the launch just completed: the deal it ran on, the costs counted up to its end)
+    if (st.deal_pending) {
+        const std::vector<uint32_t>& cost = st.cost_host;
+        if (have_cost) {
             double x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             const std::vector<uint32_t>& L = st.deal_large;
             for (size_t i = 0; i < L.size(); i++)
@@ -327,9 +461,33 @@ void stream_adapt(ErScene* s) {
             st.cost_spread = spread;
             if (verbose) fprintf(stderr, "[er_stream] counted work of the XCDs' shares on super-tiles of %u: %.4f of the mean apart (limit %.4f) -> %s\n", (unsigned)ER_STREAM_SUPER_TILE_LARGE, spread,
                                  limit, take ? "large regions" : "the default deal stays");
-            if (take) { st.deal_off = st.deal_alt_off; st.deal_n = st.deal_alt_n; }
+            if (take) { st.deal_off = st.deal_base_off = st.deal_alt_off; st.deal_n = st.deal_alt_n; st.deal_host = st.deal_large; }
         }
-        (void)stream_drop_pending_deal(s);
+        st.deal_pending = false;
+        st.deal_base = st.deal_host;      // (what the counted cost then levels)
+        st.deal_large.clear(); st.deal_large.shrink_to_fit();
+    }
+    // The deal taken, levelled by the counted cost (er_stream_level_by_cost): after the render's first sample on that sample's counts, and
+    // once more when the first CALL has completed on all of its samples' (a one-sample estimate carries ~0.5 % of noise per workgroup, four
+    // samples half of that); then the counting stops.  ER_STREAM_COST_LEVEL=0 (A/B knob, read per decision): the count deal stays and the
+    // counting stops with the decision.  Decided from counts alone: the same deal on every run of the same frame.
+    if (counted) {
+        const char* lv = getenv("ER_STREAM_COST_LEVEL");
+        const bool level = !(lv && atoi(lv) == 0) && have_cost && st.deal_lvl_cap != 0u && !st.deal_base.empty();
+        if (level) {
+            std::vector<uint32_t> lvl;
+            er_stream_level_by_cost(st.deal_base, s->tiles_x(), st.blocks, st.cost_host.data(), st.cost_host.size(), st.ring_cap / 64u, lvl);
+            if (lvl == st.deal_base) {      // (nothing to level: the deal taken is in use)
+                st.deal_off = st.deal_base_off; st.deal_n = (uint32_t)st.deal_base.size(); st.deal_levelled = false;
+                st.deal_host = st.deal_base;
+            } else if (lvl.size() <= st.deal_lvl_cap &&
+                       hipMemcpyAsync(st.d_deal.p + st.deal_lvl_off, lvl.data(), lvl.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream) == hipSuccess) {
+                (void)hipStreamSynchronize(s->stream);      // (`lvl` is pageable memory: the copy has left it)
+                st.deal_off = st.deal_lvl_off; st.deal_n = (uint32_t)lvl.size(); st.deal_levelled = true;
+                st.deal_host.swap(lvl);
+            }
+        }
+        if (!level || !st.probe_launch) (void)stream_drop_pending_deal(s);
         (void)hipStreamSynchronize(s->stream);
     }
     if (verbose && st.xcd_spread >= 0.0)

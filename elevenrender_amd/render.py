@@ -179,6 +179,21 @@ class RenderingManager:
         abi.check(self.lib.er_debug_stream_info(self.handle, C.byref(si)))
         return {n: getattr(si, n) for n, _ in abi.ErStreamInfo._fields_}
 
+    def stream_balance(self):
+        """include/eleven_hip_debug.h er_debug_stream_balance: how the streaming schedule's deal in use spreads the work -- per workgroup
+        wg_ticks (end stamp minus launch start of the last completed launch), wg_tiles, wg_cost (uint64 / uint32 arrays), the deal itself
+        ([most, blocks], 0xFFFFFFFF = none), the tile costs last read -- and the fields of ErStreamBalance."""
+        info = abi.ErStreamBalance()
+        abi.check(self.lib.er_debug_stream_balance(self.handle, C.byref(info), None, None, None, 0, None, 0, None, 0))
+        b = info.blocks
+        ticks, tiles, cost = np.zeros(b, np.uint64), np.zeros(b, np.uint32), np.zeros(b, np.uint64)
+        deal, tile_cost = np.zeros(b * info.most, np.uint32), np.zeros(info.cost_tiles, np.uint32)
+        u32, u64 = (lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64)))
+        abi.check(self.lib.er_debug_stream_balance(self.handle, C.byref(info), u64(ticks), u32(tiles), u64(cost), b, u32(deal), deal.size, u32(tile_cost), tile_cost.size))
+        d = {n: int(getattr(info, n)) for n, _ in abi.ErStreamBalance._fields_}
+        d.update(wg_ticks=ticks, wg_tiles=tiles, wg_cost=cost, deal=deal.reshape(info.most, b) if b else deal, tile_cost=tile_cost)
+        return d
+
     def accel_info(self):
         a = abi.ErAccelInfo()
         abi.check(self.lib.er_accel_info(self.handle, C.byref(a)))

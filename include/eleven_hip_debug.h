@@ -174,6 +174,32 @@ int er_debug_comm_loopback(struct ErComm* c, uint64_t bytes, double* ms);
 int er_debug_stream_deal(const uint32_t* owned, uint32_t count, uint32_t tiles_x, uint32_t blocks, int xcd_aware, uint32_t edge, uint32_t* out, uint32_t out_cap,
                          uint32_t* most);
 
+/* A deal in the layout of er_debug_stream_deal (`deal`, deal_n = blocks * its most entries) levelled by counted cost, as the streaming schedule
+ * does it after a render's first sample and again after its first call (host code, no device needed): cost[t] = counted work of tile t of
+ * the frame (tiles >= cost_n count 0), cap = the most tiles one workgroup may get.  First the XCDs (workgroup b is on XCD b % 8 if blocks is
+ * a multiple of 8): while the costliest exceeds the cheapest by more than twice the cost of the costliest one's LAST tile, that tile moves to
+ * the cheapest; then, inside each XCD, heaviest tile first to the workgroup of the smallest summed cost that is under the cap.  Integer
+ * arithmetic: the same costs give the same bytes; a total cost of 0 gives `deal` back.  out / out_cap / most as in er_debug_stream_deal. */
+int er_debug_stream_level(const uint32_t* deal, uint32_t deal_n, uint32_t tiles_x, uint32_t blocks, const uint32_t* cost, uint32_t cost_n, uint32_t cap,
+                          uint32_t* out, uint32_t out_cap, uint32_t* most);
+
+/* How the deal in use spreads the work over the workgroups, and when they finished (streaming schedule; after er_wait / a read-back).
+ * Every pointer may be NULL (nothing is copied there); a first call with info alone gives the sizes. */
+typedef struct ErStreamBalance {
+    uint32_t blocks;               /* workgroups */
+    uint32_t most;                 /* the deal in use has blocks * most entries (layout of er_debug_stream_deal) */
+    uint32_t levelled;             /* 1: the deal in use was levelled by counted cost; 0: it is dealt by tile count */
+    uint32_t counting;             /* 1: the kernel is still counting tile costs (the render's first call has not completed) */
+    uint32_t cost_tiles;           /* entries of the tile costs last read: tiles of the frame, 0 = none were counted */
+    uint32_t cap;                  /* the most tiles one workgroup may get (pixel ring cells / 64) */
+    uint64_t launch_ticks;         /* last completed launch: the latest XCD's end stamp minus the launch's start stamp, 100 MHz ticks (0: none) */
+} ErStreamBalance;
+/* wg_ticks[b]: workgroup b's end stamp minus the launch's start (0: it ran no wave), wg_tiles[b]: its tiles, wg_cost[b]: their summed cost
+ * (tile costs last read), each `blocks` entries if wg_cap >= blocks; deal: the deal in use (deal_cap >= blocks * most); tile_cost: the
+ * costs last read (cost_cap >= cost_tiles).  Measured times are for printing and logging: the library decides nothing on them. */
+int er_debug_stream_balance(struct ErScene* s, ErStreamBalance* info, uint64_t* wg_ticks, uint32_t* wg_tiles, uint64_t* wg_cost, uint32_t wg_cap,
+                            uint32_t* deal, uint32_t deal_cap, uint32_t* tile_cost, uint32_t cost_cap);
+
 /* The streaming kernel's form for a share of `tiles` tiles on `blocks` workgroups, as er_render_begin and an adaptive re-deal choose
  * it (host code, no device needed; the A/B knobs of the environment are honoured): light_query = the slots carry a point-light or
  * emitter query; flags: the render's (ER_FLAG_COUNTERS matters). */
