@@ -21,6 +21,7 @@ PASS_NAMES = {"beauty": 0, "denoise": 1, "normal": 2, "tangent": 3, "bitangent":
 FLAG_POINT_LIGHTS, FLAG_COUNTERS, FLAG_MEGAKERNEL, FLAG_PROFILE, FLAG_FUSED, FLAG_WAVEFRONT, FLAG_GPU_BUILD, FLAG_MIS, FLAG_STREAM = 1, 2, 4, 8, 16, 32, 64, 128, 256
 FLAG_HOST_BUILD = 512
 FLAG_MESH_LIGHTS = 1024     # next-event estimation of emissive triangles (csrc/er_shade.h)
+UPDATE_CAMERA, UPDATE_GEOMETRY = 1, 2     # ErSceneUpdate.what
 
 
 class ErVec3(C.Structure):
@@ -108,6 +109,15 @@ class ErAdaptiveInfo(C.Structure):
 
 class ErLightInfo(C.Structure):
     _fields_ = [("emitters", C.c_uint32), ("total_weight", C.c_float)]
+
+
+class ErSceneUpdate(C.Structure):
+    _fields_ = [("what", C.c_uint32), ("camera", ErCamera), ("vertices", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)),
+                ("tangents", C.POINTER(C.c_float))]
+
+
+class ErUpdateInfo(C.Structure):
+    _fields_ = [("updates", C.c_uint32), ("refits", C.c_uint32), ("refit_ms", C.c_float), ("update_ms", C.c_float)]
 
 
 class ErStreamInfo(C.Structure):   # include/eleven_hip_debug.h
@@ -207,6 +217,8 @@ SYMBOLS = {
     "er_unpack_owned": (C.c_int, [_P, C.c_int, C.c_uint32, _P]),
     "er_get_counters": (C.c_int, [_P, C.POINTER(ErCounters)]),
     "er_accel_info": (C.c_int, [_P, C.POINTER(ErAccelInfo)]),
+    "er_render_update": (C.c_int, [_P, C.POINTER(ErSceneUpdate)]),
+    "er_update_info": (C.c_int, [_P, C.POINTER(ErUpdateInfo)]),
     "er_adaptive_set": (C.c_int, [_P, C.POINTER(ErAdaptiveParams)]),
     "er_adaptive_info": (C.c_int, [_P, C.POINTER(ErAdaptiveInfo)]),
     "er_read_tile_state": (C.c_int, [_P, _FP, C.POINTER(C.c_uint32)]),

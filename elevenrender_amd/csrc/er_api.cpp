@@ -629,6 +629,25 @@ int begin_descriptor(ErScene* s, const ErGpuBvhDevice& g, const TexResult& tex, 
     return upload(s->d_dev, &D, 1, s->stream);
 }
 
+// stages 6-8 and the set-up launch: the render's own state -- planes, schedule, descriptor -- on a structure, materials and textures that
+// are in place.  The tail of er_render_begin, and all of what er_render_update runs again.  `uploads_done` (may be null) is recorded
+// before the descriptor goes up.  Leaves the stream idle.
+int begin_render_state(ErScene* s, BeginStaging& B, const ErGpuBvhDevice& g, const TexResult& tex, uint32_t cus, bool query_on, hipEvent_t uploads_done) {
+    int rc;
+    if ((rc = begin_planes(s, B)) != ER_OK) return rc;
+    if ((rc = begin_choose_schedule(s, B, cus)) != ER_OK) return rc;
+    if (s->params.flags & ER_FLAG_STREAM) rc = stream_begin(s, B.owned, B.deal, cus, query_on);
+    else if (s->params.flags & ER_FLAG_WAVEFRONT) rc = begin_wavefront(s, B.owned, cus, query_on);
+    if (rc != ER_OK) return rc;
+    if (uploads_done) HIP_TRY(hipEventRecord(uploads_done, s->stream));
+    if ((rc = begin_descriptor(s, g, tex, (uint32_t)B.owned.size())) != ER_OK) return rc;
+
+    er_launch_setup(s->dev, s->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return ER_OK;
+}
+
 }  // namespace
 
 static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
@@ -653,17 +672,11 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     if ((rc = begin_emitters(s, B, g.n8_pieces, lights_on)) != ER_OK) return rc;
     // the point-light or the emitter query: a second shadow record per slot
     const bool query_on = lights_on || s->light_emitters > 0;
-    if ((rc = begin_planes(s, B)) != ER_OK) return rc;
-    if ((rc = begin_choose_schedule(s, B, cus)) != ER_OK) return rc;
-    if (s->params.flags & ER_FLAG_STREAM) rc = stream_begin(s, B.owned, B.deal, cus, query_on);
-    else if (s->params.flags & ER_FLAG_WAVEFRONT) rc = begin_wavefront(s, B.owned, cus, query_on);
-    if (rc != ER_OK) return rc;
-    HIP_TRY(hipEventRecord(ev.b, s->stream));
-    if ((rc = begin_descriptor(s, g, tex, (uint32_t)B.owned.size())) != ER_OK) return rc;
-
-    er_launch_setup(s->dev, s->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->keep_accel = g;
+    s->keep_accel.nodes = s->keep_accel.geom = s->keep_accel.attr = nullptr;      // (the scene owns the buffers)
+    s->keep_hdri = tex.hdri; s->keep_buckets = tex.buckets;
+    s->keep_cus = cus; s->keep_flags = p->flags;
+    if ((rc = begin_render_state(s, B, g, tex, cus, query_on, ev.b)) != ER_OK) return rc;
     float up_ms = 0;
     (void)hipEventElapsedTime(&up_ms, ev.a, ev.b);
 
@@ -678,6 +691,100 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     for (int a = 0; a < 3; a++) { s->accel_lo[a] = g.lo[a]; s->accel_hi[a] = g.hi[a]; }
     s->accel_depth2 = g.max_depth2;
     s->begun = true;
+    return ER_OK;
+}
+
+// ---- er_render_update: edit a begun scene in place (include/eleven_hip.h) ----
+// The device work of an update, after the host copy has been edited: the refit and the emitter table if triangles moved, then the
+// render's own state exactly as er_render_begin sets it up (begin_render_state, same arguments).  The caller holds the mutex, the
+// stream is idle.
+static int update_device(ErScene* s, const ErSceneUpdate* u) {
+    int rc;
+    HIP_TRY(hipSetDevice(s->device));
+    ErGpuBvhDevice& g = s->keep_accel;
+    const bool lights_on = (s->keep_flags & ER_FLAG_POINT_LIGHTS) != 0 && !s->point_lights.empty();
+    BeginStaging B;                     // outlives begin_render_state's hipStreamSynchronize
+    if (u->what & ER_UPDATE_GEOMETRY) {
+        ErRefitBuffers b;
+        b.nodes = (ErNode*)s->d_nodes.p; b.node_count = (uint32_t)(g.nodes_f4 / 4); b.depth2 = g.max_depth2;
+        b.nodes8 = s->d_nodes8.p; b.node8_count = g.nodes8_count; b.depth8 = g.max_depth8;
+        b.isect = (ErTriIsect*)(s->d_nodes8.p + g.n8_pieces); b.attr = (ErTriAttr*)s->d_attr.p; b.tri_count = s->tri_count;
+        ErRefitArrays a;
+        a.vertices = s->vertices.data(); a.normals = s->normals.data(); a.write_normals = u->normals != nullptr;
+        a.tangents = u->tangents ? s->tangents.data() : nullptr;
+        ErRefitResult r;
+        std::string why;
+        const int frc = er_refit_device(s->refit_topo, b, a, s->stream, &r, why);
+        if (frc != 0) return fail(frc == -2 ? ER_ERR_OOM : ER_ERR_HIP, "er_render_update: refit: " + why);
+        if (s->tri_count) {
+            for (int k = 0; k < 3; k++) { g.lo[k] = s->accel_lo[k] = r.lo[k]; g.hi[k] = s->accel_hi[k] = r.hi[k]; }
+            g.lift_bound = s->accel.lift_bound = r.lift_bound;
+        }
+        s->accel.builder = 2u;
+        s->accel.build_ms = s->upd.refit_ms = r.refit_ms;
+        // the emitter table holds areas of placed triangles
+        s->d_light_tab.release(); s->light_emitters = 0; s->light_total = 0.0f;
+        if ((rc = begin_emitters(s, B, g.n8_pieces, lights_on)) != ER_OK) return rc;
+    }
+    // what a fresh scene's er_render_begin would find: no adaptive state, no samples, no open timing or profile window, the streaming
+    // schedule's host state and the wavefront schedule's pools as new
+    s->ad_on = false;
+    s->rendered = 0;
+    s->timing_open = false;
+    s->prof_used = 0;
+    s->profile = ErProfile{};
+    for (auto& set : s->unpacked) set.clear();
+    s->st.release();
+    s->st = StreamHost{};
+    for (hipEvent_t e : s->pool_events) (void)hipEventDestroy(e);
+    s->pool_events.clear();
+    for (hipStream_t st : s->pool_streams) (void)hipStreamDestroy(st);
+    s->pool_streams.clear();
+    s->wf.clear();
+    s->params.flags = s->keep_flags;      // (the schedule is chosen again, from the same flags on the same share)
+    TexResult tex;
+    tex.hdri = s->keep_hdri; tex.buckets = s->keep_buckets;
+    const bool query_on = lights_on || s->light_emitters > 0;
+    return begin_render_state(s, B, g, tex, s->keep_cus, query_on, nullptr);
+}
+
+static int er_render_update_impl(ErScene* s, const ErSceneUpdate* u) {
+    if (!s || !u) return fail(ER_ERR_INVALID_ARG, "er_render_update: NULL argument");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_render_update: er_render_begin has not succeeded");
+    if (u->what == 0 || (u->what & ~(ER_UPDATE_CAMERA | ER_UPDATE_GEOMETRY))) return fail(ER_ERR_INVALID_ARG, "er_render_update: `what` names nothing, or something unknown");
+    const size_t n9 = (size_t)s->tri_count * 9;
+    if (u->what & ER_UPDATE_GEOMETRY) {
+        if (!u->vertices) return fail(ER_ERR_INVALID_ARG, "er_render_update: ER_UPDATE_GEOMETRY without vertices");
+        for (size_t i = 0; i < n9; i++)
+            if (!std::isfinite(u->vertices[i])) return fail(ER_ERR_INVALID_ARG, "er_render_update: vertex " + std::to_string(i / 3) + " is not finite");
+    }
+    // pending asynchronous work first (the pool streams join the scene's stream at the end of every call)
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    // the host copy, before any device work: whatever happens below, a later er_render_begin builds the edited scene
+    if (u->what & ER_UPDATE_CAMERA) s->camera = u->camera;
+    if (u->what & ER_UPDATE_GEOMETRY) {
+        s->vertices.assign(u->vertices, u->vertices + n9);
+        if (u->normals) s->normals.assign(u->normals, u->normals + n9);
+        if (u->tangents) s->tangents.assign(u->tangents, u->tangents + n9);
+    }
+    const int rc = update_device(s, u);
+    if (rc != ER_OK) {
+        s->begun = false;      // (er_render_begin releases what is left and rebuilds from the edited host copy)
+        return rc;
+    }
+    s->upd.updates++;
+    if (u->what & ER_UPDATE_GEOMETRY) s->upd.refits++;
+    s->upd.update_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ER_OK;
+}
+
+static int er_update_info_impl(ErScene* s, ErUpdateInfo* out) {
+    if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_update_info: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    *out = s->upd;
     return ER_OK;
 }
 
@@ -1263,5 +1370,7 @@ int er_accel_info(ErScene* s, ErAccelInfo* out) { return guarded("er_accel_info"
 int er_adaptive_set(ErScene* s, const ErAdaptiveParams* p) { return guarded("er_adaptive_set", [&]() -> int { return er_adaptive_set_impl(s, p); }); }
 int er_adaptive_info(ErScene* s, ErAdaptiveInfo* out) { return guarded("er_adaptive_info", [&]() -> int { return er_adaptive_info_impl(s, out); }); }
 int er_light_info(ErScene* s, ErLightInfo* out) { return guarded("er_light_info", [&]() -> int { return er_light_info_impl(s, out); }); }
+int er_render_update(ErScene* s, const ErSceneUpdate* u) { return guarded("er_render_update", [&]() -> int { return er_render_update_impl(s, u); }); }
+int er_update_info(ErScene* s, ErUpdateInfo* out) { return guarded("er_update_info", [&]() -> int { return er_update_info_impl(s, out); }); }
 int er_read_tile_state(ErScene* s, float* error, uint32_t* samples) { return guarded("er_read_tile_state", [&]() -> int { return er_read_tile_state_impl(s, error, samples); }); }
 }  // extern "C"

@@ -37,78 +37,12 @@
 #include <rocprim/rocprim.hpp>
 
 #include "er_bvh.h"
+#include "er_build_dev.h"
 #include "er_gpu_build.h"
 
 namespace {
 
-struct Box3 { float lo[3], hi[3]; };
-
-__device__ __forceinline__ unsigned f2ord(float f) {   // order-preserving map float -> unsigned
-    unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
-// pass 1: largest |coordinate| (the absolute part of the box padding, as er_build_bvh)
-__global__ __launch_bounds__(256) void k_scene_bounds(const float* __restrict__ v, uint32_t n, unsigned* g /* [0] vmax bits */) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    float vm = 0;
-    if (i < n) {
-        const float* p = v + (size_t)i * 9;
-        for (int k = 0; k < 9; k++) vm = fmaxf(vm, fabsf(p[k]));
-    }
-    for (int off = 32; off >= 1; off >>= 1) vm = fmaxf(vm, __shfl_xor(vm, off, 64));
-    if ((threadIdx.x & 63) == 0) atomicMax(&g[0], __float_as_uint(vm));     // vm >= 0: the bit pattern orders like the value
-}
-
-// pass 2: padded box, lift bound (er_build_bvh's arithmetic, reference src/Tri.h:106-112)
-__global__ __launch_bounds__(256) void k_prims(const float* __restrict__ v, const float* __restrict__ nrm, uint32_t n, const unsigned* __restrict__ g,
-                                                Box3* __restrict__ boxes, float* __restrict__ lift, unsigned* __restrict__ lift_max,
-                                                unsigned* __restrict__ bounds /* lo[3], hi[3] of all padded boxes, order-preserving integers */) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    float my_lift = 0;
-    float slo[3] = {INFINITY, INFINITY, INFINITY}, shi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    if (i < n) {
-        const float pad_abs = __uint_as_float(g[0]) * 1e-6f;
-        const float* p = v + (size_t)i * 9;
-        Box3 b;
-        for (int a = 0; a < 3; a++) {
-            float lo = fminf(fminf(p[a], p[3 + a]), p[6 + a]), hi = fmaxf(fmaxf(p[a], p[3 + a]), p[6 + a]);
-            float m = fmaxf(fabsf(lo), fabsf(hi));
-            float pad = fmaxf(m * 4e-7f + 1e-37f, pad_abs);
-            float bl = lo - pad, bh = hi + pad;      // rounded outward, as er_build_bvh does
-            if ((double)bl > (double)lo - (double)pad) bl = nextafterf(bl, -INFINITY);
-            if ((double)bh < (double)hi + (double)pad) bh = nextafterf(bh, INFINITY);
-            b.lo[a] = slo[a] = bl;
-            b.hi[a] = shi[a] = bh;
-        }
-        boxes[i] = b;
-        const float* nn = nrm + (size_t)i * 9;
-        double tl = 0;
-        for (int j = 0; j < 3; j++) {
-            double nx = nn[3 * j], ny = nn[3 * j + 1], nz = nn[3 * j + 2];
-            double nl = sqrt(nx * nx + ny * ny + nz * nz);
-            for (int k = 0; k < 3; k++) {
-                if (k == j) continue;
-                double dx = (double)p[3 * k] - p[3 * j], dy = (double)p[3 * k + 1] - p[3 * j + 1], dz = (double)p[3 * k + 2] - p[3 * j + 2];
-                double l = fabs(dx * nx + dy * ny + dz * nz) * nl;
-                if (l > tl) tl = l;
-            }
-        }
-        lift[i] = (float)(tl * 1.01) + 1e-30f;
-        my_lift = (float)(tl * 1.01);
-    }
-    for (int off = 32; off >= 1; off >>= 1) my_lift = fmaxf(my_lift, __shfl_xor(my_lift, off, 64));
-    if ((threadIdx.x & 63) == 0) atomicMax(lift_max, __float_as_uint(my_lift));
-    // the scene bounds are the union of the padded boxes, as er_build_bvh's (until round 7 they were read off the root's child boxes, which
-    // are a box of the builder's own choosing when every centroid coincides and the root is split by position)
-    for (int off = 32; off >= 1; off >>= 1)
-        for (int a = 0; a < 3; a++) { slo[a] = fminf(slo[a], __shfl_xor(slo[a], off, 64)); shi[a] = fmaxf(shi[a], __shfl_xor(shi[a], off, 64)); }
-    if ((threadIdx.x & 63) == 0)
-        for (int a = 0; a < 3; a++) { atomicMin(&bounds[a], f2ord(slo[a])); atomicMax(&bounds[3 + a], f2ord(shi[a])); }
-}
+// (Box3, f2ord / ord2f, k_scene_bounds and k_prims -- passes 1 and 2 -- and the wide nodes' quantisation: er_build_dev.h, shared with er_refit.hip)
 
 // ---------------------------------------------------------------------------------------------------------
 // Round 5: the host builder's own algorithm on the device -- top-down binned SAH (er_bvh.cpp: 16 bins per axis over the
@@ -555,13 +489,7 @@ __global__ __launch_bounds__(128) void k_wide_emit(const ErNode* __restrict__ no
     float scale[3];
     for (int a = 0; a < 3; a++) {
         nd.p[a] = lo[a];
-        const float ext = hi[a] - lo[a];
-        int e = 0;
-        if (ext > 0) (void)frexpf(ext / 255.0f, &e); else e = -126;
-        if (e < -126) e = -126;
-        while (lo[a] + 255.0f * ldexpf(1.0f, e) < hi[a]) e++;
-        nd.e[a] = (uint8_t)(e + 127);
-        scale[a] = ldexpf(1.0f, e);
+        scale[a] = wide_axis_frame(lo[a], hi[a], &nd.e[a]);
     }
     const uint32_t child_base = node_base + inner_off[w];
     uint32_t tri_base = tri_base0 + tri_off_in[w];
@@ -572,16 +500,7 @@ __global__ __launch_bounds__(128) void k_wide_emit(const ErNode* __restrict__ no
         const int ci = child_in[s8];
         if (ci < 0) continue;
         const ChildD& c = ch[ci];
-        for (int a = 0; a < 3; a++) {
-            float fl = floorf((c.lo[a] - nd.p[a]) / scale[a]);
-            float fh = ceilf((c.hi[a] - nd.p[a]) / scale[a]);
-            int ql = (int)fminf(255.0f, fmaxf(0.0f, fl));
-            int qh = (int)fminf(255.0f, fmaxf(0.0f, fh));
-            while (ql > 0 && nd.p[a] + (float)ql * scale[a] > c.lo[a]) ql--;
-            while (qh < 255 && nd.p[a] + (float)qh * scale[a] < c.hi[a]) qh++;
-            nd.qlo[a][s8] = (uint8_t)ql;
-            nd.qhi[a][s8] = (uint8_t)qh;
-        }
+        for (int a = 0; a < 3; a++) wide_axis_quantise(nd.p[a], scale[a], c.lo[a], c.hi[a], &nd.qlo[a][s8], &nd.qhi[a][s8]);
         if (!c.as_leaf) {
             nd.imask |= (uint8_t)(1u << s8);
             next[inner_off[w] + n_in] = WorkD{child_base + n_in, c.ref};

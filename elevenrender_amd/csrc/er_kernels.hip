@@ -179,6 +179,7 @@ hipError_t er_probe_kernels(const char** which) {
     if ((e = er_probe_wavefront(which)) != hipSuccess) return e;
     if ((e = er_probe_stream(which)) != hipSuccess) return e;
     if ((e = er_probe_gpu_build(which)) != hipSuccess) return e;
+    if ((e = er_probe_refit(which)) != hipSuccess) return e;
     *which = nullptr;
     return hipSuccess;
 }

@@ -28,6 +28,7 @@
 #include "er_stream_host.h"
 #include "er_adaptive.h"
 #include "er_lights.h"
+#include "er_refit.h"
 
 namespace erh {
 
@@ -154,6 +155,15 @@ struct ErScene {
     ErAccelInfo accel{};
     float accel_lo[3] = {0, 0, 0}, accel_hi[3] = {0, 0, 0};   // scene bounds as the builder reported them (er_debug_read_accel)
     uint32_t accel_depth2 = 0;                                 // levels of the binary tree (the same hook)
+    // What er_render_update needs of the last er_render_begin to restart a render without running its stages again (er_api.cpp): the
+    // structure's counts, depths, bounds and lift bound (the three pointers are null: the scene owns the buffers), the texture stage's
+    // result, the device's CUs, the flags as the caller gave them (params.flags holds the schedule that was chosen)
+    ErGpuBvhDevice keep_accel;
+    DevTex keep_hdri{};
+    int keep_buckets = 0;
+    uint32_t keep_cus = 0, keep_flags = 0;
+    ErRefitTopo refit_topo;      // the trees' nodes by level, from the first refit after an er_render_begin until the next one
+    ErUpdateInfo upd{};          // er_update_info (counts since er_scene_create)
     DevBuf<float4> d_nodes, d_nodes8, d_attr, d_passes;
     DevBuf<float4> d_plane;      // staging: one pass gathered as a plane for er_read_pass
     DevBuf<ErMaterial> d_materials;
@@ -226,6 +236,7 @@ struct ErScene {
         st.release();
         d_ad_list[0].release(); d_ad_list[1].release(); d_ad_keep.release(); d_ad_snap.release(); d_ad_err.release();
         d_light_tab.release(); light_emitters = 0; light_total = 0.0f;
+        refit_topo.release();
         ad_on = false; rendered = 0;
         for (auto& kv : d_rank_tiles) kv.second.release();
         d_rank_tiles.clear();

@@ -132,6 +132,20 @@ struct RenderParameters {   // src/kernel.h:51-69
     ErAdaptiveParams adaptive_params{};
 };
 
+// What a session sent since its last successful --start.  A --start after nothing but --load_camera restarts the render in place
+// (RenderingManager::update_camera: er_render_update on every rank -- no build, no uploads); after anything else, or before the
+// first render, it is the full start_rendering.
+struct SessionEdits {
+    bool rendering = false;      // a --start has succeeded and its scenes are alive
+    bool camera = false;         // --load_camera arrived since
+    bool other = false;          // ... and anything else that changes the scene or the parameters
+    void on_camera() { camera = true; }
+    void on_other() { other = true; }
+    void on_started() { rendering = true; camera = other = false; }
+    void on_failed() { rendering = false; }
+    bool camera_only() const { return rendering && !other; }      // (no edit at all: the same render again, also without a rebuild)
+};
+
 inline int parsePass(std::string s) {   // src/kernel.cpp:50-73: unknown names -> BEAUTY
     std::transform(s.begin(), s.end(), s.begin(), [](unsigned char c) { return (char)std::tolower(c); });
     if (s == "denoise") return ER_PASS_DENOISE;
@@ -265,6 +279,26 @@ public:
                 transport_used = "in-process";
             }
         }
+    }
+    // A --start after nothing but --load_camera: er_render_update(ER_UPDATE_CAMERA) on every rank side by side, then what
+    // start_rendering does after er_render_begin (the update turns adaptive sampling off, as a begin does).  The communicators stay.
+    // Returns false -- the ranks are then no longer begun, the caller starts over with start_rendering -- if any rank's update failed.
+    bool update_camera(const Camera& c) {
+        if (ers_.empty()) return false;
+        ErSceneUpdate u{};
+        u.what = ER_UPDATE_CAMERA;
+        u.camera = ErCamera{c.focalLength, c.sensorWidth, c.sensorHeight, c.aperture, c.focusDistance,
+                            {c.rotation.x, c.rotation.y, c.rotation.z}, c.bokeh ? 1 : 0, {c.position.x, c.position.y, c.position.z}};
+        std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);
+        if (ers_.size() > 1) lk.lock();
+        std::vector<int> rcs(ers_.size(), ER_OK);
+        std::vector<std::thread> th;
+        for (size_t r = 0; r < ers_.size(); r++) th.emplace_back([&, r] { rcs[r] = er_render_update(ers_[r], &u); });
+        for (auto& t : th) t.join();
+        for (int rc : rcs) if (rc != ER_OK) return false;
+        if (pars.adaptive)
+            for (ErScene* e : ers_) if (er_adaptive_set(e, &pars.adaptive_params) != ER_OK) return false;
+        return true;
     }
     // body of kernel_render_enqueue's loop: n more samples on every rank (the launches go out side by side, then the waits).
     // With several ranks a read-back is a SEQUENCE of library calls (gathers, denoise, read) that must see one frame: if the

@@ -112,6 +112,32 @@ class RenderingManager:
         abi.check(self.lib.er_samples_done(self.handle, C.byref(v)))
         return RenderInfo(samples=v.value)
 
+    def update(self, camera=None, vertices=None, normals=None, tangents=None):
+        """er_render_update: a new camera (abi.ErCamera) and / or moved triangles ([n][3][3] float32 vertices; normals and tangents
+        optional, None = keep) for the begun scene, without a rebuild; the render starts over at sample 0.  self.scene is not changed:
+        a caller that wants to compare against a fresh start builds the edited SceneData itself."""
+        u = abi.ErSceneUpdate()
+        keep = []
+        if camera is not None:
+            u.what |= abi.UPDATE_CAMERA
+            u.camera = camera
+        if vertices is not None or normals is not None or tangents is not None:
+            u.what |= abi.UPDATE_GEOMETRY
+            for name, a in (("vertices", vertices), ("normals", normals), ("tangents", tangents)):
+                if a is None:
+                    continue
+                a = np.ascontiguousarray(a, np.float32)
+                if a.size != self.scene.tri_count * 9:
+                    raise ValueError(f"update: {name} has {a.size} floats, the scene has {self.scene.tri_count} triangles")
+                keep.append(a)
+                setattr(u, name, a.ctypes.data_as(C.POINTER(C.c_float)))
+        abi.check(self.lib.er_render_update(self.handle, C.byref(u)))
+
+    def update_info(self):
+        a = abi.ErUpdateInfo()
+        abi.check(self.lib.er_update_info(self.handle, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in abi.ErUpdateInfo._fields_}
+
     def set_adaptive(self, threshold, min_samples=0, interval=0):
         """Adaptive sampling (er_adaptive_set): between start_rendering and the first sample.  Tiles whose noise falls below
         `threshold` stop receiving samples; tests at min_samples (0 -> 16), then every `interval` (0 -> 8) samples.

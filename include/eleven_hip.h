@@ -328,9 +328,42 @@ typedef struct ErAccelInfo {
     uint32_t tri_record_bytes;         /* bytes fetched per triangle test */
     float build_ms, upload_ms;
     float lift_bound;                  /* global bound on |shadingPosition - geomPosition| */
-    uint32_t builder;                  /* 0 = host binned-SAH build, 1 = device binned-SAH build */
+    uint32_t builder;                  /* 0 = host binned-SAH build, 1 = device binned-SAH build, 2 = refit of an earlier build
+                                          (er_render_update with ER_UPDATE_GEOMETRY; build_ms then holds the refit's device time) */
 } ErAccelInfo;
 int er_accel_info(ErScene* scene, ErAccelInfo* out);
+
+/* Edit a begun scene in place: a new camera, moved triangles, or both, without the stages of er_render_begin that the edit does not
+ * concern (no build, no texture, material or record upload for a camera; a device refit of the built structure for geometry).
+ * After ER_OK every readable output -- the five planes, samples, RNG, er_get_counters, er_samples_done, er_light_info,
+ * er_adaptive_info (off again), er_state_* -- equals what er_scene_destroy, er_scene_create of the description with that camera or
+ * those arrays replaced, and er_render_begin with the same ErRenderParams would give, bit for bit: the render starts over at sample
+ * 0.  The one exception is the acceleration structure after a geometry update: its topology (child references, slot assignment,
+ * triangle order) is kept and only the boxes and the triangle records are recomputed, ErAccelInfo.builder reports 2 and build_ms the
+ * refit's device time.  Images do not depend on the tree; traversal cost grows with the deformation, and er_render_begin remains the
+ * way to a fresh tree.  A camera-only update leaves ErAccelInfo unchanged, field for field.
+ * Call order: the scene must be begun (else ER_ERR_STATE); pending asynchronous work is waited for.  NULL arguments, `what` 0 or with
+ * unknown bits, NULL vertices with ER_UPDATE_GEOMETRY, or a vertex coordinate that is not finite: ER_ERR_INVALID_ARG, the scene is
+ * untouched and still begun.  The scene's host copy (vertices, normals, tangents, camera) is replaced before any device work; if device
+ * work then fails, the scene is NO LONGER BEGUN -- every render call returns ER_ERR_STATE -- and a later er_render_begin rebuilds from
+ * the edited host copy. */
+#define ER_UPDATE_CAMERA   1u
+#define ER_UPDATE_GEOMETRY 2u
+typedef struct ErSceneUpdate {
+    uint32_t what;            /* bits above */
+    ErCamera camera;          /* read iff ER_UPDATE_CAMERA */
+    const float* vertices;    /* ER_UPDATE_GEOMETRY: [tri_count][3][3], required; tri_count is the scene's */
+    const float* normals;     /* [tri_count][3][3] or NULL = keep */
+    const float* tangents;    /* [tri_count][3][3] or NULL = keep */
+} ErSceneUpdate;
+typedef struct ErUpdateInfo {
+    uint32_t updates;         /* successful er_render_update calls since er_scene_create */
+    uint32_t refits;          /* ... of which refitted the structure */
+    float refit_ms;           /* device time of the last refit (HIP events: uploads of the arrays to the last tree level), 0 if none */
+    float update_ms;          /* host wall time of the last er_render_update */
+} ErUpdateInfo;
+int er_render_update(ErScene* scene, const ErSceneUpdate* update);
+int er_update_info(ErScene* scene, ErUpdateInfo* out);
 
 #ifdef __cplusplus
 }
