@@ -22,6 +22,8 @@ FLAG_POINT_LIGHTS, FLAG_COUNTERS, FLAG_MEGAKERNEL, FLAG_PROFILE, FLAG_FUSED, FLA
 FLAG_HOST_BUILD = 512
 FLAG_MESH_LIGHTS = 1024     # next-event estimation of emissive triangles (csrc/er_shade.h)
 UPDATE_CAMERA, UPDATE_GEOMETRY = 1, 2     # ErSceneUpdate.what
+FEATURE_ALBEDO, FEATURE_DEPTH, FEATURE_COUNT = 0, 1, 2     # er_render_features (csrc/er_features.hip)
+FEATURE_NAMES = {"albedo": 0, "depth": 1}
 
 
 class ErVec3(C.Structure):
@@ -118,6 +120,14 @@ class ErSceneUpdate(C.Structure):
 
 class ErUpdateInfo(C.Structure):
     _fields_ = [("updates", C.c_uint32), ("refits", C.c_uint32), ("refit_ms", C.c_float), ("update_ms", C.c_float)]
+
+
+class ErFeatureInfo(C.Structure):
+    _fields_ = [("valid", C.c_uint32), ("samples", C.c_uint32), ("rays", C.c_uint64), ("ms", C.c_float)]
+
+
+class ErDenoiseGuided(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("colour_sigma", C.c_float), ("albedo_sigma", C.c_float), ("depth_sigma", C.c_float)]
 
 
 class ErStreamInfo(C.Structure):   # include/eleven_hip_debug.h
@@ -225,6 +235,11 @@ SYMBOLS = {
     "er_light_info": (C.c_int, [_P, C.POINTER(ErLightInfo)]),
     "er_get_profile": (C.c_int, [_P, C.POINTER(ErProfile)]),
     "er_denoise": (C.c_int, [_P, C.c_uint32, C.c_float]),
+    "er_render_features": (C.c_int, [_P, C.c_uint32]),
+    "er_feature_info": (C.c_int, [_P, C.POINTER(ErFeatureInfo)]),
+    "er_read_feature": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
+    "er_gather_feature": (C.c_int, [_P, C.c_int, _P, C.c_uint32]),
+    "er_denoise_guided": (C.c_int, [_P, C.POINTER(ErDenoiseGuided)]),
     "er_state_size": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "er_state_export": (C.c_int, [_P, _P, C.c_uint64]),
     "er_state_import": (C.c_int, [_P, _P, C.c_uint64]),

@@ -171,6 +171,7 @@ int begin_open(ErScene* s, const ErRenderParams* p) {
     s->device = p->device;
     s->params = *p;
     s->ad_on = false;      // (adaptive sampling is set per render, after its er_render_begin)
+    s->feat_valid = false; // (the feature planes are of the scene state that ends here)
     s->rendered = 0;
     s->params.world = p->world ? p->world : 1;
     if (s->params.max_bounces == 0) s->params.max_bounces = 5;   // the literal of reference src/kernel.cpp:508
@@ -770,6 +771,8 @@ static int er_render_update_impl(ErScene* s, const ErSceneUpdate* u) {
         if (u->normals) s->normals.assign(u->normals, u->normals + n9);
         if (u->tangents) s->tangents.assign(u->tangents, u->tangents + n9);
     }
+    s->feat_valid = false;      // the feature planes show the scene before the edit (er_render_features makes them again)
+    for (auto& set : s->unpacked_feat) set.clear();
     const int rc = update_device(s, u);
     if (rc != ER_OK) {
         s->begun = false;      // (er_render_begin releases what is left and rebuilds from the edited host copy)

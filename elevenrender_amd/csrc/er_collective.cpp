@@ -203,15 +203,21 @@ static int er_comm_create_local_impl(uint32_t world, ErComm** out) {
 
 // pack -> exchange -> unpack of ONE plane (ER_PASS_COUNT = the sample-count plane).  Every rank of the communicator
 // calls it with its own scene; after it the root's full plane holds every rank's pixels.
-static int er_gather_pass_impl(ErScene* s, int pass, ErComm* c, uint32_t root) {
-    if (!s || !c) return fail(ER_ERR_INVALID_ARG, "er_gather_pass: NULL argument");
-    if (pass < 0 || pass >= ER_PASS_COUNT) return fail(ER_ERR_INVALID_ARG, "er_gather_pass: pass out of range");
-    if (root >= c->world) return fail(ER_ERR_INVALID_ARG, "er_gather_pass: root >= world");
+// (`feature`: the plane is feature `pass` of er_features.hip -- a row-major plane of its own -- instead of pass `pass` of DevScene::passes;
+// the exchange is the same, the pack and unpack kernels address the plane)
+static int gather_impl(ErScene* s, int pass, bool feature, ErComm* c, uint32_t root) {
+    const std::string who_s = feature ? "er_gather_feature" : "er_gather_pass";
+    const char* who = feature ? "er_gather_feature" : "er_gather_pass";
+    if (!s || !c) return fail(ER_ERR_INVALID_ARG, who_s + ": NULL argument");
+    if (pass < 0 || pass >= (feature ? (int)ER_FEATURE_COUNT : (int)ER_PASS_COUNT)) return fail(ER_ERR_INVALID_ARG, who_s + (feature ? ": feature out of range" : ": pass out of range"));
+    if (root >= c->world) return fail(ER_ERR_INVALID_ARG, who_s + ": root >= world");
     std::lock_guard<std::mutex> lk(s->mtx);
-    if (!s->begun) return fail(ER_ERR_STATE, "er_gather_pass: er_render_begin has not succeeded");
+    if (!s->begun) return fail(ER_ERR_STATE, who_s + ": er_render_begin has not succeeded");
+    if (feature && !s->feat_valid) return fail(ER_ERR_STATE, who_s + ": no feature planes of this scene state (er_render_features)");
     if (s->params.world != c->world || s->params.rank != c->rank)
-        return fail(ER_ERR_INVALID_ARG, "er_gather_pass: the scene's rank/world differ from the communicator's");
+        return fail(ER_ERR_INVALID_ARG, who_s + ": the scene's rank/world differ from the communicator's");
     if (c->world == 1) return ER_OK;     // the plane is already whole
+    float4* const plane = feature ? s->d_feat.p + (size_t)pass * s->x_res * s->y_res : nullptr;
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = s->stream;          // ordered after every sample enqueued so far
     int rc;
@@ -219,7 +225,8 @@ static int er_gather_pass_impl(ErScene* s, int pass, ErComm* c, uint32_t root) {
         const size_t n = (size_t)s->dev.owned_tile_count * 64;
         DevBuf<float4>& mine = s->d_gather_mine;          // (kept on the scene: allocated by the first gather)
         if (mine.n < n || !mine.p) { if ((rc = upload(mine, (const float4*)nullptr, n, st)) != ER_OK) return rc; }
-        er_launch_pack(s->dev, s->d_owned.p, s->dev.owned_tile_count, pass, mine.p, st);
+        if (feature) er_launch_pack_plane(s->dev, s->d_owned.p, s->dev.owned_tile_count, plane, mine.p, st);
+        else er_launch_pack(s->dev, s->d_owned.p, s->dev.owned_tile_count, pass, mine.p, st);
         HIP_TRY(hipGetLastError());
         if ((rc = c->t.group_start(c->self)) != ER_OK) return rc;
         rc = c->t.send(c->self, mine.p, n * sizeof(float4), root, st);
@@ -227,7 +234,7 @@ static int er_gather_pass_impl(ErScene* s, int pass, ErComm* c, uint32_t root) {
         if (rc != ER_OK) return rc;
         if (rc2 != ER_OK) return rc2;
         HIP_TRY(hipStreamSynchronize(st));   // the next gather packs into the same buffer
-        return er_scene_stream_status(s, "er_gather_pass");   // (what was sent is incomplete if the streaming schedule stopped early)
+        return er_scene_stream_status(s, who);   // (what was sent is incomplete if the streaming schedule stopped early)
     }
     // root: one receive buffer per peer, all receives in ONE group (seven xGMI links side by side), then the scatters
     // (receive buffers and the peers' tile tables live on the scene: the first gather allocates and uploads them, every later one
@@ -259,12 +266,13 @@ static int er_gather_pass_impl(ErScene* s, int pass, ErComm* c, uint32_t root) {
     for (uint32_t r = 0; r < c->world; r++) {
         if (r == root) continue;
         const DevBuf<uint32_t>& tiles = s->d_rank_tiles[r];
-        er_launch_unpack(s->dev, tiles.p, (uint32_t)tiles.n, pass, in[r], st);
+        if (feature) er_launch_unpack_plane(s->dev, tiles.p, (uint32_t)tiles.n, plane, in[r], st);
+        else er_launch_unpack(s->dev, tiles.p, (uint32_t)tiles.n, pass, in[r], st);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    for (uint32_t r = 0; r < c->world; r++) if (r != root) s->unpacked[pass].insert(r);
-    return er_scene_stream_status(s, "er_gather_pass");
+    for (uint32_t r = 0; r < c->world; r++) if (r != root) (feature ? s->unpacked_feat[pass] : s->unpacked[pass]).insert(r);
+    return er_scene_stream_status(s, who);
 }
 
 static int er_debug_gather_buffers_impl(ErScene* s, uint32_t peer, void** in_ptr, uint64_t* in_bytes, void** mine_ptr, uint64_t* mine_bytes) {
@@ -325,7 +333,10 @@ void er_comm_destroy(ErComm* c) {
     delete c;
 }
 int er_gather_pass(ErScene* s, int pass, ErComm* c, uint32_t root) {
-    return guarded("er_gather_pass", [&]() -> int { return er_gather_pass_impl(s, pass, c, root); });
+    return guarded("er_gather_pass", [&]() -> int { return gather_impl(s, pass, false, c, root); });
+}
+int er_gather_feature(ErScene* s, int feature, ErComm* c, uint32_t root) {
+    return guarded("er_gather_feature", [&]() -> int { return gather_impl(s, feature, true, c, root); });
 }
 int er_comm_create_local(uint32_t world, ErComm** out) {
     return guarded("er_comm_create_local", [&]() -> int { return er_comm_create_local_impl(world, out); });

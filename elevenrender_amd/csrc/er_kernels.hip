@@ -9,6 +9,7 @@
 // until a lane has finished all n samples instead of idling to the longest path.
 #include "er_kernels.h"
 #include "er_stream.h"
+#include "er_features.h"
 #include "er_device.h"
 #include "er_shade.h"
 
@@ -180,6 +181,7 @@ hipError_t er_probe_kernels(const char** which) {
     if ((e = er_probe_stream(which)) != hipSuccess) return e;
     if ((e = er_probe_gpu_build(which)) != hipSuccess) return e;
     if ((e = er_probe_refit(which)) != hipSuccess) return e;
+    if ((e = er_probe_features(which)) != hipSuccess) return e;
     *which = nullptr;
     return hipSuccess;
 }

@@ -29,6 +29,7 @@
 #include "er_adaptive.h"
 #include "er_lights.h"
 #include "er_refit.h"
+#include "er_features.h"
 
 namespace erh {
 
@@ -217,6 +218,16 @@ struct ErScene {
     // which ranks' pixels of each plane were unpacked into this scene since the last sample was enqueued: er_denoise on a
     // sharded frame needs the whole BEAUTY and NORMAL planes (the rank the frame was gathered to)
     std::set<uint32_t> unpacked[ER_PASS_COUNT];
+    // the feature pass (er_features.hip): the ALBEDO and DEPTH planes back to back (row-major, allocated by the first er_render_features)
+    // and the traversal's spill area of its bounded grid; valid from a pass until the next er_render_begin or er_render_update.
+    // Recomputable, so not part of the progressive state.  unpacked_feat: as `unpacked`, since the last pass.
+    DevBuf<float4> d_feat;
+    DevBuf<uint2> d_feat_spill;
+    bool feat_valid = false;
+    uint32_t feat_samples = 0;
+    uint64_t feat_rays = 0;
+    float feat_ms = 0;
+    std::set<uint32_t> unpacked_feat[ER_FEATURE_COUNT];
     std::mutex mtx;
 
     uint32_t tiles_x() const { return (x_res + ER_TILE - 1) / ER_TILE; }      // the frame in tiles of ER_TILE x ER_TILE pixels
@@ -237,6 +248,8 @@ struct ErScene {
         d_ad_list[0].release(); d_ad_list[1].release(); d_ad_keep.release(); d_ad_snap.release(); d_ad_err.release();
         d_light_tab.release(); light_emitters = 0; light_total = 0.0f;
         refit_topo.release();
+        d_feat.release(); d_feat_spill.release(); feat_valid = false;
+        for (auto& u : unpacked_feat) u.clear();
         ad_on = false; rendered = 0;
         for (auto& kv : d_rank_tiles) kv.second.release();
         d_rank_tiles.clear();

@@ -24,7 +24,10 @@
 //     (src/Math.hpp:12-20 zeroes every value above 0.04045), which cannot be intended;
 //   * config accepts the optional keys max_bounces (default 5), point_lights / mis / mesh_lights (false), schedule, and gpus / devices /
 //     transport: the frame's pixel tiles are dealt to `gpus` GPUs of this node driven by this one process, and --get_pass
-//     gathers the plane to the first of them (er_gather_pass: RCCL send/recv over xGMI, or in-process peer copies).
+//     gathers the plane to the first of them (er_gather_pass: RCCL send/recv over xGMI, or in-process peer copies);
+//   * --get_pass albedo / depth return the first-hit feature planes (er_render_features, computed once per --start or camera
+//     update, when first asked for); config "denoise_guided": true (optionally "feature_samples": 1 .. 64) makes `denoise: true` /
+//     --get_pass denoise run the filter guided by them (er_denoise_guided) instead of er_denoise.
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -287,6 +290,8 @@ private:
             if (!rm.transport_used.empty()) j["transport"] = rm.transport_used;
             j["samples_per_call"] = samples_per_call_.load();
             j["camera_updates"] = camera_updates_;
+            j["feature_samples"] = rm.pars.feature_samples ? rm.pars.feature_samples : 4u;      // rays per pixel of a feature pass (--get_pass albedo / depth, denoise_guided)
+            if (rm.pars.denoise_guided) j["denoise_guided"] = true;
             im->write_message(Message::json_data(j));
             return;
         }
@@ -380,6 +385,13 @@ private:
             if (i >= m) throw std::runtime_error("config adaptive interval must be smaller than min_samples");
             rp.adaptive = true;
         }
+        // the denoise guided by first-hit albedo and depth (er_denoise_guided) in place of er_denoise, and the rays per pixel of its feature pass
+        if (const json::Value* v = j.if_contains("denoise_guided")) rp.denoise_guided = v->as_bool();
+        if (const json::Value* v = j.if_contains("feature_samples")) {
+            const long long n = v->as_int64();
+            if (n < 1 || n > 64) throw std::runtime_error("config feature_samples out of range (1 .. 64)");
+            rp.feature_samples = (unsigned)n;
+        }
         stop_render_thread();
         rm.pars = rp;
         scene.x_res = rp.width;
@@ -430,8 +442,17 @@ private:
             if (!render_error_.empty()) throw std::runtime_error("render thread failed: " + render_error_);
         }
         std::vector<float> img;
+        if (parseFeature(pass) >= 0) {      // a feature plane: made when first asked for after a --start or a camera update
+            rm.ensure_features(rm.pars.feature_samples);
+            img = rm.get_feature(pass);
+            im->write_message(Message::float_data(img.data(), img.size(), Message::DataFormat::FLOAT4));
+            return;
+        }
         const bool want_denoise = parsePass(pass) == ER_PASS_DENOISE || (rm.pars.denoise && parsePass(pass) == ER_PASS_BEAUTY);
-        if (want_denoise) {
+        if (want_denoise && rm.pars.denoise_guided) {
+            img = rm.get_denoised_guided(rm.pars.feature_samples);      // features if there are none yet, gathers, er_denoise_guided, read: one step against the render thread
+            for (size_t i = 3; i < img.size(); i += 4) img[i] = 1.0f;
+        } else if (want_denoise) {
             img = rm.get_denoised();                    // gathers, fills the DENOISE plane from the current BEAUTY + NORMAL planes and reads it: one step against the render thread
             for (size_t i = 3; i < img.size(); i += 4) img[i] = 1.0f;   // :270-272
         } else {

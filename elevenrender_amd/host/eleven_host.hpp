@@ -130,6 +130,10 @@ struct RenderParameters {   // src/kernel.h:51-69
     // adaptive sampling (extension, off by default): applied to every rank after er_render_begin (er_adaptive_set)
     bool adaptive = false;
     ErAdaptiveParams adaptive_params{};
+    // the denoise guided by first-hit albedo and depth (extension, off by default): `denoise: true` / get_pass denoise then run
+    // er_denoise_guided on feature planes of feature_samples camera rays per pixel (0 = the library's default, 4)
+    bool denoise_guided = false;
+    unsigned feature_samples = 0;
 };
 
 // What a session sent since its last successful --start.  A --start after nothing but --load_camera restarts the render in place
@@ -145,6 +149,13 @@ struct SessionEdits {
     void on_failed() { rendering = false; }
     bool camera_only() const { return rendering && !other; }      // (no edit at all: the same render again, also without a rebuild)
 };
+
+inline int parseFeature(std::string s) {   // the feature planes of er_render_features by name, -1 = not one
+    std::transform(s.begin(), s.end(), s.begin(), [](unsigned char c) { return (char)std::tolower(c); });
+    if (s == "albedo") return ER_FEATURE_ALBEDO;
+    if (s == "depth") return ER_FEATURE_DEPTH;
+    return -1;
+}
 
 inline int parsePass(std::string s) {   // src/kernel.cpp:50-73: unknown names -> BEAUTY
     std::transform(s.begin(), s.end(), s.begin(), [](unsigned char c) { return (char)std::tolower(c); });
@@ -295,6 +306,7 @@ public:
         std::vector<std::thread> th;
         for (size_t r = 0; r < ers_.size(); r++) th.emplace_back([&, r] { rcs[r] = er_render_update(ers_[r], &u); });
         for (auto& t : th) t.join();
+        features_ready_ = false;      // (the library has invalidated the planes)
         for (int rc : rcs) if (rc != ER_OK) return false;
         if (pars.adaptive)
             for (ErScene* e : ers_) if (er_adaptive_set(e, &pars.adaptive_params) != ER_OK) return false;
@@ -336,6 +348,61 @@ public:
         denoise_unlocked(levels, colour_sigma);
         return get_pass_unlocked(ER_PASS_DENOISE);
     }
+    // The feature pass (er_render_features) on every rank side by side, then both planes gathered to rank 0.  The planes depend on the
+    // scene and the camera alone, not on the samples: once per start_rendering / update_camera is enough.
+    void render_features(unsigned n = 0) {
+        if (ers_.empty()) throw std::runtime_error("render_features: no render has been started");
+        std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);
+        if (ers_.size() > 1) lk.lock();
+        render_features_unlocked(n);
+    }
+    // ... and lazily: only if no pass has run since the last start_rendering / update_camera (get_pass albedo / depth, `denoise_guided`)
+    void ensure_features(unsigned n = 0) {
+        if (ers_.empty()) throw std::runtime_error("render_features: no render has been started");
+        std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);
+        if (ers_.size() > 1) lk.lock();
+        if (!features_ready_) render_features_unlocked(n);
+    }
+    std::vector<float> get_feature(const std::string& name) {      // "albedo" | "depth"; render_features first
+        if (ers_.empty()) throw std::runtime_error("get_feature: no render has been started");
+        const int f = parseFeature(name);
+        if (f < 0) throw std::runtime_error("get_feature: '" + name + "' is not a feature plane (albedo, depth)");
+        std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);
+        if (ers_.size() > 1) lk.lock();
+        std::vector<float> out((size_t)pars.width * pars.height * 4);
+        check(er_read_feature(ers_[0], f, out.data()));
+        return out;
+    }
+    ErFeatureInfo feature_info() {      // over the ranks: rays summed, the slowest rank's time
+        ErFeatureInfo sum{};
+        sum.valid = ers_.empty() ? 0u : 1u;
+        for (ErScene* e : ers_) {
+            ErFeatureInfo i{};
+            check(er_feature_info(e, &i));
+            sum.valid = sum.valid && i.valid ? 1u : 0u;
+            sum.samples = i.samples;
+            sum.rays += i.rays;
+            sum.ms = std::max(sum.ms, i.ms);
+        }
+        return sum;
+    }
+    // er_denoise_guided where the whole frame is: on a sharded frame on rank 0, after BEAUTY and NORMAL have been gathered there
+    // (the features were when the pass ran)
+    void denoise_guided(unsigned levels = 0, float colour_sigma = 0, float albedo_sigma = 0, float depth_sigma = 0) {
+        if (ers_.empty()) throw std::runtime_error("denoise_guided: no render has been started");
+        std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);
+        if (ers_.size() > 1) lk.lock();
+        denoise_guided_unlocked(levels, colour_sigma, albedo_sigma, depth_sigma);
+    }
+    // features if there are none yet + guided denoise + read of the DENOISE plane as ONE step against the render thread
+    std::vector<float> get_denoised_guided(unsigned feature_samples = 0, unsigned levels = 0, float colour_sigma = 0, float albedo_sigma = 0, float depth_sigma = 0) {
+        if (ers_.empty()) throw std::runtime_error("denoise_guided: no render has been started");
+        std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);
+        if (ers_.size() > 1) lk.lock();
+        if (!features_ready_) render_features_unlocked(feature_samples);
+        denoise_guided_unlocked(levels, colour_sigma, albedo_sigma, depth_sigma);
+        return get_pass_unlocked(ER_PASS_DENOISE);
+    }
     // adaptive sampling over the ranks: the ranks' tiles summed, samples_rendered of the rank that is furthest ahead (each rank stops
     // only its own tiles; the frame goes on while any rank has an active tile)
     uint32_t emitters() {      // the emitter table of ER_FLAG_MESH_LIGHTS (every rank builds the same one)
@@ -373,6 +440,25 @@ private:
     std::vector<ErScene*> ers_;
     std::vector<ErComm*> comms_;
     std::mutex frame_mtx_;
+    bool features_ready_ = false;      // a feature pass has run (and been gathered) since the last start_rendering / update_camera
+    void render_features_unlocked(unsigned n) {
+        features_ready_ = false;
+        std::vector<std::string> errs(ers_.size());
+        std::vector<std::thread> th;
+        for (size_t r = 0; r < ers_.size(); r++)
+            th.emplace_back([&, r] { if (er_render_features(ers_[r], n) != ER_OK) errs[r] = er_last_error(); });
+        for (auto& t : th) t.join();
+        for (auto& e : errs) if (!e.empty()) throw std::runtime_error(e);
+        gather(ER_FEATURE_ALBEDO, true);
+        gather(ER_FEATURE_DEPTH, true);
+        features_ready_ = true;
+    }
+    void denoise_guided_unlocked(unsigned levels, float colour_sigma, float albedo_sigma, float depth_sigma) {
+        gather(ER_PASS_BEAUTY);
+        gather(ER_PASS_NORMAL);
+        const ErDenoiseGuided p{levels, colour_sigma, albedo_sigma, depth_sigma};
+        check(er_denoise_guided(ers_[0], &p));
+    }
     std::vector<float> get_pass_unlocked(int pass) {
         std::vector<float> out((size_t)pars.width * pars.height * 4);
         gather(pass);
@@ -387,12 +473,13 @@ private:
     static void check(int rc, const char* what = nullptr) { if (rc != ER_OK) throw std::runtime_error(what ? what : er_last_error()); }
     // every rank's owned pixels of one plane -> rank 0's plane: one er_gather_pass per rank, side by side (the RCCL sends block until
     // the root has posted its receives, so the ranks cannot take turns on one thread)
-    void gather(int pass) {
-        if (ers_.size() < 2 || pass == ER_PASS_DENOISE) return;      // (the DENOISE plane is only ever written on rank 0)
+    // (feature: `pass` names a feature plane, er_gather_feature)
+    void gather(int pass, bool feature = false) {
+        if (ers_.size() < 2 || (!feature && pass == ER_PASS_DENOISE)) return;      // (the DENOISE plane is only ever written on rank 0)
         std::vector<std::string> errs(ers_.size());
         std::vector<std::thread> th;
         for (size_t r = 0; r < ers_.size(); r++)
-            th.emplace_back([&, r] { if (er_gather_pass(ers_[r], pass, comms_[r], 0) != ER_OK) errs[r] = er_last_error(); });
+            th.emplace_back([&, r] { if ((feature ? er_gather_feature(ers_[r], pass, comms_[r], 0) : er_gather_pass(ers_[r], pass, comms_[r], 0)) != ER_OK) errs[r] = er_last_error(); });
         for (auto& t : th) t.join();
         for (auto& e : errs) if (!e.empty()) throw std::runtime_error(e);
     }
@@ -401,6 +488,7 @@ private:
         comms_.clear();
         for (ErScene* e : ers_) if (e) er_scene_destroy(e);
         ers_.clear();
+        features_ready_ = false;
         transport_used.clear();
     }
 };

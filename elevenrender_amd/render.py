@@ -179,6 +179,28 @@ class RenderingManager:
         """Fill the DENOISE plane from BEAUTY + NORMAL (er_denoise); get_pass("denoise") then returns it."""
         abi.check(self.lib.er_denoise(self.handle, levels, colour_sigma))
 
+    def render_features(self, n=0):
+        """er_render_features: n camera rays per owned pixel (0 -> 4) into the ALBEDO and DEPTH feature planes; the render's own state
+        is neither read nor written."""
+        abi.check(self.lib.er_render_features(self.handle, n))
+
+    def get_feature(self, name):
+        """er_read_feature: "albedo" (xyz = mean first-hit albedo, w = coverage) or "depth" (xyz = mean hit distance, w = coverage)."""
+        f = abi.FEATURE_NAMES[str(name).lower()]
+        out = np.empty((self.scene.y_res, self.scene.x_res, 4), np.float32)
+        abi.check(self.lib.er_read_feature(self.handle, f, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def feature_info(self):
+        a = abi.ErFeatureInfo()
+        abi.check(self.lib.er_feature_info(self.handle, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in abi.ErFeatureInfo._fields_}
+
+    def denoise_guided(self, levels=0, colour_sigma=0.0, albedo_sigma=0.0, depth_sigma=0.0):
+        """Fill the DENOISE plane from BEAUTY + NORMAL + the feature planes (er_denoise_guided; render_features first)."""
+        p = abi.ErDenoiseGuided(levels, colour_sigma, albedo_sigma, depth_sigma)
+        abi.check(self.lib.er_denoise_guided(self.handle, C.byref(p)))
+
     def read_samples(self):
         out = np.empty(self.scene.x_res * self.scene.y_res, np.uint32)
         abi.check(self.lib.er_read_samples(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint32))))

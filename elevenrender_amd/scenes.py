@@ -101,6 +101,19 @@ def cornell_dim(x_res=256, y_res=256):
     return sc
 
 
+def cornell_textured(x_res=256, y_res=256):
+    """C1 with a texture on its grey surfaces (floor, ceiling, back wall): a 64 x 64 unfiltered checker of 8 x 8 texel cells,
+    (0.9, 0.85, 0.8) and (0.15, 0.2, 0.3) -- albedo detail of high contrast beside Monte-Carlo noise, the case the guided denoise
+    (er_denoise_guided) is for and the plain one blurs."""
+    sc = cornell(x_res, y_res)
+    cell = (np.arange(64)[:, None] // 8 + np.arange(64)[None, :] // 8) % 2
+    tex = np.where(cell[:, :, None] == 0, np.array([0.9, 0.85, 0.8], np.float32), np.array([0.15, 0.2, 0.3], np.float32)).astype(np.float32)
+    sc.textures = [(abi._f32(tex), 64, 64, 3, 0)]
+    sc.materials[0] = abi.default_material(albedo_tex=0)
+    sc._desc = None
+    return sc
+
+
 def soup_geometry(n_tris, seed=12345):
     """C2 distribution: centroid c ~ U([-1,1]^2 x [2,4]); v0 = c, v1,v2 = c + U([-1,1]^3) * e, e = 2/cbrt(N)."""
     r = Rand(seed, 1)

@@ -365,6 +365,40 @@ typedef struct ErUpdateInfo {
 int er_render_update(ErScene* scene, const ErSceneUpdate* update);
 int er_update_info(ErScene* scene, ErUpdateInfo* out);
 
+/* First-hit feature planes and the denoise guided by them (extension; csrc/er_features.hip gives every float32 operation).
+ * er_render_features: a stateless primary-visibility pass over the pixels this rank owns -- n camera rays per pixel (0 -> 4, at most
+ * 64; more: ER_ERR_INVALID_ARG) through the production traversal, drawn from the pixel's RNG stream as er_render_begin seeds it, so
+ * ray 0 is the camera ray of the render's first sample.  It overwrites two float4 planes (row-major like er_read_pass):
+ *   ER_FEATURE_ALBEDO  xyz = mean of the first-hit albedo as the shading step sees it (a miss counts as (1, 1, 1)), w = hits / n
+ *   ER_FEATURE_DEPTH   x = y = z = mean distance from the ray origin to Hit.position over the rays that hit (0 if none), w = hits / n
+ * The pass reads neither the planes, the sample counts nor the RNG state of the render and writes none of them; its rays are not
+ * in ErCounters but in ErFeatureInfo.  Opacity is not drawn: the first hit counts whatever its opacity.  Pending asynchronous work is
+ * waited for.  The planes are allocated by the first call (32 bytes per pixel), freed with the scene and not part of er_state_*.
+ * er_render_begin and every successful er_render_update invalidate them: er_read_feature, er_gather_feature and er_denoise_guided
+ * return ER_ERR_STATE until the pass has run again.  Before er_render_begin all five entry points return ER_ERR_STATE.
+ * er_read_feature / er_gather_feature: er_read_pass / er_gather_pass for a feature plane.
+ * er_denoise_guided: fills the DENOISE plane like er_denoise, but filters BEAUTY divided by (albedo + 0.01) -- the irradiance, which
+ * carries the noise but not the texture detail -- with the colour and NORMAL stops of er_denoise and two more on albedo and depth,
+ * and multiplies back.  levels 1..8 (0 -> 5); colour_sigma (0 -> 4: the demodulated signal is several times the radiance),
+ * albedo_sigma (0 -> 0.3), depth_sigma (0 -> 0.2, relative).  Negative or NaN: ER_ERR_INVALID_ARG.  On a sharded frame it runs on
+ * the rank that BEAUTY, NORMAL and both features have been gathered to since the last sample / feature pass; elsewhere ER_ERR_STATE. */
+typedef enum ErFeature { ER_FEATURE_ALBEDO = 0, ER_FEATURE_DEPTH = 1, ER_FEATURE_COUNT = 2 } ErFeature;
+typedef struct ErFeatureInfo {
+    uint32_t valid;           /* 1 between a feature pass and the next er_render_begin / er_render_update */
+    uint32_t samples;         /* n of the last pass */
+    uint64_t rays;            /* camera rays it traced: n x the owned pixels inside the frame */
+    float ms;                 /* its device time (HIP events) */
+} ErFeatureInfo;
+typedef struct ErDenoiseGuided {
+    uint32_t levels;
+    float colour_sigma, albedo_sigma, depth_sigma;
+} ErDenoiseGuided;
+int er_render_features(ErScene* scene, uint32_t n);
+int er_feature_info(ErScene* scene, ErFeatureInfo* out);
+int er_read_feature(ErScene* scene, int feature, float* dst_rgba);
+int er_gather_feature(ErScene* scene, int feature, ErComm* comm, uint32_t root);
+int er_denoise_guided(ErScene* scene, const ErDenoiseGuided* params);
+
 #ifdef __cplusplus
 }
 #endif
