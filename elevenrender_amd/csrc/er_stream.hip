@@ -105,6 +105,24 @@ static_assert(ER_STREAM_SLOTS <= (1u << ST_SLOT_BITS) && ST_SLOT_BITS + 2 <= ER_
 #define ST_ESC 0x200u            //   the closest-hit ray found no candidate at all: the path has left the scene
 #define ST_AMB1 0x400u           //   the HDRI shadow query ended ambiguous (the shader must resolve it by exact distances)
 #define ST_AMB2 0x800u           //   ... the point-light query
+// Hand-offs through LDS (ER_STREAM_LDS_HANDOFF, 0 = everything through the slot's record as before).  What a tracer hands to a shader wave is
+// an integer per closest-hit ray and, for almost every shadow query, one bit -- and the slot's waves share one LDS.  The winner of a closest-hit
+// ray goes to s_hit[slot]; a certain shadow verdict is a flag in s_wait beside the others (occluded; neither bit = unoccluded).  Only the rare
+// rest still travels through the record: a second candidate or an overflow (hit2 != -1: ST_HIT2 says so) and the candidates of an ambiguous
+// verdict (ST_AMB1 / ST_AMB2, as before).  A publish then has no store to device memory to wait for, and the visit is turned round: the lanes
+// that take a ray request its origin and direction BEFORE the publish and look at them after it.
+#ifndef ER_STREAM_LDS_HANDOFF
+#define ER_STREAM_LDS_HANDOFF 1
+#endif
+#define ST_OCC1 0x1000u          //   the HDRI shadow query found a certain occluder
+#define ST_OCC2 0x2000u          //   ... the point-light query
+#define ST_HIT2 0x4000u          //   the closest-hit ray left a second candidate or an overflow mark in the record's hit2 (else hit2 = -1)
+#define ST_COUNT_MASK 0xFFu      // rays of the slot still in flight (at most three)
+static_assert((ST_COUNT_MASK & (ST_FIN | ST_ESC | ST_AMB1 | ST_AMB2 | ST_OCC1 | ST_OCC2 | ST_HIT2)) == 0u &&
+                  (ST_FIN ^ ST_ESC ^ ST_AMB1 ^ ST_AMB2 ^ ST_OCC1 ^ ST_OCC2 ^ ST_HIT2) == (ST_FIN | ST_ESC | ST_AMB1 | ST_AMB2 | ST_OCC1 | ST_OCC2 | ST_HIT2) &&
+                  (ST_FIN & (ST_FIN - 1u)) == 0u && (ST_ESC & (ST_ESC - 1u)) == 0u && (ST_AMB1 & (ST_AMB1 - 1u)) == 0u && (ST_AMB2 & (ST_AMB2 - 1u)) == 0u &&
+                  (ST_OCC1 & (ST_OCC1 - 1u)) == 0u && (ST_OCC2 & (ST_OCC2 - 1u)) == 0u && (ST_HIT2 & (ST_HIT2 - 1u)) == 0u,
+              "the fields of a slot's s_wait word are single bits that overlap neither each other nor the in-flight count");
 // ring capacities (log2).  With the checked cells a full ring only makes its producers wait (shader waves for the tracers
 // to drain the ray ring -- which they do whatever the shaders are doing -- never the other way round: the shade ring holds
 // a slot at most once, so ER_STREAM_SLOTS cells can never be full), so capacities are a tuning matter, not a safety margin.
@@ -146,6 +164,11 @@ static_assert((1u << ST_RQ_LOG2) >= 3u * ER_STREAM_SLOTS, "the ray ring must hol
 #ifndef ER_STREAM_TOP_NODES
 #define ER_STREAM_TOP_NODES 900
 #endif
+// The 4 KB of s_hit (ER_STREAM_LDS_HANDOFF) fit beside 900 nodes in the forms without the ring of free slots; the speculative form, which
+// has that ring as well, gives up 40 nodes (3.2 KB) for them.  st_lds_bytes below adds the kernel's LDS up at compile time.
+#ifndef ER_STREAM_TOP_NODES_SPEC_CUT
+#define ER_STREAM_TOP_NODES_SPEC_CUT (ER_STREAM_LDS_HANDOFF ? 40 : 0)
+#endif
 #ifndef ST_MAX_TRACERS
 #define ST_MAX_TRACERS 13
 #endif
@@ -186,6 +209,11 @@ __device__ __forceinline__ uint32_t st_reserve(uint32_t* counter, bool want) {
     return base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
 }
 
+// the lanes of mask m below this one (v_mbcnt: two instructions, and no per-lane mask to keep in two registers across the tracer's loop)
+__device__ __forceinline__ uint32_t st_rank(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
 // a wave appends the payloads of its `want` lanes to a ring: one reservation, every lane puts its own cell (waiting, in
 // theory, for the previous lap's reader), then the entries are published.  All lanes of the wave call.
 template <uint32_t LOG2>
@@ -197,7 +225,7 @@ __device__ __forceinline__ void st_push(uint32_t* cells, uint32_t* ctl, bool wan
     uint32_t base = 0;
     if (lane == 0) base = er_ring_reserve(ctl, n);
     base = (uint32_t)__builtin_amdgcn_readlane((int)base, 0);
-    if (want && !er_ring_put(cells, LOG2, base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)), payload)) atomicOr(status, err);
+    if (want && !er_ring_put(cells, LOG2, base + st_rank(m), payload)) atomicOr(status, err);
     if (lane == 0) er_ring_publish(ctl, n);      // after the cells: the LDS operations of a wave execute in order
 }
 
@@ -356,6 +384,66 @@ __device__ __forceinline__ void st_write_result(const StState& W, uint32_t rec, 
     }
 }
 
+// the verdict of a slot's shadow query (record rec) as the shader reads it: from the flags the tracers left in the slot's s_wait word when it is
+// certain (HANDOFF), from the record when it is ambiguous (2, 3: amb_bit) -- or always (!HANDOFF)
+template <bool HANDOFF>
+__device__ __forceinline__ int st_verdict(const StState& W, uint32_t rec, uint32_t wflags, uint32_t amb_bit, uint32_t occ_bit) {
+    if (!HANDOFF || (wflags & amb_bit) != 0u) return W.occluded(rec);
+    return (wflags & occ_bit) != 0u ? 1 : 0;
+}
+
+// The take of a tracer wave's ring visit (all lanes call).  The lanes without a ray in traversal (`busy`; bm0 = the wave's busy lanes: a
+// lane whose finished ray is not yet published counts as free, it will be by the time the ray is begun) are granted entries of the ray ring
+// in lane order; a lane that got one (returns true, e = the entry) requests the ray's two pieces from the slot's record into o and d, which
+// stay in flight until they are first looked at (meaningless in the other lanes).  `granted`: the entries the wave was granted.
+template <uint32_t LOG2>
+__device__ __forceinline__ bool st_take_rays(uint32_t* cells, uint32_t* ctl, const StState& W, uint32_t g0, unsigned long long bm0, bool busy, uint32_t* status,
+                                             uint32_t& granted, uint32_t& e, float4& o, float4& d) {
+    unsigned long long rq_peek = 0;
+    granted = 0;
+    if (er_ring_peek_count(rq_peek = er_ring_peek(ctl)) == 0) return false;
+    uint32_t hb = 0;
+    granted = st_take(ctl, 64u - (uint32_t)__popcll(bm0), hb, rq_peek);
+    if (granted == 0) return false;
+    const uint32_t rank = st_rank(~bm0);
+    const bool take = !busy && rank < granted;
+    bool got = false;
+    if (take) {
+        got = er_ring_get(cells, LOG2, hb + rank, e);
+        if (!got) atomicOr(status, ST_ERR_RAY);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    // (the whole wave loads, the lanes without an entry the first record's ray: with no branch round the loads their registers are
+    // written by nothing else, and nothing has to wait for them before their first use)
+    const float4* rp = got ? W.ray_pair(g0 + (e & ST_SLOT_MASK), e >> ST_SLOT_BITS) : (const float4*)W.base;
+    o = rp[0];
+    d = rp[1];
+    return got;
+}
+
+// The kernel's static LDS, array by array as er_stream_kernel declares them (each rounded up to 16 bytes, the largest alignment among them):
+// a form that does not fit the CU's 160 KiB fails the build here and not at its first launch.
+// (A hand-kept sum, kept on the safe side; what the backend really allotted is read from the assembly's metadata by the Makefile rule,
+// which fails the build on the same limit: an array added to the kernel and forgotten here is still caught there.)
+constexpr uint32_t st_lds_pad(uint32_t bytes) { return (bytes + 15u) & ~15u; }
+constexpr uint32_t st_lds_bytes(int form, uint32_t top_nodes) {
+    const bool spec = form == 2;
+    uint32_t b = 0;
+    b += st_lds_pad((spec ? (1u << ST_SQ_LOG2) : 1u) * 4u);      // s_free
+    b += 5u * st_lds_pad(ER_RING_WORDS * 4u);                     // s_free_ctl, s_rq_ctl, s_sq_ctl, s_px_ctl, s_fq_ctl
+    b += st_lds_pad((1u << ST_RQ_LOG2) * 4u);                     // s_rq
+    b += 2u * st_lds_pad((1u << ST_SQ_LOG2) * 4u);                // s_sq, s_fq
+    b += st_lds_pad(ER_STREAM_SLOTS * 4u);                        // s_wait
+    b += st_lds_pad((ER_STREAM_LDS_HANDOFF ? ER_STREAM_SLOTS : 1u) * 4u);      // s_hit
+    b += st_lds_pad(ST_PXBITS_WORDS * 4u);                        // s_pxbits
+    b += st_lds_pad(C_WORDS * 4u) + st_lds_pad(4u) + st_lds_pad((spec ? 3u : 1u) * 4u);      // s_ctl, s_front, s_spec
+    b += top_nodes * 5u * 16u;                                    // s_top
+    b += st_lds_pad(13u * 4u);                                    // s_tp (ER_TIME_PROBE builds; counted always)
+    b += ST_MAX_TRACERS * WF_LDS_STACK * 64u * 8u;                // s_stack
+    return b;
+}
+#define ST_LDS_LIMIT (160u * 1024u)
+
 }  // namespace
 
 template <bool COUNT, bool EXT, bool MESH, uint32_t ST_THREADS, bool FUSE, int FORM>
@@ -367,7 +455,10 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
     // when the launch began and when each XCD's last wave left (ER_SC_START, ER_SC_END + 2 x; 100 MHz): how evenly the deal spread
     // the frame's COST over the XCDs is something only the run can tell (er_stream_host.cpp stream_adapt)
     if (threadIdx.x == 0) atomicMin((unsigned long long*)(status + ER_SC_START), (unsigned long long)wall_clock64());
-    constexpr uint32_t RQ_LOG2 = ST_RQ_LOG2, SLOTS = ER_STREAM_SLOTS, TOP_NODES = ER_STREAM_TOP_NODES;
+    constexpr uint32_t RQ_LOG2 = ST_RQ_LOG2, SLOTS = ER_STREAM_SLOTS, TOP_NODES = FORM == 2 ? ER_STREAM_TOP_NODES - ER_STREAM_TOP_NODES_SPEC_CUT : ER_STREAM_TOP_NODES;
+    constexpr bool HANDOFF = ER_STREAM_LDS_HANDOFF != 0;
+    constexpr bool EARLY_TAKE = HANDOFF;      // the tracer's take before its publish
+    static_assert(st_lds_bytes(FORM, TOP_NODES) <= ST_LDS_LIMIT, "this form of er_stream_kernel needs more LDS than a CU has: fewer top nodes (ER_STREAM_TOP_NODES, _SPEC_CUT)");
     // The kernel's FORM is a template argument: 0 -- the instances that render whole frames, the code they were in round 5; 1 -- with the rule that
     // a pixel which is behind keeps its slot (s_front), for shares of a few pixels per slot; 2 -- that and speculative sample pipelining (comment at
     // ST_DRAWS_MASK), for shares in which slots fall free.  er_launch_stream picks by owned pixels per CU (er_stream_host.cpp stream_choose_form, er_stream_launch_form below).
@@ -386,6 +477,7 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
     __shared__ uint32_t s_sq[1u << ST_SQ_LOG2];
     __shared__ uint32_t s_fq[1u << ST_SQ_LOG2];      // finish ring: slots whose path is over and whose sample waits to be accumulated
     __shared__ uint32_t s_wait[SLOTS];
+    __shared__ int s_hit[HANDOFF ? SLOTS : 1u];      // (HANDOFF) the winner of the slot's closest-hit ray: written by the tracer that publishes it, before its add to s_wait
     __shared__ uint32_t s_pxbits[ST_PXBITS_WORDS];
     __shared__ __attribute__((aligned(8))) uint32_t s_rq_ctl[ER_RING_WORDS], s_sq_ctl[ER_RING_WORDS], s_px_ctl[ER_RING_WORDS], s_fq_ctl[ER_RING_WORDS];
     __shared__ uint32_t s_ctl[C_WORDS];
@@ -398,6 +490,7 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
 #endif
     for (uint32_t i = threadIdx.x; i < TOP_NODES * 5u; i += ST_THREADS)
         s_top[i] = i / 5u < S.node8_count ? S.nodes8[(i / 5u) * ER_NODE8_PIECES + i % 5u] : make_float4(0, 0, 0, 0);
+    (void)s_hit;
     const int lane = threadIdx.x & 63;
     const uint32_t wave = threadIdx.x >> 6;
     const uint32_t g0 = blockIdx.x * SLOTS;          // this workgroup's first slot
@@ -491,21 +584,39 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
 #endif
             while (true) {
                 ER_MARK("tracer_loop_top");
-                // Every refill_min idle lanes the wave does its ring work in one go: FIRST the finished rays of the idle lanes are
-                // published (results out, then the slot's in-flight count; the tracer that takes it to zero hands the slot to the
-                // shaders), THEN the idle lanes take rays from the ring.  Between two such visits a finished lane just sits idle with
-                // its result in registers: publishing per iteration cost the whole wave ~200 instructions on 86 % of its iterations
-                // (some lane of 64 nearly always finishes), for the two or three lanes concerned.
+                // Every refill_min idle lanes the wave does its ring work in one go: the finished rays of the idle lanes are published
+                // (results out, then the slot's in-flight count; the tracer that takes it to zero hands the slot to the shaders) and the
+                // idle lanes take rays from the ring.  Between two such visits a finished lane just sits idle with its result in
+                // registers: publishing per iteration cost the whole wave ~200 instructions on 86 % of its iterations (some lane of 64
+                // nearly always finishes), for the two or three lanes concerned.
+                // (EARLY_TAKE) The take comes FIRST: its lanes -- the idle ones and those about to publish -- request origin and direction of
+                // their new rays (two 16-byte loads), the publish runs while these are on their way (all of it LDS work but for the rare
+                // second candidate or ambiguous verdict), and only then are they waited for and the rays begun: T and lsk still belong
+                // to the finished ray until its result is out.
                 const unsigned long long bm0 = __ballot(busy);
-                unsigned long long rq_peek = 0;
                 const bool visit = 64u - (unsigned)__popcll(bm0) >= refill_min || bm0 == 0;
+                bool got = false;
+                uint32_t got_e = 0, granted = 0;
+                float4 got_o, got_d;      // (only ever looked at by a lane that `got`: left unset elsewhere, so that nothing writes the loads' registers while they are in flight)
+                if (EARLY_TAKE && visit) got = st_take_rays<RQ_LOG2>(s_rq, s_rq_ctl, W, g0, bm0, busy, status, granted, got_e, got_o, got_d);
                 if (visit && __ballot(done)) {
                     ER_MARK("tracer_publish");
 #ifdef ER_TRACER_PROBE
                     trp_pub++;
 #endif
                     const uint32_t ls = lsk & ST_SLOT_MASK, kind = lsk >> ST_SLOT_BITS;
-                    if (done) st_write_result(W, g0 + ls + (kind == 2u ? W.slots : 0u), T.shadow, done_occl, T.overflow, T.s0, T.s1);
+                    if (done) {
+                        const uint32_t rec = g0 + ls + (kind == 2u ? W.slots : 0u);
+                        if (!HANDOFF) st_write_result(W, rec, T.shadow, done_occl, T.overflow, T.s0, T.s1);
+                        else if (T.shadow) {
+                            // a certain verdict is a flag; an ambiguous one (2, 3) leaves what it left before, for the shader's exact test
+                            if (!done_occl && (T.overflow || T.s0 >= 0)) st_write_result(W, rec, true, false, T.overflow, T.s0, T.s1);
+                        } else {
+                            // (st_write_result's hit and hit2)
+                            s_hit[ls] = T.s0 >= 0 ? T.s0 : T.s1;
+                            if (T.overflow || (T.s0 >= 0 && T.s1 >= 0)) W.hit2(rec) = T.overflow ? -2 : T.s1;
+                        }
+                    }
                     if (SPEC && COUNT && done) {      // this ray's visits and tests belong to its sample (counted if and when that is accumulated)
                         atomicAdd(&W.tally_nodes(g0 + ls), c_nodes - ray_n0);
                         atomicAdd(&W.tally_tris(g0 + ls), c_tris - ray_t0);
@@ -518,9 +629,12 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                     if (done) {
                         const bool esc = !T.shadow && !T.overflow && T.s0 < 0 && T.s1 < 0;
                         const bool amb = T.shadow && !done_occl && (T.overflow || T.s0 >= 0);       // (st_write_result's verdicts 2 and 3)
-                        const uint32_t add = (esc ? ST_ESC : 0u) + (amb ? (kind == 1u ? ST_AMB1 : ST_AMB2) : 0u) - 1u;
+                        // (HANDOFF) a certain occluder and a second candidate in the record are flags too (worked out here, from the ray's state: no register across the fence)
+                        const bool occf = HANDOFF && T.shadow && done_occl, hit2f = HANDOFF && !T.shadow && (T.overflow || (T.s0 >= 0 && T.s1 >= 0));
+                        const uint32_t add = (esc ? ST_ESC : 0u) + (amb ? (kind == 1u ? ST_AMB1 : ST_AMB2) : 0u) + (occf ? (kind == 1u ? ST_OCC1 : ST_OCC2) : 0u) +
+                                             (hit2f ? ST_HIT2 : 0u) - 1u;
                         fin = atomicAdd(&s_wait[ls], add) + add;
-                        last = (fin & 0xFFu) == 0u;
+                        last = (fin & ST_COUNT_MASK) == 0u;
                     }
                     // A slot whose path has just left the scene, with every pending shadow verdict certain, has nothing for a shading step
                     // to do but look up the sky: it goes straight to the finish ring (flagged), which does that for full batches of such
@@ -531,36 +645,20 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                     done = false;
                     ER_MARK("tracer_publish_end");
                 }
-                if (visit && er_ring_peek_count(rq_peek = er_ring_peek(s_rq_ctl)) > 0) {
-                    uint32_t hb = 0;
-                    const uint32_t granted = st_take(s_rq_ctl, 64u - (uint32_t)__popcll(bm0), hb, rq_peek);
-                    const bool take = !busy && (uint32_t)__popcll(~bm0 & below) < granted;
+                if (!EARLY_TAKE && visit) got = st_take_rays<RQ_LOG2>(s_rq, s_rq_ctl, W, g0, bm0, busy, status, granted, got_e, got_o, got_d);
 #ifdef ER_TRACER_PROBE
-                    if (granted > 0) trp_take++;
+                if (granted > 0) trp_take++;
 #endif
-                    if (granted > 0) {
-                        uint32_t e = 0;
-                        bool got = false;
-                        if (take) {
-                            got = er_ring_get(s_rq, RQ_LOG2, hb + (uint32_t)__popcll(~bm0 & below), e);
-                            if (!got) atomicOr(status, ST_ERR_RAY);
-                        }
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                        if (got) {
-                            lsk = e;
-                            const uint32_t kind = e >> ST_SLOT_BITS;
-                            const uint32_t rec = g0 + (e & ST_SLOT_MASK) + (kind == 2u ? W.slots : 0u);
-                            const bool shadow = kind != 0u;
-                            const float4 ro = shadow ? W.sh_o(rec) : W.ray_o(rec);
-                            const float4 rd = shadow ? W.sh_d(rec) : W.ray_d(rec);
-                            trav_begin(T, f3(ro.x, ro.y, ro.z), f3(rd.x, rd.y, rd.z), shadow, shadow ? __builtin_bit_cast(int, ro.w) : -1,
-                                       shadow ? rd.w : __builtin_inff());
-                            if (!SPEC) c_rays++;      // (SPEC: counted where the ray is queued, into its sample's tally)
-                            if (SPEC && COUNT) { ray_n0 = c_nodes; ray_t0 = c_tris; }
-                            busy = true;
-                            ER_SP(if (kind == 0u) { spA = W.stamp(rec); spB = sp_now(); })
-                        }
-                    }
+                if (got) {
+                    lsk = got_e;
+                    const uint32_t kind = got_e >> ST_SLOT_BITS;
+                    const bool shadow = kind != 0u;
+                    trav_begin(T, f3(got_o.x, got_o.y, got_o.z), f3(got_d.x, got_d.y, got_d.z), shadow, shadow ? __builtin_bit_cast(int, got_o.w) : -1,
+                               shadow ? got_d.w : __builtin_inff());
+                    if (!SPEC) c_rays++;      // (SPEC: counted where the ray is queued, into its sample's tally)
+                    if (SPEC && COUNT) { ray_n0 = c_nodes; ray_t0 = c_tris; }
+                    busy = true;
+                    ER_SP(if (kind == 0u) { spA = W.stamp(g0 + (got_e & ST_SLOT_MASK)); spB = sp_now(); })
                 }
                 ER_MARK("tracer_refill_end");
                 const unsigned long long bm = __ballot(busy);
@@ -588,7 +686,15 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                 TravStep st;
                 st.node = false; st.tri = false; st.two = false; st.tslot = 0; st.noff = 0; st.toff = 0;
                 if (busy) {
-                    if (S.node_count != 0) do_step = trav_choose(T, S, stack, spill, st);
+                    // (the instrumented instances have no register pair to keep the lane's spill-area pointer in: they form it here, from the
+                    // wave's uniform base and the lane, which the empty statement keeps the compiler from moving out of the loop again)
+                    uint2* sp_area = spill;
+                    if (COUNT) {
+                        uint32_t l = (uint32_t)lane;
+                        asm volatile("" : "+v"(l));
+                        sp_area = W.spill + ((blockIdx.x * 16u + wave) * (uint32_t)ER_SPILL_PER_WAVE + l);      // (a 32-bit index: the base stays in scalar registers)
+                    }
+                    if (S.node_count != 0) do_step = trav_choose(T, S, stack, sp_area, st);
                     finished = !do_step;
                 }
                 if (COUNT) {
@@ -736,6 +842,8 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
             bool push_closest = false, push_shadow = false, push_light = false, retire = false;
             const uint32_t ls = e & ST_SLOT_MASK;
             const uint32_t slot = g0 + ls;
+            // (HANDOFF) what the tracers left in the slot's word: nobody touches it between the last ray's add and this step's own store
+            const uint32_t wflags = (HANDOFF && have) ? s_wait[ls] : 0u;
             bool want_pixel = false, to_finish = false;
             uint32_t rs = 0, left_after = 0, done_idx = 0;
             // speculation (SPEC): this lane's sample continues in a speculative slot / wakes a parked speculative slot with this finish-ring entry /
@@ -789,7 +897,7 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                 uint32_t packed = __builtin_bit_cast(uint32_t, R4.w);
                 uint32_t bounce = packed & 0xFFFFu;
                 if (packed & WF_PENDING_BIT) {   // resolve the previous bounce's shadow query
-                    int occ = W.occluded(slot);
+                    int occ = st_verdict<HANDOFF>(W, slot, wflags, ST_AMB1, ST_OCC1);
                     if (occ >= 2) {
                         float4 so = W.sh_o(slot), sd = W.sh_d(slot);
                         Ray sr;
@@ -802,7 +910,7 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                 }
                 if (EXT && (packed & WF_LPENDING_BIT)) {   // ... then its point-light query (second half of the shadow records)
                     const uint32_t q = slot + W.slots;
-                    int occ = W.occluded(q);
+                    int occ = st_verdict<HANDOFF>(W, q, wflags, ST_AMB2, ST_OCC2);
                     if (occ >= 2) {
                         float4 so = W.sh_o(q), sd = W.sh_d(q);
                         Ray sr;
@@ -825,7 +933,7 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                     ray.o = f3(o.x, o.y, o.z);
                     ray.d = f3(d.x, d.y, d.z);
                     if (MESH) mesh_d = o.w;
-                    int hslot = resolve_closest<COUNT>(S, stack, ray, W.hit(slot), W.hit2(slot), c_nodes, c_tris);
+                    int hslot = resolve_closest<COUNT>(S, stack, ray, HANDOFF ? s_hit[ls] : W.hit(slot), (!HANDOFF || (wflags & ST_HIT2) != 0u) ? W.hit2(slot) : -1, c_nodes, c_tris);
                     c_bounce++;
                     if (EXT) prev_pdf = d.w;
 #define ER_BOUNCE_HDRI_QUERY(sr, self_slot, d_self, cv, co)                                                     \
@@ -919,12 +1027,12 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                     F3 reduction = f3(R4.x, R4.y, R4.z);
                     uint32_t bounce = packed & 0xFFFFu;
                     if (packed & WF_PENDING_BIT) {
-                        const float4 c = W.occluded(slot) ? W.c_occ(slot) : W.c_vis(slot);
+                        const float4 c = st_verdict<HANDOFF>(W, slot, wflags, 0u, ST_OCC1) ? W.c_occ(slot) : W.c_vis(slot);      // (certain: the tracers checked)
                         light = light + f3(c.x, c.y, c.z);
                     }
                     if (EXT && (packed & WF_LPENDING_BIT)) {
                         const uint32_t q = slot + W.slots;
-                        const float4 c = W.occluded(q) ? W.c_occ(q) : W.c_vis(q);
+                        const float4 c = st_verdict<HANDOFF>(W, q, wflags, 0u, ST_OCC2) ? W.c_occ(q) : W.c_vis(q);
                         light = light + f3(c.x, c.y, c.z);
                     }
                     const float4 d = W.ray_d(slot);
