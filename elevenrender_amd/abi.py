@@ -22,6 +22,7 @@ FLAG_POINT_LIGHTS, FLAG_COUNTERS, FLAG_MEGAKERNEL, FLAG_PROFILE, FLAG_FUSED, FLA
 FLAG_HOST_BUILD = 512
 FLAG_MESH_LIGHTS = 1024     # next-event estimation of emissive triangles (csrc/er_shade.h)
 UPDATE_CAMERA, UPDATE_GEOMETRY = 1, 2     # ErSceneUpdate.what
+EDIT_CAMERA, EDIT_GEOMETRY, EDIT_MATERIALS, EDIT_TEXTURES, EDIT_HDRI = 1, 2, 4, 8, 16     # ErSceneEdit.what
 FEATURE_ALBEDO, FEATURE_DEPTH, FEATURE_COUNT = 0, 1, 2     # er_render_features (csrc/er_features.hip)
 FEATURE_NAMES = {"albedo": 0, "depth": 1}
 
@@ -122,6 +123,37 @@ class ErUpdateInfo(C.Structure):
     _fields_ = [("updates", C.c_uint32), ("refits", C.c_uint32), ("refit_ms", C.c_float), ("update_ms", C.c_float)]
 
 
+class ErSceneEdit(C.Structure):
+    _fields_ = [("what", C.c_uint32), ("camera", ErCamera), ("vertices", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)),
+                ("tangents", C.POINTER(C.c_float)), ("material_count", C.c_uint32), ("materials", C.POINTER(ErMaterial)),
+                ("material_id", C.POINTER(C.c_int32)), ("texture_count", C.c_uint32), ("textures", C.POINTER(ErTexture)), ("hdri", ErHdri)]
+
+
+class ErEditInfo(C.Structure):
+    _fields_ = [("edits", C.c_uint32), ("texture_stage", C.c_uint32), ("texture_stage_ms", C.c_float), ("edit_ms", C.c_float), ("pool_floats", C.c_uint64)]
+
+
+class ErTexEntry(C.Structure):   # include/eleven_hip_debug.h (csrc/er_device.h DevTex)
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32), ("filter", C.c_int32), ("offset", C.c_uint32)]
+
+
+class ErTexturePlan(C.Structure):   # include/eleven_hip_debug.h: er_debug_texture_plan
+    _fields_ = [("texture_count", C.c_uint32), ("fused_count", C.c_uint32), ("fused_any", C.c_uint32), ("reserved", C.c_uint32), ("hdri", ErTexEntry),
+                ("pool_floats", C.c_uint64)]
+
+
+class ErTextureDump(C.Structure):   # include/eleven_hip_debug.h: er_debug_read_textures
+    _fields_ = [("texture_count", C.c_uint32), ("material_count", C.c_uint32), ("fused_count", C.c_uint32), ("cdf_count", C.c_uint32), ("guide_count", C.c_uint32),
+                ("tex_pow2", C.c_uint32), ("fused_any", C.c_uint32), ("hdri_buckets", C.c_int32), ("hdri_radiance_sum", C.c_float), ("hdri_tex", ErTexEntry),
+                ("pool_floats", C.c_uint64)]
+
+
+# numpy mirrors of the texture table's and the fused records' descriptors (elevenrender_amd/csrc/er_device.h: DevTex, DevFused)
+TEX_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("channels", "<i4"), ("filter", "<i4"), ("offset", "<u4")])
+FUSED_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("filter", "<i4"), ("offset", "<u4")])
+assert TEX_DTYPE.itemsize == 20 and FUSED_DTYPE.itemsize == 16
+
+
 class ErFeatureInfo(C.Structure):
     _fields_ = [("valid", C.c_uint32), ("samples", C.c_uint32), ("rays", C.c_uint64), ("ms", C.c_float)]
 
@@ -197,6 +229,21 @@ def debug_bvh_dump(vertices, normals, threads=0):
     return accel_dump_dict(info, nodes=nodes, nodes8=nodes8, slot_to_tri=s2t, tri_lift=lift)
 
 
+def debug_texture_plan(scene):
+    """include/eleven_hip_debug.h er_debug_texture_plan: the texture plan of a SceneData (or of an ErSceneDesc whose textures declare
+    sizes only: no texel is read; no device needed) as a dict: modes uint8[textures], table (TEX_DTYPE), fused (FUSED_DTYPE, one per
+    material), hdri (dict of the HDRI's entry), hdri_offset, pool_floats, fused_any."""
+    lib = load()
+    d = scene if isinstance(scene, ErSceneDesc) else scene.desc()
+    plan = ErTexturePlan()
+    check(lib.er_debug_texture_plan(C.byref(d), C.byref(plan), None, 0, None, 0, None, 0))
+    modes, table, fused = np.zeros(plan.texture_count, np.uint8), np.zeros(plan.texture_count, TEX_DTYPE), np.zeros(plan.fused_count, FUSED_DTYPE)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(lib.er_debug_texture_plan(C.byref(d), C.byref(plan), vp(modes), modes.nbytes, vp(table), table.nbytes, vp(fused), fused.nbytes))
+    hdri = {n: int(getattr(plan.hdri, n)) for n, _ in ErTexEntry._fields_}
+    return dict(modes=modes, table=table, fused=fused, hdri=hdri, hdri_offset=hdri["offset"], pool_floats=int(plan.pool_floats), fused_any=int(plan.fused_any))
+
+
 class ErTraceRec(C.Structure):   # include/eleven_hip_debug.h; same layout as the oracle's OracleTraceRec
     _fields_ = [("bounce", C.c_int32), ("tri", C.c_int32), ("shadow_tri", C.c_int32), ("opaque", C.c_int32),
                 ("position", C.c_float * 3), ("wi", C.c_float * 3), ("light", C.c_float * 3), ("reduction", C.c_float * 3),
@@ -229,6 +276,8 @@ SYMBOLS = {
     "er_accel_info": (C.c_int, [_P, C.POINTER(ErAccelInfo)]),
     "er_render_update": (C.c_int, [_P, C.POINTER(ErSceneUpdate)]),
     "er_update_info": (C.c_int, [_P, C.POINTER(ErUpdateInfo)]),
+    "er_render_edit": (C.c_int, [_P, C.POINTER(ErSceneEdit)]),
+    "er_edit_info": (C.c_int, [_P, C.POINTER(ErEditInfo)]),
     "er_adaptive_set": (C.c_int, [_P, C.POINTER(ErAdaptiveParams)]),
     "er_adaptive_info": (C.c_int, [_P, C.POINTER(ErAdaptiveInfo)]),
     "er_read_tile_state": (C.c_int, [_P, _FP, C.POINTER(C.c_uint32)]),
@@ -283,6 +332,8 @@ OPTIONAL_SYMBOLS = {
     "er_debug_stream_balance": (C.c_int, [_P, C.POINTER(ErStreamBalance), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32),
                                           C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]),
     "er_debug_read_accel": (C.c_int, [_P, C.POINTER(ErAccelDump), _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64]),
+    "er_debug_texture_plan": (C.c_int, [C.POINTER(ErSceneDesc), C.POINTER(ErTexturePlan), _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64]),
+    "er_debug_read_textures": (C.c_int, [_P, C.POINTER(ErTextureDump)] + [_P, C.c_uint64] * 7),
     "er_debug_bvh_dump": (C.c_int, [_FP, _FP, C.c_uint32, C.c_int, C.POINTER(ErAccelDump), _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64,
                                     _FP, C.c_uint64]),
 }

@@ -286,8 +286,8 @@ int begin_accel(ErScene* s, BeginStaging& B, hipEvent_t built_ev, ErGpuBvhDevice
     return built ? ER_OK : accel_upload_host(s, B, g);
 }
 
-// stage 3: materials, their precomputed constants, point lights
-int begin_materials(ErScene* s, BeginStaging& B) {
+// the materials and their precomputed constants (stage 3 without the point lights: what a material edit runs again)
+int upload_materials(ErScene* s, BeginStaging& B) {
     int rc;
     if ((rc = upload(s->d_materials, s->materials.data(), s->materials.size(), s->stream)) != ER_OK) return rc;
     std::vector<float4>& mat_pre = B.mat_pre;
@@ -299,62 +299,55 @@ int begin_materials(ErScene* s, BeginStaging& B) {
         mat_pre[i] = make_float4(ermath::er_pow(m.roughness, 2.2f), ermath::er_pow(m.metallic, 2.2f), a < 1.0f ? ermath::er_log(a2) : 0.0f, a < 1.0f ? 1.0f : 0.0f);
     }
     if (getenv("ER_MAT_PRE_ON_DEVICE")) for (auto& v : mat_pre) v.w = 0.0f;      // (A/B and test knob: GTR1's logarithm on the device)
-    if ((rc = upload(s->d_mat_pre, mat_pre.data(), mat_pre.size(), s->stream)) != ER_OK) return rc;
+    return upload(s->d_mat_pre, mat_pre.data(), mat_pre.size(), s->stream);
+}
+
+// stage 3: materials, their precomputed constants, point lights
+int begin_materials(ErScene* s, BeginStaging& B) {
+    int rc;
+    if ((rc = upload_materials(s, B)) != ER_OK) return rc;
     return upload(s->d_lights, s->point_lights.data(), s->point_lights.size(), s->stream);
 }
 
+// the scene's host textures as the texture plan (er_texplan.h) takes them
+void plan_of_scene(const ErScene* s, TexPlan& P) {
+    std::vector<TexDecl> decl(s->textures.size());
+    for (size_t i = 0; i < decl.size(); i++) decl[i] = TexDecl{s->textures[i].width, s->textures[i].height, s->textures[i].channels, s->textures[i].filter};
+    const TexDecl h{s->hdri_tex.width, s->hdri_tex.height, s->hdri_tex.channels, s->hdri_tex.filter};
+    er_texture_plan(decl.data(), decl.size(), s->materials.data(), s->materials.size(), h, P);
+}
+
 // stage 4: the texture pool.  Needs only the host scene; leaves the pool, the table, the fused records, the HDRI's CDF and its guide
-// on the device and the per-texture modes in s->tex_mode.
+// on the device and the per-texture modes in s->tex_mode.  Every layout decision -- modes, offsets, which materials are fused -- is the
+// texture plan's (er_texplan.h, where the rules are written down); this stage fills that layout on the HOST (er_render_edit fills the
+// same layout on the device, er_texstage.hip).
 int begin_textures(ErScene* s, BeginStaging& B, TexResult& out) {
     int rc;
     std::vector<DevTex>& table = B.table;
     std::vector<float>& pool = B.pool;
     std::vector<DevFused>& fused = B.fused;
-    // textures: one float pool + a table
-    // A texture that materials use ONLY for scalar channels -- opacity, roughness, metallic, transmission take `.x` of the fetched value
-    // (src/kernel.cpp:100-150) -- is kept on the device with its first channel alone: a one-channel fetch returns that value in .x
-    // (src/Texture.cpp:181-184), the filter's arithmetic on .x is the same, and the pool of C5 (64 x 3 noise textures of 3 channels, two
-    // of the three used for roughness and metallic) shrinks from 151 MB to 84 MB of the caches it shares with the tree.
-    // And where such a texture is read UNFILTERED and only as roughness or metallic, what it holds is the value to the power 2.2 that
-    // generateHitData takes of every fetch (src/kernel.cpp:152-153), computed here with the device's own er_pow (er_math.h: one
-    // implementation, the same bits -- as for the constants of DevScene::mat_pre); DevTex::filter = 2 marks it (fetched like filter 0).
-    std::vector<uint8_t> vec_use(s->textures.size(), 0), scal_use(s->textures.size(), 0), plain_use(s->textures.size(), 0);
-    auto mark = [&](std::vector<uint8_t>& v, int32_t id) { if (id >= 0 && (size_t)id < v.size()) v[(size_t)id] = 1; };
-    for (const ErMaterial& m : s->materials) {
-        mark(vec_use, m.albedo_tex); mark(vec_use, m.emission_tex); mark(vec_use, m.normal_tex);
-        mark(scal_use, m.opacity_tex); mark(scal_use, m.roughness_tex); mark(scal_use, m.metallic_tex); mark(scal_use, m.transmission_tex);
-        mark(plain_use, m.opacity_tex); mark(plain_use, m.transmission_tex);      // (scalar channels that are NOT raised to a power)
-    }
-    const char* compact_knob = getenv("ER_TEX_COMPACT");      // (A/B and test knob: 0 = every texture as it came)
-    const bool compact = !(compact_knob && atoi(compact_knob) == 0);
-    table.resize(s->textures.size());
-    const bool pow_on_host = !getenv("ER_MAT_PRE_ON_DEVICE");
-    // mode per texture: 0 as it came, 1 first channel alone, 2 first channel alone to the power 2.2; the one-channel copies are made by a
-    // few threads (C5: 8.4 M er_pow, ~0.2 s on one core) and appended in order
-    std::vector<uint8_t> mode(s->textures.size(), 0);
-    for (size_t i = 0; i < s->textures.size(); i++) {
-        const HostTex& t = s->textures[i];
-        if (compact && t.channels >= 1 && scal_use[i] && !vec_use[i]) {
-            const bool powered = t.filter != 1 && !plain_use[i] && pow_on_host;
-            if (t.channels > 1 || powered) mode[i] = powered ? 2 : 1;
-        }
-    }
+    TexPlan P;
+    plan_of_scene(s, P);
+    if (P.pool_floats >= (1ull << 32)) return fail(ER_ERR_INVALID_ARG, "er_render_begin: texture pool exceeds 2^32 floats");
+    table = P.table;
+    fused = P.fused;
+    const std::vector<uint8_t>& mode = P.mode;
     s->tex_mode = mode;
-    std::vector<std::vector<float>> one(s->textures.size());
-    // (sized HERE, on the calling thread: a std::bad_alloc then unwinds into guarded() -> ER_ERR_OOM; thrown inside a worker it
-    // would be an uncaught exception of that thread, i.e. std::terminate.  The workers below only compute.)
-    for (size_t i = 0; i < s->textures.size(); i++)
-        if (mode[i]) one[i].resize((size_t)s->textures[i].width * (size_t)s->textures[i].height);
+    pool.resize((size_t)P.pool_floats);
+    // the one-channel copies are made by a few threads (C5: 8.4 M er_pow, ~0.2 s on one core), each texture at its offset.
+    // (The pool is sized HERE, on the calling thread: a std::bad_alloc then unwinds into guarded() -> ER_ERR_OOM; thrown inside a
+    // worker it would be an uncaught exception of that thread, i.e. std::terminate.  The workers below only compute.)
     {
         std::atomic<size_t> next{0};
         auto work = [&]() noexcept {
             for (size_t i = next.fetch_add(1); i < s->textures.size(); i = next.fetch_add(1)) {
                 if (!mode[i]) continue;
                 const HostTex& t = s->textures[i];
-                const size_t n = one[i].size();
+                const size_t n = (size_t)t.width * (size_t)t.height;
+                float* one = pool.data() + table[i].offset;
                 for (size_t k = 0; k < n; k++) {
                     const float v = t.data[k * (size_t)t.channels];
-                    one[i][k] = mode[i] == 2 ? ermath::er_pow(v, 2.2f) : v;
+                    one[k] = mode[i] == 2 ? ermath::er_pow(v, 2.2f) : v;
                 }
             }
         };
@@ -375,59 +368,36 @@ int begin_textures(ErScene* s, BeginStaging& B, TexResult& out) {
     }
     for (size_t i = 0; i < s->textures.size(); i++) {
         const HostTex& t = s->textures[i];
-        if (mode[i]) {
-            table[i] = DevTex{t.width, t.height, 1, mode[i] == 2 ? 2 : (t.filter == 1 ? 1 : 0), (uint32_t)pool.size()};
-            pool.insert(pool.end(), one[i].begin(), one[i].end());
-            std::vector<float>().swap(one[i]);
-            continue;
-        }
-        table[i] = DevTex{t.width, t.height, t.channels, t.filter == 1 ? 1 : 0, (uint32_t)pool.size()};      // (anything but BILINEAR fetches unfiltered, src/Texture.cpp:229-236; 2 is the library's own mark)
-        pool.insert(pool.end(), t.data.begin(), t.data.end());
+        if (!mode[i] && !t.data.empty()) memcpy(pool.data() + table[i].offset, t.data.data(), t.data.size() * sizeof(float));
     }
-    // A material whose albedo, roughness and metallic textures have one size and one filter gets them texel by texel in one record of
-    // five floats (DevFused, er_device.h): one fetch, one cache line and one coordinate computation per hit instead of three.  The
-    // texel values are what Texture::getValueFromCoordinates returns for each (src/Texture.cpp:172-200); unfiltered, roughness and
-    // metallic are stored to the power 2.2 as above.  The textures themselves stay where they are for every other use.
-    fused.assign(std::max<size_t>(1, s->materials.size()), DevFused{0, 0, 0, 0});
-    const char* fuse_knob = getenv("ER_TEX_FUSE");      // (A/B knob; ER_TEX_COMPACT=0 = "every texture as it came" switches this off as well)
-    if (compact && !(fuse_knob && atoi(fuse_knob) == 0)) {
-        for (size_t m = 0; m < s->materials.size(); m++) {
-            const ErMaterial& M = s->materials[m];
-            const int32_t ids[3] = {M.albedo_tex, M.roughness_tex, M.metallic_tex};
-            bool ok = true;
-            for (int32_t id : ids) ok = ok && id >= 0 && (size_t)id < s->textures.size();
-            if (!ok) continue;
-            const HostTex &A = s->textures[(size_t)ids[0]], &R = s->textures[(size_t)ids[1]], &K = s->textures[(size_t)ids[2]];
-            if (A.width != R.width || A.width != K.width || A.height != R.height || A.height != K.height) continue;
-            if ((A.filter == 1) != (R.filter == 1) || (A.filter == 1) != (K.filter == 1)) continue;
-            if (A.channels < 1 || R.channels < 1 || K.channels < 1) continue;
-            const bool bilinear = A.filter == 1, powered = !bilinear && pow_on_host;
-            const size_t n = (size_t)A.width * (size_t)A.height;
-            if (pool.size() + 5 * n >= (1ull << 32)) continue;
-            fused[m] = DevFused{A.width, A.height, bilinear ? 1 : (powered ? 2 : 0), (uint32_t)pool.size()};
-            // (a texture the pass above already raised to the power is copied from the pool, not raised again: C5's 8.4 M texels)
-            const DevTex tr = table[(size_t)ids[1]], tk = table[(size_t)ids[2]];
-            const bool r_done = powered && tr.filter == 2, k_done = powered && tk.filter == 2;
-            for (size_t k = 0; k < n; k++) {
-                const float* a = A.data.data() + k * (size_t)A.channels;
-                const float r = r_done ? pool[tr.offset + k] : R.data[k * (size_t)R.channels], mt = k_done ? pool[tk.offset + k] : K.data[k * (size_t)K.channels];
-                // (one channel: the value three times; two: x, y, 0; three or more: the first three -- src/Texture.cpp:181-197)
-                pool.push_back(a[0]);
-                pool.push_back(A.channels == 1 ? a[0] : a[1]);
-                pool.push_back(A.channels == 1 ? a[0] : (A.channels == 2 ? 0.0f : a[2]));
-                pool.push_back(powered && !r_done ? ermath::er_pow(r, 2.2f) : r);
-                pool.push_back(powered && !k_done ? ermath::er_pow(mt, 2.2f) : mt);
-            }
+    for (size_t m = 0; m < s->materials.size(); m++) {
+        if (fused[m].width <= 0) continue;
+        const ErMaterial& M = s->materials[m];
+        const HostTex &A = s->textures[(size_t)M.albedo_tex], &R = s->textures[(size_t)M.roughness_tex], &K = s->textures[(size_t)M.metallic_tex];
+        const bool powered = fused[m].filter == 2;
+        const size_t n = (size_t)A.width * (size_t)A.height;
+        // (a texture the pass above already raised to the power is copied from the pool, not raised again: C5's 8.4 M texels)
+        const DevTex tr = table[(size_t)M.roughness_tex], tk = table[(size_t)M.metallic_tex];
+        const bool r_done = powered && tr.filter == 2, k_done = powered && tk.filter == 2;
+        float* o = pool.data() + fused[m].offset;
+        for (size_t k = 0; k < n; k++, o += 5) {
+            const float* a = A.data.data() + k * (size_t)A.channels;
+            const float r = r_done ? pool[tr.offset + k] : R.data[k * (size_t)R.channels], mt = k_done ? pool[tk.offset + k] : K.data[k * (size_t)K.channels];
+            // (one channel: the value three times; two: x, y, 0; three or more: the first three -- src/Texture.cpp:181-197)
+            o[0] = a[0];
+            o[1] = A.channels == 1 ? a[0] : a[1];
+            o[2] = A.channels == 1 ? a[0] : (A.channels == 2 ? 0.0f : a[2]);
+            o[3] = powered && !r_done ? ermath::er_pow(r, 2.2f) : r;
+            o[4] = powered && !k_done ? ermath::er_pow(mt, 2.2f) : mt;
         }
     }
-    s->fused_any = false;
-    for (const DevFused& f : fused) s->fused_any = s->fused_any || f.width > 0;
+    s->fused_any = P.fused_any;
     if ((rc = upload(s->d_mat_fused, fused.data(), fused.size(), s->stream)) != ER_OK) return rc;
-    out.hdri = DevTex{s->hdri_tex.width, s->hdri_tex.height, s->hdri_tex.channels, s->hdri_tex.filter, (uint32_t)pool.size()};
-    pool.insert(pool.end(), s->hdri_tex.data.begin(), s->hdri_tex.data.end());
-    if (pool.size() >= (1ull << 32)) return fail(ER_ERR_INVALID_ARG, "er_render_begin: texture pool exceeds 2^32 floats");
+    out.hdri = P.hdri;
+    if (!s->hdri_tex.data.empty()) memcpy(pool.data() + P.hdri.offset, s->hdri_tex.data.data(), s->hdri_tex.data.size() * sizeof(float));
     if ((rc = upload(s->d_textures, table.data(), table.size(), s->stream)) != ER_OK) return rc;
     if ((rc = upload(s->d_tex_pool, pool.data(), pool.size(), s->stream)) != ER_OK) return rc;
+    s->tex_pool_cap = pool.size();
     if ((rc = upload(s->d_cdf, s->hdri_cdf.data(), s->hdri_cdf.size(), s->stream)) != ER_OK) return rc;
     out.buckets = er_build_cdf_guide(s->hdri_cdf.data(), s->hdri_tex.width * s->hdri_tex.height, B.guide);
     return upload(s->d_guide, B.guide.data(), B.guide.size(), s->stream);
@@ -695,40 +665,43 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     return ER_OK;
 }
 
-// ---- er_render_update: edit a begun scene in place (include/eleven_hip.h) ----
-// The device work of an update, after the host copy has been edited: the refit and the emitter table if triangles moved, then the
+// ---- er_render_update, er_render_edit: edit a begun scene in place (include/eleven_hip.h) ----
+// The device work of either, after the host copy has been edited, is made of the pieces below and always ends in edit_restart: the
 // render's own state exactly as er_render_begin sets it up (begin_render_state, same arguments).  The caller holds the mutex, the
 // stream is idle.
-static int update_device(ErScene* s, const ErSceneUpdate* u) {
-    int rc;
-    HIP_TRY(hipSetDevice(s->device));
+
+// moved triangles: the refit of the built structure from the host copy's arrays
+static int edit_refit(ErScene* s, bool new_normals, bool new_tangents, const char* who) {
     ErGpuBvhDevice& g = s->keep_accel;
-    const bool lights_on = (s->keep_flags & ER_FLAG_POINT_LIGHTS) != 0 && !s->point_lights.empty();
-    BeginStaging B;                     // outlives begin_render_state's hipStreamSynchronize
-    if (u->what & ER_UPDATE_GEOMETRY) {
-        ErRefitBuffers b;
-        b.nodes = (ErNode*)s->d_nodes.p; b.node_count = (uint32_t)(g.nodes_f4 / 4); b.depth2 = g.max_depth2;
-        b.nodes8 = s->d_nodes8.p; b.node8_count = g.nodes8_count; b.depth8 = g.max_depth8;
-        b.isect = (ErTriIsect*)(s->d_nodes8.p + g.n8_pieces); b.attr = (ErTriAttr*)s->d_attr.p; b.tri_count = s->tri_count;
-        ErRefitArrays a;
-        a.vertices = s->vertices.data(); a.normals = s->normals.data(); a.write_normals = u->normals != nullptr;
-        a.tangents = u->tangents ? s->tangents.data() : nullptr;
-        ErRefitResult r;
-        std::string why;
-        const int frc = er_refit_device(s->refit_topo, b, a, s->stream, &r, why);
-        if (frc != 0) return fail(frc == -2 ? ER_ERR_OOM : ER_ERR_HIP, "er_render_update: refit: " + why);
-        if (s->tri_count) {
-            for (int k = 0; k < 3; k++) { g.lo[k] = s->accel_lo[k] = r.lo[k]; g.hi[k] = s->accel_hi[k] = r.hi[k]; }
-            g.lift_bound = s->accel.lift_bound = r.lift_bound;
-        }
-        s->accel.builder = 2u;
-        s->accel.build_ms = s->upd.refit_ms = r.refit_ms;
-        // the emitter table holds areas of placed triangles
-        s->d_light_tab.release(); s->light_emitters = 0; s->light_total = 0.0f;
-        if ((rc = begin_emitters(s, B, g.n8_pieces, lights_on)) != ER_OK) return rc;
+    ErRefitBuffers b;
+    b.nodes = (ErNode*)s->d_nodes.p; b.node_count = (uint32_t)(g.nodes_f4 / 4); b.depth2 = g.max_depth2;
+    b.nodes8 = s->d_nodes8.p; b.node8_count = g.nodes8_count; b.depth8 = g.max_depth8;
+    b.isect = (ErTriIsect*)(s->d_nodes8.p + g.n8_pieces); b.attr = (ErTriAttr*)s->d_attr.p; b.tri_count = s->tri_count;
+    ErRefitArrays a;
+    a.vertices = s->vertices.data(); a.normals = s->normals.data(); a.write_normals = new_normals;
+    a.tangents = new_tangents ? s->tangents.data() : nullptr;
+    ErRefitResult r;
+    std::string why;
+    const int frc = er_refit_device(s->refit_topo, b, a, s->stream, &r, why);
+    if (frc != 0) return fail(frc == -2 ? ER_ERR_OOM : ER_ERR_HIP, std::string(who) + ": refit: " + why);
+    if (s->tri_count) {
+        for (int k = 0; k < 3; k++) { g.lo[k] = s->accel_lo[k] = r.lo[k]; g.hi[k] = s->accel_hi[k] = r.hi[k]; }
+        g.lift_bound = s->accel.lift_bound = r.lift_bound;
     }
-    // what a fresh scene's er_render_begin would find: no adaptive state, no samples, no open timing or profile window, the streaming
-    // schedule's host state and the wavefront schedule's pools as new
+    s->accel.builder = 2u;
+    s->accel.build_ms = s->upd.refit_ms = r.refit_ms;
+    return ER_OK;
+}
+
+// ER_FLAG_MESH_LIGHTS: the emitter table again -- it holds areas of placed triangles and the emission of their materials and textures
+static int edit_emitters(ErScene* s, BeginStaging& B, bool lights_on) {
+    s->d_light_tab.release(); s->light_emitters = 0; s->light_total = 0.0f;
+    return begin_emitters(s, B, s->keep_accel.n8_pieces, lights_on);
+}
+
+// what a fresh scene's er_render_begin would find: no adaptive state, no samples, no open timing or profile window, the streaming
+// schedule's host state and the wavefront schedule's pools as new -- then stages 6-8
+static int edit_restart(ErScene* s, BeginStaging& B, bool lights_on) {
     s->ad_on = false;
     s->rendered = 0;
     s->timing_open = false;
@@ -745,15 +718,24 @@ static int update_device(ErScene* s, const ErSceneUpdate* u) {
     s->params.flags = s->keep_flags;      // (the schedule is chosen again, from the same flags on the same share)
     TexResult tex;
     tex.hdri = s->keep_hdri; tex.buckets = s->keep_buckets;
-    const bool query_on = lights_on || s->light_emitters > 0;
-    return begin_render_state(s, B, g, tex, s->keep_cus, query_on, nullptr);
+    const bool query_on = lights_on || s->light_emitters > 0;      // (recomputed: an edit can create the first emitter or remove the last)
+    return begin_render_state(s, B, s->keep_accel, tex, s->keep_cus, query_on, nullptr);
 }
 
-static int er_render_update_impl(ErScene* s, const ErSceneUpdate* u) {
-    if (!s || !u) return fail(ER_ERR_INVALID_ARG, "er_render_update: NULL argument");
-    const auto t0 = std::chrono::steady_clock::now();
-    std::lock_guard<std::mutex> lk(s->mtx);
-    if (!s->begun) return fail(ER_ERR_STATE, "er_render_update: er_render_begin has not succeeded");
+static int update_device(ErScene* s, const ErSceneUpdate* u) {
+    int rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const bool lights_on = (s->keep_flags & ER_FLAG_POINT_LIGHTS) != 0 && !s->point_lights.empty();
+    BeginStaging B;                     // outlives begin_render_state's hipStreamSynchronize
+    if (u->what & ER_UPDATE_GEOMETRY) {
+        if ((rc = edit_refit(s, u->normals != nullptr, u->tangents != nullptr, "er_render_update")) != ER_OK) return rc;
+        if ((rc = edit_emitters(s, B, lights_on)) != ER_OK) return rc;
+    }
+    return edit_restart(s, B, lights_on);
+}
+
+// er_render_update with the mutex held and the scene begun (er_render_edit with only the camera and geometry bits ends here too)
+static int update_locked(ErScene* s, const ErSceneUpdate* u, std::chrono::steady_clock::time_point t0) {
     if (u->what == 0 || (u->what & ~(ER_UPDATE_CAMERA | ER_UPDATE_GEOMETRY))) return fail(ER_ERR_INVALID_ARG, "er_render_update: `what` names nothing, or something unknown");
     const size_t n9 = (size_t)s->tri_count * 9;
     if (u->what & ER_UPDATE_GEOMETRY) {
@@ -784,10 +766,293 @@ static int er_render_update_impl(ErScene* s, const ErSceneUpdate* u) {
     return ER_OK;
 }
 
+static int er_render_update_impl(ErScene* s, const ErSceneUpdate* u) {
+    if (!s || !u) return fail(ER_ERR_INVALID_ARG, "er_render_update: NULL argument");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_render_update: er_render_begin has not succeeded");
+    return update_locked(s, u, t0);
+}
+
 static int er_update_info_impl(ErScene* s, ErUpdateInfo* out) {
     if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_update_info: NULL argument");
     std::lock_guard<std::mutex> lk(s->mtx);
     *out = s->upd;
+    return ER_OK;
+}
+
+namespace {
+
+// What the checks of er_render_edit prepare, so that nothing of the scene is replaced before the last of them has passed and nothing
+// can fail between the first replacement and the last (moves and swaps only).
+struct EditWork {
+    bool rebuild_pool = false;            // the pool is laid out again and filled on the device
+    std::vector<float> vertices, normals, tangents;
+    std::vector<ErMaterial> materials;
+    std::vector<int32_t> material_id;
+    std::vector<HostTex> textures;        // the new list; kept[i]: entry i is the scene's own texture i (moved in when the copy is replaced)
+    std::vector<uint8_t> kept;
+    HostTex hdri;
+    std::vector<float> cdf;
+    float radiance_sum = 0;
+};
+
+const int32_t* texture_ids(const ErMaterial& m, int32_t out[7]) {
+    const int32_t ids[7] = {m.albedo_tex, m.emission_tex, m.roughness_tex, m.metallic_tex, m.normal_tex, m.opacity_tex, m.transmission_tex};
+    memcpy(out, ids, sizeof(ids));
+    return out;
+}
+
+// the pool work of an edit, after the host copy has been replaced; stage_ms: device time of it
+int edit_pool(ErScene* s, uint32_t what, const EditWork& W, BeginStaging& B, uint32_t& stage, float& stage_ms) {
+    int rc;
+    stage = 0;
+    stage_ms = 0;
+    if (W.rebuild_pool) {
+        TexPlan P;
+        plan_of_scene(s, P);
+        if (P.pool_floats >= (1ull << 32)) return fail(ER_ERR_INVALID_ARG, "er_render_edit: texture pool exceeds 2^32 floats");
+        std::vector<ErTexSource> src(s->textures.size());
+        for (size_t i = 0; i < src.size(); i++) src[i] = ErTexSource{s->textures[i].data.data(), s->textures[i].width, s->textures[i].height, s->textures[i].channels};
+        const ErTexSource hsrc{s->hdri_tex.data.data(), s->hdri_tex.width, s->hdri_tex.height, s->hdri_tex.channels};
+        float* pool = nullptr;
+        std::string why;
+        const int trc = er_texstage_build(P, src.data(), src.size(), s->materials.data(), s->materials.size(), hsrc, s->stream, &pool, &stage_ms, why);
+        if (trc != 0) return fail(trc == -2 ? ER_ERR_OOM : ER_ERR_HIP, "er_render_edit: texture stage: " + why);
+        s->d_tex_pool.release();      // the new pool is swapped in
+        s->d_tex_pool.p = pool;
+        s->d_tex_pool.n = (size_t)P.pool_floats;
+        s->tex_pool_cap = std::max<size_t>((size_t)P.pool_floats, 1);
+        B.table = P.table;
+        B.fused = P.fused;
+        if ((rc = upload(s->d_textures, B.table.data(), B.table.size(), s->stream)) != ER_OK) return rc;
+        if ((rc = upload(s->d_mat_fused, B.fused.data(), B.fused.size(), s->stream)) != ER_OK) return rc;
+        s->tex_mode = P.mode;
+        s->fused_any = P.fused_any;
+        s->keep_hdri = P.hdri;
+        stage = 2;
+    } else if (what & ER_EDIT_HDRI) {
+        // the HDRI's texels lie last: the tail is rewritten in place if the allocation holds the new one, else the pool grows and
+        // its head moves over by a device-to-device copy
+        const size_t head = s->keep_hdri.offset, need = head + s->hdri_tex.data.size();
+        EventPair ev;
+        HIP_TRY(hipEventCreate(&ev.a));
+        HIP_TRY(hipEventCreate(&ev.b));
+        HIP_TRY(hipEventRecord(ev.a, s->stream));
+        if (need > s->tex_pool_cap) {
+            DevBuf<float> bigger;
+            if ((rc = upload(bigger, nullptr, need, s->stream)) != ER_OK) return rc;
+            hipError_t ce = head ? hipMemcpyAsync(bigger.p, s->d_tex_pool.p, head * sizeof(float), hipMemcpyDeviceToDevice, s->stream) : hipSuccess;
+            if (ce == hipSuccess) ce = hipStreamSynchronize(s->stream);
+            if (ce != hipSuccess) {
+                bigger.release();
+                HIP_TRY(ce);
+            }
+            s->d_tex_pool.release();
+            s->d_tex_pool = bigger;
+            s->tex_pool_cap = std::max<size_t>(need, 1);
+        }
+        if (!s->hdri_tex.data.empty())
+            HIP_TRY(hipMemcpyAsync(s->d_tex_pool.p + head, s->hdri_tex.data.data(), s->hdri_tex.data.size() * sizeof(float), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipEventRecord(ev.b, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        (void)hipEventElapsedTime(&stage_ms, ev.a, ev.b);
+        s->d_tex_pool.n = need;
+        s->keep_hdri = DevTex{s->hdri_tex.width, s->hdri_tex.height, s->hdri_tex.channels, s->hdri_tex.filter, (uint32_t)head};
+        stage = 1;
+    }
+    if (what & ER_EDIT_HDRI) {
+        if ((rc = upload(s->d_cdf, s->hdri_cdf.data(), s->hdri_cdf.size(), s->stream)) != ER_OK) return rc;
+        s->keep_buckets = er_build_cdf_guide(s->hdri_cdf.data(), s->hdri_tex.width * s->hdri_tex.height, B.guide);
+        if ((rc = upload(s->d_guide, B.guide.data(), B.guide.size(), s->stream)) != ER_OK) return rc;
+    }
+    return ER_OK;
+}
+
+// The device work of er_render_edit, the host copy replaced (section "The stages of an edit")
+int edit_device(ErScene* s, const ErSceneEdit* e, const EditWork& W, uint32_t& stage, float& stage_ms) {
+    int rc;
+    const uint32_t what = e->what;
+    const bool lights_on = (s->keep_flags & ER_FLAG_POINT_LIGHTS) != 0 && !s->point_lights.empty();
+    BeginStaging B;                     // outlives begin_render_state's hipStreamSynchronize
+    if (what & ER_EDIT_GEOMETRY)
+        if ((rc = edit_refit(s, e->normals != nullptr, e->tangents != nullptr, "er_render_edit")) != ER_OK) return rc;
+    if (what & ER_EDIT_MATERIALS) {
+        if ((rc = upload_materials(s, B)) != ER_OK) return rc;
+        if (e->material_id && s->tri_count) {
+            ScopedDevBuf<int32_t> d_ids;
+            if ((rc = upload(d_ids, s->material_id.data(), s->material_id.size(), s->stream)) != ER_OK) return rc;
+            er_launch_material_ids(s->d_nodes8.p + s->keep_accel.n8_pieces, s->d_attr.p, s->tri_count, d_ids.p, s->stream);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(s->stream));      // (d_ids goes with this block)
+        }
+    }
+    if ((rc = edit_pool(s, what, W, B, stage, stage_ms)) != ER_OK) return rc;
+    if (what & (ER_EDIT_GEOMETRY | ER_EDIT_MATERIALS | ER_EDIT_TEXTURES))
+        if ((rc = edit_emitters(s, B, lights_on)) != ER_OK) return rc;
+    return edit_restart(s, B, lights_on);
+}
+
+}  // namespace
+
+static int er_render_edit_impl(ErScene* s, const ErSceneEdit* e) {
+    if (!s || !e) return fail(ER_ERR_INVALID_ARG, "er_render_edit: NULL argument");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_render_edit: er_render_begin has not succeeded");
+    const uint32_t what = e->what, all = ER_EDIT_CAMERA | ER_EDIT_GEOMETRY | ER_EDIT_MATERIALS | ER_EDIT_TEXTURES | ER_EDIT_HDRI;
+    if (what == 0 || (what & ~all)) return fail(ER_ERR_INVALID_ARG, "er_render_edit: `what` names nothing, or something unknown");
+    if (!(what & (ER_EDIT_MATERIALS | ER_EDIT_TEXTURES | ER_EDIT_HDRI))) {      // this is er_render_update
+        ErSceneUpdate u{};
+        u.what = what; u.camera = e->camera; u.vertices = e->vertices; u.normals = e->normals; u.tangents = e->tangents;
+        return update_locked(s, &u, t0);
+    }
+    // ---- the checks: nothing of the scene is touched before the last one has passed ----
+    const size_t n = s->tri_count, n9 = n * 9;
+    if (what & ER_EDIT_GEOMETRY) {
+        if (!e->vertices) return fail(ER_ERR_INVALID_ARG, "er_render_edit: ER_EDIT_GEOMETRY without vertices");
+        for (size_t i = 0; i < n9; i++)
+            if (!std::isfinite(e->vertices[i])) return fail(ER_ERR_INVALID_ARG, "er_render_edit: vertex " + std::to_string(i / 3) + " is not finite");
+    }
+    const size_t old_ntex = s->textures.size();
+    size_t ntex = old_ntex;
+    if (what & ER_EDIT_TEXTURES) {
+        ntex = e->texture_count;
+        if (ntex < old_ntex) return fail(ER_ERR_INVALID_ARG, "er_render_edit: texture_count is below the scene's (textures are replaced or appended, never removed)");
+        if (ntex && !e->textures) return fail(ER_ERR_INVALID_ARG, "er_render_edit: ER_EDIT_TEXTURES without the texture list");
+        for (size_t i = 0; i < ntex; i++) {
+            const ErTexture& t = e->textures[i];
+            if (!t.data) {
+                if (i >= old_ntex) return fail(ER_ERR_INVALID_ARG, "er_render_edit: texture " + std::to_string(i) + " has no data and the scene has no such texture to keep");
+                continue;
+            }
+            const int rc = check_tex(t, "scene texture");
+            if (rc != ER_OK) return rc;
+        }
+    }
+    const ErMaterial* mats = s->materials.data();
+    size_t nmat = s->materials.size();
+    bool ids_differ = false;
+    if (what & ER_EDIT_MATERIALS) {
+        if (e->material_count == 0 || !e->materials) return fail(ER_ERR_INVALID_ARG, "er_render_edit: ER_EDIT_MATERIALS needs at least one material");
+        mats = e->materials;
+        nmat = e->material_count;
+        ids_differ = nmat != s->materials.size();
+        for (size_t m = 0; m < nmat; m++) {
+            int32_t a[7], b[7];
+            texture_ids(mats[m], a);
+            for (int32_t id : a)
+                if (id >= (int32_t)ntex) return fail(ER_ERR_INVALID_ARG, "er_render_edit: texture id out of range");      // (er_scene_create's rule)
+            if (!ids_differ) {
+                texture_ids(s->materials[m], b);
+                ids_differ = memcmp(a, b, sizeof(a)) != 0;
+            }
+        }
+        const int32_t* mid = e->material_id ? e->material_id : s->material_id.data();
+        for (size_t i = 0; i < n; i++)
+            if (mid[i] < 0 || (uint32_t)mid[i] >= nmat) return fail(ER_ERR_INVALID_ARG, "er_render_edit: material_id out of range");      // (the same)
+    }
+    if (what & ER_EDIT_HDRI) {
+        const int rc = check_tex(e->hdri.texture, "hdri");
+        if (rc != ER_OK) return rc;
+    }
+    EditWork W;
+    W.rebuild_pool = (what & ER_EDIT_TEXTURES) != 0 || ids_differ;
+    {   // the pool the edited scene needs, from the plan, before anything is replaced
+        const TexDecl hd = (what & ER_EDIT_HDRI) ? TexDecl{e->hdri.texture.width, e->hdri.texture.height, e->hdri.texture.channels, e->hdri.texture.filter}
+                                                 : TexDecl{s->hdri_tex.width, s->hdri_tex.height, s->hdri_tex.channels, s->hdri_tex.filter};
+        uint64_t pool_floats = 0;
+        if (W.rebuild_pool) {
+            std::vector<TexDecl> decl(ntex);
+            for (size_t i = 0; i < ntex; i++) {
+                const bool keep = !(what & ER_EDIT_TEXTURES) || !e->textures[i].data;
+                decl[i] = keep ? TexDecl{s->textures[i].width, s->textures[i].height, s->textures[i].channels, s->textures[i].filter}
+                               : TexDecl{e->textures[i].width, e->textures[i].height, e->textures[i].channels, e->textures[i].filter};
+            }
+            TexPlan P;
+            er_texture_plan(decl.data(), ntex, mats, nmat, hd, P);
+            pool_floats = P.pool_floats;
+        } else if (what & ER_EDIT_HDRI) {
+            pool_floats = (uint64_t)s->keep_hdri.offset + (uint64_t)hd.width * (uint64_t)hd.height * (uint64_t)hd.channels;
+        }
+        if (pool_floats >= (1ull << 32)) return fail(ER_ERR_INVALID_ARG, "er_render_edit: texture pool exceeds 2^32 floats");
+    }
+    // ---- the new host copy, beside the scene's (an allocation that fails here leaves the scene as it was) ----
+    if (what & ER_EDIT_GEOMETRY) {
+        W.vertices.assign(e->vertices, e->vertices + n9);
+        if (e->normals) W.normals.assign(e->normals, e->normals + n9);
+        if (e->tangents) W.tangents.assign(e->tangents, e->tangents + n9);
+    }
+    if (what & ER_EDIT_MATERIALS) {
+        W.materials.assign(e->materials, e->materials + e->material_count);
+        if (e->material_id) W.material_id.assign(e->material_id, e->material_id + n);
+    }
+    if (what & ER_EDIT_TEXTURES) {
+        W.textures.resize(ntex);
+        W.kept.assign(ntex, 0);
+        for (size_t i = 0; i < ntex; i++) {
+            if (!e->textures[i].data) { W.kept[i] = 1; continue; }
+            const int rc = copy_tex(e->textures[i], W.textures[i], "scene texture");
+            if (rc != ER_OK) return rc;
+        }
+    }
+    if (what & ER_EDIT_HDRI) {
+        const int rc = copy_tex(e->hdri.texture, W.hdri, "hdri");
+        if (rc != ER_OK) return rc;
+        if (e->hdri.cdf) {
+            W.cdf.assign(e->hdri.cdf, e->hdri.cdf + (size_t)W.hdri.width * W.hdri.height + 1);
+            W.radiance_sum = e->hdri.radiance_sum;
+        } else {
+            host_generate_cdf(W.hdri, W.cdf, W.radiance_sum);
+        }
+    }
+    // pending asynchronous work first (the pool streams join the scene's stream at the end of every call)
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    // ---- the host copy is replaced, before any device work: whatever happens below, a later er_render_begin builds the edited scene ----
+    if (what & ER_EDIT_CAMERA) s->camera = e->camera;
+    if (what & ER_EDIT_GEOMETRY) {
+        s->vertices.swap(W.vertices);
+        if (e->normals) s->normals.swap(W.normals);
+        if (e->tangents) s->tangents.swap(W.tangents);
+    }
+    if (what & ER_EDIT_MATERIALS) {
+        s->materials.swap(W.materials);
+        if (e->material_id) s->material_id.swap(W.material_id);
+    }
+    if (what & ER_EDIT_TEXTURES) {
+        for (size_t i = 0; i < ntex; i++)
+            if (W.kept[i]) std::swap(W.textures[i], s->textures[i]);
+        s->textures.swap(W.textures);
+    }
+    if (what & ER_EDIT_HDRI) {
+        std::swap(s->hdri_tex, W.hdri);
+        s->hdri_cdf.swap(W.cdf);
+        s->hdri_radiance_sum = W.radiance_sum;
+    }
+    s->feat_valid = false;      // the feature planes show the scene before the edit (er_render_features makes them again)
+    for (auto& set : s->unpacked_feat) set.clear();
+    uint32_t stage = 0;
+    float stage_ms = 0;
+    const int rc = edit_device(s, e, W, stage, stage_ms);
+    if (rc != ER_OK) {
+        s->begun = false;      // (er_render_begin releases what is left and rebuilds from the edited host copy)
+        return rc;
+    }
+    s->upd.updates++;
+    if (what & ER_EDIT_GEOMETRY) s->upd.refits++;
+    s->edit.edits++;
+    s->edit.texture_stage = stage;
+    s->edit.texture_stage_ms = stage_ms;
+    s->edit.pool_floats = s->d_tex_pool.n;
+    s->edit.edit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ER_OK;
+}
+
+static int er_edit_info_impl(ErScene* s, ErEditInfo* out) {
+    if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_edit_info: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    *out = s->edit;
     return ER_OK;
 }
 
@@ -1375,5 +1640,7 @@ int er_adaptive_info(ErScene* s, ErAdaptiveInfo* out) { return guarded("er_adapt
 int er_light_info(ErScene* s, ErLightInfo* out) { return guarded("er_light_info", [&]() -> int { return er_light_info_impl(s, out); }); }
 int er_render_update(ErScene* s, const ErSceneUpdate* u) { return guarded("er_render_update", [&]() -> int { return er_render_update_impl(s, u); }); }
 int er_update_info(ErScene* s, ErUpdateInfo* out) { return guarded("er_update_info", [&]() -> int { return er_update_info_impl(s, out); }); }
+int er_render_edit(ErScene* s, const ErSceneEdit* e) { return guarded("er_render_edit", [&]() -> int { return er_render_edit_impl(s, e); }); }
+int er_edit_info(ErScene* s, ErEditInfo* out) { return guarded("er_edit_info", [&]() -> int { return er_edit_info_impl(s, out); }); }
 int er_read_tile_state(ErScene* s, float* error, uint32_t* samples) { return guarded("er_read_tile_state", [&]() -> int { return er_read_tile_state_impl(s, error, samples); }); }
 }  // extern "C"

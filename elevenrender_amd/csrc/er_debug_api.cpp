@@ -210,6 +210,63 @@ static int er_debug_read_accel_impl(ErScene* s, ErAccelDump* info, void* nodes, 
     return ER_OK;
 }
 
+// ---- the texture pool: the plan, and what lies on the device (copies only) ----
+static_assert(sizeof(ErTexEntry) == sizeof(DevTex) && sizeof(ErFusedEntry) == sizeof(DevFused), "the debug header's entries are the device records");
+
+static int er_debug_texture_plan_impl(const ErSceneDesc* d, ErTexturePlan* out, uint8_t* modes, uint64_t modes_cap, ErTexEntry* table, uint64_t table_cap, ErFusedEntry* fused,
+                                      uint64_t fused_cap) {
+    if (!d || !out) return fail(ER_ERR_INVALID_ARG, "er_debug_texture_plan: NULL argument");
+    if ((d->texture_count && !d->textures) || (d->material_count && !d->materials)) return fail(ER_ERR_INVALID_ARG, "er_debug_texture_plan: a list is missing");
+    std::vector<TexDecl> decl(d->texture_count);
+    for (uint32_t i = 0; i < d->texture_count; i++) decl[i] = TexDecl{d->textures[i].width, d->textures[i].height, d->textures[i].channels, d->textures[i].filter};
+    const TexDecl h{d->hdri.texture.width, d->hdri.texture.height, d->hdri.texture.channels, d->hdri.texture.filter};
+    TexPlan P;
+    er_texture_plan(decl.data(), decl.size(), d->materials, d->material_count, h, P);
+    memset(out, 0, sizeof(*out));
+    out->texture_count = d->texture_count;
+    out->fused_count = (uint32_t)P.fused.size();
+    out->fused_any = P.fused_any ? 1u : 0u;
+    memcpy(&out->hdri, &P.hdri, sizeof(DevTex));
+    out->pool_floats = P.pool_floats;
+    int rc;
+    const char* who = "er_debug_texture_plan";
+    if ((rc = dump_put(who, modes, modes_cap, P.mode.data(), P.mode.size(), false, nullptr)) != ER_OK) return rc;
+    if ((rc = dump_put(who, table, table_cap, P.table.data(), P.table.size() * sizeof(DevTex), false, nullptr)) != ER_OK) return rc;
+    return dump_put(who, fused, fused_cap, P.fused.data(), P.fused.size() * sizeof(DevFused), false, nullptr);
+}
+
+static int er_debug_read_textures_impl(ErScene* s, ErTextureDump* info, void* table, uint64_t table_cap, void* pool, uint64_t pool_cap, void* fused, uint64_t fused_cap,
+                                       void* mat_pre, uint64_t mat_pre_cap, void* materials, uint64_t materials_cap, void* cdf, uint64_t cdf_cap, void* guide, uint64_t guide_cap) {
+    if (!s || !info) return fail(ER_ERR_INVALID_ARG, "er_debug_read_textures: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_debug_read_textures: er_render_begin has not succeeded");
+    const DevScene& D = s->dev;
+    memset(info, 0, sizeof(*info));
+    info->texture_count = (uint32_t)s->d_textures.n;
+    info->material_count = (uint32_t)s->d_materials.n;
+    info->fused_count = (uint32_t)s->d_mat_fused.n;
+    info->cdf_count = (uint32_t)s->d_cdf.n;
+    info->guide_count = (uint32_t)s->d_guide.n;
+    info->tex_pow2 = D.tex_pow2;
+    info->fused_any = D.fused_any;
+    info->hdri_buckets = D.hdri_buckets;
+    info->hdri_radiance_sum = D.hdri_radiance_sum;
+    memcpy(&info->hdri_tex, &D.hdri_tex, sizeof(DevTex));
+    info->pool_floats = s->d_tex_pool.n;
+    HIP_TRY(hipSetDevice(s->device));
+    int rc;
+    const char* who = "er_debug_read_textures";
+    if ((rc = dump_put(who, table, table_cap, s->d_textures.p, s->d_textures.n * sizeof(DevTex), true, s->stream)) != ER_OK) return rc;
+    if ((rc = dump_put(who, pool, pool_cap, s->d_tex_pool.p, s->d_tex_pool.n * sizeof(float), true, s->stream)) != ER_OK) return rc;
+    if ((rc = dump_put(who, fused, fused_cap, s->d_mat_fused.p, s->d_mat_fused.n * sizeof(DevFused), true, s->stream)) != ER_OK) return rc;
+    if ((rc = dump_put(who, mat_pre, mat_pre_cap, s->d_mat_pre.p, s->d_mat_pre.n * sizeof(float4), true, s->stream)) != ER_OK) return rc;
+    if ((rc = dump_put(who, materials, materials_cap, s->d_materials.p, s->d_materials.n * sizeof(ErMaterial), true, s->stream)) != ER_OK) return rc;
+    if ((rc = dump_put(who, cdf, cdf_cap, s->d_cdf.p, s->d_cdf.n * sizeof(float), true, s->stream)) != ER_OK) return rc;
+    if ((rc = dump_put(who, guide, guide_cap, s->d_guide.p, s->d_guide.n * sizeof(uint32_t), true, s->stream)) != ER_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return ER_OK;
+}
+
 static int er_debug_bvh_dump_impl(const float* vertices, const float* normals, uint32_t tri_count, int threads, ErAccelDump* info, void* nodes, uint64_t nodes_cap,
                                   void* nodes8, uint64_t nodes8_cap, uint32_t* slot_to_tri, uint64_t slot_cap, float* tri_lift, uint64_t lift_cap) {
     if (!info || (tri_count && (!vertices || !normals))) return fail(ER_ERR_INVALID_ARG, "er_debug_bvh_dump: NULL argument");
@@ -424,6 +481,15 @@ int er_debug_read_accel(ErScene* s, ErAccelDump* info, void* nodes, uint64_t nod
 int er_debug_bvh_dump(const float* vertices, const float* normals, uint32_t tri_count, int threads, ErAccelDump* info, void* nodes, uint64_t nodes_cap, void* nodes8, uint64_t nodes8_cap,
                       uint32_t* slot_to_tri, uint64_t slot_cap, float* tri_lift, uint64_t lift_cap) {
     return guarded("er_debug_bvh_dump", [&]() -> int { return er_debug_bvh_dump_impl(vertices, normals, tri_count, threads, info, nodes, nodes_cap, nodes8, nodes8_cap, slot_to_tri, slot_cap, tri_lift, lift_cap); });
+}
+int er_debug_texture_plan(const ErSceneDesc* d, ErTexturePlan* plan, uint8_t* modes, uint64_t modes_cap, ErTexEntry* table, uint64_t table_cap, ErFusedEntry* fused, uint64_t fused_cap) {
+    return guarded("er_debug_texture_plan", [&]() -> int { return er_debug_texture_plan_impl(d, plan, modes, modes_cap, table, table_cap, fused, fused_cap); });
+}
+int er_debug_read_textures(ErScene* s, ErTextureDump* info, void* table, uint64_t table_cap, void* pool, uint64_t pool_cap, void* fused, uint64_t fused_cap, void* mat_pre,
+                           uint64_t mat_pre_cap, void* materials, uint64_t materials_cap, void* cdf, uint64_t cdf_cap, void* guide, uint64_t guide_cap) {
+    return guarded("er_debug_read_textures", [&]() -> int {
+        return er_debug_read_textures_impl(s, info, table, table_cap, pool, pool_cap, fused, fused_cap, mat_pre, mat_pre_cap, materials, materials_cap, cdf, cdf_cap, guide, guide_cap);
+    });
 }
 int er_debug_bvh_check(const float* vertices, const float* normals, uint32_t tri_count, int threads, ErBvhCheck* out) { return guarded("er_debug_bvh_check", [&]() -> int { return er_debug_bvh_check_impl(vertices, normals, tri_count, threads, out); }); }
 int er_debug_trace_rays(ErScene* s, const float* origins, const float* dirs, uint32_t n, const int32_t* self_slots, const float* limits, int32_t* tri_ids,

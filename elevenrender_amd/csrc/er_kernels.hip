@@ -10,6 +10,7 @@
 #include "er_kernels.h"
 #include "er_stream.h"
 #include "er_features.h"
+#include "er_texstage.h"
 #include "er_device.h"
 #include "er_shade.h"
 
@@ -182,6 +183,7 @@ hipError_t er_probe_kernels(const char** which) {
     if ((e = er_probe_gpu_build(which)) != hipSuccess) return e;
     if ((e = er_probe_refit(which)) != hipSuccess) return e;
     if ((e = er_probe_features(which)) != hipSuccess) return e;
+    if ((e = er_probe_texstage(which)) != hipSuccess) return e;
     *which = nullptr;
     return hipSuccess;
 }

@@ -29,6 +29,8 @@
 #include "er_adaptive.h"
 #include "er_lights.h"
 #include "er_refit.h"
+#include "er_texplan.h"
+#include "er_texstage.h"
 #include "er_features.h"
 
 namespace erh {
@@ -165,6 +167,8 @@ struct ErScene {
     uint32_t keep_cus = 0, keep_flags = 0;
     ErRefitTopo refit_topo;      // the trees' nodes by level, from the first refit after an er_render_begin until the next one
     ErUpdateInfo upd{};          // er_update_info (counts since er_scene_create)
+    ErEditInfo edit{};           // er_edit_info (the same)
+    size_t tex_pool_cap = 0;     // floats the allocation of d_tex_pool holds (d_tex_pool.n: the floats of the pool in it; an HDRI edit may shrink that)
     DevBuf<float4> d_nodes, d_nodes8, d_attr, d_passes;
     DevBuf<float4> d_plane;      // staging: one pass gathered as a plane for er_read_pass
     DevBuf<ErMaterial> d_materials;
@@ -242,7 +246,7 @@ struct ErScene {
     }
     void release_device() {
         d_nodes.release(); d_nodes8.release(); d_attr.release(); d_passes.release(); d_plane.release(); d_materials.release();
-        d_textures.release(); d_tex_pool.release(); d_lights.release(); d_cdf.release(); d_samples.release(); d_rng.release();
+        d_textures.release(); d_tex_pool.release(); tex_pool_cap = 0; d_lights.release(); d_cdf.release(); d_samples.release(); d_rng.release();
         d_owned.release(); d_counters.release(); d_wf4.release(); d_wf1.release(); d_spill.release(); d_guide.release(); d_ray_log.release(); d_mat_fused.release(); d_mat_pre.release(); d_dev.release();
         st.release();
         d_ad_list[0].release(); d_ad_list[1].release(); d_ad_keep.release(); d_ad_snap.release(); d_ad_err.release();
@@ -308,9 +312,14 @@ int upload(DevBuf<T>& b, const void* src, size_t count, hipStream_t s) {
     return ER_OK;
 }
 
-inline int copy_tex(const ErTexture& in, HostTex& out, const char* what) {
+inline int check_tex(const ErTexture& in, const char* what) {      // what er_scene_create (and er_render_edit) refuse of a texture
     if (in.width <= 0 || in.height <= 0 || in.channels < 0 || (in.channels > 0 && !in.data))
         return fail(ER_ERR_INVALID_ARG, std::string("bad texture: ") + what);
+    return ER_OK;
+}
+
+inline int copy_tex(const ErTexture& in, HostTex& out, const char* what) {
+    if (check_tex(in, what) != ER_OK) return ER_ERR_INVALID_ARG;
     out.width = in.width; out.height = in.height; out.channels = in.channels; out.filter = in.filter;
     size_t n = (size_t)in.width * in.height * in.channels;
     out.data.assign(in.data, in.data + n);

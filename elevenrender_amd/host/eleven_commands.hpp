@@ -229,13 +229,16 @@ private:
     std::atomic<unsigned> samples_per_call_{0};      // what the render thread's last call was sized to (reported by --get_info)
     SessionEdits edits_;                             // what arrived since the last successful --start (eleven_host.hpp)
     unsigned camera_updates_ = 0;                    // --start commands answered by an in-place camera update (reported by --get_info)
+    unsigned scene_edits_ = 0;                       // ... by an in-place edit of materials, textures or the HDRI (the same)
 
     void dispatch(const CommandLine& cl, std::vector<Message>& extra) {
         if (cl.count("path") || cl.count("sm") || cl.count("output"))
             throw std::runtime_error("loading from a filesystem path / shared memory is not implemented (neither is it in the reference: src/CommandManager.cpp:116-150)");
         if (cl.count("load_camera")) { scene.camera = parse_camerajson(extra[0].get_json_data()); edits_.on_camera(); return ok(); }
-        if (cl.count("load_texture") || cl.count("load_config") || cl.count("load_hdri") || cl.count("load_brdf_material") || cl.count("load_object"))
-            edits_.on_other();      // (before the command runs: one that fails half-way has still touched the scene)
+        // (before the command runs: one that fails half-way has still touched the scene)
+        if (cl.count("load_hdri")) edits_.on_hdri();
+        if (cl.count("load_texture") || cl.count("load_brdf_material")) edits_.on_materials();
+        if (cl.count("load_config") || cl.count("load_object")) edits_.on_other();
         if (cl.count("load_texture")) {
             Texture t = parse_texturejson(extra[0].get_json_data(), extra[1].get_float_data(), extra[1].float_count());
             scene.addTexture(t);                                            // load_texture, src/CommandManager.cpp:364-370
@@ -290,6 +293,7 @@ private:
             if (!rm.transport_used.empty()) j["transport"] = rm.transport_used;
             j["samples_per_call"] = samples_per_call_.load();
             j["camera_updates"] = camera_updates_;
+            j["scene_edits"] = scene_edits_;
             j["feature_samples"] = rm.pars.feature_samples ? rm.pars.feature_samples : 4u;      // rays per pixel of a feature pass (--get_pass albedo / depth, denoise_guided)
             if (rm.pars.denoise_guided) j["denoise_guided"] = true;
             im->write_message(Message::json_data(j));
@@ -402,13 +406,19 @@ private:
     void start_render() {   // src/CommandManager.cpp:500-504 -> RenderingManager::start_rendering, src/Managers.cpp:234-275
         stop_render_thread();
         { std::lock_guard<std::mutex> lk(err_mtx_); render_error_.clear(); }
-        // nothing but a new camera since the last --start: the render restarts in place (no build, no uploads); else, or if that
-        // fails, the full start: builds the BVH, uploads, runs setupKernel; throws with er_last_error()
-        const bool in_place = edits_.camera_only() && rm.update_camera(scene.camera);
+        // nothing but a new camera since the last --start: the render restarts in place (no build, no uploads); nothing but a camera,
+        // an HDRI, materials and textures: the begun scenes are edited in place (no build); else, or if that fails, the full start:
+        // builds the BVH, uploads, runs setupKernel; throws with er_last_error()
+        bool in_place = false;
+        if (edits_.camera_only()) {
+            if ((in_place = rm.update_camera(scene.camera))) camera_updates_++;
+        } else if (edits_.editable()) {
+            if ((in_place = rm.edit_scene(&scene, edits_.hdri))) scene_edits_++;
+        }
         if (!in_place) {
             edits_.on_failed();
             rm.start_rendering(&scene);
-        } else camera_updates_++;
+        }
         edits_.on_started();
         const unsigned target = rm.pars.sampleTarget;
         t_rend_ = std::thread([this, target] {          // kernel_render_enqueue, src/kernel.cpp:680-706: `target` samples

@@ -137,17 +137,24 @@ struct RenderParameters {   // src/kernel.h:51-69
 };
 
 // What a session sent since its last successful --start.  A --start after nothing but --load_camera restarts the render in place
-// (RenderingManager::update_camera: er_render_update on every rank -- no build, no uploads); after anything else, or before the
-// first render, it is the full start_rendering.
+// (RenderingManager::update_camera: er_render_update on every rank -- no build, no uploads); after nothing but --load_camera,
+// --load_hdri, --load_brdf_material and --load_texture it edits the begun scenes in place (RenderingManager::edit_scene:
+// er_render_edit on every rank -- no build; the texture pool is rebuilt on the device only if an assignment or a texture changed);
+// after anything else (--load_object, --load_config), or before the first render, it is the full start_rendering.
 struct SessionEdits {
     bool rendering = false;      // a --start has succeeded and its scenes are alive
     bool camera = false;         // --load_camera arrived since
+    bool hdri = false;           // ... --load_hdri
+    bool materials = false;      // ... --load_brdf_material or --load_texture
     bool other = false;          // ... and anything else that changes the scene or the parameters
     void on_camera() { camera = true; }
+    void on_hdri() { hdri = true; }
+    void on_materials() { materials = true; }
     void on_other() { other = true; }
-    void on_started() { rendering = true; camera = other = false; }
+    void on_started() { rendering = true; camera = hdri = materials = other = false; }
     void on_failed() { rendering = false; }
-    bool camera_only() const { return rendering && !other; }      // (no edit at all: the same render again, also without a rebuild)
+    bool camera_only() const { return rendering && !other && !hdri && !materials; }      // (no edit at all: the same render again, also without a rebuild)
+    bool editable() const { return rendering && !other && (hdri || materials); }         // (a camera may have come as well)
 };
 
 inline int parseFeature(std::string s) {   // the feature planes of er_render_features by name, -1 = not one
@@ -174,6 +181,26 @@ public:
 
     ~RenderingManager() { release(); }
 
+    static std::vector<ErMaterial> er_materials(const Scene& scene) {      // the scene's materials as the library takes them
+        std::vector<ErMaterial> ms;
+        for (const Material& m : scene.materials) {
+            ErMaterial e{};
+            e.albedo_tex = m.albedoTextureID; e.emission_tex = m.emissionTextureID; e.roughness_tex = m.roughnessTextureID;
+            e.metallic_tex = m.metallicTextureID; e.normal_tex = m.normalTextureID; e.opacity_tex = m.opacityTextureID;
+            e.transmission_tex = m.transmissionTextureID; e.albedo_shader_id = m.albedoShaderID;
+            e.albedo = {m.albedo.x, m.albedo.y, m.albedo.z}; e.emission = {m.emission.x, m.emission.y, m.emission.z};
+            e.opacity = m.opacity; e.roughness = m.roughness; e.metallic = m.metallic; e.clearcoat_gloss = m.clearcoatGloss;
+            e.clearcoat = m.clearcoat; e.anisotropic = m.anisotropic; e.eta = m.eta; e.transmission = m.transmission;
+            e.specular = m.specular; e.specular_tint = m.specularTint; e.sheen_tint = m.sheenTint; e.subsurface = m.subsurface;
+            e.sheen = m.sheen; e.ax = m.ax; e.ay = m.ay;
+            ms.push_back(e);
+        }
+        return ms;
+    }
+    static ErTexture er_texture(const Texture& t) {
+        return ErTexture{t.width, t.height, (int32_t)t.channels, t.filter == Texture::Filter::BILINEAR ? 1 : 0, t.data.data()};
+    }
+
     void start_rendering(Scene* scene) {   // src/Managers.cpp:234-275 (without spawning the render thread)
         release();
         size_t n = scene->tris.size();
@@ -191,19 +218,7 @@ public:
             sign[i] = t.tangentsSign;
             mat[i] = t.materialID;
         }
-        std::vector<ErMaterial> ms;
-        for (const Material& m : scene->materials) {
-            ErMaterial e{};
-            e.albedo_tex = m.albedoTextureID; e.emission_tex = m.emissionTextureID; e.roughness_tex = m.roughnessTextureID;
-            e.metallic_tex = m.metallicTextureID; e.normal_tex = m.normalTextureID; e.opacity_tex = m.opacityTextureID;
-            e.transmission_tex = m.transmissionTextureID; e.albedo_shader_id = m.albedoShaderID;
-            e.albedo = {m.albedo.x, m.albedo.y, m.albedo.z}; e.emission = {m.emission.x, m.emission.y, m.emission.z};
-            e.opacity = m.opacity; e.roughness = m.roughness; e.metallic = m.metallic; e.clearcoat_gloss = m.clearcoatGloss;
-            e.clearcoat = m.clearcoat; e.anisotropic = m.anisotropic; e.eta = m.eta; e.transmission = m.transmission;
-            e.specular = m.specular; e.specular_tint = m.specularTint; e.sheen_tint = m.sheenTint; e.subsurface = m.subsurface;
-            e.sheen = m.sheen; e.ax = m.ax; e.ay = m.ay;
-            ms.push_back(e);
-        }
+        const std::vector<ErMaterial> ms = er_materials(*scene);
         std::vector<ErTexture> ts;
         for (const Texture& t : scene->textures)
             ts.push_back(ErTexture{t.width, t.height, (int32_t)t.channels, t.filter == Texture::Filter::BILINEAR ? 1 : 0, t.data.data()});
@@ -261,6 +276,7 @@ public:
             });
         for (auto& t : th) t.join();
         for (unsigned r = 0; r < ranks; r++) if (!errs[r].empty()) { std::string e = errs[r]; release(); throw std::runtime_error(e); }
+        textures_sent_ = scene->textures.size();
         if (pars.adaptive)
             for (ErScene* e : ers_) if (er_adaptive_set(e, &pars.adaptive_params) != ER_OK) { std::string m = er_last_error(); release(); throw std::runtime_error(m); }
         // ---- the combine's communicators ----
@@ -310,6 +326,44 @@ public:
         for (int rc : rcs) if (rc != ER_OK) return false;
         if (pars.adaptive)
             for (ErScene* e : ers_) if (er_adaptive_set(e, &pars.adaptive_params) != ER_OK) return false;
+        return true;
+    }
+    // A --start after nothing but --load_camera, --load_hdri, --load_brdf_material and --load_texture: er_render_edit on every rank
+    // side by side.  What goes over: the camera; the COMPLETE material list and the triangles' material ids as pair_materials left
+    // them (a material sent again under its name is appended, and pair_materials takes the last match: the ids move to the new
+    // entry); the texture list with data = NULL for the textures the ranks already have (addTexture never replaces one: the first of
+    // a name wins); the HDRI if one came.  Returns false -- the caller starts over with start_rendering -- if any rank refused or
+    // failed.
+    bool edit_scene(Scene* scene, bool hdri) {
+        if (ers_.empty() || scene->materials.empty() || scene->textures.size() < textures_sent_) return false;
+        const std::vector<ErMaterial> ms = er_materials(*scene);
+        std::vector<int32_t> mat(scene->tris.size());
+        for (size_t i = 0; i < mat.size(); i++) mat[i] = scene->tris[i].materialID;
+        std::vector<ErTexture> ts;
+        for (size_t i = 0; i < scene->textures.size(); i++) {
+            ts.push_back(er_texture(scene->textures[i]));
+            if (i < textures_sent_) ts.back().data = nullptr;      // (keep)
+        }
+        const Camera& c = scene->camera;
+        ErSceneEdit e{};
+        e.what = ER_EDIT_CAMERA | ER_EDIT_MATERIALS | ER_EDIT_TEXTURES | (hdri ? ER_EDIT_HDRI : 0u);
+        e.camera = ErCamera{c.focalLength, c.sensorWidth, c.sensorHeight, c.aperture, c.focusDistance,
+                            {c.rotation.x, c.rotation.y, c.rotation.z}, c.bokeh ? 1 : 0, {c.position.x, c.position.y, c.position.z}};
+        e.material_count = (uint32_t)ms.size(); e.materials = ms.data();
+        e.material_id = mat.data();
+        e.texture_count = (uint32_t)ts.size(); e.textures = ts.data();
+        if (hdri) e.hdri.texture = er_texture(scene->hdri.texture);
+        std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);
+        if (ers_.size() > 1) lk.lock();
+        std::vector<int> rcs(ers_.size(), ER_OK);
+        std::vector<std::thread> th;
+        for (size_t r = 0; r < ers_.size(); r++) th.emplace_back([&, r] { rcs[r] = er_render_edit(ers_[r], &e); });
+        for (auto& t : th) t.join();
+        features_ready_ = false;      // (the library has invalidated the planes)
+        for (int rc : rcs) if (rc != ER_OK) return false;
+        textures_sent_ = scene->textures.size();
+        if (pars.adaptive)
+            for (ErScene* s : ers_) if (er_adaptive_set(s, &pars.adaptive_params) != ER_OK) return false;
         return true;
     }
     // body of kernel_render_enqueue's loop: n more samples on every rank (the launches go out side by side, then the waits).
@@ -440,6 +494,7 @@ private:
     std::vector<ErScene*> ers_;
     std::vector<ErComm*> comms_;
     std::mutex frame_mtx_;
+    size_t textures_sent_ = 0;         // textures of the scene the ranks hold (start_rendering / edit_scene)
     bool features_ready_ = false;      // a feature pass has run (and been gathered) since the last start_rendering / update_camera
     void render_features_unlocked(unsigned n) {
         features_ready_ = false;

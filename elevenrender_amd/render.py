@@ -138,6 +138,92 @@ class RenderingManager:
         abi.check(self.lib.er_update_info(self.handle, C.byref(a)))
         return {n: getattr(a, n) for n, _ in abi.ErUpdateInfo._fields_}
 
+    def edit(self, camera=None, vertices=None, normals=None, tangents=None, materials=None, material_id=None, textures=None, hdri=None,
+             hdri_cdf=None, hdri_radiance_sum=0.0):
+        """er_render_edit: er_render_update's arguments plus `materials` (the complete new list of abi.ErMaterial; `material_id` int32[n]
+        or None = keep), `textures` (the complete new list of (data, w, h, channels, filter) tuples as in SceneData; None in place of an
+        entry = keep that texture) and `hdri` (such a tuple; hdri_cdf / hdri_radiance_sum as in SceneData, None = built by the
+        library).  The render starts over at sample 0.  self.scene is not changed."""
+        e = abi.ErSceneEdit()
+        keep = []
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        if camera is not None:
+            e.what |= abi.EDIT_CAMERA
+            e.camera = camera
+        if vertices is not None or normals is not None or tangents is not None:
+            e.what |= abi.EDIT_GEOMETRY
+            for name, a in (("vertices", vertices), ("normals", normals), ("tangents", tangents)):
+                if a is None:
+                    continue
+                a = np.ascontiguousarray(a, np.float32)
+                if a.size != self.scene.tri_count * 9:
+                    raise ValueError(f"edit: {name} has {a.size} floats, the scene has {self.scene.tri_count} triangles")
+                keep.append(a)
+                setattr(e, name, fp(a))
+        if materials is not None or material_id is not None:
+            if materials is None:
+                raise ValueError("edit: material_id comes with the material list")
+            e.what |= abi.EDIT_MATERIALS
+            mats = (abi.ErMaterial * max(1, len(materials)))(*materials)
+            keep.append(mats)
+            e.material_count, e.materials = len(materials), mats
+            if material_id is not None:
+                ids = np.ascontiguousarray(material_id, np.int32)
+                if ids.size != self.scene.tri_count:
+                    raise ValueError(f"edit: material_id has {ids.size} entries, the scene has {self.scene.tri_count} triangles")
+                keep.append(ids)
+                e.material_id = ids.ctypes.data_as(C.POINTER(C.c_int32))
+        if textures is not None:
+            e.what |= abi.EDIT_TEXTURES
+            texs = (abi.ErTexture * max(1, len(textures)))()
+            for i, t in enumerate(textures):
+                if t is None:
+                    continue      # (data NULL: keep)
+                data, w, h, ch, flt = t
+                data = abi._f32(data)
+                keep.append(data)
+                texs[i] = abi.ErTexture(int(w), int(h), int(ch), int(flt), fp(data))
+            keep.append(texs)
+            e.texture_count, e.textures = len(textures), texs
+        if hdri is not None:
+            e.what |= abi.EDIT_HDRI
+            data, w, h, ch, flt = hdri
+            data = abi._f32(data)
+            keep.append(data)
+            e.hdri.texture = abi.ErTexture(int(w), int(h), int(ch), int(flt), fp(data))
+            if hdri_cdf is not None:
+                cdf = abi._f32(hdri_cdf)
+                keep.append(cdf)
+                e.hdri.cdf = fp(cdf)
+                e.hdri.radiance_sum = float(hdri_radiance_sum)
+        abi.check(self.lib.er_render_edit(self.handle, C.byref(e)))
+
+    def edit_info(self):
+        a = abi.ErEditInfo()
+        abi.check(self.lib.er_edit_info(self.handle, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in abi.ErEditInfo._fields_}
+
+    def debug_texture_plan(self, scene=None):
+        """include/eleven_hip_debug.h er_debug_texture_plan of `scene` (default: the scene this manager was started with): abi.debug_texture_plan."""
+        return abi.debug_texture_plan(self.scene if scene is None else scene)
+
+    def debug_read_textures(self):
+        """include/eleven_hip_debug.h er_debug_read_textures: what the texture, material and HDRI stages left in device memory, as a dict:
+        table (abi.TEX_DTYPE), pool float32, fused (abi.FUSED_DTYPE), mat_pre float32[materials, 4], materials (bytes per material, uint8),
+        cdf float32, guide uint32, and the descriptor's hdri_tex (dict), hdri_buckets, hdri_radiance_sum, tex_pow2, fused_any."""
+        info = abi.ErTextureDump()
+        abi.check(self.lib.er_debug_read_textures(self.handle, C.byref(info), *([None, 0] * 7)))
+        table, pool, fused = np.zeros(info.texture_count, abi.TEX_DTYPE), np.zeros(info.pool_floats, np.float32), np.zeros(info.fused_count, abi.FUSED_DTYPE)
+        mat_pre, mats = np.zeros((info.material_count, 4), np.float32), np.zeros((info.material_count, C.sizeof(abi.ErMaterial)), np.uint8)
+        cdf, guide = np.zeros(info.cdf_count, np.float32), np.zeros(info.guide_count, np.uint32)
+        args = []
+        for a in (table, pool, fused, mat_pre, mats, cdf, guide):
+            args += [a.ctypes.data_as(C.c_void_p), a.nbytes]
+        abi.check(self.lib.er_debug_read_textures(self.handle, C.byref(info), *args))
+        return dict(table=table, pool=pool, fused=fused, mat_pre=mat_pre, materials=mats, cdf=cdf, guide=guide,
+                    hdri_tex={n: int(getattr(info.hdri_tex, n)) for n, _ in abi.ErTexEntry._fields_}, hdri_buckets=int(info.hdri_buckets),
+                    hdri_radiance_sum=np.float32(info.hdri_radiance_sum), tex_pow2=int(info.tex_pow2), fused_any=int(info.fused_any))
+
     def set_adaptive(self, threshold, min_samples=0, interval=0):
         """Adaptive sampling (er_adaptive_set): between start_rendering and the first sample.  Tiles whose noise falls below
         `threshold` stop receiving samples; tests at min_samples (0 -> 16), then every `interval` (0 -> 8) samples.

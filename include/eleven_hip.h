@@ -365,6 +365,53 @@ typedef struct ErUpdateInfo {
 int er_render_update(ErScene* scene, const ErSceneUpdate* update);
 int er_update_info(ErScene* scene, ErUpdateInfo* out);
 
+/* er_render_update extended to the rest of a look-dev session: materials, textures and the HDRI of a begun scene edited in place.
+ * The contract is er_render_update's, word for word, for every bit: after ER_OK every readable output -- the five planes, samples,
+ * RNG, er_get_counters, er_samples_done, er_light_info, er_adaptive_info (off again), er_state_* -- equals what er_scene_destroy,
+ * er_scene_create of the edited description and er_render_begin with the same ErRenderParams give, bit for bit; the render starts
+ * over at sample 0 and the feature planes are invalidated.  What an edit costs is what it touches:
+ *   MATERIALS whose texture ids all equal the current list's (same count), without TEXTURES: the materials and their constants are
+ *     uploaded (and the triangles' material ids, if given); the texture pool is not touched (texture_stage 0)
+ *   MATERIALS with another count or a changed texture id, or TEXTURES: the texture pool is laid out again and rebuilt ON THE DEVICE
+ *     (csrc/er_texstage.hip; the layout and every byte are those of er_render_begin's host fill) (texture_stage 2)
+ *   HDRI: its CDF (built by the library unless given), the search guide, and the HDRI's texels at the pool's tail, in place if the
+ *     allocation holds them (texture_stage 1, unless the pool was rebuilt in the same call)
+ * With ER_FLAG_MESH_LIGHTS the emitter table is rebuilt after MATERIALS, TEXTURES or GEOMETRY (an edit may create the first emitter
+ * or remove the last).
+ * A call with only CAMERA / GEOMETRY is er_render_update and counts in ErUpdateInfo as that; ErUpdateInfo.updates counts successful
+ * calls of either entry point and refits the refits of either; ErEditInfo.edits counts the successful calls that named one of the
+ * three new bits.
+ * ER_ERR_INVALID_ARG, the scene untouched and still begun: NULL arguments; `what` 0 or with unknown bits; a bit without its array
+ * (GEOMETRY without vertices, MATERIALS without materials, TEXTURES with a count but no list); material_count 0; a non-finite vertex;
+ * texture_count below the scene's; a texture with data == NULL at an index the scene does not have; a texture or an HDRI that
+ * er_scene_create refuses; a material_id entry (given, or kept with a shorter list) or a material's texture id beyond the new lists,
+ * as er_scene_create refuses them (a negative texture id means "no texture"); a texture pool that would reach 2^32 floats.
+ * As for er_render_update the host copy is replaced before any device work, and if device work then fails the scene is no longer
+ * begun. */
+#define ER_EDIT_CAMERA    1u   /* = ER_UPDATE_CAMERA   */
+#define ER_EDIT_GEOMETRY  2u   /* = ER_UPDATE_GEOMETRY */
+#define ER_EDIT_MATERIALS 4u
+#define ER_EDIT_TEXTURES  8u
+#define ER_EDIT_HDRI      16u
+typedef struct ErSceneEdit {
+    uint32_t what;
+    ErCamera camera;                                   /* as in ErSceneUpdate */
+    const float *vertices, *normals, *tangents;        /* as in ErSceneUpdate */
+    uint32_t material_count; const ErMaterial* materials;   /* MATERIALS: the complete new list, count >= 1 */
+    const int32_t* material_id;                        /* MATERIALS: [tri_count] or NULL = keep */
+    uint32_t texture_count; const ErTexture* textures; /* TEXTURES: the complete new list; data == NULL = keep texture i as it is */
+    ErHdri hdri;                                       /* HDRI: as in ErSceneDesc (cdf NULL = built by the library) */
+} ErSceneEdit;
+int er_render_edit(ErScene* scene, const ErSceneEdit* edit);
+typedef struct ErEditInfo {
+    uint32_t edits;            /* successful er_render_edit calls with MATERIALS, TEXTURES or HDRI since er_scene_create */
+    uint32_t texture_stage;    /* the last of them: 0 the pool was not touched, 1 only the HDRI's tail was rewritten, 2 rebuilt on the device */
+    float texture_stage_ms;    /* device time of that pool work (HIP events), 0 if none */
+    float edit_ms;             /* host wall time of the last of them */
+    uint64_t pool_floats;      /* the texture pool after it */
+} ErEditInfo;
+int er_edit_info(ErScene* scene, ErEditInfo* out);
+
 /* First-hit feature planes and the denoise guided by them (extension; csrc/er_features.hip gives every float32 operation).
  * er_render_features: a stateless primary-visibility pass over the pixels this rank owns -- n camera rays per pixel (0 -> 4, at most
  * 64; more: ER_ERR_INVALID_ARG) through the production traversal, drawn from the pixel's RNG stream as er_render_begin seeds it, so

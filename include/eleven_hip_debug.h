@@ -211,6 +211,42 @@ typedef struct ErStreamForm {
 } ErStreamForm;
 int er_debug_stream_form(uint32_t tiles, uint32_t blocks, int light_query, uint32_t tri_count, uint32_t flags, ErStreamForm* out);
 
+/* The texture pool (er_render_begin fills it on the host, er_render_edit on the device: csrc/er_texplan.h, csrc/er_texstage.hip).  Both
+ * hooks below only copy.  Entries: ErTexEntry = the device table's record of a texture (csrc/er_device.h DevTex; channels 1 and filter
+ * 0 / 1 / 2 for a texture kept by its first channel, 2 = already to the power 2.2), ErFusedEntry = a material's fused record block
+ * (DevFused; width 0 = not fused).  Buffers follow er_debug_read_accel's protocol: NULL = not wanted, capacities in bytes, a capacity
+ * smaller than the array is ER_ERR_INVALID_ARG, all NULL queries the sizes. */
+typedef struct ErTexEntry { int32_t width, height, channels, filter; uint32_t offset; } ErTexEntry;
+typedef struct ErFusedEntry { int32_t width, height, filter; uint32_t offset; } ErFusedEntry;
+typedef struct ErTexturePlan {
+    uint32_t texture_count;        /* modes: texture_count bytes (0 as it came, 1 first channel alone, 2 that to the power 2.2); table: as many ErTexEntry */
+    uint32_t fused_count;          /* fused: max(1, material_count) ErFusedEntry */
+    uint32_t fused_any, reserved;
+    ErTexEntry hdri;               /* the HDRI's texels lie last in the pool */
+    uint64_t pool_floats;          /* >= 2^32: er_render_begin and er_render_edit refuse the scene */
+} ErTexturePlan;
+/* The texture plan of a scene description, as er_render_begin and er_render_edit make it (host code, no device needed; the
+ * ER_TEX_COMPACT, ER_TEX_FUSE and ER_MAT_PRE_ON_DEVICE knobs of the environment are honoured).  Only the sizes, channels and filters of
+ * desc->textures and desc->hdri.texture and the texture ids of desc->materials are read: no texel, no triangle array. */
+struct ErSceneDesc;
+int er_debug_texture_plan(const struct ErSceneDesc* desc, ErTexturePlan* plan, uint8_t* modes, uint64_t modes_cap, ErTexEntry* table, uint64_t table_cap,
+                          ErFusedEntry* fused, uint64_t fused_cap);
+
+/* What the texture, material and HDRI stages left in DEVICE memory (after er_render_begin; before: ER_ERR_STATE): the table, the pool
+ * (pool_floats floats), the fused descriptors, mat_pre (material_count x 4 floats), the materials (material_count ErMaterial), the
+ * HDRI's CDF (cdf_count floats) and its search guide (guide_count uint32), and the fields of the kernels' scene descriptor that
+ * follow from them. */
+typedef struct ErTextureDump {
+    uint32_t texture_count, material_count, fused_count, cdf_count, guide_count;
+    uint32_t tex_pow2, fused_any;  /* the descriptor's */
+    int32_t hdri_buckets;
+    float hdri_radiance_sum;
+    ErTexEntry hdri_tex;           /* the descriptor's */
+    uint64_t pool_floats;
+} ErTextureDump;
+int er_debug_read_textures(struct ErScene* scene, ErTextureDump* info, void* table, uint64_t table_cap, void* pool, uint64_t pool_cap, void* fused, uint64_t fused_cap,
+                           void* mat_pre, uint64_t mat_pre_cap, void* materials, uint64_t materials_cap, void* cdf, uint64_t cdf_cap, void* guide, uint64_t guide_cap);
+
 /* Test hook for the out-of-memory path of the boundary: while `bytes` is non-zero, any single large host allocation the
  * library announces (scene copy in er_scene_create, build staging in er_render_begin) larger than `bytes` fails as
  * std::bad_alloc would, which the entry point must turn into ER_ERR_OOM (no exception crosses the C ABI).  0 = off. */
