@@ -23,6 +23,7 @@ FLAG_HOST_BUILD = 512
 FLAG_MESH_LIGHTS = 1024     # next-event estimation of emissive triangles (csrc/er_shade.h)
 UPDATE_CAMERA, UPDATE_GEOMETRY = 1, 2     # ErSceneUpdate.what
 EDIT_CAMERA, EDIT_GEOMETRY, EDIT_MATERIALS, EDIT_TEXTURES, EDIT_HDRI = 1, 2, 4, 8, 16     # ErSceneEdit.what
+REBUILD_NEVER, REBUILD_ALWAYS, REBUILD_AUTO = 0, 1, 2     # ErUpdatePolicy.mode
 FEATURE_ALBEDO, FEATURE_DEPTH, FEATURE_COUNT = 0, 1, 2     # er_render_features (csrc/er_features.hip)
 FEATURE_NAMES = {"albedo": 0, "depth": 1}
 
@@ -133,6 +134,23 @@ class ErEditInfo(C.Structure):
     _fields_ = [("edits", C.c_uint32), ("texture_stage", C.c_uint32), ("texture_stage_ms", C.c_float), ("edit_ms", C.c_float), ("pool_floats", C.c_uint64)]
 
 
+class ErAccelCost(C.Structure):
+    _fields_ = [("node_area", C.c_double), ("leaf_area", C.c_double), ("tri_area", C.c_double), ("cost", C.c_double), ("ms", C.c_float), ("builder", C.c_uint32)]
+
+
+class ErUpdatePolicy(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("max_cost_ratio", C.c_float)]
+
+
+class ErRebuildInfo(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("max_cost_ratio", C.c_float), ("rebuilds", C.c_uint32), ("last_decision", C.c_uint32), ("cost_built", C.c_double),
+                ("cost_refit", C.c_double), ("cost_after", C.c_double), ("cost_ms", C.c_float), ("rebuild_ms", C.c_float)]
+
+
+class ErCostSumsDebug(C.Structure):   # include/eleven_hip_debug.h: er_debug_accel_cost_terms / er_debug_accel_cost_host
+    _fields_ = [("node_area", C.c_double), ("leaf_area", C.c_double), ("tri_area", C.c_double), ("cost", C.c_double), ("ms", C.c_float), ("reserved", C.c_uint32)]
+
+
 class ErTexEntry(C.Structure):   # include/eleven_hip_debug.h (csrc/er_device.h DevTex)
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32), ("filter", C.c_int32), ("offset", C.c_uint32)]
 
@@ -229,6 +247,27 @@ def debug_bvh_dump(vertices, normals, threads=0):
     return accel_dump_dict(info, nodes=nodes, nodes8=nodes8, slot_to_tri=s2t, tri_lift=lift)
 
 
+def _cost_dict(sums, node_terms, tri_terms):
+    d = {n: getattr(sums, n) for n in ("node_area", "leaf_area", "tri_area", "cost", "ms")}
+    d.update(node_terms=node_terms, tri_terms=tri_terms)
+    return d
+
+
+def debug_accel_cost_host(nodes8, isect, tri_count):
+    """include/eleven_hip_debug.h er_debug_accel_cost_host: the host compilation of csrc/er_cost.h over a dump's wide nodes (NODE8_DTYPE,
+    packed) and intersection records (ISECT_DTYPE; the first tri_count are read) -- no device needed.  A dict: node_area, leaf_area,
+    tri_area, cost, node_terms float64[N, 2] (node_i, leaf_i), tri_terms float32[tri_count]."""
+    lib = load()
+    n8 = np.ascontiguousarray(nodes8, NODE8_DTYPE)
+    rec = np.ascontiguousarray(isect, ISECT_DTYPE)
+    n = int(tri_count)
+    assert len(rec) >= n
+    sums, nt, tt = ErCostSumsDebug(), np.zeros((len(n8), 2), np.float64), np.zeros(n, np.float32)
+    check(lib.er_debug_accel_cost_host(n8.ctypes.data_as(C.c_void_p), len(n8), NODE8_DTYPE.itemsize // 16, rec.ctypes.data_as(C.c_void_p), n, C.byref(sums),
+                                       nt.ctypes.data_as(C.POINTER(C.c_double)), nt.nbytes, _fptr(tt), tt.nbytes))
+    return _cost_dict(sums, nt, tt)
+
+
 def debug_texture_plan(scene):
     """include/eleven_hip_debug.h er_debug_texture_plan: the texture plan of a SceneData (or of an ErSceneDesc whose textures declare
     sizes only: no texel is read; no device needed) as a dict: modes uint8[textures], table (TEX_DTYPE), fused (FUSED_DTYPE, one per
@@ -278,6 +317,9 @@ SYMBOLS = {
     "er_update_info": (C.c_int, [_P, C.POINTER(ErUpdateInfo)]),
     "er_render_edit": (C.c_int, [_P, C.POINTER(ErSceneEdit)]),
     "er_edit_info": (C.c_int, [_P, C.POINTER(ErEditInfo)]),
+    "er_accel_cost": (C.c_int, [_P, C.POINTER(ErAccelCost)]),
+    "er_update_policy_set": (C.c_int, [_P, C.POINTER(ErUpdatePolicy)]),
+    "er_rebuild_info": (C.c_int, [_P, C.POINTER(ErRebuildInfo)]),
     "er_adaptive_set": (C.c_int, [_P, C.POINTER(ErAdaptiveParams)]),
     "er_adaptive_info": (C.c_int, [_P, C.POINTER(ErAdaptiveInfo)]),
     "er_read_tile_state": (C.c_int, [_P, _FP, C.POINTER(C.c_uint32)]),
@@ -336,6 +378,8 @@ OPTIONAL_SYMBOLS = {
     "er_debug_read_textures": (C.c_int, [_P, C.POINTER(ErTextureDump)] + [_P, C.c_uint64] * 7),
     "er_debug_bvh_dump": (C.c_int, [_FP, _FP, C.c_uint32, C.c_int, C.POINTER(ErAccelDump), _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64,
                                     _FP, C.c_uint64]),
+    "er_debug_accel_cost_terms": (C.c_int, [_P, C.POINTER(ErCostSumsDebug), C.POINTER(C.c_double), C.c_uint64, _FP, C.c_uint64]),
+    "er_debug_accel_cost_host": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(ErCostSumsDebug), C.POINTER(C.c_double), C.c_uint64, _FP, C.c_uint64]),
 }
 
 

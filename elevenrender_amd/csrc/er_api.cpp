@@ -283,7 +283,23 @@ int begin_accel(ErScene* s, BeginStaging& B, hipEvent_t built_ev, ErGpuBvhDevice
     if (g.max_depth8 > ER_STACK8) return fail(ER_ERR_STATE, "er_render_begin: wide BVH deeper than the traversal stack (ER_STACK8)");
     if (g.geom_f4 >= (1ull << 30)) return fail(ER_ERR_INVALID_ARG, "er_render_begin: geometry exceeds the 16 GB addressable by the wide traversal");
     s->accel.builder = built ? 1u : 0u;
+    s->accel_version++;            // (er_accel_cost's kept result and ER_REBUILD_AUTO's baseline were another tree's)
+    s->baseline_known = false;
     return built ? ER_OK : accel_upload_host(s, B, g);
+}
+
+// what er_accel_info and er_debug_read_accel report of a structure that begin_accel has just made
+void accel_publish(ErScene* s, const ErGpuBvhDevice& g, float up_ms) {
+    s->accel.node_count = g.nodes8_count;
+    s->accel.node_bytes = sizeof(ErNode8);
+    s->accel.max_depth = g.max_depth8;
+    s->accel.leaf_count = g.leaf_count;
+    s->accel.tri_record_bytes = sizeof(ErTriIsect);
+    s->accel.build_ms = (float)g.build_ms;
+    s->accel.upload_ms = up_ms;
+    s->accel.lift_bound = g.lift_bound;
+    for (int a = 0; a < 3; a++) { s->accel_lo[a] = g.lo[a]; s->accel_hi[a] = g.hi[a]; }
+    s->accel_depth2 = g.max_depth2;
 }
 
 // the materials and their precomputed constants (stage 3 without the point lights: what a material edit runs again)
@@ -651,16 +667,7 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     float up_ms = 0;
     (void)hipEventElapsedTime(&up_ms, ev.a, ev.b);
 
-    s->accel.node_count = g.nodes8_count;
-    s->accel.node_bytes = sizeof(ErNode8);
-    s->accel.max_depth = g.max_depth8;
-    s->accel.leaf_count = g.leaf_count;
-    s->accel.tri_record_bytes = sizeof(ErTriIsect);
-    s->accel.build_ms = (float)g.build_ms;
-    s->accel.upload_ms = up_ms;
-    s->accel.lift_bound = g.lift_bound;
-    for (int a = 0; a < 3; a++) { s->accel_lo[a] = g.lo[a]; s->accel_hi[a] = g.hi[a]; }
-    s->accel_depth2 = g.max_depth2;
+    accel_publish(s, g, up_ms);
     s->begun = true;
     return ER_OK;
 }
@@ -690,6 +697,91 @@ static int edit_refit(ErScene* s, bool new_normals, bool new_tangents, const cha
     }
     s->accel.builder = 2u;
     s->accel.build_ms = s->upd.refit_ms = r.refit_ms;
+    s->accel_version++;
+    return ER_OK;
+}
+
+// er_accel_cost of the structure as it lies, measured unless this version of it has been (the stream is idle, the device set)
+static int accel_cost_locked(ErScene* s, const char* who, ErAccelCost* out) {
+    if (s->cost_version != s->accel_version) {
+        const ErGpuBvhDevice& g = s->keep_accel;
+        ErCostSums c;
+        std::string why;
+        const int crc = er_cost_device(s->d_nodes8.p, g.nodes8_count, (const ErTriIsect*)(s->d_nodes8.p + g.n8_pieces), s->tri_count, s->stream, &c, nullptr, nullptr, why);
+        if (crc != 0) return fail(crc == -2 ? ER_ERR_OOM : ER_ERR_HIP, std::string(who) + ": structure cost: " + why);
+        s->cost_kept = ErAccelCost{c.node_area, c.leaf_area, c.tri_area, c.cost, c.ms, s->accel.builder};
+        s->cost_version = s->accel_version;
+        if (s->accel.builder != 2u) { s->baseline_known = true; s->baseline_cost = c.cost; }      // a BUILT tree: what a later refit is judged against
+    }
+    *out = s->cost_kept;
+    return ER_OK;
+}
+
+// ER_REBUILD_ALWAYS / AUTO: the structure stage of er_render_begin again, on the host copy as it is now.  The scene's structure
+// buffers and the refit's level lists go first; the builder is chosen as er_render_begin chooses it, and its depth checks apply.
+static int edit_rebuild(ErScene* s, BeginStaging& B) {
+    const auto t0 = std::chrono::steady_clock::now();
+    s->refit_topo.release();
+    s->d_nodes.release(); s->d_nodes8.release(); s->d_attr.release();
+    EventPair ev;
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+    ErGpuBvhDevice g;
+    int rc;
+    try {
+        rc = begin_accel(s, B, ev.a, g);
+    } catch (...) {
+        s->begun = false;      // (the old structure is gone: an exception on its way to guarded() must not leave a scene that renders)
+        throw;
+    }
+    if (rc != ER_OK) return rc;
+    HIP_TRY(hipEventRecord(ev.b, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    float up_ms = 0;
+    (void)hipEventElapsedTime(&up_ms, ev.a, ev.b);
+    s->keep_accel = g;
+    s->keep_accel.nodes = s->keep_accel.geom = s->keep_accel.attr = nullptr;      // (the scene owns the buffers)
+    accel_publish(s, g, up_ms);
+    s->rebuild.rebuilds++;
+    s->rebuild.rebuild_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ER_OK;
+}
+
+// The geometry bit of er_render_update and er_render_edit, the host copy replaced: the refit, or a fresh build, by the scene's policy
+// (include/eleven_hip.h ER_REBUILD_*).  ER_REBUILD_NEVER is the refit and nothing else.
+static int edit_geometry(ErScene* s, BeginStaging& B, bool new_normals, bool new_tangents, const char* who) {
+    const uint32_t mode = s->policy.mode;
+    if (mode == ER_REBUILD_NEVER) return edit_refit(s, new_normals, new_tangents, who);
+    int rc;
+    ErRebuildInfo& R = s->rebuild;
+    R.cost_built = R.cost_refit = R.cost_after = 0.0;
+    R.cost_ms = R.rebuild_ms = 0.0f;
+    if (mode == ER_REBUILD_ALWAYS) {
+        if ((rc = edit_rebuild(s, B)) != ER_OK) return rc;
+        R.last_decision = 3u;
+        return ER_OK;
+    }
+    ErAccelCost c;
+    uint32_t decision = 4u;      // rebuilt: no baseline
+    if (!s->baseline_known && s->accel.builder != 2u) {      // the built tree, still in place: measured before it is refitted
+        if ((rc = accel_cost_locked(s, who, &c)) != ER_OK) return rc;
+        R.cost_ms += c.ms;
+    }
+    if (s->baseline_known) {
+        R.cost_built = s->baseline_cost;
+        if ((rc = edit_refit(s, new_normals, new_tangents, who)) != ER_OK) return rc;
+        if ((rc = accel_cost_locked(s, who, &c)) != ER_OK) return rc;
+        R.cost_ms += c.ms;
+        R.cost_refit = c.cost;
+        decision = (R.cost_built != 0.0 && R.cost_refit > (double)s->policy.max_cost_ratio * R.cost_built) ? 2u : 1u;
+    }
+    if (decision != 1u) {
+        if ((rc = edit_rebuild(s, B)) != ER_OK) return rc;
+        if ((rc = accel_cost_locked(s, who, &c)) != ER_OK) return rc;      // (a built tree: this is the next baseline)
+        R.cost_ms += c.ms;
+        R.cost_after = c.cost;
+    }
+    R.last_decision = decision;
     return ER_OK;
 }
 
@@ -728,7 +820,7 @@ static int update_device(ErScene* s, const ErSceneUpdate* u) {
     const bool lights_on = (s->keep_flags & ER_FLAG_POINT_LIGHTS) != 0 && !s->point_lights.empty();
     BeginStaging B;                     // outlives begin_render_state's hipStreamSynchronize
     if (u->what & ER_UPDATE_GEOMETRY) {
-        if ((rc = edit_refit(s, u->normals != nullptr, u->tangents != nullptr, "er_render_update")) != ER_OK) return rc;
+        if ((rc = edit_geometry(s, B, u->normals != nullptr, u->tangents != nullptr, "er_render_update")) != ER_OK) return rc;
         if ((rc = edit_emitters(s, B, lights_on)) != ER_OK) return rc;
     }
     return edit_restart(s, B, lights_on);
@@ -761,7 +853,7 @@ static int update_locked(ErScene* s, const ErSceneUpdate* u, std::chrono::steady
         return rc;
     }
     s->upd.updates++;
-    if (u->what & ER_UPDATE_GEOMETRY) s->upd.refits++;
+    if ((u->what & ER_UPDATE_GEOMETRY) && s->accel.builder == 2u) s->upd.refits++;      // (under a rebuild policy the update may have ended in a build)
     s->upd.update_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return ER_OK;
 }
@@ -876,7 +968,7 @@ int edit_device(ErScene* s, const ErSceneEdit* e, const EditWork& W, uint32_t& s
     const bool lights_on = (s->keep_flags & ER_FLAG_POINT_LIGHTS) != 0 && !s->point_lights.empty();
     BeginStaging B;                     // outlives begin_render_state's hipStreamSynchronize
     if (what & ER_EDIT_GEOMETRY)
-        if ((rc = edit_refit(s, e->normals != nullptr, e->tangents != nullptr, "er_render_edit")) != ER_OK) return rc;
+        if ((rc = edit_geometry(s, B, e->normals != nullptr, e->tangents != nullptr, "er_render_edit")) != ER_OK) return rc;
     if (what & ER_EDIT_MATERIALS) {
         if ((rc = upload_materials(s, B)) != ER_OK) return rc;
         if (e->material_id && s->tri_count) {
@@ -1040,12 +1132,40 @@ static int er_render_edit_impl(ErScene* s, const ErSceneEdit* e) {
         return rc;
     }
     s->upd.updates++;
-    if (what & ER_EDIT_GEOMETRY) s->upd.refits++;
+    if ((what & ER_EDIT_GEOMETRY) && s->accel.builder == 2u) s->upd.refits++;
     s->edit.edits++;
     s->edit.texture_stage = stage;
     s->edit.texture_stage_ms = stage_ms;
     s->edit.pool_floats = s->d_tex_pool.n;
     s->edit.edit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ER_OK;
+}
+
+static int er_accel_cost_impl(ErScene* s, ErAccelCost* out) {
+    if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_accel_cost: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_accel_cost: er_render_begin has not succeeded");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));      // pending asynchronous work first
+    return accel_cost_locked(s, "er_accel_cost", out);
+}
+
+static int er_update_policy_set_impl(ErScene* s, const ErUpdatePolicy* p) {
+    if (!s || !p) return fail(ER_ERR_INVALID_ARG, "er_update_policy_set: NULL argument");
+    if (p->mode > ER_REBUILD_AUTO) return fail(ER_ERR_INVALID_ARG, "er_update_policy_set: unknown mode");
+    if (p->mode == ER_REBUILD_AUTO && !(std::isfinite(p->max_cost_ratio) && p->max_cost_ratio >= 1.0f))
+        return fail(ER_ERR_INVALID_ARG, "er_update_policy_set: ER_REBUILD_AUTO needs a finite max_cost_ratio >= 1");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    s->policy = *p;
+    return ER_OK;
+}
+
+static int er_rebuild_info_impl(ErScene* s, ErRebuildInfo* out) {
+    if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_rebuild_info: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    *out = s->rebuild;
+    out->mode = s->policy.mode;
+    out->max_cost_ratio = s->policy.max_cost_ratio;
     return ER_OK;
 }
 
@@ -1642,5 +1762,8 @@ int er_render_update(ErScene* s, const ErSceneUpdate* u) { return guarded("er_re
 int er_update_info(ErScene* s, ErUpdateInfo* out) { return guarded("er_update_info", [&]() -> int { return er_update_info_impl(s, out); }); }
 int er_render_edit(ErScene* s, const ErSceneEdit* e) { return guarded("er_render_edit", [&]() -> int { return er_render_edit_impl(s, e); }); }
 int er_edit_info(ErScene* s, ErEditInfo* out) { return guarded("er_edit_info", [&]() -> int { return er_edit_info_impl(s, out); }); }
+int er_accel_cost(ErScene* s, ErAccelCost* out) { return guarded("er_accel_cost", [&]() -> int { return er_accel_cost_impl(s, out); }); }
+int er_update_policy_set(ErScene* s, const ErUpdatePolicy* p) { return guarded("er_update_policy_set", [&]() -> int { return er_update_policy_set_impl(s, p); }); }
+int er_rebuild_info(ErScene* s, ErRebuildInfo* out) { return guarded("er_rebuild_info", [&]() -> int { return er_rebuild_info_impl(s, out); }); }
 int er_read_tile_state(ErScene* s, float* error, uint32_t* samples) { return guarded("er_read_tile_state", [&]() -> int { return er_read_tile_state_impl(s, error, samples); }); }
 }  // extern "C"

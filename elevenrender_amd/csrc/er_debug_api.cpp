@@ -210,6 +210,39 @@ static int er_debug_read_accel_impl(ErScene* s, ErAccelDump* info, void* nodes, 
     return ER_OK;
 }
 
+// ---- the terms of the structure's measured cost (er_cost.h) ----
+static_assert(sizeof(ErCostSumsDebug) == 40, "four doubles, a float and a reserved word");
+static void cost_sums_out(const ErCostSums& c, ErCostSumsDebug* out) { *out = ErCostSumsDebug{c.node_area, c.leaf_area, c.tri_area, c.cost, c.ms, 0u}; }
+
+static int er_debug_accel_cost_terms_impl(ErScene* s, ErCostSumsDebug* sums, double* node_terms, uint64_t node_cap, float* tri_terms, uint64_t tri_cap) {
+    if (!s || !sums) return fail(ER_ERR_INVALID_ARG, "er_debug_accel_cost_terms: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_debug_accel_cost_terms: er_render_begin has not succeeded");
+    const ErGpuBvhDevice& g = s->keep_accel;
+    if ((node_terms && node_cap < (uint64_t)g.nodes8_count * 16) || (tri_terms && tri_cap < (uint64_t)s->tri_count * 4))
+        return fail(ER_ERR_INVALID_ARG, "er_debug_accel_cost_terms: a buffer is smaller than its array");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    ErCostSums c;
+    std::string why;
+    const int crc = er_cost_device(s->d_nodes8.p, g.nodes8_count, (const ErTriIsect*)(s->d_nodes8.p + g.n8_pieces), s->tri_count, s->stream, &c, node_terms, tri_terms, why);
+    if (crc != 0) return fail(crc == -2 ? ER_ERR_OOM : ER_ERR_HIP, "er_debug_accel_cost_terms: " + why);
+    cost_sums_out(c, sums);
+    return ER_OK;
+}
+
+static int er_debug_accel_cost_host_impl(const void* nodes8, uint32_t node8_count, uint32_t node8_pieces, const void* isect, uint32_t tri_count, ErCostSumsDebug* sums,
+                                         double* node_terms, uint64_t node_cap, float* tri_terms, uint64_t tri_cap) {
+    if (!sums || (node8_count && !nodes8) || (tri_count && !isect)) return fail(ER_ERR_INVALID_ARG, "er_debug_accel_cost_host: NULL argument");
+    if (node8_pieces * 16u < sizeof(ErNode8)) return fail(ER_ERR_INVALID_ARG, "er_debug_accel_cost_host: node8_pieces is below a wide node's 5 pieces");
+    if ((node_terms && node_cap < (uint64_t)node8_count * 16) || (tri_terms && tri_cap < (uint64_t)tri_count * 4))
+        return fail(ER_ERR_INVALID_ARG, "er_debug_accel_cost_host: a buffer is smaller than its array");
+    ErCostSums c;
+    er_cost_host(nodes8, node8_count, node8_pieces, (const ErTriIsect*)isect, tri_count, &c, node_terms, tri_terms);
+    cost_sums_out(c, sums);
+    return ER_OK;
+}
+
 // ---- the texture pool: the plan, and what lies on the device (copies only) ----
 static_assert(sizeof(ErTexEntry) == sizeof(DevTex) && sizeof(ErFusedEntry) == sizeof(DevFused), "the debug header's entries are the device records");
 
@@ -489,6 +522,15 @@ int er_debug_read_textures(ErScene* s, ErTextureDump* info, void* table, uint64_
                            uint64_t mat_pre_cap, void* materials, uint64_t materials_cap, void* cdf, uint64_t cdf_cap, void* guide, uint64_t guide_cap) {
     return guarded("er_debug_read_textures", [&]() -> int {
         return er_debug_read_textures_impl(s, info, table, table_cap, pool, pool_cap, fused, fused_cap, mat_pre, mat_pre_cap, materials, materials_cap, cdf, cdf_cap, guide, guide_cap);
+    });
+}
+int er_debug_accel_cost_terms(ErScene* s, ErCostSumsDebug* sums, double* node_terms, uint64_t node_cap, float* tri_terms, uint64_t tri_cap) {
+    return guarded("er_debug_accel_cost_terms", [&]() -> int { return er_debug_accel_cost_terms_impl(s, sums, node_terms, node_cap, tri_terms, tri_cap); });
+}
+int er_debug_accel_cost_host(const void* nodes8, uint32_t node8_count, uint32_t node8_pieces, const void* isect, uint32_t tri_count, ErCostSumsDebug* sums, double* node_terms,
+                             uint64_t node_cap, float* tri_terms, uint64_t tri_cap) {
+    return guarded("er_debug_accel_cost_host", [&]() -> int {
+        return er_debug_accel_cost_host_impl(nodes8, node8_count, node8_pieces, isect, tri_count, sums, node_terms, node_cap, tri_terms, tri_cap);
     });
 }
 int er_debug_bvh_check(const float* vertices, const float* normals, uint32_t tri_count, int threads, ErBvhCheck* out) { return guarded("er_debug_bvh_check", [&]() -> int { return er_debug_bvh_check_impl(vertices, normals, tri_count, threads, out); }); }

@@ -29,6 +29,7 @@
 #include "er_adaptive.h"
 #include "er_lights.h"
 #include "er_refit.h"
+#include "er_cost.h"
 #include "er_texplan.h"
 #include "er_texstage.h"
 #include "er_features.h"
@@ -168,6 +169,15 @@ struct ErScene {
     ErRefitTopo refit_topo;      // the trees' nodes by level, from the first refit after an er_render_begin until the next one
     ErUpdateInfo upd{};          // er_update_info (counts since er_scene_create)
     ErEditInfo edit{};           // er_edit_info (the same)
+    // er_accel_cost / er_update_policy_set (er_api.cpp): every build and every refit bumps accel_version; the cost last measured is kept
+    // with the version it was measured at.  The baseline of ER_REBUILD_AUTO is the cost of the last BUILT tree: known once such a tree
+    // has been measured, forgotten with the next build.
+    uint64_t accel_version = 0, cost_version = ~0ull;
+    ErAccelCost cost_kept{};
+    bool baseline_known = false;
+    double baseline_cost = 0;
+    ErUpdatePolicy policy{ER_REBUILD_NEVER, 0.0f};      // lasts until er_scene_destroy
+    ErRebuildInfo rebuild{};                           // er_rebuild_info (counts since er_scene_create; mode and ratio are filled from `policy`)
     size_t tex_pool_cap = 0;     // floats the allocation of d_tex_pool holds (d_tex_pool.n: the floats of the pool in it; an HDRI edit may shrink that)
     DevBuf<float4> d_nodes, d_nodes8, d_attr, d_passes;
     DevBuf<float4> d_plane;      // staging: one pass gathered as a plane for er_read_pass

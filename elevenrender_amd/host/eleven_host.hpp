@@ -488,6 +488,38 @@ public:
         }
         return i;
     }
+    // er_update_policy_set on every rank (every rank holds the whole structure): what a geometry edit does to it -- ER_REBUILD_NEVER the
+    // refit, ALWAYS a fresh build in the same call, AUTO a fresh build once the refitted tree's measured cost exceeds max_cost_ratio x
+    // the last built tree's.  Lasts for these scenes, i.e. until the next start_rendering.
+    void set_update_policy(uint32_t mode, float max_cost_ratio = 0) {
+        if (ers_.empty()) throw std::runtime_error("set_update_policy: no render has been started");
+        const ErUpdatePolicy p{mode, max_cost_ratio};
+        for (ErScene* e : ers_) check(er_update_policy_set(e, &p));
+    }
+    ErAccelCost accel_cost() {      // the ranks hold the same structure: rank 0's figures, the slowest rank's time
+        if (ers_.empty()) throw std::runtime_error("accel_cost: no render has been started");
+        ErAccelCost out{};
+        for (size_t r = 0; r < ers_.size(); r++) {
+            ErAccelCost c{};
+            check(er_accel_cost(ers_[r], &c));
+            const float ms = std::max(out.ms, c.ms);
+            if (r == 0) out = c;
+            out.ms = ms;
+        }
+        return out;
+    }
+    ErRebuildInfo rebuild_info() {      // rank 0's decisions (the same on every rank: the same bytes measured), the slowest rank's times
+        if (ers_.empty()) throw std::runtime_error("rebuild_info: no render has been started");
+        ErRebuildInfo out{};
+        for (size_t r = 0; r < ers_.size(); r++) {
+            ErRebuildInfo i{};
+            check(er_rebuild_info(ers_[r], &i));
+            const float cms = std::max(out.cost_ms, i.cost_ms), rms = std::max(out.rebuild_ms, i.rebuild_ms);
+            if (r == 0) out = i;
+            out.cost_ms = cms; out.rebuild_ms = rms;
+        }
+        return out;
+    }
     unsigned ranks() const { return (unsigned)ers_.size(); }
 
 private:

@@ -203,6 +203,33 @@ class RenderingManager:
         abi.check(self.lib.er_edit_info(self.handle, C.byref(a)))
         return {n: getattr(a, n) for n, _ in abi.ErEditInfo._fields_}
 
+    def set_update_policy(self, mode, max_cost_ratio=0.0):
+        """er_update_policy_set: what the geometry bit of update() / edit() does to the structure -- abi.REBUILD_NEVER (the refit, a fresh
+        scene's policy), abi.REBUILD_ALWAYS (a fresh build in the same call) or abi.REBUILD_AUTO (the refit, then a fresh build if the
+        refitted tree's measured cost exceeds max_cost_ratio x the last built tree's).  Needs only start_rendering's handle; lasts until close()."""
+        abi.check(self.lib.er_update_policy_set(self.handle, C.byref(abi.ErUpdatePolicy(int(mode), float(max_cost_ratio)))))
+
+    def accel_cost(self):
+        """er_accel_cost: the measured cost of the structure as it lies in device memory (csrc/er_cost.h)."""
+        a = abi.ErAccelCost()
+        abi.check(self.lib.er_accel_cost(self.handle, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in abi.ErAccelCost._fields_}
+
+    def rebuild_info(self):
+        a = abi.ErRebuildInfo()
+        abi.check(self.lib.er_rebuild_info(self.handle, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in abi.ErRebuildInfo._fields_}
+
+    def debug_accel_cost_terms(self):
+        """include/eleven_hip_debug.h er_debug_accel_cost_terms: a measurement run for this call, with its terms -- a dict as
+        abi.debug_accel_cost_host's, plus ms."""
+        info = abi.ErAccelDump()
+        abi.check(self.lib.er_debug_read_accel(self.handle, C.byref(info), None, 0, None, 0, None, 0, None, 0))
+        sums, nt, tt = abi.ErCostSumsDebug(), np.zeros((info.node8_count, 2), np.float64), np.zeros(info.tri_count, np.float32)
+        abi.check(self.lib.er_debug_accel_cost_terms(self.handle, C.byref(sums), nt.ctypes.data_as(C.POINTER(C.c_double)), nt.nbytes,
+                                                     tt.ctypes.data_as(C.POINTER(C.c_float)), tt.nbytes))
+        return abi._cost_dict(sums, nt, tt)
+
     def debug_texture_plan(self, scene=None):
         """include/eleven_hip_debug.h er_debug_texture_plan of `scene` (default: the scene this manager was started with): abi.debug_texture_plan."""
         return abi.debug_texture_plan(self.scene if scene is None else scene)

@@ -412,6 +412,54 @@ typedef struct ErEditInfo {
 } ErEditInfo;
 int er_edit_info(ErScene* scene, ErEditInfo* out);
 
+/* A measured cost of the acceleration structure as it lies in device memory, whichever builder or refit left it (csrc/er_cost.h gives
+ * every operation): the areas of the boxes a traversal tests, weighted by the bytes fetched for each, over the areas of the triangles'
+ * own boxes --
+ *   cost = (ErAccelInfo.node_bytes x node_area + ErAccelInfo.tri_record_bytes x leaf_area) / tri_area
+ *   node_area = the root's box + every inner child box; leaf_area = every leaf child box x its triangles; tri_area = every triangle's box
+ * (0 for a scene without triangles or without area).  Translation and scale do not change it; it rises when a refit has grown node
+ * boxes around triangles that moved apart.  Only the RATIO of two costs of one scene means anything.  Bitwise reproducible.
+ * The scene must be begun (else ER_ERR_STATE); pending asynchronous work is waited for; planes, RNG and counters are neither read nor
+ * written.  The result is kept until the next build or refit, so a second call launches nothing (ms is then the first call's). */
+typedef struct ErAccelCost {
+    double node_area, leaf_area, tri_area, cost;
+    float ms;                  /* device time of the measurement (HIP events) */
+    uint32_t builder;          /* ErAccelInfo.builder of the structure measured */
+} ErAccelCost;
+int er_accel_cost(ErScene* scene, ErAccelCost* out);
+
+/* What the geometry bit of er_render_update / er_render_edit does to the structure.  ER_REBUILD_NEVER (a fresh scene's policy): the
+ * refit described above, always.  ER_REBUILD_ALWAYS: the structure stage of er_render_begin runs again on the edited arrays -- the
+ * builder chosen by the same flags, environment and thresholds -- and nothing else of er_render_begin does.  ER_REBUILD_AUTO: the refit,
+ * then er_accel_cost of the refitted tree; if that exceeds max_cost_ratio x the cost of the last BUILT tree, the structure is built
+ * fresh in the same call.  (The built tree's cost is measured before the refit unless it is known; a scene whose structure is already a
+ * refit of unknown ancestry -- earlier updates ran under NEVER -- is rebuilt once, which gives the baseline.  A built tree of cost 0 is
+ * never rebuilt by ratio.)  After an update that ended in a rebuild the exception of er_render_update's contract is gone: the
+ * structure is, byte for byte, that of a fresh er_scene_create + er_render_begin, ErAccelInfo.builder is 0 or 1, and
+ * ErUpdateInfo.refits does not count the call.  There is no library default for the ratio; DESIGN.md 3g has the measurements to choose one by.
+ * er_update_policy_set needs only a created scene; the policy lasts until er_scene_destroy.  An unknown mode, or AUTO with a ratio
+ * that is not finite or below 1: ER_ERR_INVALID_ARG, the policy unchanged. */
+#define ER_REBUILD_NEVER  0u
+#define ER_REBUILD_ALWAYS 1u
+#define ER_REBUILD_AUTO   2u
+typedef struct ErUpdatePolicy {
+    uint32_t mode;
+    float max_cost_ratio;      /* read iff ER_REBUILD_AUTO */
+} ErUpdatePolicy;
+typedef struct ErRebuildInfo {
+    uint32_t mode; float max_cost_ratio;   /* the policy in force */
+    uint32_t rebuilds;         /* geometry updates since er_scene_create that ended in a rebuild */
+    uint32_t last_decision;    /* of the last geometry update under ALWAYS or AUTO: 0 none yet, 1 refit kept, 2 rebuilt: ratio exceeded,
+                                  3 rebuilt: ALWAYS, 4 rebuilt: no baseline */
+    double cost_built;         /* AUTO: the baseline the last decision used (0 if it had none) */
+    double cost_refit;         /*       the refitted tree's cost (0 if no refit ran) */
+    double cost_after;         /*       the rebuilt tree's cost = the next baseline (0 if the refit was kept) */
+    float cost_ms;             /* device time of that update's measurements */
+    float rebuild_ms;          /* host wall time of its structure stage, 0 if the refit was kept */
+} ErRebuildInfo;
+int er_update_policy_set(ErScene* scene, const ErUpdatePolicy* policy);
+int er_rebuild_info(ErScene* scene, ErRebuildInfo* out);
+
 /* First-hit feature planes and the denoise guided by them (extension; csrc/er_features.hip gives every float32 operation).
  * er_render_features: a stateless primary-visibility pass over the pixels this rank owns -- n camera rays per pixel (0 -> 4, at most
  * 64; more: ER_ERR_INVALID_ARG) through the production traversal, drawn from the pixel's RNG stream as er_render_begin seeds it, so

@@ -56,6 +56,22 @@ int er_debug_read_accel(struct ErScene* scene, ErAccelDump* info, void* nodes, u
 int er_debug_bvh_dump(const float* vertices, const float* normals, uint32_t tri_count, int threads, ErAccelDump* info, void* nodes, uint64_t nodes_cap,
                       void* nodes8, uint64_t nodes8_cap, uint32_t* slot_to_tri, uint64_t slot_cap, float* tri_lift, uint64_t lift_cap);
 
+/* The terms behind er_accel_cost (csrc/er_cost.h).  The sums of either hook are in `sums` (node_area, leaf_area, tri_area,
+ * cost; ms = device time, 0 on the host); node_terms receives 2 doubles per wide node (node_i, leaf_i), tri_terms one float per
+ * triangle record (tri_k); either may be NULL, capacities in bytes, a capacity smaller than the array is ER_ERR_INVALID_ARG.
+ * er_debug_accel_cost_terms: a measurement of the begun scene's structure in device memory, run for this call (er_accel_cost's kept
+ * result is neither used nor replaced; the arithmetic is bitwise reproducible, so the sums equal its).  Before er_render_begin: ER_ERR_STATE.
+ * er_debug_accel_cost_host: the host compilation of the same header over caller-supplied arrays in the layouts of er_debug_bvh_dump /
+ * er_debug_read_accel -- wide nodes at a stride of node8_pieces x 16 bytes, tri_count intersection records; no device needed.  The
+ * terms are the device's bit for bit; the sums are added sequentially, ascending. */
+typedef struct ErCostSumsDebug {
+    double node_area, leaf_area, tri_area, cost;
+    float ms; uint32_t reserved;
+} ErCostSumsDebug;
+int er_debug_accel_cost_terms(struct ErScene* scene, ErCostSumsDebug* sums, double* node_terms, uint64_t node_cap, float* tri_terms, uint64_t tri_cap);
+int er_debug_accel_cost_host(const void* nodes8, uint32_t node8_count, uint32_t node8_pieces, const void* isect, uint32_t tri_count, ErCostSumsDebug* sums,
+                             double* node_terms, uint64_t node_cap, float* tri_terms, uint64_t tri_cap);
+
 /* Runs the library's HDRI CDF search (elevenrender_amd/csrc/er_cdf.h, the replacement of the 21-level
  * HDRI::binarySearch, reference src/HDRI.cpp:85-98) on the host for `count` values. */
 int er_debug_cdf_search(const float* cdf, int length, const float* values, int32_t* out, int count);
