@@ -6,13 +6,11 @@
 #include <algorithm>
 #include <chrono>
 
-#include "er_scene.h"
+#include "er_api_stages.h"
 #include <thread>
 #include <system_error>
 
 using namespace erh;
-
-extern "C" {
 
 int er_abi_version(void) { return ER_ABI_VERSION; }
 const char* er_last_error(void) { return g_err.c_str(); }
@@ -80,25 +78,15 @@ static int er_scene_create_impl(const ErSceneDesc* d, ErScene** out) {
         s->tangent_sign.assign(d->tangent_sign, d->tangent_sign + n);
         s->material_id.assign(d->material_id, d->material_id + n);
     }
-    for (size_t i = 0; i < n; i++)
-        if (s->material_id[i] < 0 || (uint32_t)s->material_id[i] >= d->material_count) {
-            return fail(ER_ERR_INVALID_ARG, "er_scene_create: material_id out of range");
-        }
+    int rc;
+    if ((rc = check_material_ids(s->material_id.data(), n, d->material_count, "er_scene_create")) != ER_OK) return rc;
     s->materials.assign(d->materials, d->materials + d->material_count);
-    for (const ErMaterial& m : s->materials) {
-        const int32_t ids[7] = {m.albedo_tex, m.emission_tex, m.roughness_tex, m.metallic_tex, m.normal_tex, m.opacity_tex, m.transmission_tex};
-        for (int32_t id : ids)
-            if (id >= (int32_t)d->texture_count) {
-                return fail(ER_ERR_INVALID_ARG, "er_scene_create: texture id out of range");
-            }
-    }
+    if ((rc = check_texture_ids(s->materials.data(), s->materials.size(), d->texture_count, "er_scene_create")) != ER_OK) return rc;
     s->textures.resize(d->texture_count);
     for (uint32_t i = 0; i < d->texture_count; i++) {
-        int rc = copy_tex(d->textures[i], s->textures[i], "scene texture");
-        if (rc != ER_OK) return rc;
+        if ((rc = copy_tex(d->textures[i], s->textures[i], "scene texture")) != ER_OK) return rc;
     }
-    int rc = copy_tex(d->hdri.texture, s->hdri_tex, "hdri");
-    if (rc != ER_OK) return rc;
+    if ((rc = copy_tex(d->hdri.texture, s->hdri_tex, "hdri")) != ER_OK) return rc;
     if (d->hdri.cdf) {
         s->hdri_cdf.assign(d->hdri.cdf, d->hdri.cdf + (size_t)s->hdri_tex.width * s->hdri_tex.height + 1);
         s->hdri_radiance_sum = d->hdri.radiance_sum;
@@ -124,31 +112,11 @@ void er_scene_destroy(ErScene* s) {
 }
 
 // ---- er_render_begin: a sequence of stages, each with an explicit result ----
-namespace {
-
-// Staging buffers of the asynchronous uploads of er_render_begin.  They live in er_render_begin_impl's frame, not in the stages',
-// until the stream has been synchronised at its end (HIP happens to make pageable host-to-device copies host-synchronous; this code
-// does not rely on it).
-struct BeginStaging {
-    ErBvhBuild bvh;
-    std::vector<ErTriIsect> isect;
-    std::vector<ErTriAttr> attr;
-    std::vector<float4> geom, mat_pre;
-    std::vector<DevTex> table;
-    std::vector<float> pool;
-    std::vector<DevFused> fused;
-    std::vector<uint32_t> guide, owned;
-    std::vector<int32_t> etex;      // ER_FLAG_MESH_LIGHTS: the textures that emit
-    StreamDeal deal;      // the owned share dealt to the CUs: what the schedule is chosen on, and what the streaming schedule starts with
-};
-
-struct TexResult {      // what the scene descriptor needs of the texture stage
-    DevTex hdri{};
-    int buckets = 0;
-};
+// (those an edit in place runs again are declared in er_api_stages.h; the others are this file's own)
+namespace erh {
 
 // stage 1: arguments and device; the device's description comes back (its CU count is used by the schedules)
-int begin_check(const ErRenderParams* p, ErDeviceInfo& info) {
+static int begin_check(const ErRenderParams* p, ErDeviceInfo& info) {
     const uint32_t world = p->world ? p->world : 1;
     if (p->rank >= world) return fail(ER_ERR_INVALID_ARG, "er_render_begin: rank >= world");
     int ndev = er_device_count();
@@ -162,7 +130,7 @@ int begin_check(const ErRenderParams* p, ErDeviceInfo& info) {
 }
 
 // ... the previous render's device state goes, the new one's stream and events are made
-int begin_open(ErScene* s, const ErRenderParams* p) {
+static int begin_open(ErScene* s, const ErRenderParams* p) {
     if (s->begun || s->stream) {
         (void)hipSetDevice(s->device);
         if (s->stream) (void)hipStreamSynchronize(s->stream);
@@ -194,7 +162,8 @@ int begin_open(ErScene* s, const ErRenderParams* p) {
 }
 
 // stage 2, host builder: the triangle and attribute records in slot order, wide nodes and triangle records in ONE buffer, uploaded
-int accel_upload_host(ErScene* s, BeginStaging& B, const ErGpuBvhDevice& g) {
+static int accel_upload_host(ErScene* s, BeginStaging& B) {
+    const ErGpuBvhDevice& g = s->kept.accel;
     const ErBvhBuild& bvh = B.bvh;
     std::vector<ErTriIsect>& isect = B.isect;
     std::vector<ErTriAttr>& attr = B.attr;
@@ -228,10 +197,12 @@ int accel_upload_host(ErScene* s, BeginStaging& B, const ErGpuBvhDevice& g) {
     return upload(s->d_attr, attr.data(), g.attr_f4, s->stream);
 }
 
-// stage 2: the acceleration structure, by the device build or the host's binned-SAH build.  Either builder fills ONE description, `g`
-// (after a host build its three pointers stay null: the scene owns the buffers either way), ONE block of checks runs on it, and
-// s->accel.builder says who built.  `built_ev` is recorded when the tree is there and the uploads begin.
-int begin_accel(ErScene* s, BeginStaging& B, hipEvent_t built_ev, ErGpuBvhDevice& g) {
+// stage 2: the acceleration structure, by the device build or the host's binned-SAH build.  Either builder fills ONE description, `g`,
+// ONE block of checks runs on it, it is kept in s->kept.accel (the scene owns the buffers either way: the record's three pointers are
+// null), and s->accel.builder says who built.  `built_ev` is recorded when the tree is there and the uploads begin.
+int begin_accel(ErScene* s, BeginStaging& B, hipEvent_t built_ev, const char* who) {
+    const std::string W = who;
+    ErGpuBvhDevice g;
     const uint32_t flags = s->params.flags;
     const size_t n = s->tri_count;
     bool built = false;
@@ -246,14 +217,14 @@ int begin_accel(ErScene* s, BeginStaging& B, hipEvent_t built_ev, ErGpuBvhDevice
         std::string why;
         ErGpuSceneArrays arrays{s->vertices.data(), s->normals.data(), s->tangents.data(), s->uvs.data(), s->tangent_sign.data(), s->material_id.data()};
         int brc = er_gpu_build_device(arrays, s->tri_count, s->device, &g, why);
-        if (brc < 0 && force_dev) return fail(brc == -2 ? ER_ERR_OOM : ER_ERR_HIP, "er_render_begin: device BVH build: " + why);
+        if (brc < 0 && force_dev) return fail(brc == -2 ? ER_ERR_OOM : ER_ERR_HIP, W + ": device BVH build: " + why);
         // What a default device build that did not deliver means: a DECLINE (> 0: too few triangles, a tree deeper than the
         // traversal stacks) and OUT OF DEVICE MEMORY (-2: the build's transient buffers beside other scenes or ranks) are ordinary -- the
         // host builder takes over silently (ER_GPU_BUILD_VERBOSE says so).  Anything else (-1: a HIP error, one of the builder's own
         // guards) is a fault of the builder: the host build still takes over -- the caller gets its image -- but never silently:
         // one line on stderr, unconditionally, with the reason.
         if (brc < 0) (void)hipGetLastError();
-        if (brc == -1) fprintf(stderr, "[eleven_hip] er_render_begin: the device BVH build FAILED (%s); the host builder takes over (seconds instead of milliseconds at this size) -- please report\n", why.c_str());
+        if (brc == -1) fprintf(stderr, "[eleven_hip] %s: the device BVH build FAILED (%s); the host builder takes over (seconds instead of milliseconds at this size) -- please report\n", who, why.c_str());
         else if (brc != 0 && getenv("ER_GPU_BUILD_VERBOSE")) fprintf(stderr, "[er_gpu_build] %s: the host builds instead\n", why.c_str());
         if (brc == 0) {
             // the scene owns the three buffers from here on (release_device frees them on any later error)
@@ -279,17 +250,20 @@ int begin_accel(ErScene* s, BeginStaging& B, hipEvent_t built_ev, ErGpuBvhDevice
     HIP_TRY(hipEventRecord(built_ev, s->stream));
     // what the kernels are sized for, whoever built (the stream schedule's and the wavefront's spill regions hold ER_STACK8 levels of
     // the wide tree per wave, the exact re-trace stacks ER_BVH_MAX_DEPTH of the binary one)
-    if (g.max_depth2 > ER_BVH_MAX_DEPTH) return fail(ER_ERR_STATE, "er_render_begin: BVH deeper than the traversal stack");
-    if (g.max_depth8 > ER_STACK8) return fail(ER_ERR_STATE, "er_render_begin: wide BVH deeper than the traversal stack (ER_STACK8)");
-    if (g.geom_f4 >= (1ull << 30)) return fail(ER_ERR_INVALID_ARG, "er_render_begin: geometry exceeds the 16 GB addressable by the wide traversal");
+    if (g.max_depth2 > ER_BVH_MAX_DEPTH) return fail(ER_ERR_STATE, W + ": BVH deeper than the traversal stack");
+    if (g.max_depth8 > ER_STACK8) return fail(ER_ERR_STATE, W + ": wide BVH deeper than the traversal stack (ER_STACK8)");
+    if (g.geom_f4 >= (1ull << 30)) return fail(ER_ERR_INVALID_ARG, W + ": geometry exceeds the 16 GB addressable by the wide traversal");
     s->accel.builder = built ? 1u : 0u;
     s->accel_version++;            // (er_accel_cost's kept result and ER_REBUILD_AUTO's baseline were another tree's)
     s->baseline_known = false;
-    return built ? ER_OK : accel_upload_host(s, B, g);
+    s->kept.accel = g;
+    s->kept.accel.nodes = s->kept.accel.geom = s->kept.accel.attr = nullptr;      // (the scene owns the buffers)
+    return built ? ER_OK : accel_upload_host(s, B);
 }
 
 // what er_accel_info and er_debug_read_accel report of a structure that begin_accel has just made
-void accel_publish(ErScene* s, const ErGpuBvhDevice& g, float up_ms) {
+void accel_publish(ErScene* s, float up_ms) {
+    const ErGpuBvhDevice& g = s->kept.accel;
     s->accel.node_count = g.nodes8_count;
     s->accel.node_bytes = sizeof(ErNode8);
     s->accel.max_depth = g.max_depth8;
@@ -319,7 +293,7 @@ int upload_materials(ErScene* s, BeginStaging& B) {
 }
 
 // stage 3: materials, their precomputed constants, point lights
-int begin_materials(ErScene* s, BeginStaging& B) {
+static int begin_materials(ErScene* s, BeginStaging& B) {
     int rc;
     if ((rc = upload_materials(s, B)) != ER_OK) return rc;
     return upload(s->d_lights, s->point_lights.data(), s->point_lights.size(), s->stream);
@@ -336,15 +310,15 @@ void plan_of_scene(const ErScene* s, TexPlan& P) {
 // stage 4: the texture pool.  Needs only the host scene; leaves the pool, the table, the fused records, the HDRI's CDF and its guide
 // on the device and the per-texture modes in s->tex_mode.  Every layout decision -- modes, offsets, which materials are fused -- is the
 // texture plan's (er_texplan.h, where the rules are written down); this stage fills that layout on the HOST (er_render_edit fills the
-// same layout on the device, er_texstage.hip).
-int begin_textures(ErScene* s, BeginStaging& B, TexResult& out) {
+// same layout on the device, er_texstage.hip).  The HDRI's table entry and its guide's buckets go to s->kept.
+static int begin_textures(ErScene* s, BeginStaging& B, const char* who) {
     int rc;
     std::vector<DevTex>& table = B.table;
     std::vector<float>& pool = B.pool;
     std::vector<DevFused>& fused = B.fused;
     TexPlan P;
     plan_of_scene(s, P);
-    if (P.pool_floats >= (1ull << 32)) return fail(ER_ERR_INVALID_ARG, "er_render_begin: texture pool exceeds 2^32 floats");
+    if ((rc = check_pool_floats(P.pool_floats, who)) != ER_OK) return rc;
     table = P.table;
     fused = P.fused;
     const std::vector<uint8_t>& mode = P.mode;
@@ -409,19 +383,19 @@ int begin_textures(ErScene* s, BeginStaging& B, TexResult& out) {
     }
     s->fused_any = P.fused_any;
     if ((rc = upload(s->d_mat_fused, fused.data(), fused.size(), s->stream)) != ER_OK) return rc;
-    out.hdri = P.hdri;
+    s->kept.hdri = P.hdri;
     if (!s->hdri_tex.data.empty()) memcpy(pool.data() + P.hdri.offset, s->hdri_tex.data.data(), s->hdri_tex.data.size() * sizeof(float));
     if ((rc = upload(s->d_textures, table.data(), table.size(), s->stream)) != ER_OK) return rc;
     if ((rc = upload(s->d_tex_pool, pool.data(), pool.size(), s->stream)) != ER_OK) return rc;
     s->tex_pool_cap = pool.size();
     if ((rc = upload(s->d_cdf, s->hdri_cdf.data(), s->hdri_cdf.size(), s->stream)) != ER_OK) return rc;
-    out.buckets = er_build_cdf_guide(s->hdri_cdf.data(), s->hdri_tex.width * s->hdri_tex.height, B.guide);
+    s->kept.buckets = er_build_cdf_guide(s->hdri_cdf.data(), s->hdri_tex.width * s->hdri_tex.height, B.guide);
     return upload(s->d_guide, B.guide.data(), B.guide.size(), s->stream);
 }
 
 // stage 5, ER_FLAG_MESH_LIGHTS: the emitter table, built on the device from the placed triangle records (er_lights.hip).  An empty
 // table leaves the render as it would be without the flag.
-int begin_emitters(ErScene* s, BeginStaging& B, size_t n8_pieces, bool point_lights_on) {
+int begin_emitters(ErScene* s, BeginStaging& B, const char* who) {
     if (!(s->params.flags & ER_FLAG_MESH_LIGHTS)) return ER_OK;
     int rc;
     std::vector<int32_t>& etex = B.etex;
@@ -432,18 +406,18 @@ int begin_emitters(ErScene* s, BeginStaging& B, size_t n8_pieces, bool point_lig
     ScopedDevBuf<int32_t> d_etex;
     if ((rc = upload(d_etex, etex.data(), etex.size(), s->stream)) != ER_OK) return rc;
     float* tab = nullptr;
-    HIP_TRY(er_lights_build(s->d_nodes8.p + n8_pieces, s->d_attr.p, s->tri_count, s->d_materials.p, s->d_textures.p, s->d_tex_pool.p, d_etex.p,
+    HIP_TRY(er_lights_build(s->d_nodes8.p + s->kept.accel.n8_pieces, s->d_attr.p, s->tri_count, s->d_materials.p, s->d_textures.p, s->d_tex_pool.p, d_etex.p,
                             (uint32_t)etex.size(), (uint32_t)s->textures.size(), &tab, &s->light_emitters, &s->light_total, s->stream));
     s->d_light_tab.p = tab;
     s->d_light_tab.n = tab ? (size_t)s->tri_count + 2 * (size_t)s->light_emitters : 0;
-    if (point_lights_on && s->light_emitters > 0)
-        return fail(ER_ERR_INVALID_ARG, "er_render_begin: ER_FLAG_POINT_LIGHTS and ER_FLAG_MESH_LIGHTS on a scene with both point lights and "
-                                        "emissive triangles: both need the one light-query record per slot");
+    if (s->lights_on() && s->light_emitters > 0)
+        return fail(ER_ERR_INVALID_ARG, std::string(who) + ": ER_FLAG_POINT_LIGHTS and ER_FLAG_MESH_LIGHTS on a scene with both point lights and "
+                                                           "emissive triangles: both need the one light-query record per slot");
     return ER_OK;
 }
 
 // stage 6: the planes, this rank's tiles, the counters ...
-int begin_planes(ErScene* s, BeginStaging& B) {
+static int begin_planes(ErScene* s, BeginStaging& B) {
     int rc;
     const size_t npx = (size_t)s->x_res * s->y_res;
     if ((rc = upload(s->d_passes, nullptr, npx * ER_PASS_COUNT, s->stream)) != ER_OK) return rc;
@@ -458,7 +432,7 @@ int begin_planes(ErScene* s, BeginStaging& B) {
 
 // ... and the schedule (into s->params.flags): forced by a flag, else the streaming schedule unless this rank's share is beyond its
 // pixel rings (see eleven_hip.h).  B.deal is made here for the streaming schedule to start with.
-int begin_choose_schedule(ErScene* s, BeginStaging& B, uint32_t cus) {
+static int begin_choose_schedule(ErScene* s, BeginStaging& B, uint32_t cus) {
     const uint32_t all = ER_FLAG_MEGAKERNEL | ER_FLAG_FUSED | ER_FLAG_WAVEFRONT | ER_FLAG_STREAM;
     uint32_t forced = s->params.flags & all;
     // (ER_FLAG_FUSED named round 1's lane-asynchronous single kernel, which the streaming schedule has overtaken at every frame size --
@@ -481,7 +455,7 @@ int begin_choose_schedule(ErScene* s, BeginStaging& B, uint32_t cus) {
 }
 
 // stage 7, ER_FLAG_WAVEFRONT (the streaming schedule's: stream_begin, er_stream_host.cpp)
-int begin_wavefront(ErScene* s, const std::vector<uint32_t>& owned, uint32_t cus, bool query_on) {
+static int begin_wavefront(ErScene* s, const std::vector<uint32_t>& owned, uint32_t cus, bool query_on) {
     int rc;
     // wavefront path state: one slot per owned pixel lane.
     // SLOT POOLS: the owned tiles are dealt round-robin to `pools` independent path pools, each with its own
@@ -547,7 +521,8 @@ int begin_wavefront(ErScene* s, const std::vector<uint32_t>& owned, uint32_t cus
 }
 
 // stage 8: the scene descriptor, on the host and on the device
-int begin_descriptor(ErScene* s, const ErGpuBvhDevice& g, const TexResult& tex, uint32_t owned_tiles) {
+static int begin_descriptor(ErScene* s, uint32_t owned_tiles) {
+    const ErGpuBvhDevice& g = s->kept.accel;
     const float lift_bound = g.lift_bound;
     float scene_scale = 0;
     for (int a = 0; a < 3; a++) scene_scale = std::max(scene_scale, std::max(std::fabs(g.lo[a]), std::fabs(g.hi[a])));
@@ -572,10 +547,10 @@ int begin_descriptor(ErScene* s, const ErGpuBvhDevice& g, const TexResult& tex, 
     D.tex_pool = s->d_tex_pool.p;
     D.mat_fused = s->d_mat_fused.p;
     D.fused_any = s->fused_any ? 1u : 0u;
-    D.hdri_tex = tex.hdri;
+    D.hdri_tex = s->kept.hdri;
     D.hdri_cdf = s->d_cdf.p;
     D.hdri_guide = s->d_guide.p;
-    D.hdri_buckets = tex.buckets;
+    D.hdri_buckets = s->kept.buckets;
     D.hdri_radiance_sum = s->hdri_radiance_sum;
     D.cam = s->camera;
     D.x_res = s->x_res;
@@ -585,7 +560,7 @@ int begin_descriptor(ErScene* s, const ErGpuBvhDevice& g, const TexResult& tex, 
     D.max_bounces = s->params.max_bounces;
     {   // power-of-two sides everywhere: texture coordinates wrap with a mask instead of a signed division (er_device.h wrap_abs)
         auto pow2 = [](int32_t v) { return v > 0 && (v & (v - 1)) == 0; };
-        bool all = pow2(tex.hdri.width) && pow2(tex.hdri.height);
+        bool all = pow2(s->kept.hdri.width) && pow2(s->kept.hdri.height);
         for (const HostTex& t : s->textures) all = all && pow2(t.width) && pow2(t.height);
         D.tex_pow2 = all ? 1u : 0u;
         if (const char* e = getenv("ER_TEX_POW2")) D.tex_pow2 = (atoi(e) != 0 && all) ? 1u : 0u;      // A/B knob: 0 = always the division
@@ -617,17 +592,19 @@ int begin_descriptor(ErScene* s, const ErGpuBvhDevice& g, const TexResult& tex, 
 }
 
 // stages 6-8 and the set-up launch: the render's own state -- planes, schedule, descriptor -- on a structure, materials and textures that
-// are in place.  The tail of er_render_begin, and all of what er_render_update runs again.  `uploads_done` (may be null) is recorded
+// are in place.  The tail of er_render_begin, and what every edit in place ends in.  `uploads_done` (may be null) is recorded
 // before the descriptor goes up.  Leaves the stream idle.
-int begin_render_state(ErScene* s, BeginStaging& B, const ErGpuBvhDevice& g, const TexResult& tex, uint32_t cus, bool query_on, hipEvent_t uploads_done) {
+int begin_render_state(ErScene* s, BeginStaging& B, hipEvent_t uploads_done) {
     int rc;
+    const uint32_t cus = s->kept.cus;
+    const bool query_on = s->query_on();
     if ((rc = begin_planes(s, B)) != ER_OK) return rc;
     if ((rc = begin_choose_schedule(s, B, cus)) != ER_OK) return rc;
     if (s->params.flags & ER_FLAG_STREAM) rc = stream_begin(s, B.owned, B.deal, cus, query_on);
     else if (s->params.flags & ER_FLAG_WAVEFRONT) rc = begin_wavefront(s, B.owned, cus, query_on);
     if (rc != ER_OK) return rc;
     if (uploads_done) HIP_TRY(hipEventRecord(uploads_done, s->stream));
-    if ((rc = begin_descriptor(s, g, tex, (uint32_t)B.owned.size())) != ER_OK) return rc;
+    if ((rc = begin_descriptor(s, (uint32_t)B.owned.size())) != ER_OK) return rc;
 
     er_launch_setup(s->dev, s->stream);
     HIP_TRY(hipGetLastError());
@@ -635,7 +612,7 @@ int begin_render_state(ErScene* s, BeginStaging& B, const ErGpuBvhDevice& g, con
     return ER_OK;
 }
 
-}  // namespace
+}  // namespace erh
 
 static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     if (!s || !p) return fail(ER_ERR_INVALID_ARG, "er_render_begin: NULL argument");
@@ -644,535 +621,23 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
     ErDeviceInfo info;
     if ((rc = begin_check(p, info)) != ER_OK) return rc;
     if ((rc = begin_open(s, p)) != ER_OK) return rc;
-    const uint32_t cus = std::max(1u, info.compute_units);
+    const char* who = "er_render_begin";
+    s->kept.cus = std::max(1u, info.compute_units);
+    s->kept.flags = p->flags;
     EventPair ev;                       // (upload time: from the tree being there to the last upload enqueued) destroyed on every return path
     HIP_TRY(hipEventCreate(&ev.a));
     HIP_TRY(hipEventCreate(&ev.b));
     BeginStaging B;                     // outlives the hipStreamSynchronize below
-    ErGpuBvhDevice g;
-    TexResult tex;
-    if ((rc = begin_accel(s, B, ev.a, g)) != ER_OK) return rc;
+    if ((rc = begin_accel(s, B, ev.a, who)) != ER_OK) return rc;
     if ((rc = begin_materials(s, B)) != ER_OK) return rc;
-    // point-light queries double the shadow records and the shadow queues of the wavefront schedule (er_wavefront.h)
-    const bool lights_on = (p->flags & ER_FLAG_POINT_LIGHTS) != 0 && !s->point_lights.empty();
-    if ((rc = begin_textures(s, B, tex)) != ER_OK) return rc;
-    if ((rc = begin_emitters(s, B, g.n8_pieces, lights_on)) != ER_OK) return rc;
-    // the point-light or the emitter query: a second shadow record per slot
-    const bool query_on = lights_on || s->light_emitters > 0;
-    s->keep_accel = g;
-    s->keep_accel.nodes = s->keep_accel.geom = s->keep_accel.attr = nullptr;      // (the scene owns the buffers)
-    s->keep_hdri = tex.hdri; s->keep_buckets = tex.buckets;
-    s->keep_cus = cus; s->keep_flags = p->flags;
-    if ((rc = begin_render_state(s, B, g, tex, cus, query_on, ev.b)) != ER_OK) return rc;
+    if ((rc = begin_textures(s, B, who)) != ER_OK) return rc;
+    if ((rc = begin_emitters(s, B, who)) != ER_OK) return rc;
+    if ((rc = begin_render_state(s, B, ev.b)) != ER_OK) return rc;
     float up_ms = 0;
     (void)hipEventElapsedTime(&up_ms, ev.a, ev.b);
 
-    accel_publish(s, g, up_ms);
+    accel_publish(s, up_ms);
     s->begun = true;
-    return ER_OK;
-}
-
-// ---- er_render_update, er_render_edit: edit a begun scene in place (include/eleven_hip.h) ----
-// The device work of either, after the host copy has been edited, is made of the pieces below and always ends in edit_restart: the
-// render's own state exactly as er_render_begin sets it up (begin_render_state, same arguments).  The caller holds the mutex, the
-// stream is idle.
-
-// moved triangles: the refit of the built structure from the host copy's arrays
-static int edit_refit(ErScene* s, bool new_normals, bool new_tangents, const char* who) {
-    ErGpuBvhDevice& g = s->keep_accel;
-    ErRefitBuffers b;
-    b.nodes = (ErNode*)s->d_nodes.p; b.node_count = (uint32_t)(g.nodes_f4 / 4); b.depth2 = g.max_depth2;
-    b.nodes8 = s->d_nodes8.p; b.node8_count = g.nodes8_count; b.depth8 = g.max_depth8;
-    b.isect = (ErTriIsect*)(s->d_nodes8.p + g.n8_pieces); b.attr = (ErTriAttr*)s->d_attr.p; b.tri_count = s->tri_count;
-    ErRefitArrays a;
-    a.vertices = s->vertices.data(); a.normals = s->normals.data(); a.write_normals = new_normals;
-    a.tangents = new_tangents ? s->tangents.data() : nullptr;
-    ErRefitResult r;
-    std::string why;
-    const int frc = er_refit_device(s->refit_topo, b, a, s->stream, &r, why);
-    if (frc != 0) return fail(frc == -2 ? ER_ERR_OOM : ER_ERR_HIP, std::string(who) + ": refit: " + why);
-    if (s->tri_count) {
-        for (int k = 0; k < 3; k++) { g.lo[k] = s->accel_lo[k] = r.lo[k]; g.hi[k] = s->accel_hi[k] = r.hi[k]; }
-        g.lift_bound = s->accel.lift_bound = r.lift_bound;
-    }
-    s->accel.builder = 2u;
-    s->accel.build_ms = s->upd.refit_ms = r.refit_ms;
-    s->accel_version++;
-    return ER_OK;
-}
-
-// er_accel_cost of the structure as it lies, measured unless this version of it has been (the stream is idle, the device set)
-static int accel_cost_locked(ErScene* s, const char* who, ErAccelCost* out) {
-    if (s->cost_version != s->accel_version) {
-        const ErGpuBvhDevice& g = s->keep_accel;
-        ErCostSums c;
-        std::string why;
-        const int crc = er_cost_device(s->d_nodes8.p, g.nodes8_count, (const ErTriIsect*)(s->d_nodes8.p + g.n8_pieces), s->tri_count, s->stream, &c, nullptr, nullptr, why);
-        if (crc != 0) return fail(crc == -2 ? ER_ERR_OOM : ER_ERR_HIP, std::string(who) + ": structure cost: " + why);
-        s->cost_kept = ErAccelCost{c.node_area, c.leaf_area, c.tri_area, c.cost, c.ms, s->accel.builder};
-        s->cost_version = s->accel_version;
-        if (s->accel.builder != 2u) { s->baseline_known = true; s->baseline_cost = c.cost; }      // a BUILT tree: what a later refit is judged against
-    }
-    *out = s->cost_kept;
-    return ER_OK;
-}
-
-// ER_REBUILD_ALWAYS / AUTO: the structure stage of er_render_begin again, on the host copy as it is now.  The scene's structure
-// buffers and the refit's level lists go first; the builder is chosen as er_render_begin chooses it, and its depth checks apply.
-static int edit_rebuild(ErScene* s, BeginStaging& B) {
-    const auto t0 = std::chrono::steady_clock::now();
-    s->refit_topo.release();
-    s->d_nodes.release(); s->d_nodes8.release(); s->d_attr.release();
-    EventPair ev;
-    HIP_TRY(hipEventCreate(&ev.a));
-    HIP_TRY(hipEventCreate(&ev.b));
-    ErGpuBvhDevice g;
-    int rc;
-    try {
-        rc = begin_accel(s, B, ev.a, g);
-    } catch (...) {
-        s->begun = false;      // (the old structure is gone: an exception on its way to guarded() must not leave a scene that renders)
-        throw;
-    }
-    if (rc != ER_OK) return rc;
-    HIP_TRY(hipEventRecord(ev.b, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    float up_ms = 0;
-    (void)hipEventElapsedTime(&up_ms, ev.a, ev.b);
-    s->keep_accel = g;
-    s->keep_accel.nodes = s->keep_accel.geom = s->keep_accel.attr = nullptr;      // (the scene owns the buffers)
-    accel_publish(s, g, up_ms);
-    s->rebuild.rebuilds++;
-    s->rebuild.rebuild_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return ER_OK;
-}
-
-// The geometry bit of er_render_update and er_render_edit, the host copy replaced: the refit, or a fresh build, by the scene's policy
-// (include/eleven_hip.h ER_REBUILD_*).  ER_REBUILD_NEVER is the refit and nothing else.
-static int edit_geometry(ErScene* s, BeginStaging& B, bool new_normals, bool new_tangents, const char* who) {
-    const uint32_t mode = s->policy.mode;
-    if (mode == ER_REBUILD_NEVER) return edit_refit(s, new_normals, new_tangents, who);
-    int rc;
-    ErRebuildInfo& R = s->rebuild;
-    R.cost_built = R.cost_refit = R.cost_after = 0.0;
-    R.cost_ms = R.rebuild_ms = 0.0f;
-    if (mode == ER_REBUILD_ALWAYS) {
-        if ((rc = edit_rebuild(s, B)) != ER_OK) return rc;
-        R.last_decision = 3u;
-        return ER_OK;
-    }
-    ErAccelCost c;
-    uint32_t decision = 4u;      // rebuilt: no baseline
-    if (!s->baseline_known && s->accel.builder != 2u) {      // the built tree, still in place: measured before it is refitted
-        if ((rc = accel_cost_locked(s, who, &c)) != ER_OK) return rc;
-        R.cost_ms += c.ms;
-    }
-    if (s->baseline_known) {
-        R.cost_built = s->baseline_cost;
-        if ((rc = edit_refit(s, new_normals, new_tangents, who)) != ER_OK) return rc;
-        if ((rc = accel_cost_locked(s, who, &c)) != ER_OK) return rc;
-        R.cost_ms += c.ms;
-        R.cost_refit = c.cost;
-        decision = (R.cost_built != 0.0 && R.cost_refit > (double)s->policy.max_cost_ratio * R.cost_built) ? 2u : 1u;
-    }
-    if (decision != 1u) {
-        if ((rc = edit_rebuild(s, B)) != ER_OK) return rc;
-        if ((rc = accel_cost_locked(s, who, &c)) != ER_OK) return rc;      // (a built tree: this is the next baseline)
-        R.cost_ms += c.ms;
-        R.cost_after = c.cost;
-    }
-    R.last_decision = decision;
-    return ER_OK;
-}
-
-// ER_FLAG_MESH_LIGHTS: the emitter table again -- it holds areas of placed triangles and the emission of their materials and textures
-static int edit_emitters(ErScene* s, BeginStaging& B, bool lights_on) {
-    s->d_light_tab.release(); s->light_emitters = 0; s->light_total = 0.0f;
-    return begin_emitters(s, B, s->keep_accel.n8_pieces, lights_on);
-}
-
-// what a fresh scene's er_render_begin would find: no adaptive state, no samples, no open timing or profile window, the streaming
-// schedule's host state and the wavefront schedule's pools as new -- then stages 6-8
-static int edit_restart(ErScene* s, BeginStaging& B, bool lights_on) {
-    s->ad_on = false;
-    s->rendered = 0;
-    s->timing_open = false;
-    s->prof_used = 0;
-    s->profile = ErProfile{};
-    for (auto& set : s->unpacked) set.clear();
-    s->st.release();
-    s->st = StreamHost{};
-    for (hipEvent_t e : s->pool_events) (void)hipEventDestroy(e);
-    s->pool_events.clear();
-    for (hipStream_t st : s->pool_streams) (void)hipStreamDestroy(st);
-    s->pool_streams.clear();
-    s->wf.clear();
-    s->params.flags = s->keep_flags;      // (the schedule is chosen again, from the same flags on the same share)
-    TexResult tex;
-    tex.hdri = s->keep_hdri; tex.buckets = s->keep_buckets;
-    const bool query_on = lights_on || s->light_emitters > 0;      // (recomputed: an edit can create the first emitter or remove the last)
-    return begin_render_state(s, B, s->keep_accel, tex, s->keep_cus, query_on, nullptr);
-}
-
-static int update_device(ErScene* s, const ErSceneUpdate* u) {
-    int rc;
-    HIP_TRY(hipSetDevice(s->device));
-    const bool lights_on = (s->keep_flags & ER_FLAG_POINT_LIGHTS) != 0 && !s->point_lights.empty();
-    BeginStaging B;                     // outlives begin_render_state's hipStreamSynchronize
-    if (u->what & ER_UPDATE_GEOMETRY) {
-        if ((rc = edit_geometry(s, B, u->normals != nullptr, u->tangents != nullptr, "er_render_update")) != ER_OK) return rc;
-        if ((rc = edit_emitters(s, B, lights_on)) != ER_OK) return rc;
-    }
-    return edit_restart(s, B, lights_on);
-}
-
-// er_render_update with the mutex held and the scene begun (er_render_edit with only the camera and geometry bits ends here too)
-static int update_locked(ErScene* s, const ErSceneUpdate* u, std::chrono::steady_clock::time_point t0) {
-    if (u->what == 0 || (u->what & ~(ER_UPDATE_CAMERA | ER_UPDATE_GEOMETRY))) return fail(ER_ERR_INVALID_ARG, "er_render_update: `what` names nothing, or something unknown");
-    const size_t n9 = (size_t)s->tri_count * 9;
-    if (u->what & ER_UPDATE_GEOMETRY) {
-        if (!u->vertices) return fail(ER_ERR_INVALID_ARG, "er_render_update: ER_UPDATE_GEOMETRY without vertices");
-        for (size_t i = 0; i < n9; i++)
-            if (!std::isfinite(u->vertices[i])) return fail(ER_ERR_INVALID_ARG, "er_render_update: vertex " + std::to_string(i / 3) + " is not finite");
-    }
-    // pending asynchronous work first (the pool streams join the scene's stream at the end of every call)
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    // the host copy, before any device work: whatever happens below, a later er_render_begin builds the edited scene
-    if (u->what & ER_UPDATE_CAMERA) s->camera = u->camera;
-    if (u->what & ER_UPDATE_GEOMETRY) {
-        s->vertices.assign(u->vertices, u->vertices + n9);
-        if (u->normals) s->normals.assign(u->normals, u->normals + n9);
-        if (u->tangents) s->tangents.assign(u->tangents, u->tangents + n9);
-    }
-    s->feat_valid = false;      // the feature planes show the scene before the edit (er_render_features makes them again)
-    for (auto& set : s->unpacked_feat) set.clear();
-    const int rc = update_device(s, u);
-    if (rc != ER_OK) {
-        s->begun = false;      // (er_render_begin releases what is left and rebuilds from the edited host copy)
-        return rc;
-    }
-    s->upd.updates++;
-    if ((u->what & ER_UPDATE_GEOMETRY) && s->accel.builder == 2u) s->upd.refits++;      // (under a rebuild policy the update may have ended in a build)
-    s->upd.update_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return ER_OK;
-}
-
-static int er_render_update_impl(ErScene* s, const ErSceneUpdate* u) {
-    if (!s || !u) return fail(ER_ERR_INVALID_ARG, "er_render_update: NULL argument");
-    const auto t0 = std::chrono::steady_clock::now();
-    std::lock_guard<std::mutex> lk(s->mtx);
-    if (!s->begun) return fail(ER_ERR_STATE, "er_render_update: er_render_begin has not succeeded");
-    return update_locked(s, u, t0);
-}
-
-static int er_update_info_impl(ErScene* s, ErUpdateInfo* out) {
-    if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_update_info: NULL argument");
-    std::lock_guard<std::mutex> lk(s->mtx);
-    *out = s->upd;
-    return ER_OK;
-}
-
-namespace {
-
-// What the checks of er_render_edit prepare, so that nothing of the scene is replaced before the last of them has passed and nothing
-// can fail between the first replacement and the last (moves and swaps only).
-struct EditWork {
-    bool rebuild_pool = false;            // the pool is laid out again and filled on the device
-    std::vector<float> vertices, normals, tangents;
-    std::vector<ErMaterial> materials;
-    std::vector<int32_t> material_id;
-    std::vector<HostTex> textures;        // the new list; kept[i]: entry i is the scene's own texture i (moved in when the copy is replaced)
-    std::vector<uint8_t> kept;
-    HostTex hdri;
-    std::vector<float> cdf;
-    float radiance_sum = 0;
-};
-
-const int32_t* texture_ids(const ErMaterial& m, int32_t out[7]) {
-    const int32_t ids[7] = {m.albedo_tex, m.emission_tex, m.roughness_tex, m.metallic_tex, m.normal_tex, m.opacity_tex, m.transmission_tex};
-    memcpy(out, ids, sizeof(ids));
-    return out;
-}
-
-// the pool work of an edit, after the host copy has been replaced; stage_ms: device time of it
-int edit_pool(ErScene* s, uint32_t what, const EditWork& W, BeginStaging& B, uint32_t& stage, float& stage_ms) {
-    int rc;
-    stage = 0;
-    stage_ms = 0;
-    if (W.rebuild_pool) {
-        TexPlan P;
-        plan_of_scene(s, P);
-        if (P.pool_floats >= (1ull << 32)) return fail(ER_ERR_INVALID_ARG, "er_render_edit: texture pool exceeds 2^32 floats");
-        std::vector<ErTexSource> src(s->textures.size());
-        for (size_t i = 0; i < src.size(); i++) src[i] = ErTexSource{s->textures[i].data.data(), s->textures[i].width, s->textures[i].height, s->textures[i].channels};
-        const ErTexSource hsrc{s->hdri_tex.data.data(), s->hdri_tex.width, s->hdri_tex.height, s->hdri_tex.channels};
-        float* pool = nullptr;
-        std::string why;
-        const int trc = er_texstage_build(P, src.data(), src.size(), s->materials.data(), s->materials.size(), hsrc, s->stream, &pool, &stage_ms, why);
-        if (trc != 0) return fail(trc == -2 ? ER_ERR_OOM : ER_ERR_HIP, "er_render_edit: texture stage: " + why);
-        s->d_tex_pool.release();      // the new pool is swapped in
-        s->d_tex_pool.p = pool;
-        s->d_tex_pool.n = (size_t)P.pool_floats;
-        s->tex_pool_cap = std::max<size_t>((size_t)P.pool_floats, 1);
-        B.table = P.table;
-        B.fused = P.fused;
-        if ((rc = upload(s->d_textures, B.table.data(), B.table.size(), s->stream)) != ER_OK) return rc;
-        if ((rc = upload(s->d_mat_fused, B.fused.data(), B.fused.size(), s->stream)) != ER_OK) return rc;
-        s->tex_mode = P.mode;
-        s->fused_any = P.fused_any;
-        s->keep_hdri = P.hdri;
-        stage = 2;
-    } else if (what & ER_EDIT_HDRI) {
-        // the HDRI's texels lie last: the tail is rewritten in place if the allocation holds the new one, else the pool grows and
-        // its head moves over by a device-to-device copy
-        const size_t head = s->keep_hdri.offset, need = head + s->hdri_tex.data.size();
-        EventPair ev;
-        HIP_TRY(hipEventCreate(&ev.a));
-        HIP_TRY(hipEventCreate(&ev.b));
-        HIP_TRY(hipEventRecord(ev.a, s->stream));
-        if (need > s->tex_pool_cap) {
-            DevBuf<float> bigger;
-            if ((rc = upload(bigger, nullptr, need, s->stream)) != ER_OK) return rc;
-            hipError_t ce = head ? hipMemcpyAsync(bigger.p, s->d_tex_pool.p, head * sizeof(float), hipMemcpyDeviceToDevice, s->stream) : hipSuccess;
-            if (ce == hipSuccess) ce = hipStreamSynchronize(s->stream);
-            if (ce != hipSuccess) {
-                bigger.release();
-                HIP_TRY(ce);
-            }
-            s->d_tex_pool.release();
-            s->d_tex_pool = bigger;
-            s->tex_pool_cap = std::max<size_t>(need, 1);
-        }
-        if (!s->hdri_tex.data.empty())
-            HIP_TRY(hipMemcpyAsync(s->d_tex_pool.p + head, s->hdri_tex.data.data(), s->hdri_tex.data.size() * sizeof(float), hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(hipEventRecord(ev.b, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        (void)hipEventElapsedTime(&stage_ms, ev.a, ev.b);
-        s->d_tex_pool.n = need;
-        s->keep_hdri = DevTex{s->hdri_tex.width, s->hdri_tex.height, s->hdri_tex.channels, s->hdri_tex.filter, (uint32_t)head};
-        stage = 1;
-    }
-    if (what & ER_EDIT_HDRI) {
-        if ((rc = upload(s->d_cdf, s->hdri_cdf.data(), s->hdri_cdf.size(), s->stream)) != ER_OK) return rc;
-        s->keep_buckets = er_build_cdf_guide(s->hdri_cdf.data(), s->hdri_tex.width * s->hdri_tex.height, B.guide);
-        if ((rc = upload(s->d_guide, B.guide.data(), B.guide.size(), s->stream)) != ER_OK) return rc;
-    }
-    return ER_OK;
-}
-
-// The device work of er_render_edit, the host copy replaced (section "The stages of an edit")
-int edit_device(ErScene* s, const ErSceneEdit* e, const EditWork& W, uint32_t& stage, float& stage_ms) {
-    int rc;
-    const uint32_t what = e->what;
-    const bool lights_on = (s->keep_flags & ER_FLAG_POINT_LIGHTS) != 0 && !s->point_lights.empty();
-    BeginStaging B;                     // outlives begin_render_state's hipStreamSynchronize
-    if (what & ER_EDIT_GEOMETRY)
-        if ((rc = edit_geometry(s, B, e->normals != nullptr, e->tangents != nullptr, "er_render_edit")) != ER_OK) return rc;
-    if (what & ER_EDIT_MATERIALS) {
-        if ((rc = upload_materials(s, B)) != ER_OK) return rc;
-        if (e->material_id && s->tri_count) {
-            ScopedDevBuf<int32_t> d_ids;
-            if ((rc = upload(d_ids, s->material_id.data(), s->material_id.size(), s->stream)) != ER_OK) return rc;
-            er_launch_material_ids(s->d_nodes8.p + s->keep_accel.n8_pieces, s->d_attr.p, s->tri_count, d_ids.p, s->stream);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(s->stream));      // (d_ids goes with this block)
-        }
-    }
-    if ((rc = edit_pool(s, what, W, B, stage, stage_ms)) != ER_OK) return rc;
-    if (what & (ER_EDIT_GEOMETRY | ER_EDIT_MATERIALS | ER_EDIT_TEXTURES))
-        if ((rc = edit_emitters(s, B, lights_on)) != ER_OK) return rc;
-    return edit_restart(s, B, lights_on);
-}
-
-}  // namespace
-
-static int er_render_edit_impl(ErScene* s, const ErSceneEdit* e) {
-    if (!s || !e) return fail(ER_ERR_INVALID_ARG, "er_render_edit: NULL argument");
-    const auto t0 = std::chrono::steady_clock::now();
-    std::lock_guard<std::mutex> lk(s->mtx);
-    if (!s->begun) return fail(ER_ERR_STATE, "er_render_edit: er_render_begin has not succeeded");
-    const uint32_t what = e->what, all = ER_EDIT_CAMERA | ER_EDIT_GEOMETRY | ER_EDIT_MATERIALS | ER_EDIT_TEXTURES | ER_EDIT_HDRI;
-    if (what == 0 || (what & ~all)) return fail(ER_ERR_INVALID_ARG, "er_render_edit: `what` names nothing, or something unknown");
-    if (!(what & (ER_EDIT_MATERIALS | ER_EDIT_TEXTURES | ER_EDIT_HDRI))) {      // this is er_render_update
-        ErSceneUpdate u{};
-        u.what = what; u.camera = e->camera; u.vertices = e->vertices; u.normals = e->normals; u.tangents = e->tangents;
-        return update_locked(s, &u, t0);
-    }
-    // ---- the checks: nothing of the scene is touched before the last one has passed ----
-    const size_t n = s->tri_count, n9 = n * 9;
-    if (what & ER_EDIT_GEOMETRY) {
-        if (!e->vertices) return fail(ER_ERR_INVALID_ARG, "er_render_edit: ER_EDIT_GEOMETRY without vertices");
-        for (size_t i = 0; i < n9; i++)
-            if (!std::isfinite(e->vertices[i])) return fail(ER_ERR_INVALID_ARG, "er_render_edit: vertex " + std::to_string(i / 3) + " is not finite");
-    }
-    const size_t old_ntex = s->textures.size();
-    size_t ntex = old_ntex;
-    if (what & ER_EDIT_TEXTURES) {
-        ntex = e->texture_count;
-        if (ntex < old_ntex) return fail(ER_ERR_INVALID_ARG, "er_render_edit: texture_count is below the scene's (textures are replaced or appended, never removed)");
-        if (ntex && !e->textures) return fail(ER_ERR_INVALID_ARG, "er_render_edit: ER_EDIT_TEXTURES without the texture list");
-        for (size_t i = 0; i < ntex; i++) {
-            const ErTexture& t = e->textures[i];
-            if (!t.data) {
-                if (i >= old_ntex) return fail(ER_ERR_INVALID_ARG, "er_render_edit: texture " + std::to_string(i) + " has no data and the scene has no such texture to keep");
-                continue;
-            }
-            const int rc = check_tex(t, "scene texture");
-            if (rc != ER_OK) return rc;
-        }
-    }
-    const ErMaterial* mats = s->materials.data();
-    size_t nmat = s->materials.size();
-    bool ids_differ = false;
-    if (what & ER_EDIT_MATERIALS) {
-        if (e->material_count == 0 || !e->materials) return fail(ER_ERR_INVALID_ARG, "er_render_edit: ER_EDIT_MATERIALS needs at least one material");
-        mats = e->materials;
-        nmat = e->material_count;
-        ids_differ = nmat != s->materials.size();
-        for (size_t m = 0; m < nmat; m++) {
-            int32_t a[7], b[7];
-            texture_ids(mats[m], a);
-            for (int32_t id : a)
-                if (id >= (int32_t)ntex) return fail(ER_ERR_INVALID_ARG, "er_render_edit: texture id out of range");      // (er_scene_create's rule)
-            if (!ids_differ) {
-                texture_ids(s->materials[m], b);
-                ids_differ = memcmp(a, b, sizeof(a)) != 0;
-            }
-        }
-        const int32_t* mid = e->material_id ? e->material_id : s->material_id.data();
-        for (size_t i = 0; i < n; i++)
-            if (mid[i] < 0 || (uint32_t)mid[i] >= nmat) return fail(ER_ERR_INVALID_ARG, "er_render_edit: material_id out of range");      // (the same)
-    }
-    if (what & ER_EDIT_HDRI) {
-        const int rc = check_tex(e->hdri.texture, "hdri");
-        if (rc != ER_OK) return rc;
-    }
-    EditWork W;
-    W.rebuild_pool = (what & ER_EDIT_TEXTURES) != 0 || ids_differ;
-    {   // the pool the edited scene needs, from the plan, before anything is replaced
-        const TexDecl hd = (what & ER_EDIT_HDRI) ? TexDecl{e->hdri.texture.width, e->hdri.texture.height, e->hdri.texture.channels, e->hdri.texture.filter}
-                                                 : TexDecl{s->hdri_tex.width, s->hdri_tex.height, s->hdri_tex.channels, s->hdri_tex.filter};
-        uint64_t pool_floats = 0;
-        if (W.rebuild_pool) {
-            std::vector<TexDecl> decl(ntex);
-            for (size_t i = 0; i < ntex; i++) {
-                const bool keep = !(what & ER_EDIT_TEXTURES) || !e->textures[i].data;
-                decl[i] = keep ? TexDecl{s->textures[i].width, s->textures[i].height, s->textures[i].channels, s->textures[i].filter}
-                               : TexDecl{e->textures[i].width, e->textures[i].height, e->textures[i].channels, e->textures[i].filter};
-            }
-            TexPlan P;
-            er_texture_plan(decl.data(), ntex, mats, nmat, hd, P);
-            pool_floats = P.pool_floats;
-        } else if (what & ER_EDIT_HDRI) {
-            pool_floats = (uint64_t)s->keep_hdri.offset + (uint64_t)hd.width * (uint64_t)hd.height * (uint64_t)hd.channels;
-        }
-        if (pool_floats >= (1ull << 32)) return fail(ER_ERR_INVALID_ARG, "er_render_edit: texture pool exceeds 2^32 floats");
-    }
-    // ---- the new host copy, beside the scene's (an allocation that fails here leaves the scene as it was) ----
-    if (what & ER_EDIT_GEOMETRY) {
-        W.vertices.assign(e->vertices, e->vertices + n9);
-        if (e->normals) W.normals.assign(e->normals, e->normals + n9);
-        if (e->tangents) W.tangents.assign(e->tangents, e->tangents + n9);
-    }
-    if (what & ER_EDIT_MATERIALS) {
-        W.materials.assign(e->materials, e->materials + e->material_count);
-        if (e->material_id) W.material_id.assign(e->material_id, e->material_id + n);
-    }
-    if (what & ER_EDIT_TEXTURES) {
-        W.textures.resize(ntex);
-        W.kept.assign(ntex, 0);
-        for (size_t i = 0; i < ntex; i++) {
-            if (!e->textures[i].data) { W.kept[i] = 1; continue; }
-            const int rc = copy_tex(e->textures[i], W.textures[i], "scene texture");
-            if (rc != ER_OK) return rc;
-        }
-    }
-    if (what & ER_EDIT_HDRI) {
-        const int rc = copy_tex(e->hdri.texture, W.hdri, "hdri");
-        if (rc != ER_OK) return rc;
-        if (e->hdri.cdf) {
-            W.cdf.assign(e->hdri.cdf, e->hdri.cdf + (size_t)W.hdri.width * W.hdri.height + 1);
-            W.radiance_sum = e->hdri.radiance_sum;
-        } else {
-            host_generate_cdf(W.hdri, W.cdf, W.radiance_sum);
-        }
-    }
-    // pending asynchronous work first (the pool streams join the scene's stream at the end of every call)
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    // ---- the host copy is replaced, before any device work: whatever happens below, a later er_render_begin builds the edited scene ----
-    if (what & ER_EDIT_CAMERA) s->camera = e->camera;
-    if (what & ER_EDIT_GEOMETRY) {
-        s->vertices.swap(W.vertices);
-        if (e->normals) s->normals.swap(W.normals);
-        if (e->tangents) s->tangents.swap(W.tangents);
-    }
-    if (what & ER_EDIT_MATERIALS) {
-        s->materials.swap(W.materials);
-        if (e->material_id) s->material_id.swap(W.material_id);
-    }
-    if (what & ER_EDIT_TEXTURES) {
-        for (size_t i = 0; i < ntex; i++)
-            if (W.kept[i]) std::swap(W.textures[i], s->textures[i]);
-        s->textures.swap(W.textures);
-    }
-    if (what & ER_EDIT_HDRI) {
-        std::swap(s->hdri_tex, W.hdri);
-        s->hdri_cdf.swap(W.cdf);
-        s->hdri_radiance_sum = W.radiance_sum;
-    }
-    s->feat_valid = false;      // the feature planes show the scene before the edit (er_render_features makes them again)
-    for (auto& set : s->unpacked_feat) set.clear();
-    uint32_t stage = 0;
-    float stage_ms = 0;
-    const int rc = edit_device(s, e, W, stage, stage_ms);
-    if (rc != ER_OK) {
-        s->begun = false;      // (er_render_begin releases what is left and rebuilds from the edited host copy)
-        return rc;
-    }
-    s->upd.updates++;
-    if ((what & ER_EDIT_GEOMETRY) && s->accel.builder == 2u) s->upd.refits++;
-    s->edit.edits++;
-    s->edit.texture_stage = stage;
-    s->edit.texture_stage_ms = stage_ms;
-    s->edit.pool_floats = s->d_tex_pool.n;
-    s->edit.edit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return ER_OK;
-}
-
-static int er_accel_cost_impl(ErScene* s, ErAccelCost* out) {
-    if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_accel_cost: NULL argument");
-    std::lock_guard<std::mutex> lk(s->mtx);
-    if (!s->begun) return fail(ER_ERR_STATE, "er_accel_cost: er_render_begin has not succeeded");
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));      // pending asynchronous work first
-    return accel_cost_locked(s, "er_accel_cost", out);
-}
-
-static int er_update_policy_set_impl(ErScene* s, const ErUpdatePolicy* p) {
-    if (!s || !p) return fail(ER_ERR_INVALID_ARG, "er_update_policy_set: NULL argument");
-    if (p->mode > ER_REBUILD_AUTO) return fail(ER_ERR_INVALID_ARG, "er_update_policy_set: unknown mode");
-    if (p->mode == ER_REBUILD_AUTO && !(std::isfinite(p->max_cost_ratio) && p->max_cost_ratio >= 1.0f))
-        return fail(ER_ERR_INVALID_ARG, "er_update_policy_set: ER_REBUILD_AUTO needs a finite max_cost_ratio >= 1");
-    std::lock_guard<std::mutex> lk(s->mtx);
-    s->policy = *p;
-    return ER_OK;
-}
-
-static int er_rebuild_info_impl(ErScene* s, ErRebuildInfo* out) {
-    if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_rebuild_info: NULL argument");
-    std::lock_guard<std::mutex> lk(s->mtx);
-    *out = s->rebuild;
-    out->mode = s->policy.mode;
-    out->max_cost_ratio = s->policy.max_cost_ratio;
-    return ER_OK;
-}
-
-static int er_edit_info_impl(ErScene* s, ErEditInfo* out) {
-    if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_edit_info: NULL argument");
-    std::lock_guard<std::mutex> lk(s->mtx);
-    *out = s->edit;
     return ER_OK;
 }
 
@@ -1730,7 +1195,6 @@ static int er_read_tile_state_impl(ErScene* s, float* error, uint32_t* samples) 
     }
     return ER_OK;
 }
-}  // extern "C"
 
 // ---- the exported entry points: every body above runs inside guarded() (no exception crosses the C ABI) ----
 extern "C" {
@@ -1758,12 +1222,5 @@ int er_accel_info(ErScene* s, ErAccelInfo* out) { return guarded("er_accel_info"
 int er_adaptive_set(ErScene* s, const ErAdaptiveParams* p) { return guarded("er_adaptive_set", [&]() -> int { return er_adaptive_set_impl(s, p); }); }
 int er_adaptive_info(ErScene* s, ErAdaptiveInfo* out) { return guarded("er_adaptive_info", [&]() -> int { return er_adaptive_info_impl(s, out); }); }
 int er_light_info(ErScene* s, ErLightInfo* out) { return guarded("er_light_info", [&]() -> int { return er_light_info_impl(s, out); }); }
-int er_render_update(ErScene* s, const ErSceneUpdate* u) { return guarded("er_render_update", [&]() -> int { return er_render_update_impl(s, u); }); }
-int er_update_info(ErScene* s, ErUpdateInfo* out) { return guarded("er_update_info", [&]() -> int { return er_update_info_impl(s, out); }); }
-int er_render_edit(ErScene* s, const ErSceneEdit* e) { return guarded("er_render_edit", [&]() -> int { return er_render_edit_impl(s, e); }); }
-int er_edit_info(ErScene* s, ErEditInfo* out) { return guarded("er_edit_info", [&]() -> int { return er_edit_info_impl(s, out); }); }
-int er_accel_cost(ErScene* s, ErAccelCost* out) { return guarded("er_accel_cost", [&]() -> int { return er_accel_cost_impl(s, out); }); }
-int er_update_policy_set(ErScene* s, const ErUpdatePolicy* p) { return guarded("er_update_policy_set", [&]() -> int { return er_update_policy_set_impl(s, p); }); }
-int er_rebuild_info(ErScene* s, ErRebuildInfo* out) { return guarded("er_rebuild_info", [&]() -> int { return er_rebuild_info_impl(s, out); }); }
 int er_read_tile_state(ErScene* s, float* error, uint32_t* samples) { return guarded("er_read_tile_state", [&]() -> int { return er_read_tile_state_impl(s, error, samples); }); }
 }  // extern "C"

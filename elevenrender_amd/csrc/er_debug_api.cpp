@@ -218,7 +218,7 @@ static int er_debug_accel_cost_terms_impl(ErScene* s, ErCostSumsDebug* sums, dou
     if (!s || !sums) return fail(ER_ERR_INVALID_ARG, "er_debug_accel_cost_terms: NULL argument");
     std::lock_guard<std::mutex> lk(s->mtx);
     if (!s->begun) return fail(ER_ERR_STATE, "er_debug_accel_cost_terms: er_render_begin has not succeeded");
-    const ErGpuBvhDevice& g = s->keep_accel;
+    const ErGpuBvhDevice& g = s->kept.accel;
     if ((node_terms && node_cap < (uint64_t)g.nodes8_count * 16) || (tri_terms && tri_cap < (uint64_t)s->tri_count * 4))
         return fail(ER_ERR_INVALID_ARG, "er_debug_accel_cost_terms: a buffer is smaller than its array");
     HIP_TRY(hipSetDevice(s->device));

@@ -215,7 +215,7 @@ int features_impl(ErScene* s, uint32_t n) {
     HIP_TRY(hipStreamSynchronize(s->stream));      // pending asynchronous work first
     int rc;
     const size_t npx = (size_t)s->x_res * s->y_res;
-    const uint32_t blocks = std::max(1u, s->keep_cus) * ER_FEATURE_BLOCKS_PER_CU;
+    const uint32_t blocks = std::max(1u, s->kept.cus) * ER_FEATURE_BLOCKS_PER_CU;
     s->feat_valid = false;
     for (auto& u : s->unpacked_feat) u.clear();      // other ranks' pixels gathered earlier are overwritten below
     if (s->d_feat.n < 2 * npx && (rc = upload(s->d_feat, nullptr, 2 * npx, s->stream)) != ER_OK) return rc;

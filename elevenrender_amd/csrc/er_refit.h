@@ -1,4 +1,4 @@
-// er_refit.h -- device refit of a built acceleration structure after its triangles moved (er_refit.hip; er_render_update, er_api.cpp).
+// er_refit.h -- device refit of a built acceleration structure after its triangles moved (er_refit.hip; er_render_update, er_api_edit.cpp).
 // The topology stays -- child references, slot assignment, triangle order --; the triangle records, every box of the binary tree and
 // every wide node's origin, exponents and quantised child boxes are recomputed from the new arrays, bottom-up, one launch per tree level.
 #pragma once

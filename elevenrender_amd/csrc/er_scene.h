@@ -1,5 +1,5 @@
 // er_scene.h -- host-side state behind the opaque ErScene handle of include/eleven_hip.h, and the small helpers the
-// translation units of the boundary share (er_api.cpp: the drop-in entry points; er_stream_host.cpp: the streaming schedule's host
+// translation units of the boundary share (er_api.cpp: the drop-in entry points; er_api_edit.cpp: the in-place edits; er_stream_host.cpp: the streaming schedule's host
 // side; er_debug_api.cpp: inspection hooks of include/eleven_hip_debug.h; er_collective.cpp: the RCCL framebuffer combine).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -159,17 +159,21 @@ struct ErScene {
     ErAccelInfo accel{};
     float accel_lo[3] = {0, 0, 0}, accel_hi[3] = {0, 0, 0};   // scene bounds as the builder reported them (er_debug_read_accel)
     uint32_t accel_depth2 = 0;                                 // levels of the binary tree (the same hook)
-    // What er_render_update needs of the last er_render_begin to restart a render without running its stages again (er_api.cpp): the
-    // structure's counts, depths, bounds and lift bound (the three pointers are null: the scene owns the buffers), the texture stage's
-    // result, the device's CUs, the flags as the caller gave them (params.flags holds the schedule that was chosen)
-    ErGpuBvhDevice keep_accel;
-    DevTex keep_hdri{};
-    int keep_buckets = 0;
-    uint32_t keep_cus = 0, keep_flags = 0;
+    // What a restart in place (er_render_update, er_render_edit: er_api_edit.cpp) needs of the stages it does not run again.  Each value
+    // is written once, by the stage that produces it, and read by begin_render_state and begin_descriptor (er_api.cpp), whoever calls
+    // them: the structure's counts, depths, bounds and lift bound (begin_accel; a refit replaces bounds and lift bound), the HDRI's
+    // table entry and the buckets of its search guide (begin_textures; the pool stage of an edit), the device's CUs and the flags as
+    // the caller gave them (er_render_begin; params.flags holds the schedule that was chosen).
+    struct Kept {
+        ErGpuBvhDevice accel;      // (its three pointers are null: the scene owns the buffers)
+        DevTex hdri{};
+        int buckets = 0;
+        uint32_t cus = 0, flags = 0;
+    } kept;
     ErRefitTopo refit_topo;      // the trees' nodes by level, from the first refit after an er_render_begin until the next one
     ErUpdateInfo upd{};          // er_update_info (counts since er_scene_create)
     ErEditInfo edit{};           // er_edit_info (the same)
-    // er_accel_cost / er_update_policy_set (er_api.cpp): every build and every refit bumps accel_version; the cost last measured is kept
+    // er_accel_cost / er_update_policy_set (er_api_edit.cpp): every build and every refit bumps accel_version; the cost last measured is kept
     // with the version it was measured at.  The baseline of ER_REBUILD_AUTO is the cost of the last BUILT tree: known once such a tree
     // has been measured, forgotten with the next build.
     uint64_t accel_version = 0, cost_version = ~0ull;
@@ -246,6 +250,11 @@ struct ErScene {
 
     uint32_t tiles_x() const { return (x_res + ER_TILE - 1) / ER_TILE; }      // the frame in tiles of ER_TILE x ER_TILE pixels
     uint32_t tiles_y() const { return (y_res + ER_TILE - 1) / ER_TILE; }
+    // point-light queries are on (they double the shadow records and the shadow queues of the wavefront schedule, er_wavefront.h) ...
+    bool lights_on() const { return (kept.flags & ER_FLAG_POINT_LIGHTS) != 0 && !point_lights.empty(); }
+    // ... and so is the second shadow record per slot: the point-light or the emitter query (after the emitter stage: an edit can create
+    // the first emitter or remove the last)
+    bool query_on() const { return lights_on() || light_emitters > 0; }
     std::vector<uint32_t> tiles_of(uint32_t rank, uint32_t world) const {
         std::vector<uint32_t> t;
         const uint32_t nx = tiles_x(), ny = tiles_y();
@@ -319,6 +328,28 @@ int upload(DevBuf<T>& b, const void* src, size_t count, hipStream_t s) {
     HIP_TRY(hipMalloc((void**)&b.p, bytes));
     b.n = count;
     if (count && src) HIP_TRY(hipMemcpyAsync(b.p, src, count * sizeof(T), hipMemcpyHostToDevice, s));
+    return ER_OK;
+}
+
+// The two range rules of a scene's lists, for er_scene_create and for the lists an edit would leave (er_api_edit.cpp).
+inline void texture_ids(const ErMaterial& m, int32_t out[7]) {
+    const int32_t ids[7] = {m.albedo_tex, m.emission_tex, m.roughness_tex, m.metallic_tex, m.normal_tex, m.opacity_tex, m.transmission_tex};
+    memcpy(out, ids, sizeof(ids));
+}
+// every texture id of every material is below `ntex` (a negative id means "no texture")
+inline int check_texture_ids(const ErMaterial* mats, size_t nmat, size_t ntex, const char* who) {
+    for (size_t m = 0; m < nmat; m++) {
+        int32_t ids[7];
+        texture_ids(mats[m], ids);
+        for (int32_t id : ids)
+            if (id >= (int32_t)ntex) return fail(ER_ERR_INVALID_ARG, std::string(who) + ": texture id out of range");
+    }
+    return ER_OK;
+}
+// every triangle's material id names one of `nmat` materials
+inline int check_material_ids(const int32_t* ids, size_t n, size_t nmat, const char* who) {
+    for (size_t i = 0; i < n; i++)
+        if (ids[i] < 0 || (uint32_t)ids[i] >= nmat) return fail(ER_ERR_INVALID_ARG, std::string(who) + ": material_id out of range");
     return ER_OK;
 }
 

@@ -1,6 +1,6 @@
 // er_texplan.h -- the texture plan: every layout decision of the texture pool, made once, on the host, from the sizes alone.
 // er_render_begin fills the pool on the host by this plan (er_api.cpp begin_textures), er_render_edit fills it on the device
-// (er_texstage.hip); both read the one plan, so the two layouts can not drift, and tests/test_gpu_edit.py compares the bytes.
+// (er_texstage.hip, from er_api_edit.cpp edit_pool); both read the one plan, so the two layouts can not drift, and tests/test_gpu_edit.py compares the bytes.
 // The plan never reads a texel.
 #pragma once
 #include <stdint.h>

@@ -1,4 +1,4 @@
-// er_texstage.h -- the texture stage on the device (er_texstage.hip; er_render_edit, er_api.cpp): the pool of a texture plan
+// er_texstage.h -- the texture stage on the device (er_texstage.hip; er_render_edit, er_api_edit.cpp): the pool of a texture plan
 // (er_texplan.h) filled by copies and kernels instead of by the host loops of er_render_begin.  Same layout, same bytes.
 #pragma once
 #include <hip/hip_runtime_api.h>

@@ -112,25 +112,31 @@ class RenderingManager:
         abi.check(self.lib.er_samples_done(self.handle, C.byref(v)))
         return RenderInfo(samples=v.value)
 
-    def update(self, camera=None, vertices=None, normals=None, tangents=None):
-        """er_render_update: a new camera (abi.ErCamera) and / or moved triangles ([n][3][3] float32 vertices; normals and tangents
-        optional, None = keep) for the begun scene, without a rebuild; the render starts over at sample 0.  self.scene is not changed:
-        a caller that wants to compare against a fresh start builds the edited SceneData itself."""
-        u = abi.ErSceneUpdate()
+    def _camera_and_geometry(self, call, who, camera, vertices, normals, tangents):
+        """the first two bits of an abi.ErSceneUpdate or abi.ErSceneEdit (the same bits, the same fields) filled in; returns the arrays
+        its pointers point into"""
         keep = []
         if camera is not None:
-            u.what |= abi.UPDATE_CAMERA
-            u.camera = camera
+            call.what |= abi.UPDATE_CAMERA
+            call.camera = camera
         if vertices is not None or normals is not None or tangents is not None:
-            u.what |= abi.UPDATE_GEOMETRY
+            call.what |= abi.UPDATE_GEOMETRY
             for name, a in (("vertices", vertices), ("normals", normals), ("tangents", tangents)):
                 if a is None:
                     continue
                 a = np.ascontiguousarray(a, np.float32)
                 if a.size != self.scene.tri_count * 9:
-                    raise ValueError(f"update: {name} has {a.size} floats, the scene has {self.scene.tri_count} triangles")
+                    raise ValueError(f"{who}: {name} has {a.size} floats, the scene has {self.scene.tri_count} triangles")
                 keep.append(a)
-                setattr(u, name, a.ctypes.data_as(C.POINTER(C.c_float)))
+                setattr(call, name, a.ctypes.data_as(C.POINTER(C.c_float)))
+        return keep
+
+    def update(self, camera=None, vertices=None, normals=None, tangents=None):
+        """er_render_update: a new camera (abi.ErCamera) and / or moved triangles ([n][3][3] float32 vertices; normals and tangents
+        optional, None = keep) for the begun scene, without a rebuild; the render starts over at sample 0.  self.scene is not changed:
+        a caller that wants to compare against a fresh start builds the edited SceneData itself."""
+        u = abi.ErSceneUpdate()
+        keep = self._camera_and_geometry(u, "update", camera, vertices, normals, tangents)      # (alive until the call returns)
         abi.check(self.lib.er_render_update(self.handle, C.byref(u)))
 
     def update_info(self):
@@ -145,21 +151,8 @@ class RenderingManager:
         entry = keep that texture) and `hdri` (such a tuple; hdri_cdf / hdri_radiance_sum as in SceneData, None = built by the
         library).  The render starts over at sample 0.  self.scene is not changed."""
         e = abi.ErSceneEdit()
-        keep = []
+        keep = self._camera_and_geometry(e, "edit", camera, vertices, normals, tangents)
         fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
-        if camera is not None:
-            e.what |= abi.EDIT_CAMERA
-            e.camera = camera
-        if vertices is not None or normals is not None or tangents is not None:
-            e.what |= abi.EDIT_GEOMETRY
-            for name, a in (("vertices", vertices), ("normals", normals), ("tangents", tangents)):
-                if a is None:
-                    continue
-                a = np.ascontiguousarray(a, np.float32)
-                if a.size != self.scene.tri_count * 9:
-                    raise ValueError(f"edit: {name} has {a.size} floats, the scene has {self.scene.tri_count} triangles")
-                keep.append(a)
-                setattr(e, name, fp(a))
         if materials is not None or material_id is not None:
             if materials is None:
                 raise ValueError("edit: material_id comes with the material list")

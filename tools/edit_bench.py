@@ -8,6 +8,7 @@ On the scenes of BASELINE configs C5 (scenes.torture(): 1 M triangles, 64 materi
   c  one texture replaced by new texels of the same size                                          [C5]
   d  a new HDRI of the same size
   e  a new HDRI of twice the size (the first round grows the pool's allocation, the later ones find it large enough)
+  f  all bits in one call: the camera, every vertex (+ (40, -3, 7)), a's constants, c's texture [C5], d's HDRI
 Per round, alternated on one box: the edit (wall time of er_render_edit, and ErEditInfo.texture_stage / texture_stage_ms), then
 er_render_begin again on the same begun scene (wall), then er_scene_create + er_render_begin of the edited description (wall).  Every
 round's edit is a real change (the rounds go back and forth between two values).  Medians over --rounds rounds at the end.
@@ -48,9 +49,13 @@ def begin_again(rm, max_bounces):
     return (time.perf_counter() - t0) * 1e3
 
 
-def with_changes(sc, materials=None, textures=None, hdri=None):
+def with_changes(sc, materials=None, textures=None, hdri=None, vertices=None, camera=None):
     out = copy.copy(sc)
     out._desc = None
+    if vertices is not None:
+        out.vertices = vertices
+    if camera is not None:
+        out.camera = camera
     if materials is not None:
         out.materials = materials
     if textures is not None:
@@ -92,6 +97,16 @@ def edits_of(sc, textured):
     big = scenes.sky_hdri(2 * w, 2 * h) if w > 1 else (np.full((2, 2, 3), 0.4, np.float32), 2, 2, 3, 0)
     big = (abi._f32(big[0]),) + tuple(big[1:])
     out["e hdri, twice the size"] = ((dict(hdri=big), with_changes(sc, hdri=big)), None)      # (B: back to the scene's own, not measured)
+    shift = np.array([40.0, -3.0, 7.0], np.float32)
+    moved = np.ascontiguousarray((sc.vertices.reshape(-1, 3, 3) + shift).reshape(sc.vertices.shape))
+    cam = abi.ErCamera.from_buffer_copy(sc.camera)
+    cam.position = abi.ErVec3(sc.camera.position.x + 40.0, sc.camera.position.y - 3.0, sc.camera.position.z + 7.0)
+    fa = dict(camera=cam, vertices=moved, materials=ma, hdri=same)
+    fb = dict(camera=sc.camera, vertices=sc.vertices, materials=mb, hdri=sc.hdri)
+    if textured:
+        fa["textures"], fb["textures"] = ta, tb
+    out["f all bits"] = ((fa, with_changes(sc, ma, full if textured else None, same, moved, cam)),
+                         (fb, with_changes(sc, mb, list(sc.textures) if textured else None, sc.hdri)))
     return out
 
 
@@ -102,7 +117,7 @@ def bench(name, sc, max_bounces, rounds, textured):
     rm.render(2)
     summary = []
     for tag, (A, B) in edits_of(sc, textured).items():
-        ew, es, bw, fw = [], [], [], []
+        ew, em, es, bw, fw = [], [], [], [], []
         for k in range(rounds):
             args, desc = A if (k % 2 == 0 or B is None) else B
             rm.render(1)
@@ -119,12 +134,12 @@ def bench(name, sc, max_bounces, rounds, textured):
                 rm.edit(hdri=sc.hdri)             # back, for the next round
             say(f"   {tag:24s} round {k}: er_render_edit {e:9.3f} ms wall (edit_ms {info['edit_ms']:.3f}, texture_stage {info['texture_stage']}, texture_stage_ms {info['texture_stage_ms']:.3f},"
                 f" pool {info['pool_floats'] * 4 / 1e6:.1f} MB)   er_render_begin again {b:8.2f} ms   create + begin {f:8.2f} ms")
-            ew.append(e); es.append(info["texture_stage_ms"]); bw.append(b); fw.append(f)
-        summary.append((tag, np.median(ew), np.median(es), np.median(bw), np.median(fw)))
+            ew.append(e); em.append(info["edit_ms"]); es.append(info["texture_stage_ms"]); bw.append(b); fw.append(f)
+        summary.append((tag, np.median(ew), np.median(em), min(em), max(em), np.median(es), np.median(bw), np.median(fw)))
     rm.close()
-    say(f"   medians of {rounds} rounds, ms:   edit wall   texture_stage_ms   er_render_begin again   create + begin")
-    for tag, e, s, b, f in summary:
-        say(f"   {name} {tag:24s} {e:10.3f} {s:18.3f} {b:24.2f} {f:16.2f}")
+    say(f"   medians of {rounds} rounds, ms:   edit wall   edit_ms (min .. max)   texture_stage_ms   er_render_begin again   create + begin")
+    for tag, e, m, lo, hi, s, b, f in summary:
+        say(f"   {name} {tag:24s} {e:10.3f} {m:9.3f} ({lo:.3f} .. {hi:.3f}) {s:18.3f} {b:24.2f} {f:16.2f}")
 
 
 def main():
