@@ -124,6 +124,16 @@ class ErUpdateInfo(C.Structure):
     _fields_ = [("updates", C.c_uint32), ("refits", C.c_uint32), ("refit_ms", C.c_float), ("update_ms", C.c_float)]
 
 
+class ErSparseUpdate(C.Structure):
+    _fields_ = [("what", C.c_uint32), ("camera", ErCamera), ("count", C.c_uint32), ("tri_ids", C.POINTER(C.c_uint32)), ("vertices", C.POINTER(C.c_float)),
+                ("normals", C.POINTER(C.c_float)), ("tangents", C.POINTER(C.c_float))]
+
+
+class ErSparseInfo(C.Structure):
+    _fields_ = [("calls", C.c_uint32), ("path", C.c_uint32), ("why_full", C.c_uint32), ("moved", C.c_uint32), ("dirty_nodes2", C.c_uint32),
+                ("dirty_nodes8", C.c_uint32), ("bytes_uploaded", C.c_uint64), ("refit_ms", C.c_float)]
+
+
 class ErSceneEdit(C.Structure):
     _fields_ = [("what", C.c_uint32), ("camera", ErCamera), ("vertices", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)),
                 ("tangents", C.POINTER(C.c_float)), ("material_count", C.c_uint32), ("materials", C.POINTER(ErMaterial)),
@@ -315,6 +325,8 @@ SYMBOLS = {
     "er_accel_info": (C.c_int, [_P, C.POINTER(ErAccelInfo)]),
     "er_render_update": (C.c_int, [_P, C.POINTER(ErSceneUpdate)]),
     "er_update_info": (C.c_int, [_P, C.POINTER(ErUpdateInfo)]),
+    "er_render_update_sparse": (C.c_int, [_P, C.POINTER(ErSparseUpdate)]),
+    "er_sparse_info": (C.c_int, [_P, C.POINTER(ErSparseInfo)]),
     "er_render_edit": (C.c_int, [_P, C.POINTER(ErSceneEdit)]),
     "er_edit_info": (C.c_int, [_P, C.POINTER(ErEditInfo)]),
     "er_accel_cost": (C.c_int, [_P, C.POINTER(ErAccelCost)]),

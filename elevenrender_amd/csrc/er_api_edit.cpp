@@ -2,7 +2,8 @@
 // ONE function, edit_locked: every check with nothing touched, the host copy replaced, then the device stages the edit reaches --
 // geometry, materials, pool, emitters -- and always edit_restart: the render's own state exactly as er_render_begin sets it up
 // (begin_render_state, er_api_stages.h).  Also here: what the geometry stage decides by (er_accel_cost, er_update_policy_set) and the
-// three info getters.
+// info getters.  er_render_update_sparse is the same function once more: its list of moved triangles (er_sparse_host.h) takes the place
+// of the complete arrays in the checks, in the replacement of the host copy and in the refit, and nothing else knows of it.
 #include <algorithm>
 #include <chrono>
 
@@ -18,8 +19,8 @@ const uint32_t LOOK_BITS = ER_EDIT_MATERIALS | ER_EDIT_TEXTURES | ER_EDIT_HDRI; 
 
 // The pieces below run with the mutex held, the device set, the stream idle and the host copy already edited.
 
-// moved triangles: the refit of the built structure from the host copy's arrays
-int edit_refit(ErScene* s, bool new_normals, bool new_tangents, const char* who) {
+// moved triangles: the refit of the built structure from the host copy's arrays, or -- sp -- from the listed triangles alone
+int edit_refit(ErScene* s, bool new_normals, bool new_tangents, const ErSparseList* sp, const char* who) {
     ErGpuBvhDevice& g = s->kept.accel;
     ErRefitBuffers b;
     b.nodes = (ErNode*)s->d_nodes.p; b.node_count = (uint32_t)(g.nodes_f4 / 4); b.depth2 = g.max_depth2;
@@ -30,7 +31,17 @@ int edit_refit(ErScene* s, bool new_normals, bool new_tangents, const char* who)
     a.tangents = new_tangents ? s->tangents.data() : nullptr;
     ErRefitResult r;
     std::string why;
-    const int frc = er_refit_device(s->refit_topo, b, a, s->stream, &r, why);
+    int frc;
+    if (sp) {
+        ErSparseResult sr;
+        frc = er_refit_sparse(s->refit_topo, b, *sp, s->stream, &sr, why);
+        r = sr.refit;
+        s->sparse.path = sr.path; s->sparse.why_full = sr.why_full;
+        s->sparse.dirty_nodes2 = sr.dirty_nodes2; s->sparse.dirty_nodes8 = sr.dirty_nodes8;
+        s->sparse.bytes_uploaded = sr.bytes_uploaded; s->sparse.refit_ms = r.refit_ms;
+    } else {
+        frc = er_refit_device(s->refit_topo, b, a, s->stream, &r, why);
+    }
     if (frc != 0) return fail(frc == -2 ? ER_ERR_OOM : ER_ERR_HIP, std::string(who) + ": refit: " + why);
     if (s->tri_count) {
         for (int k = 0; k < 3; k++) { g.lo[k] = s->accel_lo[k] = r.lo[k]; g.hi[k] = s->accel_hi[k] = r.hi[k]; }
@@ -87,9 +98,9 @@ int edit_rebuild(ErScene* s, BeginStaging& B, const char* who) {
 
 // The geometry bit: the refit, or a fresh build, by the scene's policy (include/eleven_hip.h ER_REBUILD_*).  ER_REBUILD_NEVER is the
 // refit and nothing else.
-int edit_geometry(ErScene* s, BeginStaging& B, bool new_normals, bool new_tangents, const char* who) {
+int edit_geometry(ErScene* s, BeginStaging& B, bool new_normals, bool new_tangents, const ErSparseList* sp, const char* who) {
     const uint32_t mode = s->policy.mode;
-    if (mode == ER_REBUILD_NEVER) return edit_refit(s, new_normals, new_tangents, who);
+    if (mode == ER_REBUILD_NEVER) return edit_refit(s, new_normals, new_tangents, sp, who);
     int rc;
     ErRebuildInfo& R = s->rebuild;
     R.cost_built = R.cost_refit = R.cost_after = 0.0;
@@ -107,7 +118,7 @@ int edit_geometry(ErScene* s, BeginStaging& B, bool new_normals, bool new_tangen
     }
     if (s->baseline_known) {
         R.cost_built = s->baseline_cost;
-        if ((rc = edit_refit(s, new_normals, new_tangents, who)) != ER_OK) return rc;
+        if ((rc = edit_refit(s, new_normals, new_tangents, sp, who)) != ER_OK) return rc;
         if ((rc = accel_cost_locked(s, who, &c)) != ER_OK) return rc;
         R.cost_ms += c.ms;
         R.cost_refit = c.cost;
@@ -242,25 +253,30 @@ int edit_restart(ErScene* s, BeginStaging& B) {
 }
 
 // The device work of an edit, the host copy replaced (section "The stages of an edit"): an absent bit skips its piece
-int edit_device(ErScene* s, const ErSceneEdit* e, bool rebuild_pool, const char* who, uint32_t& stage, float& stage_ms) {
+int edit_device(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, bool rebuild_pool, const char* who, uint32_t& stage, float& stage_ms) {
     int rc;
     const uint32_t what = e->what;
     BeginStaging B;                     // outlives begin_render_state's hipStreamSynchronize
-    if ((what & ER_EDIT_GEOMETRY) && (rc = edit_geometry(s, B, e->normals != nullptr, e->tangents != nullptr, who)) != ER_OK) return rc;
+    const bool new_normals = sp ? sp->normals != nullptr : e->normals != nullptr, new_tangents = sp ? sp->tangents != nullptr : e->tangents != nullptr;
+    if ((what & ER_EDIT_GEOMETRY) && (rc = edit_geometry(s, B, new_normals, new_tangents, sp, who)) != ER_OK) return rc;
     if ((what & ER_EDIT_MATERIALS) && (rc = edit_materials(s, B, e->material_id != nullptr)) != ER_OK) return rc;
     if ((rc = edit_pool(s, what, rebuild_pool, B, who, stage, stage_ms)) != ER_OK) return rc;
     if ((what & (ER_EDIT_GEOMETRY | ER_EDIT_MATERIALS | ER_EDIT_TEXTURES)) && (rc = edit_emitters(s, B, who)) != ER_OK) return rc;
     return edit_restart(s, B);
 }
 
-// Every check of an edit, with nothing of the scene touched; W gets the new lists that the replacement will move in.
-int edit_check(const ErScene* s, const ErSceneEdit* e, uint32_t known, const char* who, EditWork& W) {
+// Every check of an edit, with nothing of the scene touched; W gets the new lists that the replacement will move in.  sp: the
+// geometry bit's arrays are that list's (er_render_update_sparse), checked in O(count).
+int edit_check(const ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, uint32_t known, const char* who, EditWork& W) {
     const std::string pre = std::string(who) + ": ";
     const uint32_t what = e->what;
     int rc;
     if (what == 0 || (what & ~known)) return fail(ER_ERR_INVALID_ARG, pre + "`what` names nothing, or something unknown");
     const size_t n = s->tri_count, n9 = n * 9;
-    if (what & ER_EDIT_GEOMETRY) {
+    if ((what & ER_EDIT_GEOMETRY) && sp) {
+        std::string why;
+        if (!er_sparse_check(s->tri_count, *sp, why)) return fail(ER_ERR_INVALID_ARG, pre + why);
+    } else if (what & ER_EDIT_GEOMETRY) {
         if (!e->vertices) return fail(ER_ERR_INVALID_ARG, pre + "the geometry bit without vertices");
         for (size_t i = 0; i < n9; i++)
             if (!std::isfinite(e->vertices[i])) return fail(ER_ERR_INVALID_ARG, pre + "vertex " + std::to_string(i / 3) + " is not finite");
@@ -343,11 +359,13 @@ int edit_check(const ErScene* s, const ErSceneEdit* e, uint32_t known, const cha
 // The host copy replaced, after the last check.  Nothing here can throw or fail: er_scene_create fixes vertices, normals and tangents
 // at 9 x tri_count floats and material_id at tri_count entries for the life of the scene, so std::copy into them writes into storage
 // that is there and never allocates; the lists that change size were made in W and are swapped in.
-void edit_replace(ErScene* s, const ErSceneEdit* e, EditWork& W) noexcept {
+void edit_replace(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, EditWork& W) noexcept {
     const uint32_t what = e->what;
     const size_t n = s->tri_count, n9 = n * 9;
     if (what & ER_EDIT_CAMERA) s->camera = e->camera;
-    if (what & ER_EDIT_GEOMETRY) {
+    if ((what & ER_EDIT_GEOMETRY) && sp) {
+        er_sparse_patch(*sp, s->vertices.data(), s->normals.data(), s->tangents.data());
+    } else if (what & ER_EDIT_GEOMETRY) {
         std::copy(e->vertices, e->vertices + n9, s->vertices.begin());
         if (e->normals) std::copy(e->normals, e->normals + n9, s->normals.begin());
         if (e->tangents) std::copy(e->tangents, e->tangents + n9, s->tangents.begin());
@@ -368,21 +386,28 @@ void edit_replace(ErScene* s, const ErSceneEdit* e, EditWork& W) noexcept {
     }
 }
 
-// er_render_update (known = its two bits) and er_render_edit, with the mutex held and the scene begun
-int edit_locked(ErScene* s, const ErSceneEdit* e, uint32_t known, const char* who, std::chrono::steady_clock::time_point t0) {
+// er_render_update (known = its two bits), er_render_edit and er_render_update_sparse (sp: its list), with the mutex held and the
+// scene begun
+int edit_locked(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, uint32_t known, const char* who, std::chrono::steady_clock::time_point t0) {
     int rc;
     EditWork W;
-    if ((rc = edit_check(s, e, known, who, W)) != ER_OK) return rc;
+    if ((rc = edit_check(s, e, sp, known, who, W)) != ER_OK) return rc;
     // pending asynchronous work first (the pool streams join the scene's stream at the end of every call)
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
     // the host copy, before any device work: whatever happens below, a later er_render_begin builds the edited scene
-    edit_replace(s, e, W);
+    edit_replace(s, e, sp, W);
     s->feat_valid = false;      // the feature planes show the scene before the edit (er_render_features makes them again)
     for (auto& set : s->unpacked_feat) set.clear();
     uint32_t stage = 0;
     float stage_ms = 0;
-    if ((rc = edit_device(s, e, W.rebuild_pool, who, stage, stage_ms)) != ER_OK) {
+    const bool sparse_geometry = sp && (e->what & ER_EDIT_GEOMETRY);
+    if (sparse_geometry) {      // (a call that ends in a rebuild without a refit leaves these)
+        const uint32_t calls = s->sparse.calls;
+        s->sparse = ErSparseInfo{};
+        s->sparse.calls = calls;
+    }
+    if ((rc = edit_device(s, e, sp, W.rebuild_pool, who, stage, stage_ms)) != ER_OK) {
         s->begun = false;      // (er_render_begin releases what is left and rebuilds from the edited host copy)
         return rc;
     }
@@ -390,6 +415,11 @@ int edit_locked(ErScene* s, const ErSceneEdit* e, uint32_t known, const char* wh
     // CAMERA / GEOMETRY, through either, is an update: it leaves its wall time in upd.update_ms and ErEditInfo alone.  A call that named
     // one of the other bits is an edit: it writes ErEditInfo and leaves upd.update_ms alone.
     s->upd.updates++;
+    if (sparse_geometry) {
+        s->sparse.calls++;
+        s->sparse.moved = sp->count;
+        if (s->accel.builder != 2u) s->sparse.path = 3u;      // the policy ended the call in a build: the refit's figures, if one ran, stay
+    }
     if ((e->what & ER_EDIT_GEOMETRY) && s->accel.builder == 2u) s->upd.refits++;      // (under a rebuild policy the call may have ended in a build)
     const float wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (e->what & LOOK_BITS) {
@@ -413,7 +443,26 @@ static int er_render_update_impl(ErScene* s, const ErSceneUpdate* u) {
     if (!s->begun) return fail(ER_ERR_STATE, "er_render_update: er_render_begin has not succeeded");
     ErSceneEdit e{};
     e.what = u->what; e.camera = u->camera; e.vertices = u->vertices; e.normals = u->normals; e.tangents = u->tangents;
-    return edit_locked(s, &e, ER_UPDATE_CAMERA | ER_UPDATE_GEOMETRY, "er_render_update", t0);
+    return edit_locked(s, &e, nullptr, ER_UPDATE_CAMERA | ER_UPDATE_GEOMETRY, "er_render_update", t0);
+}
+
+static int er_render_update_sparse_impl(ErScene* s, const ErSparseUpdate* u) {
+    if (!s || !u) return fail(ER_ERR_INVALID_ARG, "er_render_update_sparse: NULL argument");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_render_update_sparse: er_render_begin has not succeeded");
+    ErSceneEdit e{};      // (its arrays stay NULL: the list stands for them)
+    e.what = u->what; e.camera = u->camera;
+    ErSparseList l;
+    l.count = u->count; l.tri_ids = u->tri_ids; l.vertices = u->vertices; l.normals = u->normals; l.tangents = u->tangents;
+    return edit_locked(s, &e, &l, ER_UPDATE_CAMERA | ER_UPDATE_GEOMETRY, "er_render_update_sparse", t0);
+}
+
+static int er_sparse_info_impl(ErScene* s, ErSparseInfo* out) {
+    if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_sparse_info: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    *out = s->sparse;
+    return ER_OK;
 }
 
 static int er_render_edit_impl(ErScene* s, const ErSceneEdit* e) {
@@ -421,7 +470,7 @@ static int er_render_edit_impl(ErScene* s, const ErSceneEdit* e) {
     const auto t0 = std::chrono::steady_clock::now();
     std::lock_guard<std::mutex> lk(s->mtx);
     if (!s->begun) return fail(ER_ERR_STATE, "er_render_edit: er_render_begin has not succeeded");
-    return edit_locked(s, e, ER_EDIT_CAMERA | ER_EDIT_GEOMETRY | LOOK_BITS, "er_render_edit", t0);
+    return edit_locked(s, e, nullptr, ER_EDIT_CAMERA | ER_EDIT_GEOMETRY | LOOK_BITS, "er_render_edit", t0);
 }
 
 static int er_accel_cost_impl(ErScene* s, ErAccelCost* out) {
@@ -470,6 +519,8 @@ static int er_rebuild_info_impl(ErScene* s, ErRebuildInfo* out) {
 extern "C" {
 int er_render_update(ErScene* s, const ErSceneUpdate* u) { return guarded("er_render_update", [&]() -> int { return er_render_update_impl(s, u); }); }
 int er_update_info(ErScene* s, ErUpdateInfo* out) { return guarded("er_update_info", [&]() -> int { return er_update_info_impl(s, out); }); }
+int er_render_update_sparse(ErScene* s, const ErSparseUpdate* u) { return guarded("er_render_update_sparse", [&]() -> int { return er_render_update_sparse_impl(s, u); }); }
+int er_sparse_info(ErScene* s, ErSparseInfo* out) { return guarded("er_sparse_info", [&]() -> int { return er_sparse_info_impl(s, out); }); }
 int er_render_edit(ErScene* s, const ErSceneEdit* e) { return guarded("er_render_edit", [&]() -> int { return er_render_edit_impl(s, e); }); }
 int er_edit_info(ErScene* s, ErEditInfo* out) { return guarded("er_edit_info", [&]() -> int { return er_edit_info_impl(s, out); }); }
 int er_accel_cost(ErScene* s, ErAccelCost* out) { return guarded("er_accel_cost", [&]() -> int { return er_accel_cost_impl(s, out); }); }

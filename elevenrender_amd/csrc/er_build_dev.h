@@ -38,7 +38,38 @@ __global__ __launch_bounds__(256) void k_scene_bounds(const float* __restrict__ 
     if ((threadIdx.x & 63) == 0) atomicMax(&g[0], __float_as_uint(vm));     // vm >= 0: the bit pattern orders like the value
 }
 
-// pass 2: padded box, lift bound (er_build_bvh's arithmetic, reference src/Tri.h:106-112)
+// One triangle's padded box and the term of the scene's lift maximum (er_build_bvh's arithmetic, reference src/Tri.h:106-112): p = its
+// [3][3] vertices, nn = its [3][3] normals, pad_abs = the scene's largest |coordinate| x 1e-6.  k_prims and the sparse refit
+// (er_refit.hip) both call these: one implementation.
+__device__ __forceinline__ void prim_padded_box(const float* p, float pad_abs, Box3* b) {
+    for (int a = 0; a < 3; a++) {
+        float lo = fminf(fminf(p[a], p[3 + a]), p[6 + a]), hi = fmaxf(fmaxf(p[a], p[3 + a]), p[6 + a]);
+        float m = fmaxf(fabsf(lo), fabsf(hi));
+        float pad = fmaxf(m * 4e-7f + 1e-37f, pad_abs);
+        float bl = lo - pad, bh = hi + pad;      // rounded outward, as er_build_bvh does
+        if ((double)bl > (double)lo - (double)pad) bl = nextafterf(bl, -INFINITY);
+        if ((double)bh < (double)hi + (double)pad) bh = nextafterf(bh, INFINITY);
+        b->lo[a] = bl;
+        b->hi[a] = bh;
+    }
+}
+// (float)(tl * 1.01); the record's lift is that + 1e-30f
+__device__ __forceinline__ float prim_lift(const float* p, const float* nn) {
+    double tl = 0;
+    for (int j = 0; j < 3; j++) {
+        double nx = nn[3 * j], ny = nn[3 * j + 1], nz = nn[3 * j + 2];
+        double nl = sqrt(nx * nx + ny * ny + nz * nz);
+        for (int k = 0; k < 3; k++) {
+            if (k == j) continue;
+            double dx = (double)p[3 * k] - p[3 * j], dy = (double)p[3 * k + 1] - p[3 * j + 1], dz = (double)p[3 * k + 2] - p[3 * j + 2];
+            double l = fabs(dx * nx + dy * ny + dz * nz) * nl;
+            if (l > tl) tl = l;
+        }
+    }
+    return (float)(tl * 1.01);
+}
+
+// pass 2: padded box, lift bound
 __global__ __launch_bounds__(256) void k_prims(const float* __restrict__ v, const float* __restrict__ nrm, uint32_t n, const unsigned* __restrict__ g,
                                                 Box3* __restrict__ boxes, float* __restrict__ lift, unsigned* __restrict__ lift_max,
                                                 unsigned* __restrict__ bounds /* lo[3], hi[3] of all padded boxes, order-preserving integers */) {
@@ -49,31 +80,11 @@ __global__ __launch_bounds__(256) void k_prims(const float* __restrict__ v, cons
         const float pad_abs = __uint_as_float(g[0]) * 1e-6f;
         const float* p = v + (size_t)i * 9;
         Box3 b;
-        for (int a = 0; a < 3; a++) {
-            float lo = fminf(fminf(p[a], p[3 + a]), p[6 + a]), hi = fmaxf(fmaxf(p[a], p[3 + a]), p[6 + a]);
-            float m = fmaxf(fabsf(lo), fabsf(hi));
-            float pad = fmaxf(m * 4e-7f + 1e-37f, pad_abs);
-            float bl = lo - pad, bh = hi + pad;      // rounded outward, as er_build_bvh does
-            if ((double)bl > (double)lo - (double)pad) bl = nextafterf(bl, -INFINITY);
-            if ((double)bh < (double)hi + (double)pad) bh = nextafterf(bh, INFINITY);
-            b.lo[a] = slo[a] = bl;
-            b.hi[a] = shi[a] = bh;
-        }
+        prim_padded_box(p, pad_abs, &b);
+        for (int a = 0; a < 3; a++) { slo[a] = b.lo[a]; shi[a] = b.hi[a]; }
         boxes[i] = b;
-        const float* nn = nrm + (size_t)i * 9;
-        double tl = 0;
-        for (int j = 0; j < 3; j++) {
-            double nx = nn[3 * j], ny = nn[3 * j + 1], nz = nn[3 * j + 2];
-            double nl = sqrt(nx * nx + ny * ny + nz * nz);
-            for (int k = 0; k < 3; k++) {
-                if (k == j) continue;
-                double dx = (double)p[3 * k] - p[3 * j], dy = (double)p[3 * k + 1] - p[3 * j + 1], dz = (double)p[3 * k + 2] - p[3 * j + 2];
-                double l = fabs(dx * nx + dy * ny + dz * nz) * nl;
-                if (l > tl) tl = l;
-            }
-        }
-        lift[i] = (float)(tl * 1.01) + 1e-30f;
-        my_lift = (float)(tl * 1.01);
+        my_lift = prim_lift(p, nrm + (size_t)i * 9);
+        lift[i] = my_lift + 1e-30f;
     }
     for (int off = 32; off >= 1; off >>= 1) my_lift = fmaxf(my_lift, __shfl_xor(my_lift, off, 64));
     if ((threadIdx.x & 63) == 0) atomicMax(lift_max, __float_as_uint(my_lift));

@@ -9,20 +9,36 @@
 #include <vector>
 
 #include "er_bvh.h"
+#include "er_sparse_host.h"      // ErSparseList: the listed triangles of er_render_update_sparse, already checked
 
-// Per topology: the nodes of either tree by level, as index lists on the device (level L of a tree = entries [off[L], off[L + 1])).
+// Per topology: the nodes of either tree by level, as index lists on the device (level L of a tree = entries [off[L], off[L + 1])),
+// and what the sparse refit needs to find its way UP from a triangle: the slot of every triangle id, the binary and the wide node that
+// hold each slot, and every node's parent (0xffffffff: none).  Each target has one writer, because the structure is a tree.
 // Derived at the first refit after an er_render_begin, kept until the next one.
+// Kept boxes: every refit, full or sparse, leaves the per-slot padded boxes (six floats each), the per-slot term of the lift maximum and
+// the per-wide-node float boxes here (the float boxes cannot be recovered from the quantised nodes, and a requantised parent needs its
+// clean children's exact boxes to reproduce the full refit's bytes).  They describe the structure only after a refit has filled them
+// (`boxes_valid`), under the largest |coordinate| they were padded with (`vmax_bits`).
+// The dirty marks hold the epoch of the sparse refit that set them, so nothing is cleared between calls.
 struct ErRefitTopo {
     bool valid = false;
     uint32_t* d_lv2 = nullptr;      // binary nodes, by depth
     uint32_t* d_lv8 = nullptr;      // wide nodes, by depth
     std::vector<uint32_t> off2, off8;
+    uint32_t *d_slot_of = nullptr, *d_leaf2 = nullptr, *d_leaf8 = nullptr;      // [tri_count] each
+    uint32_t *d_par2 = nullptr, *d_mark2 = nullptr;                               // [node_count]
+    uint32_t *d_par8 = nullptr, *d_mark8 = nullptr;                               // [node8_count]
+    float *d_sbox = nullptr, *d_slift = nullptr, *d_nbox = nullptr;               // [tri_count][6], [tri_count], [node8_count][6]
+    bool boxes_valid = false;
+    uint32_t vmax_bits = 0, epoch = 0;
     void release() {
-        if (d_lv2) (void)hipFree(d_lv2);
-        if (d_lv8) (void)hipFree(d_lv8);
-        d_lv2 = d_lv8 = nullptr;
+        void* all[] = {d_lv2, d_lv8, d_slot_of, d_leaf2, d_leaf8, d_par2, d_mark2, d_par8, d_mark8, d_sbox, d_slift, d_nbox};
+        for (void* q : all) if (q) (void)hipFree(q);
+        d_lv2 = d_lv8 = d_slot_of = d_leaf2 = d_leaf8 = d_par2 = d_mark2 = d_par8 = d_mark8 = nullptr;
+        d_sbox = d_slift = d_nbox = nullptr;
         off2.clear(); off8.clear();
-        valid = false;
+        valid = boxes_valid = false;
+        vmax_bits = epoch = 0;
     }
 };
 
@@ -48,6 +64,16 @@ struct ErRefitResult {
     float refit_ms = 0;             // device time from the first upload to the last level's kernel (HIP events on `stream`)
 };
 
+struct ErSparseResult {
+    ErRefitResult refit;
+    uint32_t path = 0, why_full = 0;     // ErSparseInfo's
+    uint32_t dirty_nodes2 = 0, dirty_nodes8 = 0;
+    uint64_t bytes_uploaded = 0;
+};
+
 // Returns 0; -2 = out of device memory, -1 = any other HIP error or a guard of the refit itself (`err` says which).  Blocks until done.
 int er_refit_device(ErRefitTopo& topo, const ErRefitBuffers& b, const ErRefitArrays& a, hipStream_t stream, ErRefitResult* out, std::string& err);
-hipError_t er_probe_refit(const char** which);   // see er_kernels.h
+// The same structure as er_refit_device of the complete arrays would leave, byte for byte, from the listed triangles alone.
+int er_refit_sparse(ErRefitTopo& topo, const ErRefitBuffers& b, const ErSparseList& a, hipStream_t stream, ErSparseResult* out, std::string& err);
+hipError_t er_probe_refit(const char** which);          // see er_kernels.h
+hipError_t er_probe_refit_sparse(const char** which);

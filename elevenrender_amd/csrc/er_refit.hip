@@ -14,6 +14,10 @@
 // Level-synchronous on purpose: a level's launch reads only what deeper launches on the same stream wrote, so no workgroup ever waits
 // for another inside a kernel -- no arrival counters, no spinning, nothing that depends on when one XCD's L2 shows another's stores.
 // The depth of every node is derived once per topology (top-down passes, then a counting sort on the host) and kept as index lists.
+//
+// The sparse refit (er_refit_sparse) gets a LIST of moved triangles and leaves the same bytes: records scattered through
+// slot_of, the largest coordinate reduced over the records, and -- if its bits are those the kept boxes were padded with -- only the
+// marked nodes recomputed, level by level, by the same node code; else the whole refit above from arrays gathered out of the records.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -52,10 +56,56 @@ __global__ __launch_bounds__(256) void k_depth8_pass(const float4* __restrict__ 
     }
 }
 
+// ---- topology maps: the way UP from a triangle (the sparse refit) ----
+__global__ __launch_bounds__(256) void k_map_slots(const ErTriIsect* __restrict__ isect, uint32_t n, uint32_t* slot_of) {
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t id = (uint32_t)isect[k].tri_id;
+    if (id < n) slot_of[id] = k;
+}
+
+__global__ __launch_bounds__(256) void k_map_binary(const ErNode* __restrict__ nodes, uint32_t node_count, const uint32_t* __restrict__ list, uint32_t m, uint32_t n,
+                                                     uint32_t* par2, uint32_t* leaf2) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= m) return;
+    const uint32_t i = list[t];
+    if (i >= node_count) return;
+    const int c[2] = {nodes[i].c0, nodes[i].c1};
+    for (int k = 0; k < 2; k++) {
+        if (c[k] < 0) {
+            const uint32_t code = (uint32_t)~c[k], first = code >> 3, cnt = (code & 7u) + 1u;
+            for (uint32_t j = 0; j < cnt; j++) if (first + j < n) leaf2[first + j] = i;
+        } else if (ref_inner(c[k]) && (uint32_t)c[k] < node_count && (uint32_t)c[k] != i) {
+            par2[c[k]] = i;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_map_wide(const float4* __restrict__ nodes8, uint32_t node8_count, const uint32_t* __restrict__ list, uint32_t m, uint32_t n,
+                                                   uint32_t* par8, uint32_t* leaf8) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= m) return;
+    const uint32_t i = list[t];
+    if (i >= node8_count) return;
+    const ErNode8* nd = node8_at(nodes8, i);
+    uint32_t inner_rank = 0, tri_pos = nd->tri_base;
+    for (int s = 0; s < 8; s++) {
+        if ((nd->imask >> s) & 1u) {
+            const uint32_t c = nd->child_base + inner_rank++;
+            if (c < node8_count && c > i) par8[c] = i;
+        } else {
+            const uint32_t cnt = ((nd->tri_present >> (2 * s)) & 1u) + ((nd->tri_present >> (2 * s + 1)) & 1u);
+            for (uint32_t j = 0; j < cnt; j++) if (tri_pos + j < n) leaf8[tri_pos + j] = i;
+            tri_pos += cnt;
+        }
+    }
+}
+
 // ---- records ----
+// (nrm_all: the scene's normals whether they are written or not -- the term of the lift maximum is kept per slot for the sparse refit)
 __global__ __launch_bounds__(256) void k_refit_records(uint32_t n, const Box3* __restrict__ boxes, const float* __restrict__ lift, const float* __restrict__ v,
                                                         const float* __restrict__ nrm, const float* __restrict__ tan, ErTriIsect* isect, ErTriAttr* attr,
-                                                        Box3* __restrict__ sbox) {
+                                                        Box3* __restrict__ sbox, const float* __restrict__ nrm_all, float* __restrict__ slift) {
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
     float4* q = (float4*)(isect + k);
@@ -65,6 +115,7 @@ __global__ __launch_bounds__(256) void k_refit_records(uint32_t n, const Box3* _
         Box3 e;
         for (int a = 0; a < 3; a++) { e.lo[a] = INFINITY; e.hi[a] = -INFINITY; }
         sbox[k] = e;
+        slift[k] = 0.0f;
         return;
     }
     const float* p = v + (size_t)id * 9;
@@ -74,6 +125,7 @@ __global__ __launch_bounds__(256) void k_refit_records(uint32_t n, const Box3* _
     if (nrm) for (int j = 0; j < 3; j++) for (int a = 0; a < 3; a++) attr[k].n[j][a] = nrm[(size_t)id * 9 + 3 * j + a];
     if (tan) for (int j = 0; j < 3; j++) for (int a = 0; a < 3; a++) attr[k].t[j][a] = tan[(size_t)id * 9 + 3 * j + a];
     sbox[k] = boxes[id];
+    slift[k] = prim_lift(p, nrm_all + (size_t)id * 9);
 }
 
 __device__ __forceinline__ void box_empty(float* lo, float* hi) {
@@ -88,13 +140,8 @@ __device__ __forceinline__ void box_of_slots(const Box3* __restrict__ sbox, uint
         if (first + j < n) { const Box3 b = sbox[first + j]; box_add(lo, hi, b.lo, b.hi); }
 }
 
-// ---- binary tree, one level ----
-__global__ __launch_bounds__(256) void k_refit_binary(ErNode* nodes, uint32_t node_count, const uint32_t* __restrict__ list, uint32_t m,
-                                                       const Box3* __restrict__ sbox, uint32_t n) {
-    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= m) return;
-    const uint32_t i = list[t];
-    if (i >= node_count) return;
+// ---- binary tree: one node (i < node_count), its deeper levels done ----
+__device__ __forceinline__ void refit_binary_node(ErNode* nodes, uint32_t node_count, uint32_t i, const Box3* __restrict__ sbox, uint32_t n) {
     ErNode nd = nodes[i];
     const int c[2] = {nd.c0, nd.c1};
     for (int k = 0; k < 2; k++) {
@@ -115,13 +162,17 @@ __global__ __launch_bounds__(256) void k_refit_binary(ErNode* nodes, uint32_t no
     nodes[i] = nd;
 }
 
-// ---- wide tree, one level ----
-__global__ __launch_bounds__(256) void k_refit_wide(float4* nodes8, uint32_t node8_count, const uint32_t* __restrict__ list, uint32_t m,
-                                                     const Box3* __restrict__ sbox, uint32_t n, Box3* nbox) {
+__global__ __launch_bounds__(256) void k_refit_binary(ErNode* nodes, uint32_t node_count, const uint32_t* __restrict__ list, uint32_t m,
+                                                       const Box3* __restrict__ sbox, uint32_t n) {
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     if (t >= m) return;
     const uint32_t i = list[t];
-    if (i >= node8_count) return;
+    if (i >= node_count) return;
+    refit_binary_node(nodes, node_count, i, sbox, n);
+}
+
+// ---- wide tree: one node (i < node8_count), its deeper levels done ----
+__device__ __forceinline__ void refit_wide_node(float4* nodes8, uint32_t node8_count, uint32_t i, const Box3* __restrict__ sbox, uint32_t n, Box3* nbox) {
     ErNode8* out = (ErNode8*)(nodes8 + (size_t)i * ER_NODE8_PIECES);
     ErNode8 nd = *out;
     float clo[8][3], chi[8][3];
@@ -157,6 +208,132 @@ __global__ __launch_bounds__(256) void k_refit_wide(float4* nodes8, uint32_t nod
         for (int a = 0; a < 3; a++) wide_axis_quantise(nd.p[a], scale[a], clo[s][a], chi[s][a], &nd.qlo[a][s], &nd.qhi[a][s]);
     }
     *out = nd;
+}
+
+__global__ __launch_bounds__(256) void k_refit_wide(float4* nodes8, uint32_t node8_count, const uint32_t* __restrict__ list, uint32_t m,
+                                                     const Box3* __restrict__ sbox, uint32_t n, Box3* nbox) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= m) return;
+    const uint32_t i = list[t];
+    if (i >= node8_count) return;
+    refit_wide_node(nodes8, node8_count, i, sbox, n, nbox);
+}
+
+// ---- the sparse refit ----
+// the listed triangles into their records, found through slot_of: one writer per record (no id is listed twice)
+__global__ __launch_bounds__(256) void k_sparse_scatter(uint32_t count, const uint32_t* __restrict__ ids, const float* __restrict__ v, const float* __restrict__ nrm,
+                                                         const float* __restrict__ tan, const uint32_t* __restrict__ slot_of, uint32_t n, ErTriIsect* isect,
+                                                         ErTriAttr* attr) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= count) return;
+    const uint32_t id = ids[t];
+    if (id >= n) return;
+    const uint32_t k = slot_of[id];
+    if (k >= n) return;
+    float4* q = (float4*)(isect + k);
+    const float* p = v + (size_t)t * 9;
+    q[0] = make_float4(p[0], p[1], p[2], q[0].w);
+    q[1] = make_float4(p[3], p[4], p[5], q[1].w);
+    q[2] = make_float4(p[6], p[7], p[8], q[2].w);
+    if (nrm) for (int j = 0; j < 3; j++) for (int a = 0; a < 3; a++) attr[k].n[j][a] = nrm[(size_t)t * 9 + 3 * j + a];
+    if (tan) for (int j = 0; j < 3; j++) for (int a = 0; a < 3; a++) attr[k].t[j][a] = tan[(size_t)t * 9 + 3 * j + a];
+}
+
+// k_scene_bounds over the records: the largest |coordinate| of what lies on the device (a maximum: the order does not matter).
+// This and k_sparse_globals stride over the slots with a bounded grid (REDUCE_BLOCKS): one atomic per wave of a grid of n threads is
+// 7 x n / 64 atomics on the same few words, and at 10 M triangles those, not the bytes, set the time.
+__global__ __launch_bounds__(256) void k_records_vmax(const ErTriIsect* __restrict__ isect, uint32_t n, unsigned* g /* [0] vmax bits */) {
+    float vm = 0;
+    for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < n; k += gridDim.x * 256) {
+        const ErTriIsect r = isect[k];
+        if ((uint32_t)r.tri_id < n)
+            for (int a = 0; a < 3; a++) vm = fmaxf(vm, fmaxf(fabsf(r.v0[a]), fmaxf(fabsf(r.v1[a]), fabsf(r.v2[a]))));
+    }
+    for (int off = 32; off >= 1; off >>= 1) vm = fmaxf(vm, __shfl_xor(vm, off, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(&g[0], __float_as_uint(vm));
+}
+
+// path 1, per listed triangle: lift and padded box by k_prims' own arithmetic from what its record and attribute record now hold,
+// and the marks on the two nodes that hold its slot
+__global__ __launch_bounds__(256) void k_sparse_prims(uint32_t count, const uint32_t* __restrict__ ids, const uint32_t* __restrict__ slot_of, uint32_t n,
+                                                       ErTriIsect* isect, const ErTriAttr* __restrict__ attr, const unsigned* __restrict__ g, Box3* sbox, float* slift,
+                                                       const uint32_t* __restrict__ leaf2, uint32_t* mark2, uint32_t node_count,
+                                                       const uint32_t* __restrict__ leaf8, uint32_t* mark8, uint32_t node8_count, uint32_t epoch) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= count) return;
+    const uint32_t id = ids[t];
+    if (id >= n) return;
+    const uint32_t k = slot_of[id];
+    if (k >= n) return;
+    const ErTriIsect r = isect[k];
+    float p[9], nn[9];
+    for (int a = 0; a < 3; a++) { p[a] = r.v0[a]; p[3 + a] = r.v1[a]; p[6 + a] = r.v2[a]; }
+    for (int j = 0; j < 3; j++) for (int a = 0; a < 3; a++) nn[3 * j + a] = attr[k].n[j][a];
+    Box3 b;
+    prim_padded_box(p, __uint_as_float(g[0]) * 1e-6f, &b);
+    const float raw = prim_lift(p, nn);
+    sbox[k] = b;
+    slift[k] = raw;
+    isect[k].lift = raw + 1e-30f;
+    const uint32_t l2 = leaf2[k], l8 = leaf8[k];
+    if (l2 < node_count) mark2[l2] = epoch;
+    if (l8 < node8_count) mark8[l8] = epoch;
+}
+
+// path 1: the scene bounds and the lift maximum from the kept per-slot values, as k_prims reduces them
+__global__ __launch_bounds__(256) void k_sparse_globals(uint32_t n, const Box3* __restrict__ sbox, const float* __restrict__ slift, unsigned* g) {
+    float my_lift = 0;
+    float slo[3] = {INFINITY, INFINITY, INFINITY}, shi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < n; k += gridDim.x * 256) {
+        const Box3 b = sbox[k];
+        for (int a = 0; a < 3; a++) { slo[a] = fminf(slo[a], b.lo[a]); shi[a] = fmaxf(shi[a], b.hi[a]); }
+        my_lift = fmaxf(my_lift, slift[k]);
+    }
+    for (int off = 32; off >= 1; off >>= 1) my_lift = fmaxf(my_lift, __shfl_xor(my_lift, off, 64));
+    for (int off = 32; off >= 1; off >>= 1)
+        for (int a = 0; a < 3; a++) { slo[a] = fminf(slo[a], __shfl_xor(slo[a], off, 64)); shi[a] = fmaxf(shi[a], __shfl_xor(shi[a], off, 64)); }
+    if ((threadIdx.x & 63) == 0) {
+        atomicMax(&g[7], __float_as_uint(my_lift));
+        for (int a = 0; a < 3; a++) { atomicMin(&g[1 + a], f2ord(slo[a])); atomicMax(&g[4 + a], f2ord(shi[a])); }
+    }
+}
+
+// path 1, one level: a node that no deeper launch (or k_sparse_prims) marked returns after one flag read; a marked one is recomputed by
+// the full refit's own code and marks its parent, which a LATER launch reads.  g[8], g[9]: the nodes rewritten.
+__global__ __launch_bounds__(256) void k_dirty_binary(ErNode* nodes, uint32_t node_count, const uint32_t* __restrict__ list, uint32_t m, const Box3* __restrict__ sbox,
+                                                       uint32_t n, uint32_t* mark2, const uint32_t* __restrict__ par2, uint32_t epoch, unsigned* g) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= m) return;
+    const uint32_t i = list[t];
+    if (i >= node_count || mark2[i] != epoch) return;
+    refit_binary_node(nodes, node_count, i, sbox, n);
+    const uint32_t up = par2[i];
+    if (up < node_count) mark2[up] = epoch;
+    atomicAdd(&g[8], 1u);
+}
+
+__global__ __launch_bounds__(256) void k_dirty_wide(float4* nodes8, uint32_t node8_count, const uint32_t* __restrict__ list, uint32_t m, const Box3* __restrict__ sbox,
+                                                     uint32_t n, Box3* nbox, uint32_t* mark8, const uint32_t* __restrict__ par8, uint32_t epoch, unsigned* g) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= m) return;
+    const uint32_t i = list[t];
+    if (i >= node8_count || mark8[i] != epoch) return;
+    refit_wide_node(nodes8, node8_count, i, sbox, n, nbox);
+    const uint32_t up = par8[i];
+    if (up < node8_count) mark8[up] = epoch;
+    atomicAdd(&g[9], 1u);
+}
+
+// path 2: triangle-ordered vertices and normals out of the records, for the full refit's kernels
+__global__ __launch_bounds__(256) void k_gather_arrays(uint32_t n, const ErTriIsect* __restrict__ isect, const ErTriAttr* __restrict__ attr, float* v, float* nrm) {
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const ErTriIsect r = isect[k];
+    const uint32_t id = (uint32_t)r.tri_id;
+    if (id >= n) return;
+    float* p = v + (size_t)id * 9;
+    for (int a = 0; a < 3; a++) { p[a] = r.v0[a]; p[3 + a] = r.v1[a]; p[6 + a] = r.v2[a]; }
+    for (int j = 0; j < 3; j++) for (int a = 0; a < 3; a++) nrm[(size_t)id * 9 + 3 * j + a] = attr[k].n[j][a];
 }
 
 template <class T>
@@ -197,6 +374,35 @@ int level_lists(const std::vector<uint32_t>& depth, uint32_t max_levels, uint32_
     return 0;
 }
 
+// the maps of the sparse refit and the storage of the kept boxes, once the level lists exist
+int derive_maps(ErRefitTopo& topo, const ErRefitBuffers& b, hipStream_t st, std::string& err) {
+    const size_t n = b.tri_count, n2 = std::max<size_t>(1, b.node_count), n8 = std::max<size_t>(1, b.node8_count);
+    RF_OK(hipMalloc((void**)&topo.d_slot_of, n * 4));
+    RF_OK(hipMalloc((void**)&topo.d_leaf2, n * 4));
+    RF_OK(hipMalloc((void**)&topo.d_leaf8, n * 4));
+    RF_OK(hipMalloc((void**)&topo.d_par2, n2 * 4));
+    RF_OK(hipMalloc((void**)&topo.d_mark2, n2 * 4));
+    RF_OK(hipMalloc((void**)&topo.d_par8, n8 * 4));
+    RF_OK(hipMalloc((void**)&topo.d_mark8, n8 * 4));
+    RF_OK(hipMalloc((void**)&topo.d_sbox, n * sizeof(Box3)));
+    RF_OK(hipMalloc((void**)&topo.d_slift, n * 4));
+    RF_OK(hipMalloc((void**)&topo.d_nbox, n8 * sizeof(Box3)));
+    RF_OK(hipMemsetAsync(topo.d_slot_of, 0xff, n * 4, st));
+    RF_OK(hipMemsetAsync(topo.d_leaf2, 0xff, n * 4, st));
+    RF_OK(hipMemsetAsync(topo.d_leaf8, 0xff, n * 4, st));
+    RF_OK(hipMemsetAsync(topo.d_par2, 0xff, n2 * 4, st));
+    RF_OK(hipMemsetAsync(topo.d_par8, 0xff, n8 * 4, st));
+    RF_OK(hipMemsetAsync(topo.d_mark2, 0, n2 * 4, st));
+    RF_OK(hipMemsetAsync(topo.d_mark8, 0, n8 * 4, st));
+    hipLaunchKernelGGL(k_map_slots, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, st, b.isect, b.tri_count, topo.d_slot_of);
+    const uint32_t m2 = topo.off2.empty() ? 0u : topo.off2.back(), m8 = topo.off8.empty() ? 0u : topo.off8.back();
+    if (m2) hipLaunchKernelGGL(k_map_binary, dim3((m2 + 255) / 256), dim3(256), 0, st, b.nodes, b.node_count, topo.d_lv2, m2, b.tri_count, topo.d_par2, topo.d_leaf2);
+    if (m8) hipLaunchKernelGGL(k_map_wide, dim3((m8 + 255) / 256), dim3(256), 0, st, b.nodes8, b.node8_count, topo.d_lv8, m8, b.tri_count, topo.d_par8, topo.d_leaf8);
+    RF_OK(hipGetLastError());
+    RF_OK(hipStreamSynchronize(st));
+    return 0;
+}
+
 int derive_topology(ErRefitTopo& topo, const ErRefitBuffers& b, hipStream_t st, std::string& err) {
     topo.release();
     const uint32_t zero = 0;
@@ -222,8 +428,45 @@ int derive_topology(ErRefitTopo& topo, const ErRefitBuffers& b, hipStream_t st, 
         int rc = level_lists(depth, max_levels, which == 0 ? &topo.d_lv2 : &topo.d_lv8, which == 0 ? topo.off2 : topo.off8, st, err);
         if (rc != 0) { topo.release(); return rc; }
     }
+    const int rc = derive_maps(topo, b, st, err);
+    if (rc != 0) { topo.release(); return rc; }
     topo.valid = true;
     return 0;
+}
+
+// [0] vmax, [1..6] scene bounds (order-preserving integers), [7] lift max: the layout of the builder's counters; [8], [9] the sparse
+// refit's counts of rewritten nodes
+constexpr int G_WORDS = 16;
+constexpr uint32_t REDUCE_BLOCKS = 2048;      // grid bound of the strided reductions: eight workgroups for each of the 256 CUs
+void globals_init(unsigned* g) {
+    for (int k = 0; k < G_WORDS; k++) g[k] = (k >= 1 && k <= 3) ? 0xffffffffu : 0u;
+}
+
+// The whole refit from triangle-ordered arrays ON THE DEVICE (d_t: NULL = keep; normals are written only if write_normals), d_g
+// initialised: bounds, records, both trees level by level.  Fills the kept boxes of `topo`.  Launches only.
+int refit_full_launch(ErRefitTopo& topo, const ErRefitBuffers& b, const float* d_v, const float* d_n, const float* d_t, bool write_normals, unsigned* d_g,
+                      Box3* d_box, float* d_lift, hipStream_t st, std::string& err) {
+    const uint32_t n = b.tri_count, blocks = (n + 255) / 256;
+    Box3 *sbox = (Box3*)topo.d_sbox, *nbox = (Box3*)topo.d_nbox;
+    hipLaunchKernelGGL(k_scene_bounds, dim3(blocks), dim3(256), 0, st, d_v, n, d_g);
+    hipLaunchKernelGGL(k_prims, dim3(blocks), dim3(256), 0, st, d_v, d_n, n, d_g, d_box, d_lift, d_g + 7, d_g + 1);
+    hipLaunchKernelGGL(k_refit_records, dim3(blocks), dim3(256), 0, st, n, d_box, d_lift, d_v, write_normals ? d_n : (const float*)nullptr, d_t, b.isect, b.attr, sbox,
+                       d_n, topo.d_slift);
+    for (size_t l = topo.off2.size(); l-- > 1;) {      // deepest level first
+        const uint32_t first = topo.off2[l - 1], m = topo.off2[l] - first;
+        if (m) hipLaunchKernelGGL(k_refit_binary, dim3((m + 255) / 256), dim3(256), 0, st, b.nodes, b.node_count, topo.d_lv2 + first, m, sbox, n);
+    }
+    for (size_t l = topo.off8.size(); l-- > 1;) {
+        const uint32_t first = topo.off8[l - 1], m = topo.off8[l] - first;
+        if (m) hipLaunchKernelGGL(k_refit_wide, dim3((m + 255) / 256), dim3(256), 0, st, b.nodes8, b.node8_count, topo.d_lv8 + first, m, sbox, n, nbox);
+    }
+    RF_OK(hipGetLastError());
+    return 0;
+}
+
+void result_of_globals(const unsigned* g, ErRefitResult* out) {
+    for (int k = 0; k < 3; k++) { out->lo[k] = er_ord2f_host(g[1 + k]); out->hi[k] = er_ord2f_host(g[4 + k]); }
+    memcpy(&out->lift_bound, &g[7], 4);
 }
 
 }  // namespace
@@ -232,6 +475,12 @@ hipError_t er_probe_refit(const char** which) {
     hipFuncAttributes at;
     *which = "k_refit_wide (er_refit.hip)";
     return hipFuncGetAttributes(&at, (const void*)k_refit_wide);
+}
+
+hipError_t er_probe_refit_sparse(const char** which) {
+    hipFuncAttributes at;
+    *which = "k_dirty_wide (er_refit.hip)";
+    return hipFuncGetAttributes(&at, (const void*)k_dirty_wide);
 }
 
 int er_refit_device(ErRefitTopo& topo, const ErRefitBuffers& b, const ErRefitArrays& a, hipStream_t st, ErRefitResult* out, std::string& err) {
@@ -247,43 +496,124 @@ int er_refit_device(ErRefitTopo& topo, const ErRefitBuffers& b, const ErRefitArr
     RF_OK(hipEventCreate(&ev.a));
     RF_OK(hipEventCreate(&ev.b));
     Tmp<float> d_v, d_n, d_t, d_lift;
-    Tmp<Box3> d_box, d_sbox, d_nbox;
+    Tmp<Box3> d_box;
     Tmp<unsigned> d_g;
     RF_OK(hipMalloc((void**)&d_v.p, (size_t)n * 36));
     RF_OK(hipMalloc((void**)&d_n.p, (size_t)n * 36));
     if (a.tangents) RF_OK(hipMalloc((void**)&d_t.p, (size_t)n * 36));
     RF_OK(hipMalloc((void**)&d_lift.p, (size_t)n * 4));
     RF_OK(hipMalloc((void**)&d_box.p, (size_t)n * sizeof(Box3)));
-    RF_OK(hipMalloc((void**)&d_sbox.p, (size_t)n * sizeof(Box3)));
-    RF_OK(hipMalloc((void**)&d_nbox.p, std::max<size_t>(1, b.node8_count) * sizeof(Box3)));
-    RF_OK(hipMalloc((void**)&d_g.p, 12 * 4));
+    RF_OK(hipMalloc((void**)&d_g.p, G_WORDS * 4));
+    topo.boxes_valid = false;      // (until the last level has run)
     RF_OK(hipEventRecord(ev.a, st));
     RF_OK(hipMemcpyAsync(d_v.p, a.vertices, (size_t)n * 36, hipMemcpyHostToDevice, st));
     RF_OK(hipMemcpyAsync(d_n.p, a.normals, (size_t)n * 36, hipMemcpyHostToDevice, st));
     if (a.tangents) RF_OK(hipMemcpyAsync(d_t.p, a.tangents, (size_t)n * 36, hipMemcpyHostToDevice, st));
-    // [0] vmax, [1..6] scene bounds (order-preserving integers), [7] lift max: the layout of the builder's counters
-    unsigned g[12];
-    for (int k = 0; k < 12; k++) g[k] = (k >= 1 && k <= 3) ? 0xffffffffu : 0u;
+    unsigned g[G_WORDS];
+    globals_init(g);
     RF_OK(hipMemcpyAsync(d_g.p, g, sizeof(g), hipMemcpyHostToDevice, st));
-    const uint32_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(k_scene_bounds, dim3(blocks), dim3(256), 0, st, d_v.p, n, d_g.p);
-    hipLaunchKernelGGL(k_prims, dim3(blocks), dim3(256), 0, st, d_v.p, d_n.p, n, d_g.p, d_box.p, d_lift.p, d_g.p + 7, d_g.p + 1);
-    hipLaunchKernelGGL(k_refit_records, dim3(blocks), dim3(256), 0, st, n, d_box.p, d_lift.p, d_v.p, a.write_normals ? d_n.p : (const float*)nullptr,
-                       (const float*)d_t.p, b.isect, b.attr, d_sbox.p);
-    for (size_t l = topo.off2.size(); l-- > 1;) {      // deepest level first
-        const uint32_t first = topo.off2[l - 1], m = topo.off2[l] - first;
-        if (m) hipLaunchKernelGGL(k_refit_binary, dim3((m + 255) / 256), dim3(256), 0, st, b.nodes, b.node_count, topo.d_lv2 + first, m, d_sbox.p, n);
-    }
-    for (size_t l = topo.off8.size(); l-- > 1;) {
-        const uint32_t first = topo.off8[l - 1], m = topo.off8[l] - first;
-        if (m) hipLaunchKernelGGL(k_refit_wide, dim3((m + 255) / 256), dim3(256), 0, st, b.nodes8, b.node8_count, topo.d_lv8 + first, m, d_sbox.p, n, d_nbox.p);
-    }
-    RF_OK(hipGetLastError());
+    int rc = refit_full_launch(topo, b, d_v.p, d_n.p, d_t.p, a.write_normals, d_g.p, d_box.p, d_lift.p, st, err);
+    if (rc != 0) return rc;
     RF_OK(hipEventRecord(ev.b, st));
     RF_OK(hipMemcpyAsync(g, d_g.p, sizeof(g), hipMemcpyDeviceToHost, st));
     RF_OK(hipStreamSynchronize(st));
-    for (int k = 0; k < 3; k++) { out->lo[k] = er_ord2f_host(g[1 + k]); out->hi[k] = er_ord2f_host(g[4 + k]); }
-    memcpy(&out->lift_bound, &g[7], 4);
+    result_of_globals(g, out);
+    topo.vmax_bits = g[0];
+    topo.boxes_valid = true;
     (void)hipEventElapsedTime(&out->refit_ms, ev.a, ev.b);
+    return 0;
+}
+
+int er_refit_sparse(ErRefitTopo& topo, const ErRefitBuffers& b, const ErSparseList& a, hipStream_t st, ErSparseResult* out, std::string& err) {
+    const uint32_t n = b.tri_count, count = a.count;
+    *out = ErSparseResult{};
+    if (n == 0 || count == 0 || !a.tri_ids || !a.vertices || !b.isect || !b.attr || !b.nodes8) { err = "sparse refit: missing array"; return -1; }
+    if (!topo.valid) {
+        int rc = derive_topology(topo, b, st, err);
+        if (rc != 0) return rc;
+    }
+    Events ev;
+    RF_OK(hipEventCreate(&ev.a));
+    RF_OK(hipEventCreate(&ev.b));
+    Tmp<uint32_t> d_ids;
+    Tmp<float> d_v, d_n, d_t;
+    Tmp<unsigned> d_g;
+    const size_t list_bytes = (size_t)count * 36;
+    RF_OK(hipMalloc((void**)&d_ids.p, (size_t)count * 4));
+    RF_OK(hipMalloc((void**)&d_v.p, list_bytes));
+    if (a.normals) RF_OK(hipMalloc((void**)&d_n.p, list_bytes));
+    if (a.tangents) RF_OK(hipMalloc((void**)&d_t.p, list_bytes));
+    RF_OK(hipMalloc((void**)&d_g.p, G_WORDS * 4));
+    const bool had_boxes = topo.boxes_valid;
+    topo.boxes_valid = false;      // (until the last level has run)
+    RF_OK(hipEventRecord(ev.a, st));
+    RF_OK(hipMemcpyAsync(d_ids.p, a.tri_ids, (size_t)count * 4, hipMemcpyHostToDevice, st));
+    RF_OK(hipMemcpyAsync(d_v.p, a.vertices, list_bytes, hipMemcpyHostToDevice, st));
+    if (a.normals) RF_OK(hipMemcpyAsync(d_n.p, a.normals, list_bytes, hipMemcpyHostToDevice, st));
+    if (a.tangents) RF_OK(hipMemcpyAsync(d_t.p, a.tangents, list_bytes, hipMemcpyHostToDevice, st));
+    unsigned g[G_WORDS];
+    globals_init(g);
+    RF_OK(hipMemcpyAsync(d_g.p, g, sizeof(g), hipMemcpyHostToDevice, st));
+    out->bytes_uploaded = (uint64_t)count * 4 + list_bytes * (1 + (a.normals ? 1 : 0) + (a.tangents ? 1 : 0)) + sizeof(g);
+    const uint32_t blocks = (n + 255) / 256, lblocks = (count + 255) / 256;
+    hipLaunchKernelGGL(k_sparse_scatter, dim3(lblocks), dim3(256), 0, st, count, d_ids.p, d_v.p, (const float*)d_n.p, (const float*)d_t.p, topo.d_slot_of, n, b.isect, b.attr);
+    const uint32_t rblocks = std::min(blocks, REDUCE_BLOCKS);
+    hipLaunchKernelGGL(k_records_vmax, dim3(rblocks), dim3(256), 0, st, b.isect, n, d_g.p);
+    RF_OK(hipGetLastError());
+    unsigned vmax = 0;
+    RF_OK(hipMemcpyAsync(&vmax, d_g.p, 4, hipMemcpyDeviceToHost, st));
+    RF_OK(hipStreamSynchronize(st));
+    // The largest |coordinate| sets the absolute padding of EVERY box: only under the bits the kept boxes were padded with do the
+    // boxes of the triangles that did not move still hold.
+    out->why_full = !had_boxes ? 1u : vmax != topo.vmax_bits ? 2u : 0u;
+    Tmp<float> d_av, d_an, d_lift;      // path 2's temporaries
+    Tmp<Box3> d_box;
+    if (out->why_full) {
+        out->path = 2;
+        RF_OK(hipMalloc((void**)&d_av.p, (size_t)n * 36));
+        RF_OK(hipMalloc((void**)&d_an.p, (size_t)n * 36));
+        RF_OK(hipMalloc((void**)&d_lift.p, (size_t)n * 4));
+        RF_OK(hipMalloc((void**)&d_box.p, (size_t)n * sizeof(Box3)));
+        RF_OK(hipMemsetAsync(d_av.p, 0, (size_t)n * 36, st));      // (a triangle id that no record names: cannot happen in a structure that checks clean)
+        RF_OK(hipMemsetAsync(d_an.p, 0, (size_t)n * 36, st));
+        RF_OK(hipMemcpyAsync(d_g.p, g, sizeof(g), hipMemcpyHostToDevice, st));      // k_scene_bounds finds the maximum again, from the gathered array
+        out->bytes_uploaded += sizeof(g);
+        hipLaunchKernelGGL(k_gather_arrays, dim3(blocks), dim3(256), 0, st, n, b.isect, b.attr, d_av.p, d_an.p);
+        // (the records already hold the listed normals and tangents: nothing but vertices, lifts and boxes is written)
+        int rc = refit_full_launch(topo, b, d_av.p, d_an.p, nullptr, false, d_g.p, d_box.p, d_lift.p, st, err);
+        if (rc != 0) return rc;
+        out->dirty_nodes2 = b.node_count;
+        out->dirty_nodes8 = b.node8_count;
+    } else {
+        out->path = 1;
+        if (++topo.epoch == 0) {      // the epoch wrapped: marks of 2^32 calls ago would read as this call's
+            RF_OK(hipMemsetAsync(topo.d_mark2, 0, std::max<size_t>(1, b.node_count) * 4, st));
+            RF_OK(hipMemsetAsync(topo.d_mark8, 0, std::max<size_t>(1, b.node8_count) * 4, st));
+            topo.epoch = 1;
+        }
+        Box3 *sbox = (Box3*)topo.d_sbox, *nbox = (Box3*)topo.d_nbox;
+        hipLaunchKernelGGL(k_sparse_prims, dim3(lblocks), dim3(256), 0, st, count, d_ids.p, topo.d_slot_of, n, b.isect, b.attr, d_g.p, sbox, topo.d_slift, topo.d_leaf2,
+                           topo.d_mark2, b.node_count, topo.d_leaf8, topo.d_mark8, b.node8_count, topo.epoch);
+        hipLaunchKernelGGL(k_sparse_globals, dim3(rblocks), dim3(256), 0, st, n, sbox, topo.d_slift, d_g.p);
+        for (size_t l = topo.off2.size(); l-- > 1;) {      // deepest level first
+            const uint32_t first = topo.off2[l - 1], m = topo.off2[l] - first;
+            if (m) hipLaunchKernelGGL(k_dirty_binary, dim3((m + 255) / 256), dim3(256), 0, st, b.nodes, b.node_count, topo.d_lv2 + first, m, sbox, n, topo.d_mark2,
+                                      topo.d_par2, topo.epoch, d_g.p);
+        }
+        for (size_t l = topo.off8.size(); l-- > 1;) {
+            const uint32_t first = topo.off8[l - 1], m = topo.off8[l] - first;
+            if (m) hipLaunchKernelGGL(k_dirty_wide, dim3((m + 255) / 256), dim3(256), 0, st, b.nodes8, b.node8_count, topo.d_lv8 + first, m, sbox, n, nbox, topo.d_mark8,
+                                      topo.d_par8, topo.epoch, d_g.p);
+        }
+        RF_OK(hipGetLastError());
+    }
+    RF_OK(hipEventRecord(ev.b, st));
+    RF_OK(hipMemcpyAsync(g, d_g.p, sizeof(g), hipMemcpyDeviceToHost, st));
+    RF_OK(hipStreamSynchronize(st));
+    result_of_globals(g, &out->refit);
+    if (out->path == 1) { out->dirty_nodes2 = g[8]; out->dirty_nodes8 = g[9]; }
+    topo.vmax_bits = g[0];
+    topo.boxes_valid = true;
+    (void)hipEventElapsedTime(&out->refit.refit_ms, ev.a, ev.b);
     return 0;
 }

@@ -173,6 +173,7 @@ struct ErScene {
     ErRefitTopo refit_topo;      // the trees' nodes by level, from the first refit after an er_render_begin until the next one
     ErUpdateInfo upd{};          // er_update_info (counts since er_scene_create)
     ErEditInfo edit{};           // er_edit_info (the same)
+    ErSparseInfo sparse{};       // er_sparse_info (the same)
     // er_accel_cost / er_update_policy_set (er_api_edit.cpp): every build and every refit bumps accel_version; the cost last measured is kept
     // with the version it was measured at.  The baseline of ER_REBUILD_AUTO is the cost of the last BUILT tree: known once such a tree
     // has been measured, forgotten with the next build.

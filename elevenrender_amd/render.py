@@ -131,13 +131,46 @@ class RenderingManager:
                 setattr(call, name, a.ctypes.data_as(C.POINTER(C.c_float)))
         return keep
 
-    def update(self, camera=None, vertices=None, normals=None, tangents=None):
+    def update(self, camera=None, vertices=None, normals=None, tangents=None, tri_ids=None):
         """er_render_update: a new camera (abi.ErCamera) and / or moved triangles ([n][3][3] float32 vertices; normals and tangents
         optional, None = keep) for the begun scene, without a rebuild; the render starts over at sample 0.  self.scene is not changed:
-        a caller that wants to compare against a fresh start builds the edited SceneData itself."""
+        a caller that wants to compare against a fresh start builds the edited SceneData itself.
+        With tri_ids (distinct triangle ids) the arrays are [len(tri_ids)][3][3], one entry per listed triangle, the other triangles
+        stay, and er_render_update_sparse is called: the same result, at a cost that follows the list and not the scene."""
+        if tri_ids is not None:
+            return self._update_sparse(camera, tri_ids, vertices, normals, tangents)
         u = abi.ErSceneUpdate()
         keep = self._camera_and_geometry(u, "update", camera, vertices, normals, tangents)      # (alive until the call returns)
         abi.check(self.lib.er_render_update(self.handle, C.byref(u)))
+
+    def _update_sparse(self, camera, tri_ids, vertices, normals, tangents):
+        u = abi.ErSparseUpdate()
+        if camera is not None:
+            u.what |= abi.UPDATE_CAMERA
+            u.camera = camera
+        ids = np.ascontiguousarray(tri_ids)
+        if ids.ndim != 1 or ids.dtype.kind not in "iu" or (ids.size and (int(ids.min()) < 0 or int(ids.max()) > 0xffffffff)):
+            raise ValueError("update: tri_ids is a one-dimensional array of triangle ids")
+        ids = ids.astype(np.uint32)
+        if vertices is None:
+            raise ValueError("update: tri_ids comes with the listed triangles' vertices")
+        keep = [ids]
+        u.what |= abi.UPDATE_GEOMETRY
+        u.count, u.tri_ids = ids.size, ids.ctypes.data_as(C.POINTER(C.c_uint32))
+        for name, a in (("vertices", vertices), ("normals", normals), ("tangents", tangents)):
+            if a is None:
+                continue
+            a = np.ascontiguousarray(a, np.float32)
+            if a.size != ids.size * 9:
+                raise ValueError(f"update: {name} has {a.size} floats, tri_ids lists {ids.size} triangles")
+            keep.append(a)      # (alive until the call returns)
+            setattr(u, name, a.ctypes.data_as(C.POINTER(C.c_float)))
+        abi.check(self.lib.er_render_update_sparse(self.handle, C.byref(u)))
+
+    def sparse_info(self):
+        a = abi.ErSparseInfo()
+        abi.check(self.lib.er_sparse_info(self.handle, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in abi.ErSparseInfo._fields_}
 
     def update_info(self):
         a = abi.ErUpdateInfo()

@@ -460,6 +460,41 @@ typedef struct ErRebuildInfo {
 int er_update_policy_set(ErScene* scene, const ErUpdatePolicy* policy);
 int er_rebuild_info(ErScene* scene, ErRebuildInfo* out);
 
+/* er_render_update for an edit that moves FEW triangles: the listed ones are given, the others stay.  After ER_OK everything
+ * observable -- planes, samples, RNG, counters, er_state_*, er_light_info, the structure byte for byte (er_debug_read_accel),
+ * ErAccelInfo except build_ms, ErUpdateInfo.updates / .refits, and every decision of er_update_policy_set with its ErRebuildInfo --
+ * equals what er_render_update with the same `what` and camera and the COMPLETE arrays (the scene's current ones with the listed
+ * triangles replaced) would leave.  What differs is the cost: nothing of the geometry stage is proportional to tri_count on the host
+ * or over PCIe.  The listed records are scattered on the device; if the scene's largest |coordinate| kept its bits, only the nodes above
+ * the moved triangles are recomputed, from boxes kept on the device since the last refit (path 1).  If it changed -- it sets the
+ * absolute padding of EVERY box -- or if no refit has run on this topology yet (after er_render_begin or a rebuild the kept boxes do
+ * not exist), the whole refit runs from the records on the device (path 2); still nothing but the listed triangles is uploaded.
+ * ER_ERR_STATE unless the scene is begun.  ER_ERR_INVALID_ARG, the scene untouched and still begun: NULL arguments; `what` 0 or with
+ * unknown bits; GEOMETRY with count 0 or without tri_ids or vertices; an id >= tri_count; an id listed twice; a listed vertex
+ * coordinate that is not finite.  The checks cost O(count) time and memory. */
+typedef struct ErSparseUpdate {
+    uint32_t what;            /* ER_UPDATE_CAMERA | ER_UPDATE_GEOMETRY, as ErSceneUpdate */
+    ErCamera camera;          /* read iff ER_UPDATE_CAMERA */
+    uint32_t count;           /* ER_UPDATE_GEOMETRY: number of listed triangles, >= 1 */
+    const uint32_t* tri_ids;  /* [count], each < tri_count, no id twice */
+    const float* vertices;    /* [count][3][3], required */
+    const float* normals;     /* [count][3][3] or NULL = keep */
+    const float* tangents;    /* [count][3][3] or NULL = keep */
+} ErSparseUpdate;
+int er_render_update_sparse(ErScene* scene, const ErSparseUpdate* update);
+
+typedef struct ErSparseInfo {
+    uint32_t calls;           /* successful sparse geometry updates since er_scene_create */
+    uint32_t path;            /* the last one: 1 = dirty ancestors only, 2 = whole refit from device-resident data,
+                                 3 = ended in a rebuild (policy) */
+    uint32_t why_full;        /* path 2: 1 = no kept boxes for this topology yet, 2 = the largest |coordinate| changed */
+    uint32_t moved;           /* = count */
+    uint32_t dirty_nodes2, dirty_nodes8;   /* binary / wide nodes rewritten (path 1; the node counts on path 2) */
+    uint64_t bytes_uploaded;  /* host-to-device bytes of the geometry stage */
+    float refit_ms;           /* device time, HIP events, as ErUpdateInfo.refit_ms */
+} ErSparseInfo;
+int er_sparse_info(ErScene* scene, ErSparseInfo* out);
+
 /* First-hit feature planes and the denoise guided by them (extension; csrc/er_features.hip gives every float32 operation).
  * er_render_features: a stateless primary-visibility pass over the pixels this rank owns -- n camera rays per pixel (0 -> 4, at most
  * 64; more: ER_ERR_INVALID_ARG) through the production traversal, drawn from the pixel's RNG stream as er_render_begin seeds it, so

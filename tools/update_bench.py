@@ -19,6 +19,15 @@ er_accel_cost(refitted) / er_accel_cost(built) and cost_ms, update_ms of the sam
 alternated as above, and er_render_begin again on the begun scene for comparison.
 
     python tools/update_bench.py --rebuild [--configs C2,C4,C5] [--ratio 2] [--log FILE]
+
+--sparse: one object moved back and forth -- C4: the middle blob instance onto its neighbour's place; C2: the innermost
+1 % of the triangles by (0.05, 0.02, 0.03) -- through er_render_update_sparse on one manager (A) and through er_render_update with
+the complete arrays on another (B), and a camera-only update on A, alternated, --rounds (at least 5) times each in one process:
+update_ms and refit_ms of the first sparse call (path 2: the topology has no kept boxes yet) and the medians of the later ones
+(path 1), of the full update and of the camera-only update, the sparse / full ratio and the sparse update's distance to the
+camera-only one; then the rate on A against B (the same bytes: a sanity line).
+
+    python tools/update_bench.py --sparse [--configs C2,C4] [--rounds 5] [--log FILE]
 """
 import argparse
 import ctypes as C
@@ -214,6 +223,58 @@ def rebuild_bench(name, sc, max_bounces, steps, rounds, instances, ratio):
         b.close()
 
 
+def sparse_bench(name, sc, max_bounces, steps, rounds, instances):
+    v = sc.vertices.reshape(-1, 3, 3)
+    n = len(v)
+    if instances:
+        per = n // instances
+        mid = instances // 2
+        ids = np.arange(mid * per, (mid + 1) * per)
+        delta = (v[(mid + 1) * per:(mid + 2) * per].reshape(-1, 3).mean(0) - v[ids].reshape(-1, 3).mean(0)).astype(np.float32)
+    else:
+        ids = np.argsort(np.abs(v).reshape(n, -1).max(1), kind="stable")[:n // 100]
+        delta = np.array([0.05, 0.02, 0.03], np.float32)
+    ids = np.random.default_rng(3).permutation(ids)
+    say(f"== {name} (sparse updates): {n} triangles, {sc.x_res}x{sc.y_res}, max_bounces {max_bounces}; {len(ids)} triangles ({100.0 * len(ids) / n:.3f} %) moved by {delta.tolist()} and back")
+    a, _ = manager(sc, max_bounces)
+    b, _ = manager(sc, max_bounces)
+    rate(a, 2)
+    rate(b, 2)
+    home, away = np.ascontiguousarray(v[ids]), np.ascontiguousarray(v[ids] + delta)
+    full_home, full_away = v, v.copy()
+    full_away[ids] = away
+    cam2 = shifted_camera(sc.camera, (0.05, 0.02, -0.1))
+    rows = {"sparse": [], "full": [], "camera": []}
+    for k in range(rounds + 1):      # round 0: the first call of either kind on this topology
+        out = k % 2 == 0
+        a.update(tri_ids=ids, vertices=away if out else home)
+        si, ui = a.sparse_info(), a.update_info()
+        b.update(vertices=full_away if out else full_home)
+        fi = b.update_info()
+        a.update(camera=cam2 if out else sc.camera)
+        ci = a.update_info()
+        say(f"   round {k}: sparse update_ms {ui['update_ms']:8.3f} refit_ms {si['refit_ms']:7.3f} path {si['path']} why_full {si['why_full']} dirty nodes {si['dirty_nodes2']} / {si['dirty_nodes8']}"
+            f" uploaded {si['bytes_uploaded']} B   full update_ms {fi['update_ms']:8.3f} refit_ms {fi['refit_ms']:7.3f}   camera update_ms {ci['update_ms']:7.3f}")
+        if k:
+            rows["sparse"].append((ui["update_ms"], si["refit_ms"], si["path"]))
+            rows["full"].append((fi["update_ms"], fi["refit_ms"]))
+            rows["camera"].append(ci["update_ms"])
+    med = lambda xs: float(np.median(xs))
+    su, sr = med([r[0] for r in rows["sparse"]]), med([r[1] for r in rows["sparse"]])
+    fu, fr = med([r[0] for r in rows["full"]]), med([r[1] for r in rows["full"]])
+    cu = med(rows["camera"])
+    say(f"   medians of rounds 1..{rounds} (paths {sorted(set(r[2] for r in rows['sparse']))}): sparse update_ms {su:.3f} refit_ms {sr:.3f}   full update_ms {fu:.3f} refit_ms {fr:.3f}"
+        f"   camera update_ms {cu:.3f}   sparse / full {su / fu:.4f} (refit {sr / fr:.4f})   sparse - camera {su - cu:.3f} ms")
+    ra, rb = [], []
+    for _ in range(min(rounds, 3)):
+        ra.append(rate(a, steps))
+        rb.append(rate(b, steps))
+    say(f"   Msamples/s of {steps} steps, A = after the sparse moves {' '.join(f'{x:7.1f}' for x in ra)}   B = after the full updates {' '.join(f'{x:7.1f}' for x in rb)}"
+        f"   median A/B {np.median(ra) / np.median(rb):.4f}")
+    a.close()
+    b.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C2,C4")
@@ -221,6 +282,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--log")
     ap.add_argument("--rebuild", action="store_true", help="the rebuild policies of er_update_policy_set instead of the update / refit figures")
+    ap.add_argument("--sparse", action="store_true", help="er_render_update_sparse against the full and the camera-only update")
     ap.add_argument("--ratio", type=float, default=2.0, help="--rebuild: max_cost_ratio of the ER_REBUILD_AUTO runs")
     args = ap.parse_args()
     if args.log:
@@ -228,7 +290,14 @@ def main():
         LOG = args.log
         open(LOG, "w").close()
     for cfg in args.configs.split(","):
-        if args.rebuild:
+        if args.sparse:
+            if cfg == "C2":
+                sparse_bench("C2", scenes.soup(1_000_000, 1920, 1080, seed=12345), 8, args.steps, max(5, args.rounds), 0)
+            elif cfg == "C4":
+                sparse_bench("C4", scenes.blob_instances(x_res=3840, y_res=2160), 8, args.steps, max(5, args.rounds), 10000)
+            else:
+                raise SystemExit(f"unknown config {cfg}")
+        elif args.rebuild:
             if cfg == "C2":
                 rebuild_bench("C2", scenes.soup(1_000_000, 1920, 1080, seed=12345), 8, args.steps, args.rounds, 0, args.ratio)
             elif cfg == "C4":
