@@ -134,6 +134,19 @@ class ErSparseInfo(C.Structure):
                 ("dirty_nodes8", C.c_uint32), ("bytes_uploaded", C.c_uint64), ("refit_ms", C.c_float)]
 
 
+class ErObjectTransform(C.Structure):   # row-major 3x4: x' = L x + t
+    _fields_ = [("object", C.c_uint32), ("m", C.c_float * 12)]
+
+
+class ErTransformUpdate(C.Structure):
+    _fields_ = [("what", C.c_uint32), ("camera", ErCamera), ("count", C.c_uint32), ("transforms", C.POINTER(ErObjectTransform))]
+
+
+class ErTransformInfo(C.Structure):
+    _fields_ = [("calls", C.c_uint32), ("objects", C.c_uint32), ("moved", C.c_uint32), ("path", C.c_uint32), ("why_full", C.c_uint32), ("dirty_nodes2", C.c_uint32),
+                ("dirty_nodes8", C.c_uint32), ("reserved", C.c_uint32), ("bytes_uploaded", C.c_uint64), ("refit_ms", C.c_float)]
+
+
 class ErSceneEdit(C.Structure):
     _fields_ = [("what", C.c_uint32), ("camera", ErCamera), ("vertices", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)),
                 ("tangents", C.POINTER(C.c_float)), ("material_count", C.c_uint32), ("materials", C.POINTER(ErMaterial)),
@@ -257,6 +270,18 @@ def debug_bvh_dump(vertices, normals, threads=0):
     return accel_dump_dict(info, nodes=nodes, nodes8=nodes8, slot_to_tri=s2t, tri_lift=lift)
 
 
+def debug_transform_apply(m, vertices, normals, tangents):
+    """include/eleven_hip_debug.h er_debug_transform_apply: the host form of er_render_transform's arithmetic (csrc/er_xform.h; no device
+    needed) on [n][3][3] rest arrays: the posed (vertices, normals, tangents)."""
+    lib = load()
+    mm = np.ascontiguousarray(m, np.float32).reshape(12)
+    v, n, t = (np.ascontiguousarray(a, np.float32).reshape(-1, 3, 3) for a in (vertices, normals, tangents))
+    assert v.shape == n.shape == t.shape
+    out = [np.empty_like(v) for _ in range(3)]
+    check(lib.er_debug_transform_apply(_fptr(mm), len(v), _fptr(v), _fptr(n), _fptr(t), *(_fptr(o) for o in out)))
+    return tuple(out)
+
+
 def _cost_dict(sums, node_terms, tri_terms):
     d = {n: getattr(sums, n) for n in ("node_area", "leaf_area", "tri_area", "cost", "ms")}
     d.update(node_terms=node_terms, tri_terms=tri_terms)
@@ -327,6 +352,9 @@ SYMBOLS = {
     "er_update_info": (C.c_int, [_P, C.POINTER(ErUpdateInfo)]),
     "er_render_update_sparse": (C.c_int, [_P, C.POINTER(ErSparseUpdate)]),
     "er_sparse_info": (C.c_int, [_P, C.POINTER(ErSparseInfo)]),
+    "er_objects_set": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "er_render_transform": (C.c_int, [_P, C.POINTER(ErTransformUpdate)]),
+    "er_transform_info": (C.c_int, [_P, C.POINTER(ErTransformInfo)]),
     "er_render_edit": (C.c_int, [_P, C.POINTER(ErSceneEdit)]),
     "er_edit_info": (C.c_int, [_P, C.POINTER(ErEditInfo)]),
     "er_accel_cost": (C.c_int, [_P, C.POINTER(ErAccelCost)]),
@@ -391,6 +419,7 @@ OPTIONAL_SYMBOLS = {
     "er_debug_bvh_dump": (C.c_int, [_FP, _FP, C.c_uint32, C.c_int, C.POINTER(ErAccelDump), _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64,
                                     _FP, C.c_uint64]),
     "er_debug_accel_cost_terms": (C.c_int, [_P, C.POINTER(ErCostSumsDebug), C.POINTER(C.c_double), C.c_uint64, _FP, C.c_uint64]),
+    "er_debug_transform_apply": (C.c_int, [_FP, C.c_uint32, _FP, _FP, _FP, _FP, _FP, _FP]),
     "er_debug_accel_cost_host": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(ErCostSumsDebug), C.POINTER(C.c_double), C.c_uint64, _FP, C.c_uint64]),
 }
 

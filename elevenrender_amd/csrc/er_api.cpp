@@ -203,6 +203,7 @@ static int accel_upload_host(ErScene* s, BeginStaging& B) {
 int begin_accel(ErScene* s, BeginStaging& B, hipEvent_t built_ev, const char* who) {
     const std::string W = who;
     ErGpuBvhDevice g;
+    s->flush_poses();      // (er_render_transform leaves the host arrays behind: the builders read them)
     const uint32_t flags = s->params.flags;
     const size_t n = s->tri_count;
     bool built = false;

@@ -4,6 +4,9 @@
 // (begin_render_state, er_api_stages.h).  Also here: what the geometry stage decides by (er_accel_cost, er_update_policy_set) and the
 // info getters.  er_render_update_sparse is the same function once more: its list of moved triangles (er_sparse_host.h) takes the place
 // of the complete arrays in the checks, in the replacement of the host copy and in the refit, and nothing else knows of it.
+// er_render_transform is the same function a third time: its list of posed OBJECTS (er_xform.h) takes the place of the sparse list in the
+// same three places -- checked in O(objects), the host copy only marked (ErScene::flush_poses applies the marks where the arrays are
+// read), the listed triangles posed on the device by the refit itself.  Also here: er_objects_set.
 #include <algorithm>
 #include <chrono>
 
@@ -17,28 +20,46 @@ namespace {
 
 const uint32_t LOOK_BITS = ER_EDIT_MATERIALS | ER_EDIT_TEXTURES | ER_EDIT_HDRI;      // what er_render_edit adds to er_render_update
 
+// er_render_transform's list: the caller's transforms, and what the checks derive from them (the upload entries, the triangles moved)
+struct XformList {
+    uint32_t count = 0;
+    const ErObjectTransform* x = nullptr;
+    std::vector<ErXformEntry> entries;
+    uint32_t moved = 0;
+};
+
 // The pieces below run with the mutex held, the device set, the stream idle and the host copy already edited.
 
-// moved triangles: the refit of the built structure from the host copy's arrays, or -- sp -- from the listed triangles alone
-int edit_refit(ErScene* s, bool new_normals, bool new_tangents, const ErSparseList* sp, const char* who) {
+// moved triangles: the refit of the built structure from the host copy's arrays, or -- sp -- from the listed triangles alone, or -- xf --
+// from the device-resident rest copy of the listed objects
+int edit_refit(ErScene* s, bool new_normals, bool new_tangents, const ErSparseList* sp, const XformList* xf, const char* who) {
     ErGpuBvhDevice& g = s->kept.accel;
     ErRefitBuffers b;
     b.nodes = (ErNode*)s->d_nodes.p; b.node_count = (uint32_t)(g.nodes_f4 / 4); b.depth2 = g.max_depth2;
     b.nodes8 = s->d_nodes8.p; b.node8_count = g.nodes8_count; b.depth8 = g.max_depth8;
     b.isect = (ErTriIsect*)(s->d_nodes8.p + g.n8_pieces); b.attr = (ErTriAttr*)s->d_attr.p; b.tri_count = s->tri_count;
+    if (!sp && !xf) s->flush_poses();      // (the full form reads the host arrays; edit_replace has left nothing pending)
     ErRefitArrays a;
     a.vertices = s->vertices.data(); a.normals = s->normals.data(); a.write_normals = new_normals;
     a.tangents = new_tangents ? s->tangents.data() : nullptr;
     ErRefitResult r;
     std::string why;
     int frc;
-    if (sp) {
+    if (sp || xf) {
         ErSparseResult sr;
-        frc = er_refit_sparse(s->refit_topo, b, *sp, s->stream, &sr, why);
+        if (sp) {
+            frc = er_refit_sparse(s->refit_topo, b, *sp, s->stream, &sr, why);
+        } else {
+            frc = s->xform_dev.valid ? 0 : er_xform_table_build(s->xform_dev, s->objects, s->stream, why);      // once per er_objects_set / er_render_begin
+            ErXformCall c;
+            c.table = &s->xform_dev; c.entries = (uint32_t)xf->entries.size(); c.list = xf->entries.data(); c.moved = xf->moved;
+            if (frc == 0) frc = er_refit_xform(s->refit_topo, b, c, s->stream, &sr, why);
+        }
         r = sr.refit;
-        s->sparse.path = sr.path; s->sparse.why_full = sr.why_full;
-        s->sparse.dirty_nodes2 = sr.dirty_nodes2; s->sparse.dirty_nodes8 = sr.dirty_nodes8;
-        s->sparse.bytes_uploaded = sr.bytes_uploaded; s->sparse.refit_ms = r.refit_ms;
+        ErSparseInfo& I = sp ? s->sparse : s->xform;
+        I.path = sr.path; I.why_full = sr.why_full;
+        I.dirty_nodes2 = sr.dirty_nodes2; I.dirty_nodes8 = sr.dirty_nodes8;
+        I.bytes_uploaded = sr.bytes_uploaded; I.refit_ms = r.refit_ms;
     } else {
         frc = er_refit_device(s->refit_topo, b, a, s->stream, &r, why);
     }
@@ -98,9 +119,9 @@ int edit_rebuild(ErScene* s, BeginStaging& B, const char* who) {
 
 // The geometry bit: the refit, or a fresh build, by the scene's policy (include/eleven_hip.h ER_REBUILD_*).  ER_REBUILD_NEVER is the
 // refit and nothing else.
-int edit_geometry(ErScene* s, BeginStaging& B, bool new_normals, bool new_tangents, const ErSparseList* sp, const char* who) {
+int edit_geometry(ErScene* s, BeginStaging& B, bool new_normals, bool new_tangents, const ErSparseList* sp, const XformList* xf, const char* who) {
     const uint32_t mode = s->policy.mode;
-    if (mode == ER_REBUILD_NEVER) return edit_refit(s, new_normals, new_tangents, sp, who);
+    if (mode == ER_REBUILD_NEVER) return edit_refit(s, new_normals, new_tangents, sp, xf, who);
     int rc;
     ErRebuildInfo& R = s->rebuild;
     R.cost_built = R.cost_refit = R.cost_after = 0.0;
@@ -118,7 +139,7 @@ int edit_geometry(ErScene* s, BeginStaging& B, bool new_normals, bool new_tangen
     }
     if (s->baseline_known) {
         R.cost_built = s->baseline_cost;
-        if ((rc = edit_refit(s, new_normals, new_tangents, sp, who)) != ER_OK) return rc;
+        if ((rc = edit_refit(s, new_normals, new_tangents, sp, xf, who)) != ER_OK) return rc;
         if ((rc = accel_cost_locked(s, who, &c)) != ER_OK) return rc;
         R.cost_ms += c.ms;
         R.cost_refit = c.cost;
@@ -253,12 +274,12 @@ int edit_restart(ErScene* s, BeginStaging& B) {
 }
 
 // The device work of an edit, the host copy replaced (section "The stages of an edit"): an absent bit skips its piece
-int edit_device(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, bool rebuild_pool, const char* who, uint32_t& stage, float& stage_ms) {
+int edit_device(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, const XformList* xf, bool rebuild_pool, const char* who, uint32_t& stage, float& stage_ms) {
     int rc;
     const uint32_t what = e->what;
     BeginStaging B;                     // outlives begin_render_state's hipStreamSynchronize
     const bool new_normals = sp ? sp->normals != nullptr : e->normals != nullptr, new_tangents = sp ? sp->tangents != nullptr : e->tangents != nullptr;
-    if ((what & ER_EDIT_GEOMETRY) && (rc = edit_geometry(s, B, new_normals, new_tangents, sp, who)) != ER_OK) return rc;
+    if ((what & ER_EDIT_GEOMETRY) && (rc = edit_geometry(s, B, new_normals, new_tangents, sp, xf, who)) != ER_OK) return rc;
     if ((what & ER_EDIT_MATERIALS) && (rc = edit_materials(s, B, e->material_id != nullptr)) != ER_OK) return rc;
     if ((rc = edit_pool(s, what, rebuild_pool, B, who, stage, stage_ms)) != ER_OK) return rc;
     if ((what & (ER_EDIT_GEOMETRY | ER_EDIT_MATERIALS | ER_EDIT_TEXTURES)) && (rc = edit_emitters(s, B, who)) != ER_OK) return rc;
@@ -266,8 +287,9 @@ int edit_device(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, bool r
 }
 
 // Every check of an edit, with nothing of the scene touched; W gets the new lists that the replacement will move in.  sp: the
-// geometry bit's arrays are that list's (er_render_update_sparse), checked in O(count).
-int edit_check(const ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, uint32_t known, const char* who, EditWork& W) {
+// geometry bit's arrays are that list's (er_render_update_sparse), checked in O(count); xf: they are the listed objects' poses
+// (er_render_transform), checked in O(objects listed), and xf gets the upload entries.
+int edit_check(const ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, XformList* xf, uint32_t known, const char* who, EditWork& W) {
     const std::string pre = std::string(who) + ": ";
     const uint32_t what = e->what;
     int rc;
@@ -276,6 +298,9 @@ int edit_check(const ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, u
     if ((what & ER_EDIT_GEOMETRY) && sp) {
         std::string why;
         if (!er_sparse_check(s->tri_count, *sp, why)) return fail(ER_ERR_INVALID_ARG, pre + why);
+    } else if ((what & ER_EDIT_GEOMETRY) && xf) {
+        std::string why;
+        if (!er_xform_check(s->objects, xf->count, xf->x, xf->entries, xf->moved, why)) return fail(ER_ERR_INVALID_ARG, pre + why);
     } else if (what & ER_EDIT_GEOMETRY) {
         if (!e->vertices) return fail(ER_ERR_INVALID_ARG, pre + "the geometry bit without vertices");
         for (size_t i = 0; i < n9; i++)
@@ -359,13 +384,20 @@ int edit_check(const ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, u
 // The host copy replaced, after the last check.  Nothing here can throw or fail: er_scene_create fixes vertices, normals and tangents
 // at 9 x tri_count floats and material_id at tri_count entries for the life of the scene, so std::copy into them writes into storage
 // that is there and never allocates; the lists that change size were made in W and are swapped in.
-void edit_replace(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, EditWork& W) noexcept {
+// The poses that er_render_transform left pending (er_xform.h: no allocation, no failure either) are applied before a list patches the
+// arrays or a full update keeps some of them, and forgotten where all three arrays are replaced whole; a transform only marks.
+void edit_replace(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, const XformList* xf, EditWork& W) noexcept {
     const uint32_t what = e->what;
     const size_t n = s->tri_count, n9 = n * 9;
     if (what & ER_EDIT_CAMERA) s->camera = e->camera;
     if ((what & ER_EDIT_GEOMETRY) && sp) {
+        s->flush_poses();
         er_sparse_patch(*sp, s->vertices.data(), s->normals.data(), s->tangents.data());
+    } else if ((what & ER_EDIT_GEOMETRY) && xf) {
+        er_objects_mark(s->objects, xf->entries.data(), (uint32_t)xf->entries.size());
     } else if (what & ER_EDIT_GEOMETRY) {
+        if (e->normals && e->tangents) s->objects.forget_pending();
+        else s->flush_poses();
         std::copy(e->vertices, e->vertices + n9, s->vertices.begin());
         if (e->normals) std::copy(e->normals, e->normals + n9, s->normals.begin());
         if (e->tangents) std::copy(e->tangents, e->tangents + n9, s->tangents.begin());
@@ -388,15 +420,15 @@ void edit_replace(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, Edit
 
 // er_render_update (known = its two bits), er_render_edit and er_render_update_sparse (sp: its list), with the mutex held and the
 // scene begun
-int edit_locked(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, uint32_t known, const char* who, std::chrono::steady_clock::time_point t0) {
+int edit_locked(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, XformList* xf, uint32_t known, const char* who, std::chrono::steady_clock::time_point t0) {
     int rc;
     EditWork W;
-    if ((rc = edit_check(s, e, sp, known, who, W)) != ER_OK) return rc;
+    if ((rc = edit_check(s, e, sp, xf, known, who, W)) != ER_OK) return rc;
     // pending asynchronous work first (the pool streams join the scene's stream at the end of every call)
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
     // the host copy, before any device work: whatever happens below, a later er_render_begin builds the edited scene
-    edit_replace(s, e, sp, W);
+    edit_replace(s, e, sp, xf, W);
     s->feat_valid = false;      // the feature planes show the scene before the edit (er_render_features makes them again)
     for (auto& set : s->unpacked_feat) set.clear();
     uint32_t stage = 0;
@@ -407,7 +439,13 @@ int edit_locked(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, uint32
         s->sparse = ErSparseInfo{};
         s->sparse.calls = calls;
     }
-    if ((rc = edit_device(s, e, sp, W.rebuild_pool, who, stage, stage_ms)) != ER_OK) {
+    const bool xform_geometry = xf && (e->what & ER_EDIT_GEOMETRY);
+    if (xform_geometry) {
+        const uint32_t calls = s->xform.calls;
+        s->xform = ErSparseInfo{};
+        s->xform.calls = calls;
+    }
+    if ((rc = edit_device(s, e, sp, xf, W.rebuild_pool, who, stage, stage_ms)) != ER_OK) {
         s->begun = false;      // (er_render_begin releases what is left and rebuilds from the edited host copy)
         return rc;
     }
@@ -419,6 +457,12 @@ int edit_locked(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, uint32
         s->sparse.calls++;
         s->sparse.moved = sp->count;
         if (s->accel.builder != 2u) s->sparse.path = 3u;      // the policy ended the call in a build: the refit's figures, if one ran, stay
+    }
+    if (xform_geometry) {
+        s->xform.calls++;
+        s->xform.moved = xf->moved;
+        s->xform_objects = xf->count;
+        if (s->accel.builder != 2u) s->xform.path = 3u;
     }
     if ((e->what & ER_EDIT_GEOMETRY) && s->accel.builder == 2u) s->upd.refits++;      // (under a rebuild policy the call may have ended in a build)
     const float wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -443,7 +487,7 @@ static int er_render_update_impl(ErScene* s, const ErSceneUpdate* u) {
     if (!s->begun) return fail(ER_ERR_STATE, "er_render_update: er_render_begin has not succeeded");
     ErSceneEdit e{};
     e.what = u->what; e.camera = u->camera; e.vertices = u->vertices; e.normals = u->normals; e.tangents = u->tangents;
-    return edit_locked(s, &e, nullptr, ER_UPDATE_CAMERA | ER_UPDATE_GEOMETRY, "er_render_update", t0);
+    return edit_locked(s, &e, nullptr, nullptr, ER_UPDATE_CAMERA | ER_UPDATE_GEOMETRY, "er_render_update", t0);
 }
 
 static int er_render_update_sparse_impl(ErScene* s, const ErSparseUpdate* u) {
@@ -455,7 +499,7 @@ static int er_render_update_sparse_impl(ErScene* s, const ErSparseUpdate* u) {
     e.what = u->what; e.camera = u->camera;
     ErSparseList l;
     l.count = u->count; l.tri_ids = u->tri_ids; l.vertices = u->vertices; l.normals = u->normals; l.tangents = u->tangents;
-    return edit_locked(s, &e, &l, ER_UPDATE_CAMERA | ER_UPDATE_GEOMETRY, "er_render_update_sparse", t0);
+    return edit_locked(s, &e, &l, nullptr, ER_UPDATE_CAMERA | ER_UPDATE_GEOMETRY, "er_render_update_sparse", t0);
 }
 
 static int er_sparse_info_impl(ErScene* s, ErSparseInfo* out) {
@@ -465,12 +509,49 @@ static int er_sparse_info_impl(ErScene* s, ErSparseInfo* out) {
     return ER_OK;
 }
 
+static int er_objects_set_impl(ErScene* s, uint32_t object_count, const uint32_t* first, const uint32_t* tri_ids) {
+    if (!s || (object_count && !first)) return fail(ER_ERR_INVALID_ARG, "er_objects_set: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    std::string why;
+    if (!er_objects_check(s->tri_count, object_count, first, tri_ids, why)) return fail(ER_ERR_INVALID_ARG, "er_objects_set: " + why);
+    if (object_count) host_reserve((uint64_t)first[object_count] * (27 + 1) * 4 + (uint64_t)object_count * 20 * 4);
+    s->flush_poses();      // the rest pose is the CURRENT pose
+    er_objects_take(s->objects, object_count, first, tri_ids, s->vertices.data(), s->normals.data(), s->tangents.data());
+    if (s->xform_dev.valid || s->xform_dev.d_rest) {      // the device form was the old table's: the next transform builds the new one
+        (void)hipSetDevice(s->device);
+        if (s->stream) (void)hipStreamSynchronize(s->stream);
+        s->xform_dev.release();
+    }
+    return ER_OK;
+}
+
+static int er_render_transform_impl(ErScene* s, const ErTransformUpdate* u) {
+    if (!s || !u) return fail(ER_ERR_INVALID_ARG, "er_render_transform: NULL argument");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_render_transform: er_render_begin has not succeeded");
+    if ((u->what & ER_UPDATE_GEOMETRY) && s->objects.objects() == 0) return fail(ER_ERR_STATE, "er_render_transform: the geometry bit without an object table (er_objects_set)");
+    ErSceneEdit e{};      // (its arrays stay NULL: the listed objects stand for them)
+    e.what = u->what; e.camera = u->camera;
+    XformList l;
+    l.count = u->count; l.x = u->transforms;
+    return edit_locked(s, &e, nullptr, &l, ER_UPDATE_CAMERA | ER_UPDATE_GEOMETRY, "er_render_transform", t0);
+}
+
+static int er_transform_info_impl(ErScene* s, ErTransformInfo* out) {
+    if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_transform_info: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    const ErSparseInfo& x = s->xform;
+    *out = ErTransformInfo{x.calls, s->xform_objects, x.moved, x.path, x.why_full, x.dirty_nodes2, x.dirty_nodes8, 0u, x.bytes_uploaded, x.refit_ms};
+    return ER_OK;
+}
+
 static int er_render_edit_impl(ErScene* s, const ErSceneEdit* e) {
     if (!s || !e) return fail(ER_ERR_INVALID_ARG, "er_render_edit: NULL argument");
     const auto t0 = std::chrono::steady_clock::now();
     std::lock_guard<std::mutex> lk(s->mtx);
     if (!s->begun) return fail(ER_ERR_STATE, "er_render_edit: er_render_begin has not succeeded");
-    return edit_locked(s, e, nullptr, ER_EDIT_CAMERA | ER_EDIT_GEOMETRY | LOOK_BITS, "er_render_edit", t0);
+    return edit_locked(s, e, nullptr, nullptr, ER_EDIT_CAMERA | ER_EDIT_GEOMETRY | LOOK_BITS, "er_render_edit", t0);
 }
 
 static int er_accel_cost_impl(ErScene* s, ErAccelCost* out) {
@@ -521,6 +602,9 @@ int er_render_update(ErScene* s, const ErSceneUpdate* u) { return guarded("er_re
 int er_update_info(ErScene* s, ErUpdateInfo* out) { return guarded("er_update_info", [&]() -> int { return er_update_info_impl(s, out); }); }
 int er_render_update_sparse(ErScene* s, const ErSparseUpdate* u) { return guarded("er_render_update_sparse", [&]() -> int { return er_render_update_sparse_impl(s, u); }); }
 int er_sparse_info(ErScene* s, ErSparseInfo* out) { return guarded("er_sparse_info", [&]() -> int { return er_sparse_info_impl(s, out); }); }
+int er_objects_set(ErScene* s, uint32_t object_count, const uint32_t* first, const uint32_t* tri_ids) { return guarded("er_objects_set", [&]() -> int { return er_objects_set_impl(s, object_count, first, tri_ids); }); }
+int er_render_transform(ErScene* s, const ErTransformUpdate* u) { return guarded("er_render_transform", [&]() -> int { return er_render_transform_impl(s, u); }); }
+int er_transform_info(ErScene* s, ErTransformInfo* out) { return guarded("er_transform_info", [&]() -> int { return er_transform_info_impl(s, out); }); }
 int er_render_edit(ErScene* s, const ErSceneEdit* e) { return guarded("er_render_edit", [&]() -> int { return er_render_edit_impl(s, e); }); }
 int er_edit_info(ErScene* s, ErEditInfo* out) { return guarded("er_edit_info", [&]() -> int { return er_edit_info_impl(s, out); }); }
 int er_accel_cost(ErScene* s, ErAccelCost* out) { return guarded("er_accel_cost", [&]() -> int { return er_accel_cost_impl(s, out); }); }

@@ -550,4 +550,11 @@ int er_debug_eval(ErScene* s, int kind, const float* in, uint32_t n, uint32_t in
 int er_measure_hbm_peak(int device, uint64_t bytes, uint32_t iters, float* copy_GBps, float* read_GBps) {
     return guarded("er_measure_hbm_peak", [&]() -> int { return er_measure_hbm_peak_impl(device, bytes, iters, copy_GBps, read_GBps); });
 }
+int er_debug_transform_apply(const float* m, uint32_t count, const float* v, const float* n, const float* t, float* ov, float* on, float* ot) {
+    return guarded("er_debug_transform_apply", [&]() -> int {
+        if (!m || (count && (!v || !n || !t || !ov || !on || !ot))) return fail(ER_ERR_INVALID_ARG, "er_debug_transform_apply: NULL argument");
+        if (!er_xform_apply(m, count, v, n, t, ov, on, ot)) return fail(ER_ERR_INVALID_ARG, "er_debug_transform_apply: a matrix entry is not finite, or det(L) is not > 0");
+        return ER_OK;
+    });
+}
 }  // extern "C"

@@ -10,6 +10,7 @@
 
 #include "er_bvh.h"
 #include "er_sparse_host.h"      // ErSparseList: the listed triangles of er_render_update_sparse, already checked
+#include "er_xform.h"            // ErXformEntry, ErObjectTable: the listed objects of er_render_transform, already checked
 
 // Per topology: the nodes of either tree by level, as index lists on the device (level L of a tree = entries [off[L], off[L + 1])),
 // and what the sparse refit needs to find its way UP from a triangle: the slot of every triangle id, the binary and the wide node that
@@ -75,5 +76,38 @@ struct ErSparseResult {
 int er_refit_device(ErRefitTopo& topo, const ErRefitBuffers& b, const ErRefitArrays& a, hipStream_t stream, ErRefitResult* out, std::string& err);
 // The same structure as er_refit_device of the complete arrays would leave, byte for byte, from the listed triangles alone.
 int er_refit_sparse(ErRefitTopo& topo, const ErRefitBuffers& b, const ErSparseList& a, hipStream_t stream, ErSparseResult* out, std::string& err);
+
+// The object table of er_objects_set on the device, built at the first er_render_transform after it or after an er_render_begin: the
+// rest pose of every listed triangle in CSR order as SEVEN 16-byte pieces -- 27 floats (vertices, normals, tangents) and the triangle's
+// id in the last word -- piece-major: piece p of CSR position j lies at d_rest[p * total + j], so the 64 lanes of a wave load 1 KiB
+// of consecutive bytes per piece.  112 bytes per listed triangle (108 of pose + the id, no padding) + 4 bytes per object for `first`.
+struct ErXformDev {
+    bool valid = false;
+    float4* d_rest = nullptr;        // [7][total]
+    uint32_t* d_first = nullptr;     // [objects + 1]
+    uint32_t total = 0, objects = 0;
+    void release() {
+        if (d_rest) (void)hipFree(d_rest);
+        if (d_first) (void)hipFree(d_first);
+        d_rest = nullptr; d_first = nullptr;
+        total = objects = 0;
+        valid = false;
+    }
+};
+constexpr uint32_t ER_XFORM_PIECES = 7;
+
+struct ErXformCall {                 // one er_render_transform: the listed objects' entries (host) over the device-resident table
+    const ErXformDev* table = nullptr;
+    uint32_t entries = 0;
+    const ErXformEntry* list = nullptr;
+    uint32_t moved = 0;              // triangles of the listed objects
+};
+
+// `dev` from the host table (one upload of 112 bytes per listed triangle).  Blocks until done.  Returns as er_refit_device.
+int er_xform_table_build(ErXformDev& dev, const ErObjectTable& t, hipStream_t stream, std::string& err);
+// er_refit_sparse with the listed triangles posed ON THE DEVICE from the rest copy (k_xform_scatter): nothing but the entries is uploaded.
+// The same structure, byte for byte, as er_refit_sparse given the listed objects' ids with their posed vertices, normals and tangents.
+int er_refit_xform(ErRefitTopo& topo, const ErRefitBuffers& b, const ErXformCall& x, hipStream_t stream, ErSparseResult* out, std::string& err);
 hipError_t er_probe_refit(const char** which);          // see er_kernels.h
+hipError_t er_probe_xform(const char** which);
 hipError_t er_probe_refit_sparse(const char** which);

@@ -18,11 +18,17 @@
 // The sparse refit (er_refit_sparse) gets a LIST of moved triangles and leaves the same bytes: records scattered through
 // slot_of, the largest coordinate reduced over the records, and -- if its bits are those the kept boxes were padded with -- only the
 // marked nodes recomputed, level by level, by the same node code; else the whole refit above from arrays gathered out of the records.
+//
+// The transform refit (er_refit_xform) is the sparse refit with one kernel exchanged: the listed triangles are not uploaded
+// but posed by k_xform_scatter from a rest copy that lies on the device (er_xform.h has the arithmetic), which also writes the id list
+// that everything behind the scatter runs over.  refit_listed is the one body of both.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -237,6 +243,53 @@ __global__ __launch_bounds__(256) void k_sparse_scatter(uint32_t count, const ui
     q[2] = make_float4(p[6], p[7], p[8], q[2].w);
     if (nrm) for (int j = 0; j < 3; j++) for (int a = 0; a < 3; a++) attr[k].n[j][a] = nrm[(size_t)t * 9 + 3 * j + a];
     if (tan) for (int j = 0; j < 3; j++) for (int a = 0; a < 3; a++) attr[k].t[j][a] = tan[(size_t)t * 9 + 3 * j + a];
+}
+
+// er_render_transform: the triangles of the listed objects posed from the device-resident rest copy (er_xform.h has the arithmetic) into
+// their records, found through slot_of.  One work item per triangle of the listed objects; `ent` holds each listed object's first work
+// item (a prefix of their sizes), so a work item finds its object by bisection over the few entries and its CSR position from `first`.
+// Pure bandwidth.  Per triangle it READS seven 16-byte pieces of the rest copy (112 bytes; consecutive lanes, consecutive addresses),
+// 4 bytes of slot_of and the three w words of its record (tri_id, lift, sign: kept, as k_sparse_scatter keeps them), and WRITES the
+// record's 48 bytes as three 16-byte stores, n and t of the attribute record (72 bytes: four 16-byte stores and one of 8) and its id into
+// ids_out (4 bytes: the list the rest of the sparse refit runs over).  Plain vector stores; one writer per record (no triangle is in
+// two objects, no object is listed twice); no atomics.
+__global__ __launch_bounds__(256) void k_xform_scatter(uint32_t moved, uint32_t entries, const ErXformEntry* __restrict__ ent, const uint32_t* __restrict__ first,
+                                                        const float4* __restrict__ rest, uint32_t total, const uint32_t* __restrict__ slot_of, uint32_t n,
+                                                        ErTriIsect* isect, ErTriAttr* attr, uint32_t* __restrict__ ids_out) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= moved) return;
+    uint32_t lo = 0, hi = entries;      // the LAST entry that starts at or before t (an empty object shares its start with the next one)
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (ent[mid].start <= t) lo = mid; else hi = mid;
+    }
+    const ErXformEntry* e = ent + lo;
+    const uint32_t j = first[e->object] + (t - e->start);
+    ids_out[t] = 0xffffffffu;           // (names no triangle: the kernels behind this one skip it)
+    if (j >= total) return;             // cannot happen with a checked list
+    float r[4 * ER_XFORM_PIECES];
+    for (uint32_t p = 0; p < ER_XFORM_PIECES; p++) {
+        const float4 q = rest[(size_t)p * total + j];
+        r[4 * p] = q.x; r[4 * p + 1] = q.y; r[4 * p + 2] = q.z; r[4 * p + 3] = q.w;
+    }
+    const uint32_t id = __float_as_uint(r[27]);
+    if (id >= n) return;
+    ids_out[t] = id;
+    const uint32_t k = slot_of[id];
+    if (k >= n) return;
+    float m[12], N[9], T[9];
+    for (int a = 0; a < 12; a++) m[a] = e->m[a];
+    for (int a = 0; a < 9; a++) { N[a] = e->N[a]; T[a] = e->T[a]; }
+    float v[9], o[18];
+    er_xform_triangle(m, N, T, r, r + 9, r + 18, v, o, o + 9);
+    float4* q = (float4*)(isect + k);
+    const float* w = (const float*)q;
+    q[0] = make_float4(v[0], v[1], v[2], w[3]);
+    q[1] = make_float4(v[3], v[4], v[5], w[7]);
+    q[2] = make_float4(v[6], v[7], v[8], w[11]);
+    float4* a4 = (float4*)(attr + k);      // n[3][3] and t[3][3] lie first in the record, back to back
+    for (int p = 0; p < 4; p++) a4[p] = make_float4(o[4 * p], o[4 * p + 1], o[4 * p + 2], o[4 * p + 3]);
+    ((float2*)a4)[8] = make_float2(o[16], o[17]);
 }
 
 // k_scene_bounds over the records: the largest |coordinate| of what lies on the device (a maximum: the order does not matter).
@@ -524,10 +577,68 @@ int er_refit_device(ErRefitTopo& topo, const ErRefitBuffers& b, const ErRefitArr
     return 0;
 }
 
-int er_refit_sparse(ErRefitTopo& topo, const ErRefitBuffers& b, const ErSparseList& a, hipStream_t st, ErSparseResult* out, std::string& err) {
-    const uint32_t n = b.tri_count, count = a.count;
-    *out = ErSparseResult{};
-    if (n == 0 || count == 0 || !a.tri_ids || !a.vertices || !b.isect || !b.attr || !b.nodes8) { err = "sparse refit: missing array"; return -1; }
+namespace {
+
+static_assert(offsetof(ErTriAttr, n) == 0 && offsetof(ErTriAttr, t) == 36, "k_xform_scatter writes n and t as the record's first 18 floats");
+
+// How the listed triangles of a sparse refit reach their records.  Either form allocates, enqueues its uploads, and scatters; what it
+// leaves is the device list of the triangles' ids that the rest of refit_listed runs over, and the bytes it uploaded.
+struct HostListed {      // er_render_update_sparse: ids and arrays come from the host and go through k_sparse_scatter
+    const ErSparseList& a;
+    uint32_t count;
+    Tmp<uint32_t> d_ids;
+    Tmp<float> d_v, d_n, d_t;
+    explicit HostListed(const ErSparseList& l) : a(l), count(l.count) {}
+    size_t list_bytes() const { return (size_t)count * 36; }
+    const uint32_t* ids() const { return d_ids.p; }
+    int allocate(std::string& err) {
+        RF_OK(hipMalloc((void**)&d_ids.p, (size_t)count * 4));
+        RF_OK(hipMalloc((void**)&d_v.p, list_bytes()));
+        if (a.normals) RF_OK(hipMalloc((void**)&d_n.p, list_bytes()));
+        if (a.tangents) RF_OK(hipMalloc((void**)&d_t.p, list_bytes()));
+        return 0;
+    }
+    int upload(hipStream_t st, uint64_t* bytes, std::string& err) {
+        RF_OK(hipMemcpyAsync(d_ids.p, a.tri_ids, (size_t)count * 4, hipMemcpyHostToDevice, st));
+        RF_OK(hipMemcpyAsync(d_v.p, a.vertices, list_bytes(), hipMemcpyHostToDevice, st));
+        if (a.normals) RF_OK(hipMemcpyAsync(d_n.p, a.normals, list_bytes(), hipMemcpyHostToDevice, st));
+        if (a.tangents) RF_OK(hipMemcpyAsync(d_t.p, a.tangents, list_bytes(), hipMemcpyHostToDevice, st));
+        *bytes = (uint64_t)count * 4 + list_bytes() * (1 + (a.normals ? 1 : 0) + (a.tangents ? 1 : 0));
+        return 0;
+    }
+    void scatter(const ErRefitTopo& topo, const ErRefitBuffers& b, hipStream_t st) {
+        hipLaunchKernelGGL(k_sparse_scatter, dim3((count + 255) / 256), dim3(256), 0, st, count, d_ids.p, d_v.p, (const float*)d_n.p, (const float*)d_t.p, topo.d_slot_of,
+                           b.tri_count, b.isect, b.attr);
+    }
+};
+
+struct DeviceListed {    // er_render_transform: the rest copy lies on the device; the entries go up and k_xform_scatter poses and scatters
+    const ErXformCall& x;
+    uint32_t count;
+    Tmp<uint32_t> d_ids;
+    Tmp<ErXformEntry> d_ent;
+    explicit DeviceListed(const ErXformCall& c) : x(c), count(c.moved) {}
+    const uint32_t* ids() const { return d_ids.p; }
+    int allocate(std::string& err) {
+        RF_OK(hipMalloc((void**)&d_ids.p, (size_t)count * 4));
+        RF_OK(hipMalloc((void**)&d_ent.p, (size_t)x.entries * sizeof(ErXformEntry)));
+        return 0;
+    }
+    int upload(hipStream_t st, uint64_t* bytes, std::string& err) {
+        RF_OK(hipMemcpyAsync(d_ent.p, x.list, (size_t)x.entries * sizeof(ErXformEntry), hipMemcpyHostToDevice, st));
+        *bytes = (uint64_t)x.entries * sizeof(ErXformEntry);
+        return 0;
+    }
+    void scatter(const ErRefitTopo& topo, const ErRefitBuffers& b, hipStream_t st) {
+        hipLaunchKernelGGL(k_xform_scatter, dim3((count + 255) / 256), dim3(256), 0, st, count, x.entries, (const ErXformEntry*)d_ent.p, (const uint32_t*)x.table->d_first,
+                           (const float4*)x.table->d_rest, x.table->total, topo.d_slot_of, b.tri_count, b.isect, b.attr, d_ids.p);
+    }
+};
+
+// The sparse refit over `L`'s triangles (its arguments checked by the caller): er_refit_sparse and er_refit_xform
+template <class Listed>
+int refit_listed(ErRefitTopo& topo, const ErRefitBuffers& b, Listed& L, hipStream_t st, ErSparseResult* out, std::string& err) {
+    const uint32_t n = b.tri_count, count = L.count;
     if (!topo.valid) {
         int rc = derive_topology(topo, b, st, err);
         if (rc != 0) return rc;
@@ -535,34 +646,28 @@ int er_refit_sparse(ErRefitTopo& topo, const ErRefitBuffers& b, const ErSparseLi
     Events ev;
     RF_OK(hipEventCreate(&ev.a));
     RF_OK(hipEventCreate(&ev.b));
-    Tmp<uint32_t> d_ids;
-    Tmp<float> d_v, d_n, d_t;
     Tmp<unsigned> d_g;
-    const size_t list_bytes = (size_t)count * 36;
-    RF_OK(hipMalloc((void**)&d_ids.p, (size_t)count * 4));
-    RF_OK(hipMalloc((void**)&d_v.p, list_bytes));
-    if (a.normals) RF_OK(hipMalloc((void**)&d_n.p, list_bytes));
-    if (a.tangents) RF_OK(hipMalloc((void**)&d_t.p, list_bytes));
+    int lrc = L.allocate(err);
+    if (lrc != 0) return lrc;
     RF_OK(hipMalloc((void**)&d_g.p, G_WORDS * 4));
     const bool had_boxes = topo.boxes_valid;
     topo.boxes_valid = false;      // (until the last level has run)
     RF_OK(hipEventRecord(ev.a, st));
-    RF_OK(hipMemcpyAsync(d_ids.p, a.tri_ids, (size_t)count * 4, hipMemcpyHostToDevice, st));
-    RF_OK(hipMemcpyAsync(d_v.p, a.vertices, list_bytes, hipMemcpyHostToDevice, st));
-    if (a.normals) RF_OK(hipMemcpyAsync(d_n.p, a.normals, list_bytes, hipMemcpyHostToDevice, st));
-    if (a.tangents) RF_OK(hipMemcpyAsync(d_t.p, a.tangents, list_bytes, hipMemcpyHostToDevice, st));
+    uint64_t list_uploaded = 0;
+    if ((lrc = L.upload(st, &list_uploaded, err)) != 0) return lrc;
     unsigned g[G_WORDS];
     globals_init(g);
     RF_OK(hipMemcpyAsync(d_g.p, g, sizeof(g), hipMemcpyHostToDevice, st));
-    out->bytes_uploaded = (uint64_t)count * 4 + list_bytes * (1 + (a.normals ? 1 : 0) + (a.tangents ? 1 : 0)) + sizeof(g);
+    out->bytes_uploaded = list_uploaded + sizeof(g);
     const uint32_t blocks = (n + 255) / 256, lblocks = (count + 255) / 256;
-    hipLaunchKernelGGL(k_sparse_scatter, dim3(lblocks), dim3(256), 0, st, count, d_ids.p, d_v.p, (const float*)d_n.p, (const float*)d_t.p, topo.d_slot_of, n, b.isect, b.attr);
+    L.scatter(topo, b, st);
     const uint32_t rblocks = std::min(blocks, REDUCE_BLOCKS);
     hipLaunchKernelGGL(k_records_vmax, dim3(rblocks), dim3(256), 0, st, b.isect, n, d_g.p);
     RF_OK(hipGetLastError());
     unsigned vmax = 0;
     RF_OK(hipMemcpyAsync(&vmax, d_g.p, 4, hipMemcpyDeviceToHost, st));
     RF_OK(hipStreamSynchronize(st));
+    const uint32_t* d_ids = L.ids();
     // The largest |coordinate| sets the absolute padding of EVERY box: only under the bits the kept boxes were padded with do the
     // boxes of the triangles that did not move still hold.
     out->why_full = !had_boxes ? 1u : vmax != topo.vmax_bits ? 2u : 0u;
@@ -592,7 +697,7 @@ int er_refit_sparse(ErRefitTopo& topo, const ErRefitBuffers& b, const ErSparseLi
             topo.epoch = 1;
         }
         Box3 *sbox = (Box3*)topo.d_sbox, *nbox = (Box3*)topo.d_nbox;
-        hipLaunchKernelGGL(k_sparse_prims, dim3(lblocks), dim3(256), 0, st, count, d_ids.p, topo.d_slot_of, n, b.isect, b.attr, d_g.p, sbox, topo.d_slift, topo.d_leaf2,
+        hipLaunchKernelGGL(k_sparse_prims, dim3(lblocks), dim3(256), 0, st, count, d_ids, topo.d_slot_of, n, b.isect, b.attr, d_g.p, sbox, topo.d_slift, topo.d_leaf2,
                            topo.d_mark2, b.node_count, topo.d_leaf8, topo.d_mark8, b.node8_count, topo.epoch);
         hipLaunchKernelGGL(k_sparse_globals, dim3(rblocks), dim3(256), 0, st, n, sbox, topo.d_slift, d_g.p);
         for (size_t l = topo.off2.size(); l-- > 1;) {      // deepest level first
@@ -615,5 +720,59 @@ int er_refit_sparse(ErRefitTopo& topo, const ErRefitBuffers& b, const ErSparseLi
     topo.vmax_bits = g[0];
     topo.boxes_valid = true;
     (void)hipEventElapsedTime(&out->refit.refit_ms, ev.a, ev.b);
+    return 0;
+}
+
+}  // namespace
+
+hipError_t er_probe_xform(const char** which) {
+    hipFuncAttributes at;
+    *which = "k_xform_scatter (er_refit.hip)";
+    return hipFuncGetAttributes(&at, (const void*)k_xform_scatter);
+}
+
+int er_refit_sparse(ErRefitTopo& topo, const ErRefitBuffers& b, const ErSparseList& a, hipStream_t st, ErSparseResult* out, std::string& err) {
+    *out = ErSparseResult{};
+    if (b.tri_count == 0 || a.count == 0 || !a.tri_ids || !a.vertices || !b.isect || !b.attr || !b.nodes8) { err = "sparse refit: missing array"; return -1; }
+    HostListed L(a);
+    return refit_listed(topo, b, L, st, out, err);
+}
+
+int er_refit_xform(ErRefitTopo& topo, const ErRefitBuffers& b, const ErXformCall& x, hipStream_t st, ErSparseResult* out, std::string& err) {
+    *out = ErSparseResult{};
+    if (b.tri_count == 0 || x.moved == 0 || x.entries == 0 || !x.list || !x.table || !x.table->valid || !x.table->d_rest || !x.table->d_first || x.moved > x.table->total ||
+        !b.isect || !b.attr || !b.nodes8) { err = "transform refit: missing array"; return -1; }
+    DeviceListed L(x);
+    return refit_listed(topo, b, L, st, out, err);
+}
+
+int er_xform_table_build(ErXformDev& dev, const ErObjectTable& t, hipStream_t st, std::string& err) {
+    dev.release();
+    const uint32_t total = (uint32_t)t.ids.size(), objects = t.objects();
+    if (!total || !objects) { err = "transform: the object table holds no triangle"; return -1; }
+    std::vector<float> pieces;
+    try {
+        pieces.resize((size_t)total * 4 * ER_XFORM_PIECES);
+    } catch (const std::bad_alloc&) {      // (as a failed device allocation: the caller ends the render, the host copy is already marked)
+        err = "transform: out of host memory for the rest copy's staging";
+        return -2;
+    }
+    for (uint32_t j = 0; j < total; j++) {
+        float r[4 * ER_XFORM_PIECES];
+        memcpy(r, &t.rest_v[(size_t)j * 9], 36);
+        memcpy(r + 9, &t.rest_n[(size_t)j * 9], 36);
+        memcpy(r + 18, &t.rest_t[(size_t)j * 9], 36);
+        memcpy(r + 27, &t.ids[j], 4);
+        for (uint32_t p = 0; p < ER_XFORM_PIECES; p++) memcpy(&pieces[((size_t)p * total + j) * 4], r + 4 * p, 16);
+    }
+    RF_OK(hipMalloc((void**)&dev.d_rest, pieces.size() * 4));
+    RF_OK(hipMalloc((void**)&dev.d_first, ((size_t)objects + 1) * 4));
+    hipError_t e = hipMemcpyAsync(dev.d_rest, pieces.data(), pieces.size() * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dev.d_first, t.first.data(), ((size_t)objects + 1) * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);      // (`pieces` goes out of scope)
+    if (e != hipSuccess) { dev.release(); RF_OK(e); }
+    dev.total = total;
+    dev.objects = objects;
+    dev.valid = true;
     return 0;
 }

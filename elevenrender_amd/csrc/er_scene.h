@@ -174,6 +174,15 @@ struct ErScene {
     ErUpdateInfo upd{};          // er_update_info (counts since er_scene_create)
     ErEditInfo edit{};           // er_edit_info (the same)
     ErSparseInfo sparse{};       // er_sparse_info (the same)
+    // er_objects_set / er_render_transform (er_xform.h): the object table with the rest copy and the lazy half of the host copy -- call
+    // er_objects_flush(objects, ...) before reading or partly overwriting vertices, normals or tangents --, its device form (built by the
+    // first transform after er_objects_set or er_render_begin), and what er_transform_info reports: the last transform's figures in an
+    // ErSparseInfo (calls, moved and the rest mean the same) and its listed objects.
+    ErObjectTable objects;
+    ErXformDev xform_dev;
+    ErSparseInfo xform{};
+    uint32_t xform_objects = 0;
+    void flush_poses() noexcept { er_objects_flush(objects, vertices.data(), normals.data(), tangents.data()); }
     // er_accel_cost / er_update_policy_set (er_api_edit.cpp): every build and every refit bumps accel_version; the cost last measured is kept
     // with the version it was measured at.  The baseline of ER_REBUILD_AUTO is the cost of the last BUILT tree: known once such a tree
     // has been measured, forgotten with the next build.
@@ -272,6 +281,7 @@ struct ErScene {
         d_ad_list[0].release(); d_ad_list[1].release(); d_ad_keep.release(); d_ad_snap.release(); d_ad_err.release();
         d_light_tab.release(); light_emitters = 0; light_total = 0.0f;
         refit_topo.release();
+        xform_dev.release();
         d_feat.release(); d_feat_spill.release(); feat_valid = false;
         for (auto& u : unpacked_feat) u.clear();
         ad_on = false; rendered = 0;

@@ -366,6 +366,41 @@ public:
             for (ErScene* s : ers_) if (er_adaptive_set(s, &pars.adaptive_params) != ER_OK) return false;
         return true;
     }
+    // Object transforms (er_objects_set / er_render_transform; no wire command names an object, so these are for hosts that link this
+    // mirror).  set_objects: the same table on every rank -- object o = tri_ids[first[o] .. first[o + 1]), the rest pose is what the ranks
+    // hold now.  transform_objects: the listed objects posed by their 3x4 matrices on every rank side by side, then what
+    // start_rendering does after er_render_begin, as update_camera.  Both return false if any rank refused or failed (after a failed
+    // transform the caller starts over with start_rendering, as after a failed update_camera).
+    bool set_objects(const std::vector<uint32_t>& first, const std::vector<uint32_t>& tri_ids) {
+        if (ers_.empty()) return false;
+        const uint32_t objects = first.empty() ? 0u : (uint32_t)first.size() - 1u;
+        std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);
+        if (ers_.size() > 1) lk.lock();
+        std::vector<int> rcs(ers_.size(), ER_OK);
+        std::vector<std::thread> th;
+        for (size_t r = 0; r < ers_.size(); r++) th.emplace_back([&, r] { rcs[r] = er_objects_set(ers_[r], objects, first.data(), tri_ids.data()); });
+        for (auto& t : th) t.join();
+        for (int rc : rcs) if (rc != ER_OK) return false;
+        return true;
+    }
+    bool transform_objects(const std::vector<ErObjectTransform>& poses) {
+        if (ers_.empty() || poses.empty()) return false;
+        ErTransformUpdate u{};
+        u.what = ER_UPDATE_GEOMETRY;
+        u.count = (uint32_t)poses.size();
+        u.transforms = poses.data();
+        std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);
+        if (ers_.size() > 1) lk.lock();
+        std::vector<int> rcs(ers_.size(), ER_OK);
+        std::vector<std::thread> th;
+        for (size_t r = 0; r < ers_.size(); r++) th.emplace_back([&, r] { rcs[r] = er_render_transform(ers_[r], &u); });
+        for (auto& t : th) t.join();
+        features_ready_ = false;      // (the library has invalidated the planes)
+        for (int rc : rcs) if (rc != ER_OK) return false;
+        if (pars.adaptive)
+            for (ErScene* e : ers_) if (er_adaptive_set(e, &pars.adaptive_params) != ER_OK) return false;
+        return true;
+    }
     // body of kernel_render_enqueue's loop: n more samples on every rank (the launches go out side by side, then the waits).
     // With several ranks a read-back is a SEQUENCE of library calls (gathers, denoise, read) that must see one frame: if the
     // render thread enqueued samples on rank 0 between the gathers and er_denoise, the library would refuse the denoise

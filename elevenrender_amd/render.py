@@ -172,6 +172,48 @@ class RenderingManager:
         abi.check(self.lib.er_sparse_info(self.handle, C.byref(a)))
         return {n: getattr(a, n) for n, _ in abi.ErSparseInfo._fields_}
 
+    def set_objects(self, objects):
+        """er_objects_set: `objects` is a list of arrays of distinct triangle ids, no id in two of them ([] clears the table).  The rest
+        pose of every listed triangle is what the scene holds now; transform() poses the objects from it."""
+        lists = [np.ascontiguousarray(o) for o in objects]
+        for ids in lists:
+            if ids.ndim != 1 or (ids.size and (ids.dtype.kind not in "iu" or int(ids.min()) < 0 or int(ids.max()) > 0xffffffff)):
+                raise ValueError("set_objects: every object is a one-dimensional array of triangle ids")
+        first = np.zeros(len(lists) + 1, np.uint32)
+        if lists:
+            first[1:] = np.cumsum([o.size for o in lists])
+        ids = np.concatenate([o.astype(np.uint32) for o in lists]) if lists else np.zeros(0, np.uint32)
+        ids = np.ascontiguousarray(ids, np.uint32)
+        up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        abi.check(self.lib.er_objects_set(self.handle, len(lists), up(first), up(ids)))
+
+    def transform(self, poses, camera=None):
+        """er_render_transform: `poses` maps an object's index to its 3x4 matrix (row-major, x' = L x + t; anything that reshapes to 12
+        float32).  Each listed object takes that pose of its REST copy on the device -- absolute, not composed with an earlier one --;
+        the others stay.  The render starts over at sample 0.  self.scene is not changed."""
+        u = abi.ErTransformUpdate()
+        if camera is not None:
+            u.what |= abi.UPDATE_CAMERA
+            u.camera = camera
+        xs = (abi.ErObjectTransform * max(1, len(poses)))()
+        for i, (obj, m) in enumerate(poses.items()):
+            m = np.ascontiguousarray(m, np.float32)
+            if m.size != 12:
+                raise ValueError(f"transform: the matrix of object {obj} has {m.size} entries, a pose is 3x4")
+            if int(obj) != obj or not 0 <= int(obj) <= 0xffffffff:
+                raise ValueError("transform: the keys of `poses` are object indices")
+            xs[i].object = int(obj)
+            xs[i].m[:] = m.reshape(12).tolist()
+        if len(poses):
+            u.what |= abi.UPDATE_GEOMETRY
+            u.count, u.transforms = len(poses), xs
+        abi.check(self.lib.er_render_transform(self.handle, C.byref(u)))
+
+    def transform_info(self):
+        a = abi.ErTransformInfo()
+        abi.check(self.lib.er_transform_info(self.handle, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in abi.ErTransformInfo._fields_ if n != "reserved"}
+
     def update_info(self):
         a = abi.ErUpdateInfo()
         abi.check(self.lib.er_update_info(self.handle, C.byref(a)))

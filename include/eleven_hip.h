@@ -495,6 +495,52 @@ typedef struct ErSparseInfo {
 } ErSparseInfo;
 int er_sparse_info(ErScene* scene, ErSparseInfo* out);
 
+/* Object transforms: registered objects posed ON THE DEVICE by matrix (csrc/er_xform.h gives every operation).
+ * er_objects_set: disjoint lists of triangle ids in CSR form -- object o = tri_ids[first[o] .. first[o + 1]) -- become the scene's object
+ * table.  Legal any time after er_scene_create.  The REST POSE of every listed triangle -- vertices, normals, tangents -- is taken from
+ * the scene's current arrays; an earlier table is replaced, object_count 0 clears it (neither array is then read).  The table belongs to
+ * the scene: it survives rebuilds and a second er_render_begin.  Triangles in no object are allowed, and so are empty objects.
+ * ER_ERR_INVALID_ARG, the scene and its table untouched: NULL arguments; a `first` that does not start at 0 or that decreases; an id that
+ * is not below tri_count; an id in two objects or twice in one.
+ * er_render_transform: every listed object takes the pose pose(rest, m): x' = L x + t for m = [L | t], row-major 3x4; normals by the
+ * cofactor matrix of L, tangents by L, both normalised (unit or zero).  The pose is ABSOLUTE, from the rest copy: a second transform of
+ * an object does not compose with the first and nothing drifts.  Objects not listed keep their current pose.  After ER_OK everything
+ * observable -- planes, samples, RNG, counters, er_state_*, er_light_info, the structure byte for byte (er_debug_read_accel), ErAccelInfo
+ * except its timings, ErUpdateInfo's counts, and every decision of er_update_policy_set with its ErRebuildInfo -- equals what
+ * er_render_update_sparse would leave when given the listed objects' ids with pose(rest, m) as vertices, normals and tangents, the same
+ * `what` and the same camera.  tangent_sign and the records' sign stay, as in every refit.  What differs is the cost: the host touches
+ * no triangle and 128 bytes per listed OBJECT go to the device (ErTransformInfo.bytes_uploaded = 128 x count + 64, + 64 on path 2); the
+ * rest copy lies on the device (112 bytes per listed triangle, uploaded by the first transform after er_objects_set or er_render_begin).
+ * The scene's host copy takes a pose lazily, when something reads it (a rebuild, er_render_begin, a sparse or partial update).  A direct
+ * edit (er_render_update, er_render_update_sparse, er_render_edit) of a triangle in an object moves its current pose only: the rest copy
+ * stays what er_objects_set saw, and the object's next transform poses it from there.
+ * ER_ERR_STATE: the scene is not begun, or ER_UPDATE_GEOMETRY without an object table.  ER_ERR_INVALID_ARG, the scene untouched and
+ * still begun: NULL arguments; `what` 0 or with unknown bits; GEOMETRY with count 0, without transforms, or with listed objects that
+ * hold no triangle; an object index not below the object count; an object listed twice; a matrix entry that is not finite; det(L) not
+ * > 0 (a mirror would have to flip the records' sign, which no refit does); a matrix with |m_i0| Bx + |m_i1| By + |m_i2| Bz + |m_i3| >
+ * 1e37 in some row, B being the object's largest rest |coordinate| per axis (what keeps every posed vertex finite).  The checks cost
+ * O(count) time and memory. */
+int er_objects_set(ErScene* scene, uint32_t object_count, const uint32_t* first /*[object_count + 1]*/, const uint32_t* tri_ids);
+typedef struct ErObjectTransform { uint32_t object; float m[12]; } ErObjectTransform;   /* row-major 3x4, x' = L x + t */
+typedef struct ErTransformUpdate {
+    uint32_t what;            /* ER_UPDATE_CAMERA | ER_UPDATE_GEOMETRY, as ErSparseUpdate */
+    ErCamera camera;          /* read iff ER_UPDATE_CAMERA */
+    uint32_t count;           /* ER_UPDATE_GEOMETRY: listed objects, each at most once */
+    const ErObjectTransform* transforms;
+} ErTransformUpdate;
+int er_render_transform(ErScene* scene, const ErTransformUpdate* update);
+typedef struct ErTransformInfo {
+    uint32_t calls;           /* successful er_render_transform calls with ER_UPDATE_GEOMETRY since er_scene_create */
+    uint32_t objects;         /* the last one: listed objects ... */
+    uint32_t moved;           /* ... and their triangles */
+    uint32_t path, why_full;  /* as ErSparseInfo */
+    uint32_t dirty_nodes2, dirty_nodes8;
+    uint32_t reserved;
+    uint64_t bytes_uploaded;  /* host-to-device bytes of the geometry stage: the entries and the refit's counter words */
+    float refit_ms;           /* device time, HIP events, as ErUpdateInfo.refit_ms */
+} ErTransformInfo;
+int er_transform_info(ErScene* scene, ErTransformInfo* out);
+
 /* First-hit feature planes and the denoise guided by them (extension; csrc/er_features.hip gives every float32 operation).
  * er_render_features: a stateless primary-visibility pass over the pixels this rank owns -- n camera rays per pixel (0 -> 4, at most
  * 64; more: ER_ERR_INVALID_ARG) through the production traversal, drawn from the pixel's RNG stream as er_render_begin seeds it, so

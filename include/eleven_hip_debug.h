@@ -274,6 +274,12 @@ void er_debug_set_host_alloc_limit(uint64_t bytes);
  * build delivers but reports a wide tree of ER_STACK8 + 1 levels (either way ER_ERR_STATE: the host builder makes the same tree). */
 void er_debug_set_gpu_build_failure(int kind);
 
+/* The host form of er_render_transform's arithmetic (csrc/er_xform.h) on caller arrays, no device needed: `count` triangles,
+ * [count][3][3] rest vertices, normals and tangents -> pose(rest, m) in the three outputs (which must not overlap the inputs).
+ * ER_ERR_INVALID_ARG: a NULL argument, a matrix entry that is not finite, det(L) not > 0.  The overflow bound is not applied here. */
+int er_debug_transform_apply(const float m[12], uint32_t count, const float* vertices, const float* normals, const float* tangents,
+                             float* out_vertices, float* out_normals, float* out_tangents);
+
 #ifdef __cplusplus
 }
 #endif

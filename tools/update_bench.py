@@ -28,6 +28,14 @@ update_ms and refit_ms of the first sparse call (path 2: the topology has no kep
 camera-only one; then the rate on A against B (the same bytes: a sanity line).
 
     python tools/update_bench.py --sparse [--configs C2,C4] [--rounds 5] [--log FILE]
+
+--transform (C4 only): two objects posed back and forth -- (a) one blob instance, onto its neighbour's place; (b) the first
+tenth of the instances as ONE object, turned a little about its centre -- through er_render_transform on one manager (A) and through
+er_render_update_sparse on another (B), whose caller poses the object's rest arrays in numpy first (elevenrender_amd/transform.py;
+timed apart), alternated, --rounds (at least 7) times each in one process: the first call of either kind, then the medians of the later
+ones: wall time of the call, update_ms, refit_ms, bytes uploaded, the caller's numpy time, and transform / sparse.
+
+    python tools/update_bench.py --transform [--rounds 7] [--log FILE]
 """
 import argparse
 import ctypes as C
@@ -38,7 +46,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from elevenrender_amd import abi, render, scenes  # noqa: E402
+from elevenrender_amd import abi, render, scenes, transform  # noqa: E402
 
 OUT = []
 LOG = None      # --log: every line is appended as it is said, so that a run that is cut short leaves what it measured
@@ -275,6 +283,59 @@ def sparse_bench(name, sc, max_bounces, steps, rounds, instances):
     b.close()
 
 
+def transform_bench(name, sc, max_bounces, rounds, instances):
+    rest = [a.reshape(-1, 3, 3) for a in (sc.vertices, sc.normals, sc.tangents)]
+    v = rest[0]
+    n = len(v)
+    per = n // instances
+    mid = instances // 2
+    blob = np.arange(mid * per, (mid + 1) * per)
+    tenth = np.arange(0, (instances // 10) * per)
+    delta = v[(mid + 1) * per:(mid + 2) * per].reshape(-1, 3).mean(0) - v[blob].reshape(-1, 3).mean(0)
+    c = v[tenth].reshape(-1, 3).mean(0).astype(np.float64)
+    a_, s_ = np.cos(0.02), np.sin(0.02)
+    L = np.array([[a_, -s_, 0], [s_, a_, 0], [0, 0, 1]])
+    home = np.concatenate([np.eye(3), np.zeros((3, 1))], 1).astype(np.float32)
+    cases = (("a", "one blob instance onto its neighbour's place", 0, blob, np.concatenate([np.eye(3), delta.astype(np.float64)[:, None]], 1).astype(np.float32)),
+             ("b", "a tenth of the instances as one object, turned by 0.02 rad about its centre", 1, tenth, np.concatenate([L, (c - L @ c)[:, None]], 1).astype(np.float32)))
+    say(f"== {name} (object transforms): {n} triangles, {sc.x_res}x{sc.y_res}, max_bounces {max_bounces}")
+    a, _ = manager(sc, max_bounces)
+    b, _ = manager(sc, max_bounces)
+    rate(a, 2)
+    rate(b, 2)
+    t0 = time.perf_counter()
+    a.set_objects([blob, tenth])
+    say(f"   er_objects_set of {len(blob)} + {len(tenth)} triangles: {(time.perf_counter() - t0) * 1e3:.2f} ms wall; the rest copy on the device takes {112 * (len(blob) + len(tenth))} bytes")
+    med = lambda xs: float(np.median(xs))
+    for tag, what, obj, ids, away in cases:
+        say(f"   ({tag}) {what}: {len(ids)} triangles ({100.0 * len(ids) / n:.2f} %)")
+        parts = [np.ascontiguousarray(r[ids]) for r in rest]      # (the caller of the sparse path keeps its object's rest arrays)
+        rows = []
+        for k in range(rounds + 1):      # round 0: the first call of either kind on this topology (and the upload of the rest copy)
+            m = away if k % 2 == 0 else home
+            t0 = time.perf_counter()
+            a.transform({obj: m})
+            wa = (time.perf_counter() - t0) * 1e3
+            ti, ua = a.transform_info(), a.update_info()
+            t0 = time.perf_counter()
+            pv, pn, pt = transform.pose(m, *parts)
+            numpy_ms = (time.perf_counter() - t0) * 1e3
+            t0 = time.perf_counter()
+            b.update(tri_ids=ids, vertices=pv, normals=pn, tangents=pt)
+            wb = (time.perf_counter() - t0) * 1e3
+            si, ub = b.sparse_info(), b.update_info()
+            say(f"      round {k}: transform wall {wa:8.3f} update_ms {ua['update_ms']:8.3f} refit_ms {ti['refit_ms']:7.3f} path {ti['path']} why_full {ti['why_full']} dirty nodes {ti['dirty_nodes2']} / {ti['dirty_nodes8']}"
+                f" uploaded {ti['bytes_uploaded']} B   sparse wall {wb:8.3f} update_ms {ub['update_ms']:8.3f} refit_ms {si['refit_ms']:7.3f} path {si['path']} uploaded {si['bytes_uploaded']} B"
+                f"   caller's numpy {numpy_ms:8.3f} ms")
+            if k:
+                rows.append((wa, ua["update_ms"], ti["refit_ms"], wb, ub["update_ms"], si["refit_ms"], numpy_ms))
+        m_ = [med([r[i] for r in rows]) for i in range(7)]
+        say(f"      medians of rounds 1..{rounds}: transform wall {m_[0]:.3f} update_ms {m_[1]:.3f} refit_ms {m_[2]:.3f}   sparse wall {m_[3]:.3f} update_ms {m_[4]:.3f} refit_ms {m_[5]:.3f}"
+            f"   caller's numpy {m_[6]:.3f}   transform / sparse: wall {m_[0] / m_[3]:.4f}, refit {m_[2] / m_[5]:.4f}; with the caller's numpy {m_[0] / (m_[3] + m_[6]):.4f}")
+    a.close()
+    b.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C2,C4")
@@ -283,12 +344,16 @@ def main():
     ap.add_argument("--log")
     ap.add_argument("--rebuild", action="store_true", help="the rebuild policies of er_update_policy_set instead of the update / refit figures")
     ap.add_argument("--sparse", action="store_true", help="er_render_update_sparse against the full and the camera-only update")
+    ap.add_argument("--transform", action="store_true", help="er_render_transform against er_render_update_sparse of the same pose (C4)")
     ap.add_argument("--ratio", type=float, default=2.0, help="--rebuild: max_cost_ratio of the ER_REBUILD_AUTO runs")
     args = ap.parse_args()
     if args.log:
         global LOG
         LOG = args.log
         open(LOG, "w").close()
+    if args.transform:
+        transform_bench("C4", scenes.blob_instances(x_res=3840, y_res=2160), 8, max(7, args.rounds), 10000)
+        return
     for cfg in args.configs.split(","):
         if args.sparse:
             if cfg == "C2":
