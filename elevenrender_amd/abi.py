@@ -26,6 +26,9 @@ EDIT_CAMERA, EDIT_GEOMETRY, EDIT_MATERIALS, EDIT_TEXTURES, EDIT_HDRI = 1, 2, 4, 
 REBUILD_NEVER, REBUILD_ALWAYS, REBUILD_AUTO = 0, 1, 2     # ErUpdatePolicy.mode
 FEATURE_ALBEDO, FEATURE_DEPTH, FEATURE_COUNT = 0, 1, 2     # er_render_features (csrc/er_features.hip)
 FEATURE_NAMES = {"albedo": 0, "depth": 1}
+ID_NONE, ID_SLOTS = 0xFFFFFFFF, 4     # er_render_ids (csrc/er_ids.hip)
+ID_TRIANGLE, ID_OBJECT, ID_MATERIAL, ID_KIND_COUNT = 0, 1, 2, 3
+ID_KIND_NAMES = {"triangle": 0, "object": 1, "material": 2}
 
 
 class ErVec3(C.Structure):
@@ -203,6 +206,16 @@ class ErDenoiseGuided(C.Structure):
     _fields_ = [("levels", C.c_uint32), ("colour_sigma", C.c_float), ("albedo_sigma", C.c_float), ("depth_sigma", C.c_float)]
 
 
+class ErIdInfo(C.Structure):
+    _fields_ = [("valid", C.c_uint32), ("samples", C.c_uint32), ("rays", C.c_uint64), ("ms", C.c_float), ("objects", C.c_uint32),
+                ("overflow_pixels", C.c_uint32 * ID_KIND_COUNT)]
+
+
+class ErPick(C.Structure):
+    _fields_ = [("hit", C.c_uint32), ("triangle", C.c_uint32), ("object", C.c_uint32), ("material", C.c_uint32), ("distance", C.c_float),
+                ("position", C.c_float * 3), ("uv", C.c_float * 2)]
+
+
 class ErStreamInfo(C.Structure):   # include/eleven_hip_debug.h
     _fields_ = [("waves", C.c_uint32), ("tracers", C.c_uint32), ("large_regions", C.c_uint32), ("deal_pending", C.c_uint32), ("launches", C.c_uint32),
                 ("pixels_per_cu", C.c_uint32), ("lanes_busy", C.c_double), ("launch_ms", C.c_double), ("cost_spread", C.c_double),
@@ -282,6 +295,17 @@ def debug_transform_apply(m, vertices, normals, tangents):
     return tuple(out)
 
 
+def debug_id_rank(ids):
+    """include/eleven_hip_debug.h er_debug_id_rank: the ranking er_render_ids gives a pixel (csrc/er_ids.h, the function the kernel calls;
+    no device needed) for the ids of its rays that hit, at most 64: (slot ids uint32[4], slot counts uint32[4], distinct ids)."""
+    lib = load()
+    a = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+    oi, oc, distinct = np.zeros(ID_SLOTS, np.uint32), np.zeros(ID_SLOTS, np.uint32), C.c_uint32()
+    up = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))
+    check(lib.er_debug_id_rank(up(a) if a.size else None, a.size, up(oi), up(oc), C.byref(distinct)))
+    return oi, oc, distinct.value
+
+
 def _cost_dict(sums, node_terms, tri_terms):
     d = {n: getattr(sums, n) for n in ("node_area", "leaf_area", "tri_area", "cost", "ms")}
     d.update(node_terms=node_terms, tri_terms=tri_terms)
@@ -326,7 +350,7 @@ class ErTraceRec(C.Structure):   # include/eleven_hip_debug.h; same layout as th
 
 # every symbol include/eleven_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
-_FP, _IP = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+_FP, _IP, _UP = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
 SYMBOLS = {
     "er_abi_version": (C.c_int, []),
     "er_last_error": (C.c_char_p, []),
@@ -371,6 +395,13 @@ SYMBOLS = {
     "er_read_feature": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
     "er_gather_feature": (C.c_int, [_P, C.c_int, _P, C.c_uint32]),
     "er_denoise_guided": (C.c_int, [_P, C.POINTER(ErDenoiseGuided)]),
+    "er_render_ids": (C.c_int, [_P, C.c_uint32]),
+    "er_id_info": (C.c_int, [_P, C.POINTER(ErIdInfo)]),
+    "er_read_ids": (C.c_int, [_P, C.c_int, _UP, _UP]),
+    "er_gather_ids": (C.c_int, [_P, C.c_int, _P, C.c_uint32]),
+    "er_id_matte": (C.c_int, [_P, C.c_int, _UP, C.c_uint32, _FP]),
+    "er_pick_rect": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _UP, C.c_uint32, _UP]),
+    "er_pick": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(ErPick)]),
     "er_state_size": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "er_state_export": (C.c_int, [_P, _P, C.c_uint64]),
     "er_state_import": (C.c_int, [_P, _P, C.c_uint64]),
@@ -421,6 +452,7 @@ OPTIONAL_SYMBOLS = {
     "er_debug_accel_cost_terms": (C.c_int, [_P, C.POINTER(ErCostSumsDebug), C.POINTER(C.c_double), C.c_uint64, _FP, C.c_uint64]),
     "er_debug_transform_apply": (C.c_int, [_FP, C.c_uint32, _FP, _FP, _FP, _FP, _FP, _FP]),
     "er_debug_accel_cost_host": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(ErCostSumsDebug), C.POINTER(C.c_double), C.c_uint64, _FP, C.c_uint64]),
+    "er_debug_id_rank": (C.c_int, [_UP, C.c_uint32, _UP, _UP, _UP]),
 }
 
 

@@ -140,6 +140,7 @@ static int begin_open(ErScene* s, const ErRenderParams* p) {
     s->params = *p;
     s->ad_on = false;      // (adaptive sampling is set per render, after its er_render_begin)
     s->feat_valid = false; // (the feature planes are of the scene state that ends here)
+    s->ids_invalidate();   // (and so are the id planes)
     s->rendered = 0;
     s->params.world = p->world ? p->world : 1;
     if (s->params.max_bounces == 0) s->params.max_bounces = 5;   // the literal of reference src/kernel.cpp:508
@@ -154,6 +155,7 @@ static int begin_open(ErScene* s, const ErRenderParams* p) {
     {
         const char* which = nullptr;
         hipError_t pe = er_probe_kernels(&which);
+        if (pe == hipSuccess) pe = er_probe_ids(&which);
         if (pe != hipSuccess)
             return fail(ER_ERR_HIP, std::string("er_render_begin: libeleven_hip.so has no usable gfx950 code object for ") + (which ? which : "?") +
                                         " on this device (" + hipGetErrorString(pe) + "); rebuild with `make -C elevenrender_amd/csrc`");

@@ -431,6 +431,7 @@ int edit_locked(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, XformL
     edit_replace(s, e, sp, xf, W);
     s->feat_valid = false;      // the feature planes show the scene before the edit (er_render_features makes them again)
     for (auto& set : s->unpacked_feat) set.clear();
+    s->ids_invalidate();        // (and so do the id planes: er_render_ids)
     uint32_t stage = 0;
     float stage_ms = 0;
     const bool sparse_geometry = sp && (e->what & ER_EDIT_GEOMETRY);
@@ -522,6 +523,8 @@ static int er_objects_set_impl(ErScene* s, uint32_t object_count, const uint32_t
         if (s->stream) (void)hipStreamSynchronize(s->stream);
         s->xform_dev.release();
     }
+    s->ids_invalidate();      // the OBJECT plane and the tri -> object map were the old table's (er_ids.hip)
+    s->id_map_valid = false;
     return ER_OK;
 }
 

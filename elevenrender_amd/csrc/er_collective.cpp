@@ -203,21 +203,14 @@ static int er_comm_create_local_impl(uint32_t world, ErComm** out) {
 
 // pack -> exchange -> unpack of ONE plane (ER_PASS_COUNT = the sample-count plane).  Every rank of the communicator
 // calls it with its own scene; after it the root's full plane holds every rank's pixels.
-// (`feature`: the plane is feature `pass` of er_features.hip -- a row-major plane of its own -- instead of pass `pass` of DevScene::passes;
-// the exchange is the same, the pack and unpack kernels address the plane)
-static int gather_impl(ErScene* s, int pass, bool feature, ErComm* c, uint32_t root) {
-    const std::string who_s = feature ? "er_gather_feature" : "er_gather_pass";
-    const char* who = feature ? "er_gather_feature" : "er_gather_pass";
-    if (!s || !c) return fail(ER_ERR_INVALID_ARG, who_s + ": NULL argument");
-    if (pass < 0 || pass >= (feature ? (int)ER_FEATURE_COUNT : (int)ER_PASS_COUNT)) return fail(ER_ERR_INVALID_ARG, who_s + (feature ? ": feature out of range" : ": pass out of range"));
-    if (root >= c->world) return fail(ER_ERR_INVALID_ARG, who_s + ": root >= world");
-    std::lock_guard<std::mutex> lk(s->mtx);
-    if (!s->begun) return fail(ER_ERR_STATE, who_s + ": er_render_begin has not succeeded");
-    if (feature && !s->feat_valid) return fail(ER_ERR_STATE, who_s + ": no feature planes of this scene state (er_render_features)");
+// `plane`: a row-major plane of 16 bytes per pixel of its own (a feature plane of er_features.hip, an id or count plane of er_ids.hip:
+// the pack and unpack kernels copy bits) -- or NULL: pass `pass` of DevScene::passes.  The exchange is the same.  `unpacked`, if given,
+// notes at the root whose pixels arrived.  The caller has checked its arguments, holds the scene's mutex and has seen it begun.
+static int gather_plane(ErScene* s, int pass, float4* plane, const char* who, std::set<uint32_t>* unpacked, ErComm* c, uint32_t root) {
+    const std::string who_s = who;
     if (s->params.world != c->world || s->params.rank != c->rank)
         return fail(ER_ERR_INVALID_ARG, who_s + ": the scene's rank/world differ from the communicator's");
     if (c->world == 1) return ER_OK;     // the plane is already whole
-    float4* const plane = feature ? s->d_feat.p + (size_t)pass * s->x_res * s->y_res : nullptr;
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = s->stream;          // ordered after every sample enqueued so far
     int rc;
@@ -225,7 +218,7 @@ static int gather_impl(ErScene* s, int pass, bool feature, ErComm* c, uint32_t r
         const size_t n = (size_t)s->dev.owned_tile_count * 64;
         DevBuf<float4>& mine = s->d_gather_mine;          // (kept on the scene: allocated by the first gather)
         if (mine.n < n || !mine.p) { if ((rc = upload(mine, (const float4*)nullptr, n, st)) != ER_OK) return rc; }
-        if (feature) er_launch_pack_plane(s->dev, s->d_owned.p, s->dev.owned_tile_count, plane, mine.p, st);
+        if (plane) er_launch_pack_plane(s->dev, s->d_owned.p, s->dev.owned_tile_count, plane, mine.p, st);
         else er_launch_pack(s->dev, s->d_owned.p, s->dev.owned_tile_count, pass, mine.p, st);
         HIP_TRY(hipGetLastError());
         if ((rc = c->t.group_start(c->self)) != ER_OK) return rc;
@@ -266,13 +259,43 @@ static int gather_impl(ErScene* s, int pass, bool feature, ErComm* c, uint32_t r
     for (uint32_t r = 0; r < c->world; r++) {
         if (r == root) continue;
         const DevBuf<uint32_t>& tiles = s->d_rank_tiles[r];
-        if (feature) er_launch_unpack_plane(s->dev, tiles.p, (uint32_t)tiles.n, plane, in[r], st);
+        if (plane) er_launch_unpack_plane(s->dev, tiles.p, (uint32_t)tiles.n, plane, in[r], st);
         else er_launch_unpack(s->dev, tiles.p, (uint32_t)tiles.n, pass, in[r], st);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    for (uint32_t r = 0; r < c->world; r++) if (r != root) (feature ? s->unpacked_feat[pass] : s->unpacked[pass]).insert(r);
+    if (unpacked) for (uint32_t r = 0; r < c->world; r++) if (r != root) unpacked->insert(r);
     return er_scene_stream_status(s, who);
+}
+
+// the three gathers: their own checks, then gather_plane per plane
+static int gather_pass_impl(ErScene* s, int pass, ErComm* c, uint32_t root) {
+    if (!s || !c) return fail(ER_ERR_INVALID_ARG, "er_gather_pass: NULL argument");
+    if (pass < 0 || pass >= (int)ER_PASS_COUNT) return fail(ER_ERR_INVALID_ARG, "er_gather_pass: pass out of range");
+    if (root >= c->world) return fail(ER_ERR_INVALID_ARG, "er_gather_pass: root >= world");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_gather_pass: er_render_begin has not succeeded");
+    return gather_plane(s, pass, nullptr, "er_gather_pass", &s->unpacked[pass], c, root);
+}
+static int gather_feature_impl(ErScene* s, int feature, ErComm* c, uint32_t root) {
+    if (!s || !c) return fail(ER_ERR_INVALID_ARG, "er_gather_feature: NULL argument");
+    if (feature < 0 || feature >= (int)ER_FEATURE_COUNT) return fail(ER_ERR_INVALID_ARG, "er_gather_feature: feature out of range");
+    if (root >= c->world) return fail(ER_ERR_INVALID_ARG, "er_gather_feature: root >= world");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_gather_feature: er_render_begin has not succeeded");
+    if (!s->feat_valid) return fail(ER_ERR_STATE, "er_gather_feature: no feature planes of this scene state (er_render_features)");
+    return gather_plane(s, feature, s->d_feat.p + (size_t)feature * s->x_res * s->y_res, "er_gather_feature", &s->unpacked_feat[feature], c, root);
+}
+static int gather_ids_impl(ErScene* s, int kind, ErComm* c, uint32_t root) {
+    if (!s || !c) return fail(ER_ERR_INVALID_ARG, "er_gather_ids: NULL argument");
+    if (kind < 0 || kind >= (int)ER_ID_KIND_COUNT) return fail(ER_ERR_INVALID_ARG, "er_gather_ids: kind out of range");
+    if (root >= c->world) return fail(ER_ERR_INVALID_ARG, "er_gather_ids: root >= world");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_gather_ids: er_render_begin has not succeeded");
+    if (!s->ids_valid) return fail(ER_ERR_STATE, "er_gather_ids: no id planes of this scene state (er_render_ids)");
+    float4* const ids = s->d_id_planes.p + (size_t)(2 * kind) * s->x_res * s->y_res;      // (the kind's id plane, then its count plane: er_scene.h)
+    const int rc = gather_plane(s, kind, ids, "er_gather_ids", nullptr, c, root);
+    return rc != ER_OK ? rc : gather_plane(s, kind, ids + (size_t)s->x_res * s->y_res, "er_gather_ids", nullptr, c, root);
 }
 
 static int er_debug_gather_buffers_impl(ErScene* s, uint32_t peer, void** in_ptr, uint64_t* in_bytes, void** mine_ptr, uint64_t* mine_bytes) {
@@ -333,10 +356,13 @@ void er_comm_destroy(ErComm* c) {
     delete c;
 }
 int er_gather_pass(ErScene* s, int pass, ErComm* c, uint32_t root) {
-    return guarded("er_gather_pass", [&]() -> int { return gather_impl(s, pass, false, c, root); });
+    return guarded("er_gather_pass", [&]() -> int { return gather_pass_impl(s, pass, c, root); });
 }
 int er_gather_feature(ErScene* s, int feature, ErComm* c, uint32_t root) {
-    return guarded("er_gather_feature", [&]() -> int { return gather_impl(s, feature, true, c, root); });
+    return guarded("er_gather_feature", [&]() -> int { return gather_feature_impl(s, feature, c, root); });
+}
+int er_gather_ids(ErScene* s, int kind, ErComm* c, uint32_t root) {
+    return guarded("er_gather_ids", [&]() -> int { return gather_ids_impl(s, kind, c, root); });
 }
 int er_comm_create_local(uint32_t world, ErComm** out) {
     return guarded("er_comm_create_local", [&]() -> int { return er_comm_create_local_impl(world, out); });

@@ -557,4 +557,12 @@ int er_debug_transform_apply(const float* m, uint32_t count, const float* v, con
         return ER_OK;
     });
 }
+int er_debug_id_rank(const uint32_t* ids, uint32_t count, uint32_t* out_ids, uint32_t* out_counts, uint32_t* distinct) {
+    return guarded("er_debug_id_rank", [&]() -> int {
+        if ((count && !ids) || !out_ids || !out_counts || !distinct) return fail(ER_ERR_INVALID_ARG, "er_debug_id_rank: NULL argument");
+        if (count > 64) return fail(ER_ERR_INVALID_ARG, "er_debug_id_rank: at most 64 ids");
+        *distinct = er_id_rank(ids, 1, count, out_ids, out_counts);
+        return ER_OK;
+    });
+}
 }  // extern "C"

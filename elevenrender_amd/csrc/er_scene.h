@@ -33,6 +33,7 @@
 #include "er_texplan.h"
 #include "er_texstage.h"
 #include "er_features.h"
+#include "er_ids.h"
 
 namespace erh {
 
@@ -256,6 +257,19 @@ struct ErScene {
     uint64_t feat_rays = 0;
     float feat_ms = 0;
     std::set<uint32_t> unpacked_feat[ER_FEATURE_COUNT];
+    // the id pass (er_ids.hip): per kind an id plane and a count plane, 16 bytes per pixel each, back to back -- plane 2 * kind + 0 /
+    // + 1, row-major, allocated by the first er_render_ids; ids_valid from a pass until the next er_render_begin, edit of any kind or
+    // er_objects_set (ids_invalidate).  d_id_map: tri -> object of the current table (tri_count words), made again when the table
+    // changed.  d_id_work: the words the consumers work in, grown on demand and kept (er_pick_rect: marks, block counts, offsets, the
+    // selection; er_id_matte: the plane and the list; er_pick: one ErPick).  d_id_over: the pass's three overflow counters.  The
+    // traversal's spill area is the feature pass's (d_feat_spill): both passes run alone on the scene's stream.
+    DevBuf<float4> d_id_planes;
+    DevBuf<uint32_t> d_id_map, d_id_work, d_id_over;
+    bool ids_valid = false, id_map_valid = false;
+    uint32_t ids_samples = 0, ids_objects = 0, ids_overflow[ER_ID_KIND_COUNT] = {0, 0, 0};
+    uint64_t ids_rays = 0;
+    float ids_ms = 0;
+    void ids_invalidate() noexcept { ids_valid = false; }
     std::mutex mtx;
 
     uint32_t tiles_x() const { return (x_res + ER_TILE - 1) / ER_TILE; }      // the frame in tiles of ER_TILE x ER_TILE pixels
@@ -284,6 +298,7 @@ struct ErScene {
         xform_dev.release();
         d_feat.release(); d_feat_spill.release(); feat_valid = false;
         for (auto& u : unpacked_feat) u.clear();
+        d_id_planes.release(); d_id_map.release(); d_id_work.release(); d_id_over.release(); ids_valid = id_map_valid = false;
         ad_on = false; rendered = 0;
         for (auto& kv : d_rank_tiles) kv.second.release();
         d_rank_tiles.clear();

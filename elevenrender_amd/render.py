@@ -382,6 +382,59 @@ class RenderingManager:
         p = abi.ErDenoiseGuided(levels, colour_sigma, albedo_sigma, depth_sigma)
         abi.check(self.lib.er_denoise_guided(self.handle, C.byref(p)))
 
+    @staticmethod
+    def _id_kind(kind):
+        """ "triangle" | "object" | "material", or the integer of ErIdKind"""
+        return abi.ID_KIND_NAMES[kind.lower()] if isinstance(kind, str) else int(kind)
+
+    def render_ids(self, n=0):
+        """er_render_ids: n camera rays per owned pixel (0 -> 4) into the id planes of the three kinds; the render's own state is neither
+        read nor written."""
+        abi.check(self.lib.er_render_ids(self.handle, n))
+
+    def get_ids(self, kind):
+        """er_read_ids: (ids, counts), each (H, W, 4) uint32 -- a pixel's distinct first-hit ids by (count descending, id ascending),
+        unused slots (abi.ID_NONE, 0)."""
+        shape = (self.scene.y_res, self.scene.x_res, abi.ID_SLOTS)
+        ids, counts = np.empty(shape, np.uint32), np.empty(shape, np.uint32)
+        up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        abi.check(self.lib.er_read_ids(self.handle, self._id_kind(kind), up(ids), up(counts)))
+        return ids, counts
+
+    def id_info(self):
+        a = abi.ErIdInfo()
+        abi.check(self.lib.er_id_info(self.handle, C.byref(a)))
+        d = {n: getattr(a, n) for n, _ in abi.ErIdInfo._fields_ if n != "overflow_pixels"}
+        d["overflow_pixels"] = tuple(a.overflow_pixels)
+        return d
+
+    def id_matte(self, kind, ids):
+        """er_id_matte: the (H, W) float32 coverage of the listed ids (a set; abi.ID_NONE is a legal member): the counts of the pixel's
+        slots that hold one of them, over the pass's n.  Computed on the device."""
+        lst = np.ascontiguousarray(np.atleast_1d(ids), np.uint32).reshape(-1)
+        out = np.empty((self.scene.y_res, self.scene.x_res), np.float32)
+        abi.check(self.lib.er_id_matte(self.handle, self._id_kind(kind), lst.ctypes.data_as(C.POINTER(C.c_uint32)) if lst.size else None, lst.size,
+                                       out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def pick_rect(self, x0, y0, x1, y1, kind):
+        """er_pick_rect: the distinct ids shown in the half-open rectangle [x0, x1) x [y0, y1), ascending, as a uint32 array: one call for
+        the size, one that fetches."""
+        k, n = self._id_kind(kind), C.c_uint32()
+        abi.check(self.lib.er_pick_rect(self.handle, x0, y0, x1, y1, k, None, 0, C.byref(n)))
+        out = np.empty(n.value, np.uint32)
+        if n.value:
+            abi.check(self.lib.er_pick_rect(self.handle, x0, y0, x1, y1, k, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size, C.byref(n)))
+        return out[:min(n.value, out.size)]
+
+    def pick(self, x, y):
+        """er_pick: what ray 0 of pixel (x, y) hits -- a dict of hit, triangle, object, material (abi.ID_NONE on a miss or outside every
+        object), distance, position (3 floats), uv (2 floats).  Needs no id pass and answers for any pixel of the frame."""
+        p = abi.ErPick()
+        abi.check(self.lib.er_pick(self.handle, x, y, C.byref(p)))
+        return dict(hit=int(p.hit), triangle=int(p.triangle), object=int(p.object), material=int(p.material), distance=np.float32(p.distance),
+                    position=np.array(list(p.position), np.float32), uv=np.array(list(p.uv), np.float32))
+
     def read_samples(self):
         out = np.empty(self.scene.x_res * self.scene.y_res, np.uint32)
         abi.check(self.lib.er_read_samples(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint32))))

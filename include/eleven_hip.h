@@ -575,6 +575,60 @@ int er_read_feature(ErScene* scene, int feature, float* dst_rgba);
 int er_gather_feature(ErScene* scene, int feature, ErComm* comm, uint32_t root);
 int er_denoise_guided(ErScene* scene, const ErDenoiseGuided* params);
 
+/* Id planes, coverage mattes and picking from a first-hit id pass (extension; csrc/er_ids.h and er_ids.hip).
+ * er_render_ids: the rays of er_render_features -- n camera rays per owned pixel (0 -> 4, more than 64: ER_ERR_INVALID_ARG), ray 0 the
+ * camera ray of the render's first sample, no opacity draw -- but the ids of what they hit are kept instead of shaded.  The id of a ray
+ * that hits, per kind:
+ *   ER_ID_TRIANGLE  the scene index of the triangle
+ *   ER_ID_OBJECT    the index of the object of the scene's current table (er_objects_set) that lists it; ER_ID_NONE if none does, or
+ *                   if the scene has no table
+ *   ER_ID_MATERIAL  the triangle's current material_id
+ * Per pixel and kind the distinct ids of the rays that hit are ordered by (count descending, id ascending as unsigned); the first
+ * ER_ID_SLOTS become the pixel's slots (id, count), unused slots are (ER_ID_NONE, 0).  A hit on geometry in no object is an entry like
+ * any other: id ER_ID_NONE, count > 0, last among equal counts.  Misses contribute nothing.  Ids beyond the fourth are dropped and the
+ * pixel counts in ErIdInfo.overflow_pixels[kind].  Pixels of other ranks read as empty slots until gathered.
+ * Like the feature pass it reads neither planes, sample counts, RNG nor counters of the render and writes none of them; its rays are
+ * in ErIdInfo, not in ErCounters.  Pending asynchronous work is waited for.  The planes are allocated by the first call (96 bytes per
+ * pixel), freed with the scene and not part of er_state_*.  er_render_begin, every successful er_render_update, er_render_edit,
+ * er_render_update_sparse and er_render_transform, and a successful er_objects_set invalidate them: er_read_ids, er_gather_ids,
+ * er_id_matte and er_pick_rect return ER_ERR_STATE until the pass has run again.  Before er_render_begin all seven entry points return
+ * ER_ERR_STATE; NULL arguments and a kind out of range are ER_ERR_INVALID_ARG.
+ * er_read_ids: both planes of one kind, row-major, [y_res * x_res][ER_ID_SLOTS] each; either destination may be NULL, not both.
+ * er_gather_ids: er_gather_feature for both planes of one kind.
+ * er_id_matte: dst[p] = (float)(sum of the counts of pixel p's slots whose id is in the list) / (float)n, computed on the device.  The
+ * list is a set: duplicates are allowed and ER_ID_NONE is a legal member; count 0 or a NULL list: ER_ERR_INVALID_ARG.  It reads the
+ * planes as they lie: ungathered pixels give 0.
+ * er_pick_rect: the distinct ids with count > 0 in any slot of any pixel of the half-open rectangle [x0, x1) x [y0, y1), ascending as
+ * unsigned, reduced on the device; at most `capacity` of them are written, *count is the number found (ids may be NULL with capacity
+ * 0 to ask for it).  x0 >= x1, y0 >= y1, x1 > x_res or y1 > y_res: ER_ERR_INVALID_ARG.
+ * er_pick: needs a begun scene only, no id pass.  It traces ray 0 of pixel (x, y) -- any pixel of the frame, whichever rank owns it
+ * -- and reports what it hits; the object comes from the current table, also right after er_render_transform.  It leaves the render's
+ * state, its counters and the id planes alone.  x or y outside the frame: ER_ERR_INVALID_ARG. */
+#define ER_ID_NONE  0xFFFFFFFFu
+#define ER_ID_SLOTS 4
+typedef enum ErIdKind { ER_ID_TRIANGLE = 0, ER_ID_OBJECT = 1, ER_ID_MATERIAL = 2, ER_ID_KIND_COUNT = 3 } ErIdKind;
+typedef struct ErIdInfo {
+    uint32_t valid;           /* 1 between an id pass and whatever invalidates it (above) */
+    uint32_t samples;         /* n of the last pass */
+    uint64_t rays;            /* camera rays it traced: n x the owned pixels inside the frame */
+    float ms;                 /* its device time (HIP events) */
+    uint32_t objects;         /* object count of the table the OBJECT plane was made with (0: none) */
+    uint32_t overflow_pixels[ER_ID_KIND_COUNT];   /* owned pixels with more than ER_ID_SLOTS distinct ids of that kind */
+} ErIdInfo;
+typedef struct ErPick {
+    uint32_t hit, triangle, object, material;     /* a miss: 0, ER_ID_NONE x 3, every float 0 */
+    float distance;           /* length(Hit.position - ray.o): the operations of ER_FEATURE_DEPTH */
+    float position[3];        /* Hit.position */
+    float uv[2];              /* the texture coordinates the shading step sees */
+} ErPick;
+int er_render_ids(ErScene* scene, uint32_t n);
+int er_id_info(ErScene* scene, ErIdInfo* out);
+int er_read_ids(ErScene* scene, int kind, uint32_t* ids /*[y_res * x_res][ER_ID_SLOTS]*/, uint32_t* counts /*the same shape*/);
+int er_gather_ids(ErScene* scene, int kind, ErComm* comm, uint32_t root);
+int er_id_matte(ErScene* scene, int kind, const uint32_t* ids, uint32_t count, float* dst /*[y_res * x_res]*/);
+int er_pick_rect(ErScene* scene, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, int kind, uint32_t* ids, uint32_t capacity, uint32_t* count);
+int er_pick(ErScene* scene, uint32_t x, uint32_t y, ErPick* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -280,6 +280,12 @@ void er_debug_set_gpu_build_failure(int kind);
 int er_debug_transform_apply(const float m[12], uint32_t count, const float* vertices, const float* normals, const float* tangents,
                              float* out_vertices, float* out_normals, float* out_tangents);
 
+/* The ranking er_render_ids gives every pixel (csrc/er_ids.h er_id_rank, the function the kernel calls), on caller arrays, no device
+ * needed: `count` <= 64 ids of the rays that hit (NULL with count 0) -> out_ids / out_counts [ER_ID_SLOTS] by (count descending, id
+ * ascending as unsigned), unused slots (ER_ID_NONE, 0); *distinct = the number of distinct ids.  ER_ERR_INVALID_ARG: a NULL argument,
+ * count > 64. */
+int er_debug_id_rank(const uint32_t* ids, uint32_t count, uint32_t* out_ids, uint32_t* out_counts, uint32_t* distinct);
+
 #ifdef __cplusplus
 }
 #endif
