@@ -24,6 +24,7 @@ FLAG_MESH_LIGHTS = 1024     # next-event estimation of emissive triangles (csrc/
 UPDATE_CAMERA, UPDATE_GEOMETRY = 1, 2     # ErSceneUpdate.what
 EDIT_CAMERA, EDIT_GEOMETRY, EDIT_MATERIALS, EDIT_TEXTURES, EDIT_HDRI = 1, 2, 4, 8, 16     # ErSceneEdit.what
 REBUILD_NEVER, REBUILD_ALWAYS, REBUILD_AUTO = 0, 1, 2     # ErUpdatePolicy.mode
+TOPO_REMOVE, TOPO_APPEND = 1, 2     # ErTopologyEdit.what
 FEATURE_ALBEDO, FEATURE_DEPTH, FEATURE_COUNT = 0, 1, 2     # er_render_features (csrc/er_features.hip)
 FEATURE_NAMES = {"albedo": 0, "depth": 1}
 ID_NONE, ID_SLOTS = 0xFFFFFFFF, 4     # er_render_ids (csrc/er_ids.hip)
@@ -158,6 +159,18 @@ class ErSceneEdit(C.Structure):
 
 class ErEditInfo(C.Structure):
     _fields_ = [("edits", C.c_uint32), ("texture_stage", C.c_uint32), ("texture_stage_ms", C.c_float), ("edit_ms", C.c_float), ("pool_floats", C.c_uint64)]
+
+
+class ErTopologyEdit(C.Structure):
+    _fields_ = [("what", C.c_uint32), ("remove_count", C.c_uint32), ("remove_ids", C.POINTER(C.c_uint32)), ("append_count", C.c_uint32),
+                ("vertices", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)), ("tangents", C.POINTER(C.c_float)), ("uvs", C.POINTER(C.c_float)),
+                ("tangent_sign", C.POINTER(C.c_float)), ("material_id", C.POINTER(C.c_int32)), ("append_as_object", C.c_uint32), ("rest", ErSceneEdit)]
+
+
+class ErTopologyInfo(C.Structure):
+    _fields_ = [("calls", C.c_uint32), ("removed", C.c_uint32), ("appended", C.c_uint32), ("tri_count", C.c_uint32), ("path", C.c_uint32),
+                ("texture_stage", C.c_uint32), ("bytes_uploaded", C.c_uint64), ("build_ms", C.c_float), ("store_ms", C.c_float), ("edit_ms", C.c_float),
+                ("texture_stage_ms", C.c_float)]
 
 
 class ErAccelCost(C.Structure):
@@ -384,6 +397,8 @@ SYMBOLS = {
     "er_accel_cost": (C.c_int, [_P, C.POINTER(ErAccelCost)]),
     "er_update_policy_set": (C.c_int, [_P, C.POINTER(ErUpdatePolicy)]),
     "er_rebuild_info": (C.c_int, [_P, C.POINTER(ErRebuildInfo)]),
+    "er_render_topology": (C.c_int, [_P, C.POINTER(ErTopologyEdit)]),
+    "er_topology_info": (C.c_int, [_P, C.POINTER(ErTopologyInfo)]),
     "er_adaptive_set": (C.c_int, [_P, C.POINTER(ErAdaptiveParams)]),
     "er_adaptive_info": (C.c_int, [_P, C.POINTER(ErAdaptiveInfo)]),
     "er_read_tile_state": (C.c_int, [_P, _FP, C.POINTER(C.c_uint32)]),

@@ -199,27 +199,34 @@ static int accel_upload_host(ErScene* s, BeginStaging& B) {
     return upload(s->d_attr, attr.data(), g.attr_f4, s->stream);
 }
 
+// whether stage 2 asks the device builder first
+bool accel_device_first(const ErScene* s) {
+    // Which builder: the device build (er_gpu_build.hip: the host builder's binned SAH, level by level on the GPU -- the same tree in a
+    // fraction of the time) unless the scene is small enough for the host to be done before the device has started, or the caller says so.
+    const uint32_t flags = s->params.flags;
+    const bool force_dev = (flags & ER_FLAG_GPU_BUILD) || getenv("ER_GPU_BUILD");
+    const bool force_host = !force_dev && ((flags & ER_FLAG_HOST_BUILD) || getenv("ER_HOST_BUILD"));
+    uint32_t min_tris = ER_GPU_BUILD_MIN_TRIS;
+    if (const char* e = getenv("ER_GPU_BUILD_MIN_TRIS")) min_tris = (uint32_t)std::max(0, atoi(e));
+    return !force_host && (force_dev || s->tri_count >= min_tris) && s->tri_count > ER_BVH_LEAF_MAX;
+}
+
 // stage 2: the acceleration structure, by the device build or the host's binned-SAH build.  Either builder fills ONE description, `g`,
 // ONE block of checks runs on it, it is kept in s->kept.accel (the scene owns the buffers either way: the record's three pointers are
 // null), and s->accel.builder says who built.  `built_ev` is recorded when the tree is there and the uploads begin.
-int begin_accel(ErScene* s, BeginStaging& B, hipEvent_t built_ev, const char* who) {
+int begin_accel(ErScene* s, BeginStaging& B, hipEvent_t built_ev, const char* who, const ErGpuSceneArrays* device_arrays) {
     const std::string W = who;
     ErGpuBvhDevice g;
     s->flush_poses();      // (er_render_transform leaves the host arrays behind: the builders read them)
     const uint32_t flags = s->params.flags;
     const size_t n = s->tri_count;
     bool built = false;
-    // Which builder: the device build (er_gpu_build.hip: the host builder's binned SAH, level by level on the GPU -- the same tree in a
-    // fraction of the time) unless the scene is small enough for the host to be done before the device has started, or the caller says so.
     const bool force_dev = (flags & ER_FLAG_GPU_BUILD) || getenv("ER_GPU_BUILD");
-    const bool force_host = !force_dev && ((flags & ER_FLAG_HOST_BUILD) || getenv("ER_HOST_BUILD"));
-    uint32_t min_tris = ER_GPU_BUILD_MIN_TRIS;
-    if (const char* e = getenv("ER_GPU_BUILD_MIN_TRIS")) min_tris = (uint32_t)std::max(0, atoi(e));
-    if (!force_host && (force_dev || s->tri_count >= min_tris) && s->tri_count > ER_BVH_LEAF_MAX) {
+    if (accel_device_first(s)) {
         // whole structure on the device: tree, wide-node collapse, slot order, triangle records
         std::string why;
         ErGpuSceneArrays arrays{s->vertices.data(), s->normals.data(), s->tangents.data(), s->uvs.data(), s->tangent_sign.data(), s->material_id.data()};
-        int brc = er_gpu_build_device(arrays, s->tri_count, s->device, &g, why);
+        int brc = device_arrays ? er_gpu_build_device_arrays(*device_arrays, s->tri_count, s->device, &g, why) : er_gpu_build_device(arrays, s->tri_count, s->device, &g, why);
         if (brc < 0 && force_dev) return fail(brc == -2 ? ER_ERR_OOM : ER_ERR_HIP, W + ": device BVH build: " + why);
         // What a default device build that did not deliver means: a DECLINE (> 0: too few triangles, a tree deeper than the
         // traversal stacks) and OUT OF DEVICE MEMORY (-2: the build's transient buffers beside other scenes or ranks) are ordinary -- the

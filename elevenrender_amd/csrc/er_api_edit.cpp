@@ -7,12 +7,17 @@
 // er_render_transform is the same function a third time: its list of posed OBJECTS (er_xform.h) takes the place of the sparse list in the
 // same three places -- checked in O(objects), the host copy only marked (ErScene::flush_poses applies the marks where the arrays are
 // read), the listed triangles posed on the device by the refit itself.  Also here: er_objects_set.
+// er_render_topology (at the end) changes WHICH triangles there are: its own checks and renumbering (er_topology_host.h), the checks and
+// the replacement of edit_locked for its `rest`, the geometry store (er_topology.h) in front of begin_accel, then the same stages.
 #include <algorithm>
 #include <chrono>
 
 #include "er_api_stages.h"
+#include "er_topology_host.h"
 
 using namespace erh;
+
+static_assert(ER_TOPO_REMOVE == ER_TOPO_HOST_REMOVE && ER_TOPO_APPEND == ER_TOPO_HOST_APPEND, "er_topology_host.h restates the two bits");
 
 static_assert(ER_EDIT_CAMERA == ER_UPDATE_CAMERA && ER_EDIT_GEOMETRY == ER_UPDATE_GEOMETRY, "an ErSceneUpdate's bits are the first two of an ErSceneEdit");
 
@@ -171,6 +176,30 @@ int edit_materials(ErScene* s, BeginStaging& B, bool new_ids) {
 // What the checks prepare of the lists that change size, so that nothing of the scene is replaced before the last check has passed
 // and nothing can fail between the first replacement and the last (moves and swaps only).  The arrays whose size the scene fixes
 // need no copy beside the scene's: edit_replace.
+// er_render_topology's side of edit_check: `rest` is checked against the RESULT of the topology edit
+struct TopoCtx {
+    const ErTopoList* l = nullptr;
+    const std::vector<uint32_t>* sorted = nullptr;      // the removed ids, ascending
+    uint32_t new_count = 0;
+};
+
+// the material ids the edited scene will hold against a list of nmat: those given for the whole result, or the appended ones and --
+// `kept_too`: the list may have shrunk -- the survivors'
+int topo_check_material_ids(const ErScene* s, const int32_t* given, bool kept_too, const TopoCtx& tc, size_t nmat, const char* who) {
+    int rc;
+    if (given) return check_material_ids(given, tc.new_count, nmat, who);
+    if (kept_too) {
+        const std::vector<uint32_t>& gone = *tc.sorted;
+        uint32_t from = 0;
+        for (size_t k = 0; k <= gone.size(); k++) {      // the runs between removed ids
+            const uint32_t to = k < gone.size() ? gone[k] : s->tri_count;
+            if (to > from && (rc = check_material_ids(s->material_id.data() + from, to - from, nmat, who)) != ER_OK) return rc;
+            from = to + 1;
+        }
+    }
+    return check_material_ids(tc.l->material_id, tc.l->appends(), nmat, who);
+}
+
 struct EditWork {
     bool rebuild_pool = false;            // the pool is laid out again and filled on the device
     std::vector<ErMaterial> materials;
@@ -289,11 +318,11 @@ int edit_device(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, const 
 // Every check of an edit, with nothing of the scene touched; W gets the new lists that the replacement will move in.  sp: the
 // geometry bit's arrays are that list's (er_render_update_sparse), checked in O(count); xf: they are the listed objects' poses
 // (er_render_transform), checked in O(objects listed), and xf gets the upload entries.
-int edit_check(const ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, XformList* xf, uint32_t known, const char* who, EditWork& W) {
+int edit_check(const ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, XformList* xf, uint32_t known, const char* who, EditWork& W, const TopoCtx* tc = nullptr) {
     const std::string pre = std::string(who) + ": ";
     const uint32_t what = e->what;
     int rc;
-    if (what == 0 || (what & ~known)) return fail(ER_ERR_INVALID_ARG, pre + "`what` names nothing, or something unknown");
+    if ((what == 0 && !tc) || (what & ~known)) return fail(ER_ERR_INVALID_ARG, pre + "`what` names nothing, or something unknown");      // (a topology edit may come alone)
     const size_t n = s->tri_count, n9 = n * 9;
     if ((what & ER_EDIT_GEOMETRY) && sp) {
         std::string why;
@@ -329,7 +358,9 @@ int edit_check(const ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, X
         mats = e->materials;
         nmat = e->material_count;
         if ((rc = check_texture_ids(mats, nmat, ntex, who)) != ER_OK) return rc;
-        if ((rc = check_material_ids(e->material_id ? e->material_id : s->material_id.data(), n, nmat, who)) != ER_OK) return rc;
+        if (tc) rc = topo_check_material_ids(s, e->material_id, true, *tc, nmat, who);
+        else rc = check_material_ids(e->material_id ? e->material_id : s->material_id.data(), n, nmat, who);
+        if (rc != ER_OK) return rc;
         ids_differ = nmat != s->materials.size();
         for (size_t m = 0; m < nmat && !ids_differ; m++) {
             int32_t a[7], b[7];
@@ -338,6 +369,7 @@ int edit_check(const ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, X
             ids_differ = memcmp(a, b, sizeof(a)) != 0;
         }
     }
+    if (tc && !(what & ER_EDIT_MATERIALS) && (rc = topo_check_material_ids(s, nullptr, false, *tc, nmat, who)) != ER_OK) return rc;
     if ((what & ER_EDIT_HDRI) && (rc = check_tex(e->hdri.texture, "hdri")) != ER_OK) return rc;
     W.rebuild_pool = (what & ER_EDIT_TEXTURES) != 0 || ids_differ;
     {   // the pool the edited scene needs, from the plan
@@ -381,9 +413,9 @@ int edit_check(const ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, X
     return ER_OK;
 }
 
-// The host copy replaced, after the last check.  Nothing here can throw or fail: er_scene_create fixes vertices, normals and tangents
-// at 9 x tri_count floats and material_id at tri_count entries for the life of the scene, so std::copy into them writes into storage
-// that is there and never allocates; the lists that change size were made in W and are swapped in.
+// The host copy replaced, after the last check.  Nothing here can throw or fail: vertices, normals and tangents hold 9 x tri_count
+// floats and material_id tri_count entries (er_scene_create; er_render_topology resizes all of them together, before it comes
+// here), so std::copy into them writes into storage that is there and never allocates; the lists that change size were made in W and are swapped in.
 // The poses that er_render_transform left pending (er_xform.h: no allocation, no failure either) are applied before a list patches the
 // arrays or a full update keeps some of them, and forgotten where all three arrays are replaced whole; a transform only marks.
 void edit_replace(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, const XformList* xf, EditWork& W) noexcept {
@@ -429,6 +461,7 @@ int edit_locked(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, XformL
     HIP_TRY(hipStreamSynchronize(s->stream));
     // the host copy, before any device work: whatever happens below, a later er_render_begin builds the edited scene
     edit_replace(s, e, sp, xf, W);
+    if ((e->what & ER_EDIT_GEOMETRY) || ((e->what & ER_EDIT_MATERIALS) && e->material_id)) s->store.release();      // er_render_topology's geometry store does not follow other edits
     s->feat_valid = false;      // the feature planes show the scene before the edit (er_render_features makes them again)
     for (auto& set : s->unpacked_feat) set.clear();
     s->ids_invalidate();        // (and so do the id planes: er_render_ids)
@@ -599,6 +632,147 @@ static int er_rebuild_info_impl(ErScene* s, ErRebuildInfo* out) {
     return ER_OK;
 }
 
+
+namespace {
+
+// ---- er_render_topology ----
+
+// The device work of a topology edit, the host copy replaced: the geometry store brought to the new numbering (compacted where it was
+// resident, else filled), the structure stage of er_render_begin on it -- the builder chosen as er_render_begin chooses it --, then the
+// stages of `rest` and the restart, as edit_device.  old_count: the triangle count before the edit (what a resident store holds).
+int topo_device(ErScene* s, const ErSceneEdit* rest, const ErTopoList& l, const std::vector<uint32_t>& sorted, uint32_t old_count, bool rebuild_pool, const char* who) {
+    int rc;
+    ErTopologyInfo& I = s->topo;
+    BeginStaging B;
+    ErGpuSceneArrays dev_arrays{};
+    const ErGpuSceneArrays* dev = nullptr;
+    if (accel_device_first(s)) {
+        std::string why;
+        int src;
+        if (s->store.valid && s->store.count == old_count) {
+            const ErGpuSceneArrays tail{l.vertices, l.normals, l.tangents, l.uvs, l.tangent_sign, l.material_id};
+            src = er_store_edit(s->store, l.removes(), sorted.data(), l.appends(), tail, s->stream, &I.bytes_uploaded, &I.store_ms, why);
+            I.path = 1u;
+        } else {
+            const ErGpuSceneArrays host{s->vertices.data(), s->normals.data(), s->tangents.data(), s->uvs.data(), s->tangent_sign.data(), s->material_id.data()};
+            src = er_store_fill(s->store, host, s->tri_count, s->stream, &I.bytes_uploaded, why);
+            I.path = 2u;
+        }
+        if (src == -1) return fail(ER_ERR_HIP, std::string(who) + ": geometry store: " + why);
+        if (src != 0) {      // out of device memory: no store, the structure stage runs as it is
+            (void)hipGetLastError();
+            I.path = 0u; I.bytes_uploaded = 0; I.store_ms = 0;
+        } else {
+            dev_arrays = s->store.arrays();
+            dev = &dev_arrays;
+        }
+    } else {
+        s->store.release();
+    }
+    s->refit_topo.release();      // (the sparse refit's kept boxes were the old tree's)
+    s->d_nodes.release(); s->d_nodes8.release(); s->d_attr.release();
+    EventPair ev;
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+    try {
+        rc = begin_accel(s, B, ev.a, who, dev);
+    } catch (...) {
+        s->begun = false;      // (as edit_rebuild: the old structure is gone)
+        throw;
+    }
+    if (rc != ER_OK) return rc;
+    HIP_TRY(hipEventRecord(ev.b, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    float up_ms = 0;
+    (void)hipEventElapsedTime(&up_ms, ev.a, ev.b);
+    accel_publish(s, up_ms);
+    if (s->accel.builder != 1u) {      // the device builder declined or failed and the host built: no store was used
+        s->store.release();
+        I.path = 0u; I.bytes_uploaded = 0; I.store_ms = 0;
+    }
+    I.build_ms = s->accel.build_ms;
+    const uint32_t what = rest->what;
+    if ((what & ER_EDIT_MATERIALS) && (rc = edit_materials(s, B, false)) != ER_OK) return rc;      // (the records have their material ids from the build)
+    if ((rc = edit_pool(s, what, rebuild_pool, B, who, I.texture_stage, I.texture_stage_ms)) != ER_OK) return rc;
+    if ((rc = edit_emitters(s, B, who)) != ER_OK) return rc;
+    return edit_restart(s, B);
+}
+
+}  // namespace
+
+static int er_render_topology_impl(ErScene* s, const ErTopologyEdit* t) {
+    const char* who = "er_render_topology";
+    if (!s || !t) return fail(ER_ERR_INVALID_ARG, "er_render_topology: NULL argument");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_render_topology: er_render_begin has not succeeded");
+    int rc;
+    ErTopoList l;
+    l.what = t->what; l.remove_count = t->remove_count; l.remove_ids = t->remove_ids; l.append_count = t->append_count;
+    l.vertices = t->vertices; l.normals = t->normals; l.tangents = t->tangents; l.uvs = t->uvs; l.tangent_sign = t->tangent_sign;
+    l.material_id = t->material_id; l.append_as_object = t->append_as_object;
+    // every check, with nothing of the scene touched
+    std::vector<uint32_t> sorted;
+    uint32_t new_count = 0;
+    std::string why;
+    if (!er_topo_check(s->tri_count, l, sorted, new_count, why)) return fail(ER_ERR_INVALID_ARG, std::string(who) + ": " + why);
+    if (new_count >= (1u << 28)) return fail(ER_ERR_INVALID_ARG, std::string(who) + ": too many triangles (er_scene_create refuses the result)");
+    if (t->rest.what & ER_EDIT_GEOMETRY) return fail(ER_ERR_INVALID_ARG, std::string(who) + ": ER_EDIT_GEOMETRY in rest.what (moved vertices are er_render_update's)");
+    TopoCtx tc;
+    tc.l = &l; tc.sorted = &sorted; tc.new_count = new_count;
+    EditWork W;
+    if ((rc = edit_check(s, &t->rest, nullptr, nullptr, ER_EDIT_CAMERA | LOOK_BITS, who, W, &tc)) != ER_OK) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));      // pending asynchronous work first
+    {   // the store's kernels are probed here, not by er_render_begin (er_kernels.h says why a probe at all): a render that never edits
+        // its topology loads nothing for it
+        const char* which = nullptr;
+        const hipError_t pe = er_probe_topology(&which);
+        if (pe != hipSuccess) return fail(ER_ERR_HIP, std::string(who) + ": libeleven_hip.so has no usable gfx950 code object for " + (which ? which : "?") + " (" + hipGetErrorString(pe) + ")");
+    }
+    // what can still fail for want of host memory, beside the scene: room for the appended rows, and the renumbered object table
+    const uint32_t old_count = s->tri_count;
+    if (new_count > old_count) host_reserve((uint64_t)(new_count - old_count) * (9 * 3 + 6 + 1 + 1) * 4);
+    const ErTopoArrays A{&s->vertices, &s->normals, &s->tangents, &s->uvs, &s->tangent_sign, &s->material_id};
+    er_topo_reserve(A, new_count);
+    s->flush_poses();      // (the edited description is the current one with pending poses flushed; the arrays' meaning does not change)
+    ErObjectTable table;
+    er_topo_remap_objects(s->objects, old_count, sorted, l, table);
+    // the host copy, before any device work; nothing below can fail until the device is touched
+    er_topo_apply(A, old_count, sorted, l);
+    s->tri_count = new_count;
+    std::swap(s->objects, table);
+    edit_replace(s, &t->rest, nullptr, nullptr, W);      // (rest.material_id has new_count entries: tri_count is the new one)
+    s->feat_valid = false;
+    for (auto& set : s->unpacked_feat) set.clear();
+    s->ids_invalidate();
+    s->d_id_map.release();      // the tri -> object map and the table's device form were of the old numbering: the lazy paths make them again
+    s->id_map_valid = false;
+    s->xform_dev.release();
+    if ((t->rest.what & ER_EDIT_MATERIALS) && t->rest.material_id) s->store.release();      // (the store's material ids would be stale: filled again below)
+    const uint32_t calls = s->topo.calls;
+    s->topo = ErTopologyInfo{};
+    s->topo.calls = calls;
+    if ((rc = topo_device(s, &t->rest, l, sorted, old_count, W.rebuild_pool, who)) != ER_OK) {
+        s->begun = false;      // (er_render_begin releases what is left and builds from the edited host copy)
+        s->store.release();
+        return rc;
+    }
+    s->topo.calls++;
+    s->topo.removed = l.removes();
+    s->topo.appended = l.appends();
+    s->topo.tri_count = new_count;
+    s->topo.edit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ER_OK;
+}
+
+static int er_topology_info_impl(ErScene* s, ErTopologyInfo* out) {
+    if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_topology_info: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    *out = s->topo;
+    return ER_OK;
+}
+
 // ---- the exported entry points: every body above runs inside guarded() (no exception crosses the C ABI) ----
 extern "C" {
 int er_render_update(ErScene* s, const ErSceneUpdate* u) { return guarded("er_render_update", [&]() -> int { return er_render_update_impl(s, u); }); }
@@ -613,4 +787,6 @@ int er_edit_info(ErScene* s, ErEditInfo* out) { return guarded("er_edit_info", [
 int er_accel_cost(ErScene* s, ErAccelCost* out) { return guarded("er_accel_cost", [&]() -> int { return er_accel_cost_impl(s, out); }); }
 int er_update_policy_set(ErScene* s, const ErUpdatePolicy* p) { return guarded("er_update_policy_set", [&]() -> int { return er_update_policy_set_impl(s, p); }); }
 int er_rebuild_info(ErScene* s, ErRebuildInfo* out) { return guarded("er_rebuild_info", [&]() -> int { return er_rebuild_info_impl(s, out); }); }
+int er_render_topology(ErScene* s, const ErTopologyEdit* t) { return guarded("er_render_topology", [&]() -> int { return er_render_topology_impl(s, t); }); }
+int er_topology_info(ErScene* s, ErTopologyInfo* out) { return guarded("er_topology_info", [&]() -> int { return er_topology_info_impl(s, out); }); }
 }  // extern "C"

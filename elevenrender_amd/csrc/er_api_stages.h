@@ -29,7 +29,11 @@ inline int check_pool_floats(uint64_t floats, const char* who) {
 
 // stage 2: the acceleration structure of the host copy into the scene's three buffers, described in s->kept.accel; `built_ev` is
 // recorded when the tree is there and the uploads begin.  accel_publish: what er_accel_info and er_debug_read_accel report of it.
-int begin_accel(ErScene* s, BeginStaging& B, hipEvent_t built_ev, const char* who);
+// `device_arrays` (er_render_topology's geometry store): the scene's six arrays as they already lie on the device -- the device
+// builder, where it is the one chosen, reads them instead of uploading the host copy; everything else is the same.
+int begin_accel(ErScene* s, BeginStaging& B, hipEvent_t built_ev, const char* who, const ErGpuSceneArrays* device_arrays = nullptr);
+// whether begin_accel would ask the device builder first, for the scene as it is now (flags, environment, thresholds)
+bool accel_device_first(const ErScene* s);
 void accel_publish(ErScene* s, float up_ms);
 // stage 3 without the point lights: the materials and their precomputed constants
 int upload_materials(ErScene* s, BeginStaging& B);

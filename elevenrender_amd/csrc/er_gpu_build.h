@@ -37,3 +37,6 @@ struct ErGpuBvhDevice {
 // would; 2 = as a device out-of-memory would; 3 = they deliver but report a wide tree of ER_STACK8 + 1 levels.  (Until round 6 an environment variable read on the production path.)
 inline std::atomic<int> er_debug_gpu_build_failure{0};
 int er_gpu_build_device(const ErGpuSceneArrays& arrays, uint32_t n, int device, ErGpuBvhDevice* out, std::string& err);
+// The same build from arrays that already lie on `device` (the six pointers are DEVICE pointers; they are read, never written or freed,
+// and nothing else may write them during the call): er_gpu_build_device is this after an upload.  Same kernels, same order, same bytes.
+int er_gpu_build_device_arrays(const ErGpuSceneArrays& device_arrays, uint32_t n, int device, ErGpuBvhDevice* out, std::string& err);

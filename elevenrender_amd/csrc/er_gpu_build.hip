@@ -582,7 +582,8 @@ struct Dev {
 struct GpuBuild {
     uint32_t n = 0, n_inner = 0;
     hipStream_t st = nullptr;
-    Dev<float> d_v, d_n, d_lift;
+    struct { const float* p = nullptr; } d_v, d_n;      // the scene's vertices and normals on the device: the caller's (er_gpu_build_device_arrays)
+    Dev<float> d_lift;
     Dev<Box3> d_box;
     Dev<uint32_t> d_ids2;       // slot -> triangle, the binary tree's order
     Dev<int> d_pi;              // parent link of every inner node: parent * 2 + side
@@ -598,16 +599,14 @@ struct GpuBuild {
         const uint32_t blocks = (n + 255) / 256;
         GB_OK(hipSetDevice(device));
         GB_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        GB_OK(hipMalloc(&d_v.p, (size_t)n * 36));
-        GB_OK(hipMalloc(&d_n.p, (size_t)n * 36));
+        d_v.p = vertices;
+        d_n.p = normals;
         GB_OK(hipMalloc(&d_lift.p, (size_t)n * 4));
         GB_OK(hipMalloc(&d_box.p, (size_t)n * sizeof(Box3)));
         GB_OK(hipMalloc(&d_ids2.p, (size_t)n * 4));
         GB_OK(hipMalloc(&d_pi.p, (size_t)n * 4));
         GB_OK(hipMalloc(&d_nodes.p, (size_t)n_inner * sizeof(ErNode)));
         GB_OK(hipMalloc(&d_g.p, 12 * 4));
-        GB_OK(hipMemcpyAsync(d_v.p, vertices, (size_t)n * 36, hipMemcpyHostToDevice, st));
-        GB_OK(hipMemcpyAsync(d_n.p, normals, (size_t)n * 36, hipMemcpyHostToDevice, st));
         // [0] vmax, [1..6] scene bounds (order-preserving integers), [7] lift max; [8] the deepest node's depth, [9] leaf count (set on the host by sah())
         for (int k = 0; k < 12; k++) g[k] = (k >= 1 && k <= 3) ? 0xffffffffu : 0u;
         GB_OK(hipMemcpyAsync(d_g.p, g, sizeof(g), hipMemcpyHostToDevice, st));
@@ -724,13 +723,19 @@ hipError_t er_probe_gpu_build(const char** which) {   // see er_kernels.h
     return hipFuncGetAttributes(&at, (const void*)k_scene_bounds);
 }
 
-int er_gpu_build_device(const ErGpuSceneArrays& a, uint32_t n, int device, ErGpuBvhDevice* out, std::string& err) {
-    auto t0 = std::chrono::steady_clock::now();
+// what either entry answers before it touches the device: 0 = go on
+static int build_declines(uint32_t n, std::string& err) {
     if (n <= ER_BVH_LEAF_MAX) { err = "too few triangles for the device builder"; return 1; }
     if (const int dbg = er_debug_gpu_build_failure.load(); dbg == 1 || dbg == 2) {      // (test hook er_debug_set_gpu_build_failure: the caller's handling of a failed build)
         err = dbg == 2 ? "simulated failure: out of device memory" : "simulated failure: a fault inside the builder";
         return dbg == 2 ? -2 : -1;
     }
+    return 0;
+}
+
+// The one build there is: the six pointers of `a` are DEVICE pointers, read and never written or freed.
+static int build_on_device(const ErGpuSceneArrays& a, uint32_t n, int device, ErGpuBvhDevice* out, std::string& err) {
+    auto t0 = std::chrono::steady_clock::now();
     GpuBuild B;
     int rc = B.binary(a.vertices, a.normals, n, device, err);
     if (rc != 0) return rc;
@@ -792,16 +797,6 @@ int er_gpu_build_device(const ErGpuSceneArrays& a, uint32_t n, int device, ErGpu
     // ---- binary tree follows the new slot order; final records ----
     hipLaunchKernelGGL(k_inverse, dim3((n + 255) / 256), dim3(256), 0, st, d_new_order.p, n, d_inv.p);
     hipLaunchKernelGGL(k_fix_leaves, dim3((n_inner + 255) / 256), dim3(256), 0, st, B.d_nodes.p, n_inner, d_inv.p);
-    Dev<float> d_tan, d_uv, d_sign;
-    Dev<int> d_mat;
-    GB_OK(hipMalloc(&d_tan.p, (size_t)n * 36));
-    GB_OK(hipMalloc(&d_uv.p, (size_t)n * 24));
-    GB_OK(hipMalloc(&d_sign.p, (size_t)n * 4));
-    GB_OK(hipMalloc(&d_mat.p, (size_t)n * 4));
-    GB_OK(hipMemcpyAsync(d_tan.p, a.tangents, (size_t)n * 36, hipMemcpyHostToDevice, st));
-    GB_OK(hipMemcpyAsync(d_uv.p, a.uvs, (size_t)n * 24, hipMemcpyHostToDevice, st));
-    GB_OK(hipMemcpyAsync(d_sign.p, a.tangent_sign, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    GB_OK(hipMemcpyAsync(d_mat.p, a.material_id, (size_t)n * 4, hipMemcpyHostToDevice, st));
     const size_t n8_pieces = (size_t)nodes8_count * ER_NODE8_PIECES + 8;
     const size_t geom_f4 = n8_pieces + ((size_t)n + 1) * 3;
     Dev<float4> d_geom, d_attr;
@@ -809,8 +804,8 @@ int er_gpu_build_device(const ErGpuSceneArrays& a, uint32_t n, int device, ErGpu
     GB_OK(hipMalloc(&d_attr.p, (size_t)n * ER_ATTR_PIECES * 16));
     GB_OK(hipMemsetAsync(d_geom.p, 0, n8_pieces * 16, st));
     GB_OK(hipMemcpy2DAsync(d_geom.p, (size_t)ER_NODE8_PIECES * 16, d_n8.p, sizeof(ErNode8), sizeof(ErNode8), nodes8_count, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_records, dim3((n + 256) / 256), dim3(256), 0, st, d_new_order.p, B.d_ids2.p, n, B.d_v.p, B.d_n.p, d_tan.p, d_uv.p, d_sign.p,
-                       d_mat.p, B.d_lift.p, (ErTriIsect*)(d_geom.p + n8_pieces), (ErTriAttr*)d_attr.p, d_s2t.p);
+    hipLaunchKernelGGL(k_records, dim3((n + 256) / 256), dim3(256), 0, st, d_new_order.p, B.d_ids2.p, n, B.d_v.p, B.d_n.p, a.tangents, a.uvs, a.tangent_sign,
+                       a.material_id, B.d_lift.p, (ErTriIsect*)(d_geom.p + n8_pieces), (ErTriAttr*)d_attr.p, d_s2t.p);
     GB_OK(hipGetLastError());
     GB_OK(hipStreamSynchronize(st));
     for (int k = 0; k < 3; k++) { out->lo[k] = B.bound(k); out->hi[k] = B.bound(3 + k); }
@@ -828,4 +823,34 @@ int er_gpu_build_device(const ErGpuSceneArrays& a, uint32_t n, int device, ErGpu
     out->attr = d_attr.take();
     out->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return 0;
+}
+
+int er_gpu_build_device_arrays(const ErGpuSceneArrays& a, uint32_t n, int device, ErGpuBvhDevice* out, std::string& err) {
+    if (const int d = build_declines(n, err); d != 0) return d;
+    return build_on_device(a, n, device, out, err);
+}
+
+// The build from the host copy: allocate, upload, build from the device arrays.
+int er_gpu_build_device(const ErGpuSceneArrays& a, uint32_t n, int device, ErGpuBvhDevice* out, std::string& err) {
+    auto t0 = std::chrono::steady_clock::now();
+    if (const int d = build_declines(n, err); d != 0) return d;
+    Dev<float> d_v, d_n, d_tan, d_uv, d_sign;
+    Dev<int32_t> d_mat;
+    GB_OK(hipSetDevice(device));
+    GB_OK(hipMalloc(&d_v.p, (size_t)n * 36));
+    GB_OK(hipMalloc(&d_n.p, (size_t)n * 36));
+    GB_OK(hipMalloc(&d_tan.p, (size_t)n * 36));
+    GB_OK(hipMalloc(&d_uv.p, (size_t)n * 24));
+    GB_OK(hipMalloc(&d_sign.p, (size_t)n * 4));
+    GB_OK(hipMalloc(&d_mat.p, (size_t)n * 4));
+    GB_OK(hipMemcpy(d_v.p, a.vertices, (size_t)n * 36, hipMemcpyHostToDevice));
+    GB_OK(hipMemcpy(d_n.p, a.normals, (size_t)n * 36, hipMemcpyHostToDevice));
+    GB_OK(hipMemcpy(d_tan.p, a.tangents, (size_t)n * 36, hipMemcpyHostToDevice));
+    GB_OK(hipMemcpy(d_uv.p, a.uvs, (size_t)n * 24, hipMemcpyHostToDevice));
+    GB_OK(hipMemcpy(d_sign.p, a.tangent_sign, (size_t)n * 4, hipMemcpyHostToDevice));
+    GB_OK(hipMemcpy(d_mat.p, a.material_id, (size_t)n * 4, hipMemcpyHostToDevice));
+    const ErGpuSceneArrays dev{d_v.p, d_n.p, d_tan.p, d_uv.p, d_sign.p, d_mat.p};
+    const int rc = build_on_device(dev, n, device, out, err);
+    if (rc == 0) out->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();      // (the uploads count, as they always did)
+    return rc;
 }

@@ -34,6 +34,7 @@
 #include "er_texstage.h"
 #include "er_features.h"
 #include "er_ids.h"
+#include "er_topology.h"
 
 namespace erh {
 
@@ -183,6 +184,11 @@ struct ErScene {
     ErXformDev xform_dev;
     ErSparseInfo xform{};
     uint32_t xform_objects = 0;
+    // er_render_topology (er_api_edit.cpp): the geometry store -- the six arrays on the device in id order, valid from a
+    // topology edit whose build ran on the device until anything else writes geometry or material ids (store.release() there) -- and
+    // what er_topology_info reports.
+    ErGeomStore store;
+    ErTopologyInfo topo{};
     void flush_poses() noexcept { er_objects_flush(objects, vertices.data(), normals.data(), tangents.data()); }
     // er_accel_cost / er_update_policy_set (er_api_edit.cpp): every build and every refit bumps accel_version; the cost last measured is kept
     // with the version it was measured at.  The baseline of ER_REBUILD_AUTO is the cost of the last BUILT tree: known once such a tree
@@ -296,6 +302,7 @@ struct ErScene {
         d_light_tab.release(); light_emitters = 0; light_total = 0.0f;
         refit_topo.release();
         xform_dev.release();
+        store.release();
         d_feat.release(); d_feat_spill.release(); feat_valid = false;
         for (auto& u : unpacked_feat) u.clear();
         d_id_planes.release(); d_id_map.release(); d_id_work.release(); d_id_over.release(); ids_valid = id_map_valid = false;

@@ -230,6 +230,7 @@ private:
     SessionEdits edits_;                             // what arrived since the last successful --start (eleven_host.hpp)
     unsigned camera_updates_ = 0;                    // --start commands answered by an in-place camera update (reported by --get_info)
     unsigned scene_edits_ = 0;                       // ... by an in-place edit of materials, textures or the HDRI (the same)
+    unsigned topology_edits_ = 0;                    // ... by an in-place append of the loaded objects' triangles (the same)
 
     void dispatch(const CommandLine& cl, std::vector<Message>& extra) {
         if (cl.count("path") || cl.count("sm") || cl.count("output"))
@@ -238,7 +239,8 @@ private:
         // (before the command runs: one that fails half-way has still touched the scene)
         if (cl.count("load_hdri")) edits_.on_hdri();
         if (cl.count("load_texture") || cl.count("load_brdf_material")) edits_.on_materials();
-        if (cl.count("load_config") || cl.count("load_object")) edits_.on_other();
+        if (cl.count("load_object")) edits_.on_object();
+        if (cl.count("load_config")) edits_.on_other();
         if (cl.count("load_texture")) {
             Texture t = parse_texturejson(extra[0].get_json_data(), extra[1].get_float_data(), extra[1].float_count());
             scene.addTexture(t);                                            // load_texture, src/CommandManager.cpp:364-370
@@ -294,6 +296,7 @@ private:
             j["samples_per_call"] = samples_per_call_.load();
             j["camera_updates"] = camera_updates_;
             j["scene_edits"] = scene_edits_;
+            j["topology_edits"] = topology_edits_;
             j["feature_samples"] = rm.pars.feature_samples ? rm.pars.feature_samples : 4u;      // rays per pixel of a feature pass (--get_pass albedo / depth, denoise_guided)
             if (rm.pars.denoise_guided) j["denoise_guided"] = true;
             im->write_message(Message::json_data(j));
@@ -407,13 +410,17 @@ private:
         stop_render_thread();
         { std::lock_guard<std::mutex> lk(err_mtx_); render_error_.clear(); }
         // nothing but a new camera since the last --start: the render restarts in place (no build, no uploads); nothing but a camera,
-        // an HDRI, materials and textures: the begun scenes are edited in place (no build); else, or if that fails, the full start:
+        // an HDRI, materials and textures: the begun scenes are edited in place (no build); object loads beside those: their triangles
+        // are appended in place (er_render_topology: the build, but no second host copy, texture pool, CDF or planes); else, or if
+        // that fails, the full start:
         // builds the BVH, uploads, runs setupKernel; throws with er_last_error()
         bool in_place = false;
         if (edits_.camera_only()) {
             if ((in_place = rm.update_camera(scene.camera))) camera_updates_++;
         } else if (edits_.editable()) {
             if ((in_place = rm.edit_scene(&scene, edits_.hdri))) scene_edits_++;
+        } else if (edits_.appendable()) {
+            if ((in_place = rm.append_scene(&scene, edits_.hdri))) topology_edits_++;
         }
         if (!in_place) {
             edits_.on_failed();

@@ -140,21 +140,27 @@ struct RenderParameters {   // src/kernel.h:51-69
 // (RenderingManager::update_camera: er_render_update on every rank -- no build, no uploads); after nothing but --load_camera,
 // --load_hdri, --load_brdf_material and --load_texture it edits the begun scenes in place (RenderingManager::edit_scene:
 // er_render_edit on every rank -- no build; the texture pool is rebuilt on the device only if an assignment or a texture changed);
-// after anything else (--load_object, --load_config), or before the first render, it is the full start_rendering.
+// after object loads beside those (--load_object appends triangles and never touches the ones there are) it changes the begun scenes'
+// topology in place (RenderingManager::append_scene: er_render_topology on every rank -- the appended triangles, the complete material
+// and texture lists in its `rest`; the one build this edit needs, nothing else of a start); after anything else (--load_config), or before
+// the first render, it is the full start_rendering.
 struct SessionEdits {
     bool rendering = false;      // a --start has succeeded and its scenes are alive
     bool camera = false;         // --load_camera arrived since
     bool hdri = false;           // ... --load_hdri
     bool materials = false;      // ... --load_brdf_material or --load_texture
+    bool objects = false;        // ... --load_object
     bool other = false;          // ... and anything else that changes the scene or the parameters
     void on_camera() { camera = true; }
     void on_hdri() { hdri = true; }
     void on_materials() { materials = true; }
+    void on_object() { objects = true; }
     void on_other() { other = true; }
-    void on_started() { rendering = true; camera = hdri = materials = other = false; }
+    void on_started() { rendering = true; camera = hdri = materials = objects = other = false; }
     void on_failed() { rendering = false; }
-    bool camera_only() const { return rendering && !other && !hdri && !materials; }      // (no edit at all: the same render again, also without a rebuild)
-    bool editable() const { return rendering && !other && (hdri || materials); }         // (a camera may have come as well)
+    bool camera_only() const { return rendering && !other && !objects && !hdri && !materials; }      // (no edit at all: the same render again, also without a rebuild)
+    bool editable() const { return rendering && !other && !objects && (hdri || materials); }         // (a camera may have come as well)
+    bool appendable() const { return rendering && !other && objects; }                               // (and so may an HDRI, materials and textures)
 };
 
 inline int parseFeature(std::string s) {   // the feature planes of er_render_features by name, -1 = not one
@@ -201,23 +207,36 @@ public:
         return ErTexture{t.width, t.height, (int32_t)t.channels, t.filter == Texture::Filter::BILINEAR ? 1 : 0, t.data.data()};
     }
 
+    // the scene's triangles [from, to) as the library's six flat arrays
+    struct TriArrays {
+        std::vector<float> v, nn, tt, uv, sign;
+        std::vector<int32_t> mat;
+    };
+    static TriArrays tri_arrays(const Scene& scene, size_t from, size_t to) {
+        const size_t n = to - from;
+        TriArrays A;
+        A.v.resize(n * 9); A.nn.resize(n * 9); A.tt.resize(n * 9); A.uv.resize(n * 6); A.sign.resize(n); A.mat.resize(n);
+        for (size_t i = 0; i < n; i++) {
+            const Tri& t = scene.tris[from + i];
+            for (int k = 0; k < 3; k++) {
+                const Vector3* src[3] = {&t.vertices[k], &t.normals[k], &t.tangents[k]};
+                float* dst[3] = {&A.v[i * 9 + k * 3], &A.nn[i * 9 + k * 3], &A.tt[i * 9 + k * 3]};
+                for (int a = 0; a < 3; a++) { dst[a][0] = src[a]->x; dst[a][1] = src[a]->y; dst[a][2] = src[a]->z; }
+                A.uv[i * 6 + k * 2] = t.uv[k].x;
+                A.uv[i * 6 + k * 2 + 1] = t.uv[k].y;
+            }
+            A.sign[i] = t.tangentsSign;
+            A.mat[i] = t.materialID;
+        }
+        return A;
+    }
+
     void start_rendering(Scene* scene) {   // src/Managers.cpp:234-275 (without spawning the render thread)
         release();
         size_t n = scene->tris.size();
-        std::vector<float> v(n * 9), nn(n * 9), tt(n * 9), uv(n * 6), sign(n);
-        std::vector<int32_t> mat(n);
-        for (size_t i = 0; i < n; i++) {
-            const Tri& t = scene->tris[i];
-            for (int k = 0; k < 3; k++) {
-                const Vector3* src[3] = {&t.vertices[k], &t.normals[k], &t.tangents[k]};
-                float* dst[3] = {&v[i * 9 + k * 3], &nn[i * 9 + k * 3], &tt[i * 9 + k * 3]};
-                for (int a = 0; a < 3; a++) { dst[a][0] = src[a]->x; dst[a][1] = src[a]->y; dst[a][2] = src[a]->z; }
-                uv[i * 6 + k * 2] = t.uv[k].x;
-                uv[i * 6 + k * 2 + 1] = t.uv[k].y;
-            }
-            sign[i] = t.tangentsSign;
-            mat[i] = t.materialID;
-        }
+        TriArrays A = tri_arrays(*scene, 0, n);
+        std::vector<float>&v = A.v, &nn = A.nn, &tt = A.tt, &uv = A.uv, &sign = A.sign;
+        std::vector<int32_t>& mat = A.mat;
         const std::vector<ErMaterial> ms = er_materials(*scene);
         std::vector<ErTexture> ts;
         for (const Texture& t : scene->textures)
@@ -277,6 +296,7 @@ public:
         for (auto& t : th) t.join();
         for (unsigned r = 0; r < ranks; r++) if (!errs[r].empty()) { std::string e = errs[r]; release(); throw std::runtime_error(e); }
         textures_sent_ = scene->textures.size();
+        mats_sent_ = mat;
         if (pars.adaptive)
             for (ErScene* e : ers_) if (er_adaptive_set(e, &pars.adaptive_params) != ER_OK) { std::string m = er_last_error(); release(); throw std::runtime_error(m); }
         // ---- the combine's communicators ----
@@ -335,7 +355,7 @@ public:
     // a name wins); the HDRI if one came.  Returns false -- the caller starts over with start_rendering -- if any rank refused or
     // failed.
     bool edit_scene(Scene* scene, bool hdri) {
-        if (ers_.empty() || scene->materials.empty() || scene->textures.size() < textures_sent_) return false;
+        if (ers_.empty() || scene->materials.empty() || scene->textures.size() < textures_sent_ || scene->tris.size() != mats_sent_.size()) return false;
         const std::vector<ErMaterial> ms = er_materials(*scene);
         std::vector<int32_t> mat(scene->tris.size());
         for (size_t i = 0; i < mat.size(); i++) mat[i] = scene->tris[i].materialID;
@@ -362,6 +382,52 @@ public:
         features_ready_ = false;      // (the library has invalidated the planes)
         for (int rc : rcs) if (rc != ER_OK) return false;
         textures_sent_ = scene->textures.size();
+        mats_sent_ = mat;
+        if (pars.adaptive)
+            for (ErScene* s : ers_) if (er_adaptive_set(s, &pars.adaptive_params) != ER_OK) return false;
+        return true;
+    }
+    // A --start after object loads (and perhaps a camera, an HDRI, materials, textures): er_render_topology on every rank side by side.
+    // addMeshObject only ever appends, so the triangles beyond the ranks' count are the edit; the COMPLETE material and texture lists go
+    // through `rest` as in edit_scene, and the triangles' material ids only if pair_materials moved one of the triangles the ranks
+    // already hold (the ranks' device-resident geometry then stays valid for the next such start).  Returns false -- the caller starts
+    // over with start_rendering -- if nothing was appended or any rank refused or failed.
+    bool append_scene(Scene* scene, bool hdri) {
+        const size_t have = mats_sent_.size(), n = scene->tris.size();
+        if (ers_.empty() || scene->materials.empty() || scene->textures.size() < textures_sent_ || n <= have) return false;
+        const TriArrays A = tri_arrays(*scene, have, n);
+        const std::vector<ErMaterial> ms = er_materials(*scene);
+        std::vector<int32_t> mat(n);
+        for (size_t i = 0; i < n; i++) mat[i] = scene->tris[i].materialID;
+        const bool ids_moved = !std::equal(mats_sent_.begin(), mats_sent_.end(), mat.begin());
+        std::vector<ErTexture> ts;
+        for (size_t i = 0; i < scene->textures.size(); i++) {
+            ts.push_back(er_texture(scene->textures[i]));
+            if (i < textures_sent_) ts.back().data = nullptr;      // (keep)
+        }
+        const Camera& c = scene->camera;
+        ErTopologyEdit t{};
+        t.what = ER_TOPO_APPEND;
+        t.append_count = (uint32_t)(n - have);
+        t.vertices = A.v.data(); t.normals = A.nn.data(); t.tangents = A.tt.data(); t.uvs = A.uv.data(); t.tangent_sign = A.sign.data(); t.material_id = A.mat.data();
+        ErSceneEdit& e = t.rest;
+        e.what = ER_EDIT_CAMERA | ER_EDIT_MATERIALS | ER_EDIT_TEXTURES | (hdri ? ER_EDIT_HDRI : 0u);
+        e.camera = ErCamera{c.focalLength, c.sensorWidth, c.sensorHeight, c.aperture, c.focusDistance,
+                            {c.rotation.x, c.rotation.y, c.rotation.z}, c.bokeh ? 1 : 0, {c.position.x, c.position.y, c.position.z}};
+        e.material_count = (uint32_t)ms.size(); e.materials = ms.data();
+        e.material_id = ids_moved ? mat.data() : nullptr;
+        e.texture_count = (uint32_t)ts.size(); e.textures = ts.data();
+        if (hdri) e.hdri.texture = er_texture(scene->hdri.texture);
+        std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);
+        if (ers_.size() > 1) lk.lock();
+        std::vector<int> rcs(ers_.size(), ER_OK);
+        std::vector<std::thread> th;
+        for (size_t r = 0; r < ers_.size(); r++) th.emplace_back([&, r] { rcs[r] = er_render_topology(ers_[r], &t); });
+        for (auto& x : th) x.join();
+        features_ready_ = false;      // (the library has invalidated the planes)
+        for (int rc : rcs) if (rc != ER_OK) return false;
+        textures_sent_ = scene->textures.size();
+        mats_sent_ = mat;
         if (pars.adaptive)
             for (ErScene* s : ers_) if (er_adaptive_set(s, &pars.adaptive_params) != ER_OK) return false;
         return true;
@@ -561,7 +627,8 @@ private:
     std::vector<ErScene*> ers_;
     std::vector<ErComm*> comms_;
     std::mutex frame_mtx_;
-    size_t textures_sent_ = 0;         // textures of the scene the ranks hold (start_rendering / edit_scene)
+    size_t textures_sent_ = 0;         // textures of the scene the ranks hold (start_rendering / edit_scene / append_scene)
+    std::vector<int32_t> mats_sent_;   // the material id of every triangle the ranks hold (the same three)
     bool features_ready_ = false;      // a feature pass has run (and been gathered) since the last start_rendering / update_camera
     void render_features_unlocked(unsigned n) {
         features_ready_ = false;

@@ -13,7 +13,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import abi
+from . import abi, topology as topo
 
 
 @dataclass
@@ -67,12 +67,14 @@ class RenderingManager:
         self.lib = abi.load()
         self.handle = C.c_void_p()
         self.scene = None
+        self._topo_count = None      # the triangle count a topology() left (self.scene keeps the started one)
 
     # -- reference: RenderingManager::start_rendering(Scene*) (src/Managers.cpp:234-275).  The
     #    reference also spawns the render thread here; callers of this mirror call render().
     def start_rendering(self, scene: abi.SceneData):
         self.close()
         self.scene = scene
+        self._topo_count = None
         self.pars.width, self.pars.height = scene.x_res, scene.y_res
         abi.check(self.lib.er_scene_create(C.byref(scene.desc()), C.byref(self.handle)))
         dev = 0
@@ -125,8 +127,8 @@ class RenderingManager:
                 if a is None:
                     continue
                 a = np.ascontiguousarray(a, np.float32)
-                if a.size != self.scene.tri_count * 9:
-                    raise ValueError(f"{who}: {name} has {a.size} floats, the scene has {self.scene.tri_count} triangles")
+                if a.size != self._tri_count() * 9:
+                    raise ValueError(f"{who}: {name} has {a.size} floats, the scene has {self._tri_count()} triangles")
                 keep.append(a)
                 setattr(call, name, a.ctypes.data_as(C.POINTER(C.c_float)))
         return keep
@@ -219,26 +221,25 @@ class RenderingManager:
         abi.check(self.lib.er_update_info(self.handle, C.byref(a)))
         return {n: getattr(a, n) for n, _ in abi.ErUpdateInfo._fields_}
 
-    def edit(self, camera=None, vertices=None, normals=None, tangents=None, materials=None, material_id=None, textures=None, hdri=None,
-             hdri_cdf=None, hdri_radiance_sum=0.0):
-        """er_render_edit: er_render_update's arguments plus `materials` (the complete new list of abi.ErMaterial; `material_id` int32[n]
-        or None = keep), `textures` (the complete new list of (data, w, h, channels, filter) tuples as in SceneData; None in place of an
-        entry = keep that texture) and `hdri` (such a tuple; hdri_cdf / hdri_radiance_sum as in SceneData, None = built by the
-        library).  The render starts over at sample 0.  self.scene is not changed."""
-        e = abi.ErSceneEdit()
-        keep = self._camera_and_geometry(e, "edit", camera, vertices, normals, tangents)
+    def _tri_count(self):
+        """the begun scene's triangle count: self.scene's until a topology() changed it"""
+        return self.scene.tri_count if self._topo_count is None else self._topo_count
+
+    def _look(self, e, who, tri_count, materials, material_id, textures, hdri, hdri_cdf, hdri_radiance_sum):
+        """the materials, textures and HDRI bits of an abi.ErSceneEdit filled in; returns what its pointers point into"""
+        keep = []
         fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
         if materials is not None or material_id is not None:
             if materials is None:
-                raise ValueError("edit: material_id comes with the material list")
+                raise ValueError(f"{who}: material_id comes with the material list")
             e.what |= abi.EDIT_MATERIALS
             mats = (abi.ErMaterial * max(1, len(materials)))(*materials)
             keep.append(mats)
             e.material_count, e.materials = len(materials), mats
             if material_id is not None:
                 ids = np.ascontiguousarray(material_id, np.int32)
-                if ids.size != self.scene.tri_count:
-                    raise ValueError(f"edit: material_id has {ids.size} entries, the scene has {self.scene.tri_count} triangles")
+                if ids.size != tri_count:
+                    raise ValueError(f"{who}: material_id has {ids.size} entries, the scene has {tri_count} triangles")
                 keep.append(ids)
                 e.material_id = ids.ctypes.data_as(C.POINTER(C.c_int32))
         if textures is not None:
@@ -264,7 +265,58 @@ class RenderingManager:
                 keep.append(cdf)
                 e.hdri.cdf = fp(cdf)
                 e.hdri.radiance_sum = float(hdri_radiance_sum)
+        return keep
+
+    def edit(self, camera=None, vertices=None, normals=None, tangents=None, materials=None, material_id=None, textures=None, hdri=None,
+             hdri_cdf=None, hdri_radiance_sum=0.0):
+        """er_render_edit: er_render_update's arguments plus `materials` (the complete new list of abi.ErMaterial; `material_id` int32[n]
+        or None = keep), `textures` (the complete new list of (data, w, h, channels, filter) tuples as in SceneData; None in place of an
+        entry = keep that texture) and `hdri` (such a tuple; hdri_cdf / hdri_radiance_sum as in SceneData, None = built by the
+        library).  The render starts over at sample 0.  self.scene is not changed."""
+        e = abi.ErSceneEdit()
+        keep = self._camera_and_geometry(e, "edit", camera, vertices, normals, tangents)
+        keep += self._look(e, "edit", self._tri_count(), materials, material_id, textures, hdri, hdri_cdf, hdri_radiance_sum)
         abi.check(self.lib.er_render_edit(self.handle, C.byref(e)))
+
+    def topology(self, remove=None, append=None, as_object=False, camera=None, materials=None, material_id=None, textures=None, hdri=None,
+                 hdri_cdf=None, hdri_radiance_sum=0.0):
+        """er_render_topology: `remove` (distinct triangle ids in the current numbering) leave the begun scene, then `append` (a dict or
+        SceneData-like object holding vertices, normals, tangents, uvs, tangent_sign, material_id) joins it at the end -- with as_object
+        and an object table present as a new last object --, then the rest as edit() takes it (material_id for the RESULT).  The
+        render starts over at sample 0.  self.scene is not changed: topology.apply(...) gives the edited SceneData."""
+        t = abi.ErTopologyEdit()
+        keep = []
+        n = self._tri_count()
+        if remove is not None:
+            ids = np.ascontiguousarray(remove)
+            if ids.ndim != 1 or (ids.size and (ids.dtype.kind not in "iu" or int(ids.min()) < 0 or int(ids.max()) > 0xffffffff)):
+                raise ValueError("topology: remove is a one-dimensional array of triangle ids")
+            ids = ids.astype(np.uint32)
+            keep.append(ids)
+            t.what |= abi.TOPO_REMOVE
+            t.remove_count, t.remove_ids = ids.size, ids.ctypes.data_as(C.POINTER(C.c_uint32))
+            n -= min(n, ids.size)
+        if append is not None:
+            tail, count = topo.append_arrays(append)
+            keep.append(tail)
+            t.what |= abi.TOPO_APPEND
+            t.append_count = count
+            for name in ("vertices", "normals", "tangents", "uvs", "tangent_sign"):
+                setattr(t, name, tail[name].ctypes.data_as(C.POINTER(C.c_float)))
+            t.material_id = tail["material_id"].ctypes.data_as(C.POINTER(C.c_int32))
+            t.append_as_object = 1 if as_object else 0
+            n += count
+        if camera is not None:
+            t.rest.what |= abi.EDIT_CAMERA
+            t.rest.camera = camera
+        keep += self._look(t.rest, "topology", n, materials, material_id, textures, hdri, hdri_cdf, hdri_radiance_sum)
+        abi.check(self.lib.er_render_topology(self.handle, C.byref(t)))
+        self._topo_count = self.topology_info()["tri_count"]
+
+    def topology_info(self):
+        a = abi.ErTopologyInfo()
+        abi.check(self.lib.er_topology_info(self.handle, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in abi.ErTopologyInfo._fields_}
 
     def edit_info(self):
         a = abi.ErEditInfo()

@@ -541,6 +541,64 @@ typedef struct ErTransformInfo {
 } ErTransformInfo;
 int er_transform_info(ErScene* scene, ErTransformInfo* out);
 
+/* Add and remove triangles of a begun scene in place (csrc/er_topology_host.h states the numbering once).
+ * The edit is applied in this order: the listed triangles are removed, the given ones appended, then `rest` -- an er_render_edit of the
+ * RESULT, so a rest.material_id has the new tri_count entries and overrides the appended ones.  Survivors keep their relative order:
+ *   new_id(old) = old - |{r in remove_ids : r < old}|;   appended triangle j gets id survivors + j.
+ * A result of 0 triangles is legal.  The contract is er_render_update's: after ER_OK every readable output -- the five planes, samples,
+ * RNG, er_get_counters, er_samples_done, er_light_info, er_adaptive_info (off again), er_state_* -- equals, bit for bit, what
+ * er_scene_destroy, er_scene_create of the edited description (the current host copy with pending poses flushed, then the three steps
+ * above), the same er_update_policy_set and er_render_begin with the same ErRenderParams would give.  The structure equals the fresh
+ * one byte for byte (er_debug_read_accel) and ErAccelInfo equals the fresh one except its timings: builder is 0 or 1, never 2, chosen as
+ * er_render_begin chooses it.  The render starts over at sample 0; feature planes and id planes are invalidated; the sparse refit's kept
+ * boxes are released and the rebuild baseline is forgotten, as after any build; with ER_FLAG_MESH_LIGHTS the emitter table is rebuilt.
+ * The counts of ErUpdateInfo, ErEditInfo, ErSparseInfo, ErTransformInfo and ErRebuildInfo do not move: the call has ErTopologyInfo.
+ * The object table survives, renumbered: removed ids leave their objects (an object may become empty), the rest copy keeps the surviving
+ * rows as er_objects_set saw them, per-object bounds are recomputed from them, and appended triangles are in no object -- unless
+ * append_as_object is set and a table is present: they then become a new last object whose rest pose is the arrays given.  A later
+ * er_render_transform gives the outputs of the same absolute poses on a fresh scene made from the edited rest arrays with the
+ * renumbered table.
+ * The geometry store: where the device builder builds, the call keeps the scene's six arrays on the device in id order (140 bytes per
+ * triangle) and the next topology edit compacts them there (csrc/er_topology.hip) instead of uploading them again -- path 1, with
+ *   bytes_uploaded = 4 x remove_count + 140 x append_count,
+ * whatever tri_count is.  Every other call that writes vertices, normals, tangents or material ids (er_render_update,
+ * er_render_update_sparse, er_render_transform with GEOMETRY, er_render_edit with GEOMETRY or a material_id, a rest.material_id here),
+ * er_render_begin and a failed topology edit release the store; the next topology edit fills it from the host copy (path 2,
+ * bytes_uploaded = 140 x tri_count).  Path 0: no store was used -- the host builder built (by size or flag, or because the device builder
+ * declined or failed without ER_FLAG_GPU_BUILD), or the store could not be allocated.
+ * ER_ERR_STATE unless the scene is begun.  ER_ERR_INVALID_ARG, the scene untouched and still begun: NULL arguments; `what` without a
+ * TOPO bit or with unknown bits; a bit with count 0 or without its arrays; a removed id not below tri_count, or listed twice; an
+ * appended vertex coordinate that is not finite; ER_EDIT_GEOMETRY in rest.what; anything er_render_edit refuses in `rest`; a material_id
+ * (appended, kept, or given in rest) beyond the resulting material list; a resulting triangle count that does not fit 32 bits or that
+ * er_scene_create refuses (2^28 and more).  The checks cost O(remove_count log remove_count + append_count) plus what `rest` costs.
+ * As in every edit path the host copy is replaced before any device work; if device work then fails the scene is no longer begun and a
+ * later er_render_begin builds from the edited copy. */
+#define ER_TOPO_REMOVE 1u
+#define ER_TOPO_APPEND 2u
+typedef struct ErTopologyEdit {
+    uint32_t what;                  /* ER_TOPO_* bits, at least one */
+    uint32_t remove_count; const uint32_t* remove_ids;    /* REMOVE: ids in the CURRENT numbering, each < tri_count, none twice */
+    uint32_t append_count;                                /* APPEND: >= 1 */
+    const float *vertices, *normals, *tangents;           /* [append_count][3][3], all required */
+    const float *uvs; const float* tangent_sign;          /* [append_count][3][2], [append_count], required */
+    const int32_t* material_id;                           /* [append_count], required */
+    uint32_t append_as_object;      /* != 0 with an object table present: the appended triangles become a new last object */
+    ErSceneEdit rest;               /* what = 0, or any of CAMERA | MATERIALS | TEXTURES | HDRI with er_render_edit's meaning */
+} ErTopologyEdit;
+typedef struct ErTopologyInfo {
+    uint32_t calls;            /* successful er_render_topology calls since er_scene_create */
+    uint32_t removed, appended, tri_count;   /* the last one: its two counts and the triangle count it left */
+    uint32_t path;             /* 1 = the store was resident, 2 = it was filled from the host copy in this call, 0 = no store used */
+    uint32_t texture_stage;    /* of the `rest` part, as ErEditInfo */
+    uint64_t bytes_uploaded;   /* host-to-device bytes of the geometry stage (path 0: not counted, 0) */
+    float build_ms;            /* the builder's own figure (ErAccelInfo.build_ms) */
+    float store_ms;            /* device time of the compaction (HIP events), 0 unless path 1 */
+    float edit_ms;             /* host wall time of the call */
+    float texture_stage_ms;    /* as ErEditInfo */
+} ErTopologyInfo;
+int er_render_topology(ErScene* scene, const ErTopologyEdit* edit);
+int er_topology_info(ErScene* scene, ErTopologyInfo* out);
+
 /* First-hit feature planes and the denoise guided by them (extension; csrc/er_features.hip gives every float32 operation).
  * er_render_features: a stateless primary-visibility pass over the pixels this rank owns -- n camera rays per pixel (0 -> 4, at most
  * 64; more: ER_ERR_INVALID_ARG) through the production traversal, drawn from the pixel's RNG stream as er_render_begin seeds it, so
