@@ -224,6 +224,15 @@ class ErIdInfo(C.Structure):
                 ("overflow_pixels", C.c_uint32 * ID_KIND_COUNT)]
 
 
+class ErHistoryParams(C.Structure):
+    _fields_ = [("depth_tolerance", C.c_float), ("max_weight", C.c_float)]
+
+
+class ErHistoryInfo(C.Structure):
+    _fields_ = [("captured", C.c_uint32), ("resolved", C.c_uint32), ("moved_objects", C.c_uint32), ("pixels_valid", C.c_uint64), ("pixels_partial", C.c_uint64),
+                ("pixels_offscreen", C.c_uint64), ("pixels_rejected", C.c_uint64), ("pixels_sky", C.c_uint64), ("capture_ms", C.c_float), ("resolve_ms", C.c_float)]
+
+
 class ErPick(C.Structure):
     _fields_ = [("hit", C.c_uint32), ("triangle", C.c_uint32), ("object", C.c_uint32), ("material", C.c_uint32), ("distance", C.c_float),
                 ("position", C.c_float * 3), ("uv", C.c_float * 2)]
@@ -317,6 +326,67 @@ def debug_id_rank(ids):
     up = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))
     check(lib.er_debug_id_rank(up(a) if a.size else None, a.size, up(oi), up(oc), C.byref(distinct)))
     return oi, oc, distinct.value
+
+
+def debug_history_camera(camera):
+    """include/eleven_hip_debug.h er_debug_history_camera: the 12 floats the reprojection projects through (csrc/er_reproject.h) for an
+    ErCamera: position, sensor size, focal length and the rotation's cosines and sines as the library evaluates them."""
+    out = np.zeros(12, np.float32)
+    check(load().er_debug_history_camera(C.byref(camera), _fptr(out)))
+    return out
+
+
+def debug_history_project(cam, x_res, y_res, points):
+    """er_debug_history_project: (xy float32[n][2], ok bool[n]) -- elevenrender_amd/history.py project() restates it"""
+    c, p = np.ascontiguousarray(cam, np.float32).reshape(12), np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    xy, ok = np.zeros((len(p), 2), np.float32), np.zeros(len(p), np.uint32)
+    check(load().er_debug_history_project(_fptr(c), x_res, y_res, len(p), _fptr(p), _fptr(xy), ok.ctypes.data_as(_UP)))
+    return xy, ok != 0
+
+
+def debug_history_back_matrix(m_capture, m_now):
+    """er_debug_history_back_matrix: float32[12], or None where the library refuses the pair"""
+    a, b = np.ascontiguousarray(m_capture, np.float32).reshape(12), np.ascontiguousarray(m_now, np.float32).reshape(12)
+    out = np.zeros(12, np.float32)
+    rc = load().er_debug_history_back_matrix(_fptr(a), _fptr(b), _fptr(out))
+    if rc == ER_ERR_INVALID_ARG:
+        return None
+    check(rc)
+    return out
+
+
+def debug_history_taps(cam, x_res, y_res, tol, hit, obj, P, moved, back, old_hit, old_obj, old_dist, old_cw):
+    """er_debug_history_taps: (rgbw float32[n][4], state uint32[n][4], class uint32[n]) -- history.py resolve() restates it"""
+    u32 = lambda a: np.ascontiguousarray(a, np.uint32).reshape(-1)
+    f32 = lambda a: np.ascontiguousarray(a, np.float32).reshape(-1)
+    c, hit, obj, P, moved, back = f32(cam), u32(hit), u32(obj), f32(P), u32(moved), f32(back)
+    old_hit, old_obj, old_dist, old_cw = u32(old_hit), u32(old_obj), f32(old_dist), f32(old_cw)
+    n = len(hit)
+    assert len(P) == 3 * n and len(back) == 12 * n and len(moved) == n and len(obj) == n
+    assert len(old_hit) == len(old_obj) == len(old_dist) == x_res * y_res and len(old_cw) == 4 * x_res * y_res
+    rgbw, state, cls = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.uint32), np.zeros(n, np.uint32)
+    up = lambda a: a.ctypes.data_as(_UP)
+    check(load().er_debug_history_taps(_fptr(c), x_res, y_res, float(tol), n, up(hit), up(obj), _fptr(P), up(moved), _fptr(back), up(old_hit), up(old_obj),
+                                       _fptr(old_dist), _fptr(old_cw), _fptr(rgbw), up(state), up(cls)))
+    return rgbw, state, cls
+
+
+def debug_history_capture(beauty, samples, hist, max_weight):
+    """er_debug_history_capture: (C.rgb, W) float32[n][4]; hist None = no resolved history"""
+    b, s = np.ascontiguousarray(beauty, np.float32).reshape(-1, 4), np.ascontiguousarray(samples, np.uint32).reshape(-1)
+    h = None if hist is None else np.ascontiguousarray(hist, np.float32).reshape(-1, 4)
+    out = np.zeros((len(s), 4), np.float32)
+    check(load().er_debug_history_capture(len(s), _fptr(b), s.ctypes.data_as(_UP), None if h is None else _fptr(h), float(max_weight), _fptr(out)))
+    return out
+
+
+def debug_history_blend(beauty, samples, hist):
+    """er_debug_history_blend: float32[n][4]"""
+    b, s = np.ascontiguousarray(beauty, np.float32).reshape(-1, 4), np.ascontiguousarray(samples, np.uint32).reshape(-1)
+    h = np.ascontiguousarray(hist, np.float32).reshape(-1, 4)
+    out = np.zeros((len(s), 4), np.float32)
+    check(load().er_debug_history_blend(len(s), _fptr(b), s.ctypes.data_as(_UP), _fptr(h), _fptr(out)))
+    return out
 
 
 def _cost_dict(sums, node_terms, tri_terms):
@@ -417,6 +487,11 @@ SYMBOLS = {
     "er_id_matte": (C.c_int, [_P, C.c_int, _UP, C.c_uint32, _FP]),
     "er_pick_rect": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _UP, C.c_uint32, _UP]),
     "er_pick": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(ErPick)]),
+    "er_history_capture": (C.c_int, [_P, C.POINTER(ErHistoryParams)]),
+    "er_history_resolve": (C.c_int, [_P]),
+    "er_history_info": (C.c_int, [_P, C.POINTER(ErHistoryInfo)]),
+    "er_read_history": (C.c_int, [_P, _FP]),
+    "er_read_blended": (C.c_int, [_P, _FP]),
     "er_state_size": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "er_state_export": (C.c_int, [_P, _P, C.c_uint64]),
     "er_state_import": (C.c_int, [_P, _P, C.c_uint64]),
@@ -468,6 +543,12 @@ OPTIONAL_SYMBOLS = {
     "er_debug_transform_apply": (C.c_int, [_FP, C.c_uint32, _FP, _FP, _FP, _FP, _FP, _FP]),
     "er_debug_accel_cost_host": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(ErCostSumsDebug), C.POINTER(C.c_double), C.c_uint64, _FP, C.c_uint64]),
     "er_debug_id_rank": (C.c_int, [_UP, C.c_uint32, _UP, _UP, _UP]),
+    "er_debug_history_camera": (C.c_int, [_P, _FP]),
+    "er_debug_history_project": (C.c_int, [_FP, C.c_uint32, C.c_uint32, C.c_uint32, _FP, _FP, _UP]),
+    "er_debug_history_back_matrix": (C.c_int, [_FP, _FP, _FP]),
+    "er_debug_history_taps": (C.c_int, [_FP, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, _UP, _UP, _FP, _UP, _FP, _UP, _UP, _FP, _FP, _FP, _UP, _UP]),
+    "er_debug_history_capture": (C.c_int, [C.c_uint32, _FP, _UP, _FP, C.c_float, _FP]),
+    "er_debug_history_blend": (C.c_int, [C.c_uint32, _FP, _UP, _FP, _FP]),
 }
 
 

@@ -141,6 +141,7 @@ static int begin_open(ErScene* s, const ErRenderParams* p) {
     s->ad_on = false;      // (adaptive sampling is set per render, after its er_render_begin)
     s->feat_valid = false; // (the feature planes are of the scene state that ends here)
     s->ids_invalidate();   // (and so are the id planes)
+    s->history_invalidate();   // (and the reprojection history)
     s->rendered = 0;
     s->params.world = p->world ? p->world : 1;
     if (s->params.max_bounces == 0) s->params.max_bounces = 5;   // the literal of reference src/kernel.cpp:508
@@ -156,6 +157,7 @@ static int begin_open(ErScene* s, const ErRenderParams* p) {
         const char* which = nullptr;
         hipError_t pe = er_probe_kernels(&which);
         if (pe == hipSuccess) pe = er_probe_ids(&which);
+        if (pe == hipSuccess) pe = er_probe_history(&which);
         if (pe != hipSuccess)
             return fail(ER_ERR_HIP, std::string("er_render_begin: libeleven_hip.so has no usable gfx950 code object for ") + (which ? which : "?") +
                                         " on this device (" + hipGetErrorString(pe) + "); rebuild with `make -C elevenrender_amd/csrc`");
@@ -923,6 +925,7 @@ static int er_state_import_impl(ErScene* s, const void* src, uint64_t bytes) {
     p += npx * sizeof(uint32_t);
     HIP_TRY(hipMemcpyAsync(s->d_rng.p, p, npx * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));      // the caller's buffer may go away
+    s->history_invalidate();      // (the planes are another render's: er_history.hip)
     return ER_OK;
 }
 

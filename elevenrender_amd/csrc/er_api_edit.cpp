@@ -465,6 +465,7 @@ int edit_locked(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, XformL
     s->feat_valid = false;      // the feature planes show the scene before the edit (er_render_features makes them again)
     for (auto& set : s->unpacked_feat) set.clear();
     s->ids_invalidate();        // (and so do the id planes: er_render_ids)
+    if (((e->what & ER_EDIT_GEOMETRY) && !xf) || (e->what & LOOK_BITS)) s->history_invalidate();      // a camera or a pose keeps the history (er_history.hip)
     uint32_t stage = 0;
     float stage_ms = 0;
     const bool sparse_geometry = sp && (e->what & ER_EDIT_GEOMETRY);
@@ -557,6 +558,7 @@ static int er_objects_set_impl(ErScene* s, uint32_t object_count, const uint32_t
         s->xform_dev.release();
     }
     s->ids_invalidate();      // the OBJECT plane and the tri -> object map were the old table's (er_ids.hip)
+    s->history_invalidate();      // (and the captured poses)
     s->id_map_valid = false;
     return ER_OK;
 }
@@ -746,6 +748,7 @@ static int er_render_topology_impl(ErScene* s, const ErTopologyEdit* t) {
     s->feat_valid = false;
     for (auto& set : s->unpacked_feat) set.clear();
     s->ids_invalidate();
+    s->history_invalidate();
     s->d_id_map.release();      // the tri -> object map and the table's device form were of the old numbering: the lazy paths make them again
     s->id_map_valid = false;
     s->xform_dev.release();

@@ -392,6 +392,10 @@ int pick_impl(ErScene* s, uint32_t x, uint32_t y, ErPick* out) {
 
 }  // namespace
 
+// what er_history.hip shares with the pass: the spill area and the tri -> object map
+int er_id_prepare(ErScene* s, uint32_t blocks) { return id_prepare(s, blocks); }
+const uint32_t* er_id_map(ErScene* s) { return id_map(s); }
+
 extern "C" {
 int er_render_ids(ErScene* s, uint32_t n) { return guarded("er_render_ids", [&]() -> int { return render_ids_impl(s, n); }); }
 int er_id_info(ErScene* s, ErIdInfo* out) { return guarded("er_id_info", [&]() -> int { return id_info_impl(s, out); }); }

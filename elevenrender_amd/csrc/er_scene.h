@@ -34,6 +34,7 @@
 #include "er_texstage.h"
 #include "er_features.h"
 #include "er_ids.h"
+#include "er_history.h"
 #include "er_topology.h"
 
 namespace erh {
@@ -276,6 +277,10 @@ struct ErScene {
     uint64_t ids_rays = 0;
     float ids_ms = 0;
     void ids_invalidate() noexcept { ids_valid = false; }
+    // the temporal reprojection (er_history.hip): key planes, the captured colours and the resolved history; dropped by whatever changes
+    // the look or moves a triangle other than by a pose (history_invalidate)
+    ErHistoryState hist;
+    void history_invalidate() noexcept { hist.invalidate(); }
     std::mutex mtx;
 
     uint32_t tiles_x() const { return (x_res + ER_TILE - 1) / ER_TILE; }      // the frame in tiles of ER_TILE x ER_TILE pixels
@@ -306,6 +311,7 @@ struct ErScene {
         d_feat.release(); d_feat_spill.release(); feat_valid = false;
         for (auto& u : unpacked_feat) u.clear();
         d_id_planes.release(); d_id_map.release(); d_id_work.release(); d_id_over.release(); ids_valid = id_map_valid = false;
+        hist.release();
         ad_on = false; rendered = 0;
         for (auto& kv : d_rank_tiles) kv.second.release();
         d_rank_tiles.clear();

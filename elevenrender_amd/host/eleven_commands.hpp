@@ -299,6 +299,7 @@ private:
             j["topology_edits"] = topology_edits_;
             j["feature_samples"] = rm.pars.feature_samples ? rm.pars.feature_samples : 4u;      // rays per pixel of a feature pass (--get_pass albedo / depth, denoise_guided)
             if (rm.pars.denoise_guided) j["denoise_guided"] = true;
+            if (rm.pars.history) j["history_resolves"] = rm.history_resolves;      // (only with the key: a session without it answers as before)
             im->write_message(Message::json_data(j));
             return;
         }
@@ -399,6 +400,9 @@ private:
             if (n < 1 || n > 64) throw std::runtime_error("config feature_samples out of range (1 .. 64)");
             rp.feature_samples = (unsigned)n;
         }
+        // temporal reprojection across camera updates (er_history_capture / er_history_resolve): --get_pass blended
+        if (const json::Value* v = j.if_contains("history")) rp.history = v->as_bool();
+        if (rp.history && rp.gpus > 1) throw std::runtime_error("config history needs gpus 1 (a sharded frame keeps no history)");
         stop_render_thread();
         rm.pars = rp;
         scene.x_res = rp.width;
@@ -462,6 +466,14 @@ private:
         if (parseFeature(pass) >= 0) {      // a feature plane: made when first asked for after a --start or a camera update
             rm.ensure_features(rm.pars.feature_samples);
             img = rm.get_feature(pass);
+            im->write_message(Message::float_data(img.data(), img.size(), Message::DataFormat::FLOAT4));
+            return;
+        }
+        std::string lower = pass;
+        std::transform(lower.begin(), lower.end(), lower.begin(), [](unsigned char ch) { return (char)std::tolower(ch); });
+        if (lower == "blended") {           // the history of the last camera update and the current BEAUTY (config "history": true)
+            if (!rm.pars.history) throw std::runtime_error("get_pass blended needs \"history\": true in the config");
+            img = rm.get_blended();
             im->write_message(Message::float_data(img.data(), img.size(), Message::DataFormat::FLOAT4));
             return;
         }

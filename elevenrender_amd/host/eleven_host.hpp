@@ -134,6 +134,9 @@ struct RenderParameters {   // src/kernel.h:51-69
     // er_denoise_guided on feature planes of feature_samples camera rays per pixel (0 = the library's default, 4)
     bool denoise_guided = false;
     unsigned feature_samples = 0;
+    // temporal reprojection (extension, off by default): a --start answered by the camera-update path captures the frame before the
+    // update and resolves it after (er_history_capture / er_history_resolve); --get_pass blended then answers er_read_blended.  One GPU.
+    bool history = false;
 };
 
 // What a session sent since its last successful --start.  A --start after nothing but --load_camera restarts the render in place
@@ -338,12 +341,16 @@ public:
                             {c.rotation.x, c.rotation.y, c.rotation.z}, c.bokeh ? 1 : 0, {c.position.x, c.position.y, c.position.z}};
         std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);
         if (ers_.size() > 1) lk.lock();
+        // `history`: the frame as it is goes into a capture first (a refused capture only means this restart carries nothing over)
+        const ErHistoryParams hp{0.0f, 0.0f};
+        const bool captured = pars.history && ers_.size() == 1 && er_history_capture(ers_[0], &hp) == ER_OK;
         std::vector<int> rcs(ers_.size(), ER_OK);
         std::vector<std::thread> th;
         for (size_t r = 0; r < ers_.size(); r++) th.emplace_back([&, r] { rcs[r] = er_render_update(ers_[r], &u); });
         for (auto& t : th) t.join();
         features_ready_ = false;      // (the library has invalidated the planes)
         for (int rc : rcs) if (rc != ER_OK) return false;
+        if (captured && er_history_resolve(ers_[0]) == ER_OK) history_resolves++;
         if (pars.adaptive)
             for (ErScene* e : ers_) if (er_adaptive_set(e, &pars.adaptive_params) != ER_OK) return false;
         return true;
@@ -481,6 +488,16 @@ public:
         for (ErScene* e : ers_) if (er_wait(e, nullptr) != ER_OK && err.empty()) err = er_last_error();
         if (!err.empty()) throw std::runtime_error(err);
     }
+    // er_read_blended: the reprojected history and the current BEAUTY combined (`history`; throws until a camera update has resolved one)
+    std::vector<float> get_blended() {
+        if (ers_.empty()) throw std::runtime_error("get_blended: no render has been started");
+        std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);
+        if (ers_.size() > 1) lk.lock();
+        std::vector<float> out((size_t)pars.width * pars.height * 4);
+        check(er_read_blended(ers_[0], out.data()));
+        return out;
+    }
+    unsigned history_resolves = 0;      // camera updates whose frame was carried over (reported by --get_info)
     std::vector<float> get_pass(const std::string& pass) {   // src/Managers.cpp:287-302
         if (ers_.empty()) throw std::runtime_error("get_pass: no render has been started");
         std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);

@@ -133,17 +133,25 @@ class RenderingManager:
                 setattr(call, name, a.ctypes.data_as(C.POINTER(C.c_float)))
         return keep
 
-    def update(self, camera=None, vertices=None, normals=None, tangents=None, tri_ids=None):
+    def update(self, camera=None, vertices=None, normals=None, tangents=None, tri_ids=None, keep_history=False):
         """er_render_update: a new camera (abi.ErCamera) and / or moved triangles ([n][3][3] float32 vertices; normals and tangents
         optional, None = keep) for the begun scene, without a rebuild; the render starts over at sample 0.  self.scene is not changed:
         a caller that wants to compare against a fresh start builds the edited SceneData itself.
         With tri_ids (distinct triangle ids) the arrays are [len(tri_ids)][3][3], one entry per listed triangle, the other triangles
-        stay, and er_render_update_sparse is called: the same result, at a cost that follows the list and not the scene."""
+        stay, and er_render_update_sparse is called: the same result, at a cost that follows the list and not the scene.
+        keep_history: history_capture() before the call and history_resolve() after it; only a camera-only call keeps a capture, any
+        other raises ValueError."""
+        if keep_history:
+            if vertices is not None or tri_ids is not None:
+                raise ValueError("update: keep_history goes with a camera-only call (moved vertices drop the history)")
+            self.history_capture()
         if tri_ids is not None:
             return self._update_sparse(camera, tri_ids, vertices, normals, tangents)
         u = abi.ErSceneUpdate()
         keep = self._camera_and_geometry(u, "update", camera, vertices, normals, tangents)      # (alive until the call returns)
         abi.check(self.lib.er_render_update(self.handle, C.byref(u)))
+        if keep_history:
+            self.history_resolve()
 
     def _update_sparse(self, camera, tri_ids, vertices, normals, tangents):
         u = abi.ErSparseUpdate()
@@ -189,10 +197,13 @@ class RenderingManager:
         up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
         abi.check(self.lib.er_objects_set(self.handle, len(lists), up(first), up(ids)))
 
-    def transform(self, poses, camera=None):
+    def transform(self, poses, camera=None, keep_history=False):
         """er_render_transform: `poses` maps an object's index to its 3x4 matrix (row-major, x' = L x + t; anything that reshapes to 12
         float32).  Each listed object takes that pose of its REST copy on the device -- absolute, not composed with an earlier one --;
-        the others stay.  The render starts over at sample 0.  self.scene is not changed."""
+        the others stay.  The render starts over at sample 0.  self.scene is not changed.
+        keep_history: history_capture() before the call and history_resolve() after it (poses and cameras keep a capture)."""
+        if keep_history:
+            self.history_capture()
         u = abi.ErTransformUpdate()
         if camera is not None:
             u.what |= abi.UPDATE_CAMERA
@@ -210,6 +221,8 @@ class RenderingManager:
             u.what |= abi.UPDATE_GEOMETRY
             u.count, u.transforms = len(poses), xs
         abi.check(self.lib.er_render_transform(self.handle, C.byref(u)))
+        if keep_history:
+            self.history_resolve()
 
     def transform_info(self):
         a = abi.ErTransformInfo()
@@ -268,15 +281,22 @@ class RenderingManager:
         return keep
 
     def edit(self, camera=None, vertices=None, normals=None, tangents=None, materials=None, material_id=None, textures=None, hdri=None,
-             hdri_cdf=None, hdri_radiance_sum=0.0):
+             hdri_cdf=None, hdri_radiance_sum=0.0, keep_history=False):
         """er_render_edit: er_render_update's arguments plus `materials` (the complete new list of abi.ErMaterial; `material_id` int32[n]
         or None = keep), `textures` (the complete new list of (data, w, h, channels, filter) tuples as in SceneData; None in place of an
         entry = keep that texture) and `hdri` (such a tuple; hdri_cdf / hdri_radiance_sum as in SceneData, None = built by the
-        library).  The render starts over at sample 0.  self.scene is not changed."""
+        library).  The render starts over at sample 0.  self.scene is not changed.
+        keep_history: as update()'s -- only a camera-only call keeps a capture, any other raises ValueError."""
+        if keep_history:
+            if any(a is not None for a in (vertices, materials, material_id, textures, hdri)):
+                raise ValueError("edit: keep_history goes with a camera-only call (geometry and look edits drop the history)")
+            self.history_capture()
         e = abi.ErSceneEdit()
         keep = self._camera_and_geometry(e, "edit", camera, vertices, normals, tangents)
         keep += self._look(e, "edit", self._tri_count(), materials, material_id, textures, hdri, hdri_cdf, hdri_radiance_sum)
         abi.check(self.lib.er_render_edit(self.handle, C.byref(e)))
+        if keep_history:
+            self.history_resolve()
 
     def topology(self, remove=None, append=None, as_object=False, camera=None, materials=None, material_id=None, textures=None, hdri=None,
                  hdri_cdf=None, hdri_radiance_sum=0.0):
@@ -486,6 +506,32 @@ class RenderingManager:
         abi.check(self.lib.er_pick(self.handle, x, y, C.byref(p)))
         return dict(hit=int(p.hit), triangle=int(p.triangle), object=int(p.object), material=int(p.material), distance=np.float32(p.distance),
                     position=np.array(list(p.position), np.float32), uv=np.array(list(p.uv), np.float32))
+
+    def history_capture(self, depth_tolerance=0.0, max_weight=0.0):
+        """er_history_capture, before an edit: the key plane, the camera, the poses and per pixel the colour and weight the next
+        history_resolve() reprojects (0 -> depth_tolerance 0.02, max_weight 32).  The render's own state is not written."""
+        abi.check(self.lib.er_history_capture(self.handle, C.byref(abi.ErHistoryParams(float(depth_tolerance), float(max_weight)))))
+
+    def history_resolve(self):
+        """er_history_resolve, after the edit: the captured colours reprojected into the frame as it is now."""
+        abi.check(self.lib.er_history_resolve(self.handle))
+
+    def history_info(self):
+        a = abi.ErHistoryInfo()
+        abi.check(self.lib.er_history_info(self.handle, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in abi.ErHistoryInfo._fields_}
+
+    def get_history(self):
+        """er_read_history: (H, W, 4) float32 -- rgb = the reprojected colour, a = the carried sample weight (0: none)."""
+        out = np.empty((self.scene.y_res, self.scene.x_res, 4), np.float32)
+        abi.check(self.lib.er_read_history(self.handle, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def get_blended(self):
+        """er_read_blended: (H, W, 4) float32 -- the history and the current BEAUTY combined by their sample weights, alpha 1."""
+        out = np.empty((self.scene.y_res, self.scene.x_res, 4), np.float32)
+        abi.check(self.lib.er_read_blended(self.handle, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
 
     def read_samples(self):
         out = np.empty(self.scene.x_res * self.scene.y_res, np.uint32)

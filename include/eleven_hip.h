@@ -687,6 +687,53 @@ int er_id_matte(ErScene* scene, int kind, const uint32_t* ids, uint32_t count, f
 int er_pick_rect(ErScene* scene, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, int kind, uint32_t* ids, uint32_t capacity, uint32_t* count);
 int er_pick(ErScene* scene, uint32_t x, uint32_t y, ErPick* out);
 
+/* Keeping the image across camera moves and object poses by temporal reprojection (extension; csrc/er_reproject.h and er_history.hip;
+ * DESIGN.md 3l).  A display-side aid like the DENOISE plane: the render's planes, sample counts, RNG and counters are neither read for
+ * anything but the colour nor written, so a render with these calls in between is, bit for bit, the render without them.
+ * A KEY PLANE holds one pinhole ray per pixel through the production traversal -- camera_ray with r1 = r2 = 0.5 and bokeh taken as 0, so
+ * pixel x samples continuous coordinate x exactly --: a hit flag, the object of the current table (ER_ID_NONE if the triangle is in no
+ * object or there is no table), the distance length(Hit.position - ray.o), Hit.position, and for a miss the ray's direction.
+ * er_history_capture (before an edit): makes the key plane of the scene as it is now unless the previous resolve left one that is still
+ * current (same camera and poses, bit for bit), stores the camera and every object's pose, and per pixel a colour C and a weight W: with
+ * n = samples - 1 and m = BEAUTY.rgb * ((float)samples / (float)n) for n > 0,  C = (w H + n m) / (w + n)  where (H, w) is the pixel's
+ * resolved history if one is valid (else w = 0), C = 0 if w + n = 0;  W = min(w + n, max_weight).  History therefore accumulates over
+ * a sequence of edits.  params may name 0 for a default (depth_tolerance 0.02, relative; max_weight 32).
+ * er_history_resolve (after it): makes the key plane of the scene as it is now and keeps it for the next capture.  For a pixel that
+ * hits, P_old = B_o P_new with B_o = M_capture o M_now^-1 of the pixel's object (computed on the host in double, rounded to float once);
+ * objects whose two poses are bitwise equal, and ER_ID_NONE, take P_old = P_new bit for bit.  For a pixel that misses, P_old = the old
+ * camera position + the ray's direction.  P_old is projected through the captured camera to continuous pixel coordinates (invalid if
+ * the point is not in front of the camera or a coordinate is not finite), and four bilinear taps are taken around them.  A tap is valid
+ * if it is inside the frame, the captured key there has the same hit flag and, for hits, the same object and
+ * |d_exp - d_old| <= depth_tolerance * d_exp, d_exp = |P_old - old camera position|.  History rgb and w are the bilinear means of C and
+ * W over the valid taps, weights renormalised; w = 0 if no tap is valid.  Every pixel is in exactly one class of ErHistoryInfo: sky (it
+ * misses), valid (four valid taps), partial (one to three), offscreen (no tap inside the frame), rejected (the rest).
+ * er_read_history: rgb = the reprojected colour, a = the carried weight w (0: none).
+ * er_read_blended: (w H + n m) / (w + n) per pixel from the current BEAUTY and sample counts, alpha 1; the setup colour where w + n = 0.
+ * A changed camera keeps a capture, through any edit path; so do er_render_transform and er_render_samples.  er_render_begin,
+ * er_render_topology, er_objects_set, er_state_import, every direct geometry edit (er_render_update / _sparse / er_render_edit with the
+ * geometry bit) and every materials, textures or HDRI edit drop the capture and the resolved history: er_history_resolve and the two
+ * reads then return ER_ERR_STATE.
+ * ER_ERR_STATE: the scene is not begun; resolve without a capture; a read without a resolve; world > 1 (a sharded frame would need the
+ * old pixels of other ranks: not built).  ER_ERR_INVALID_ARG: NULL arguments; negative or NaN parameters.
+ * Stated limits: view-dependent shading and moved shadows go stale, bounded by max_weight; the first hit counts regardless of opacity,
+ * as in the feature pass.  The planes (80 bytes per pixel) are allocated by the first capture, freed with the scene and not part of
+ * er_state_*. */
+typedef struct ErHistoryParams {
+    float depth_tolerance;    /* 0 -> 0.02: relative */
+    float max_weight;         /* 0 -> 32: cap on the carried sample weight */
+} ErHistoryParams;
+typedef struct ErHistoryInfo {
+    uint32_t captured, resolved;      /* a capture is held / a history plane is valid */
+    uint32_t moved_objects;           /* objects whose pose differs between capture and resolve */
+    uint64_t pixels_valid, pixels_partial, pixels_offscreen, pixels_rejected, pixels_sky;   /* of the last resolve */
+    float capture_ms, resolve_ms;     /* device time of the last capture / resolve (HIP events) */
+} ErHistoryInfo;
+int er_history_capture(ErScene* scene, const ErHistoryParams* params);
+int er_history_resolve(ErScene* scene);
+int er_history_info(ErScene* scene, ErHistoryInfo* out);
+int er_read_history(ErScene* scene, float* dst_rgba);
+int er_read_blended(ErScene* scene, float* dst_rgba);
+
 #ifdef __cplusplus
 }
 #endif

@@ -286,6 +286,30 @@ int er_debug_transform_apply(const float m[12], uint32_t count, const float* ver
  * count > 64. */
 int er_debug_id_rank(const uint32_t* ids, uint32_t count, uint32_t* out_ids, uint32_t* out_counts, uint32_t* distinct);
 
+/* The arithmetic of the temporal reprojection (csrc/er_reproject.h, the functions the kernels call), on caller arrays, no device needed.
+ * A projection camera is 12 floats: position[3], sensor_width, sensor_height, focal_length, then cos and sin of the rotation about x,
+ * y and z as the library evaluates them (cx, sx, cy, sy, cz, sz).
+ * er_debug_history_camera: the 12 floats of an ErCamera.
+ * er_debug_history_project: `count` world points [count][3] -> out_xy [count][2] continuous pixel coordinates and out_ok [count]
+ *   (0: not in front of the camera, or a coordinate not finite; the coordinates are then 0).
+ * er_debug_history_back_matrix: B = M_capture o M_now^-1 of two row-major 3x4 poses; ER_ERR_INVALID_ARG if an entry is not finite or
+ *   det(L_now) is not > 0.
+ * er_debug_history_taps: one resolve of `count` pixels against a captured frame of x_res x y_res pixels.  Per pixel i: the new key --
+ *   hit[i], object[i], P[i][3] (Hit.position, or the ray's direction of a miss) -- and moved[i] != 0 with back[i][12] if its object's
+ *   pose changed.  The captured frame: old_hit, old_object, old_dist [y_res * x_res] and old_cw [y_res * x_res][4] = (C.rgb, W).
+ *   Out: out_rgbw [count][4] = (H.rgb, w), out_state [count][4] = the four taps' states (0 valid, 1 outside the frame, 2 hit flag, 3
+ *   object, 4 depth), out_class [count] (0 valid, 1 partial, 2 offscreen, 3 rejected, 4 sky).
+ * er_debug_history_capture / _blend: `count` pixels of a capture (hist may be NULL: no resolved history) or of er_read_blended:
+ *   beauty [count][4], samples [count], hist [count][4] -> out [count][4]. */
+int er_debug_history_camera(const void* camera /* an ErCamera of eleven_hip.h */, float out[12]);
+int er_debug_history_project(const float cam[12], uint32_t x_res, uint32_t y_res, uint32_t count, const float* points, float* out_xy, uint32_t* out_ok);
+int er_debug_history_back_matrix(const float m_capture[12], const float m_now[12], float out[12]);
+int er_debug_history_taps(const float cam[12], uint32_t x_res, uint32_t y_res, float depth_tolerance, uint32_t count, const uint32_t* hit, const uint32_t* object,
+                          const float* P, const uint32_t* moved, const float* back, const uint32_t* old_hit, const uint32_t* old_object, const float* old_dist,
+                          const float* old_cw, float* out_rgbw, uint32_t* out_state, uint32_t* out_class);
+int er_debug_history_capture(uint32_t count, const float* beauty, const uint32_t* samples, const float* hist, float max_weight, float* out);
+int er_debug_history_blend(uint32_t count, const float* beauty, const uint32_t* samples, const float* hist, float* out);
+
 #ifdef __cplusplus
 }
 #endif
