@@ -233,6 +233,15 @@ class ErHistoryInfo(C.Structure):
                 ("pixels_offscreen", C.c_uint64), ("pixels_rejected", C.c_uint64), ("pixels_sky", C.c_uint64), ("capture_ms", C.c_float), ("resolve_ms", C.c_float)]
 
 
+class ErVarianceInfo(C.Structure):
+    _fields_ = [("folds", C.c_uint32), ("reserved", C.c_uint32), ("pixels_folded", C.c_uint64), ("pixels_known", C.c_uint64), ("fold_ms", C.c_float),
+                ("filter_ms", C.c_float)]
+
+
+class ErDenoiseVariance(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("colour_sigma", C.c_float), ("albedo_sigma", C.c_float), ("depth_sigma", C.c_float)]
+
+
 class ErPick(C.Structure):
     _fields_ = [("hit", C.c_uint32), ("triangle", C.c_uint32), ("object", C.c_uint32), ("material", C.c_uint32), ("distance", C.c_float),
                 ("position", C.c_float * 3), ("uv", C.c_float * 2)]
@@ -389,6 +398,52 @@ def debug_history_blend(beauty, samples, hist):
     return out
 
 
+def debug_variance_mark(beauty, samples):
+    """include/eleven_hip_debug.h er_debug_variance_mark: the state float32[n][12] of a reset (csrc/er_variance.h; no device needed) --
+    elevenrender_amd/variance.py mark() restates it"""
+    b, s = np.ascontiguousarray(beauty, np.float32).reshape(-1, 4), np.ascontiguousarray(samples, np.uint32).reshape(-1)
+    st = np.zeros((len(s), 12), np.float32)
+    check(load().er_debug_variance_mark(len(s), _fptr(b), s.ctypes.data_as(_UP), _fptr(st)))
+    return st
+
+
+def debug_variance_fold(state, beauty, samples):
+    """er_debug_variance_fold: (new state float32[n][12], folded bool[n]); `state` is not changed"""
+    st = np.ascontiguousarray(state, np.float32).reshape(-1, 12).copy()
+    b, s = np.ascontiguousarray(beauty, np.float32).reshape(-1, 4), np.ascontiguousarray(samples, np.uint32).reshape(-1)
+    assert len(st) == len(b) == len(s)
+    folded = np.zeros(len(s), np.uint32)
+    check(load().er_debug_variance_fold(len(s), _fptr(b), s.ctypes.data_as(_UP), _fptr(st), folded.ctypes.data_as(_UP)))
+    return st, folded != 0
+
+
+def debug_variance_value(state, samples):
+    """er_debug_variance_value: float32[n][4] = er_read_variance's pixels"""
+    st, s = np.ascontiguousarray(state, np.float32).reshape(-1, 12), np.ascontiguousarray(samples, np.uint32).reshape(-1)
+    assert len(st) == len(s)
+    out = np.zeros((len(s), 4), np.float32)
+    check(load().er_debug_variance_value(len(s), _fptr(st), s.ctypes.data_as(_UP), _fptr(out)))
+    return out
+
+
+def debug_variance_split(value, albedo):
+    """er_debug_variance_split: the demodulated variance float32[n][4] (w: the K >= 2 flag)"""
+    v, a = np.ascontiguousarray(value, np.float32).reshape(-1, 4), np.ascontiguousarray(albedo, np.float32).reshape(-1, 4)
+    assert len(v) == len(a)
+    out = np.zeros((len(v), 4), np.float32)
+    check(load().er_debug_variance_split(len(v), _fptr(v), _fptr(a), _fptr(out)))
+    return out
+
+
+def debug_variance_level(e, ve, normal, albedo, depth, w, h, step, kc, ka, kz):
+    """er_debug_variance_level_px: one level of er_denoise_variance over a frame of w x h pixels: (e', ve') float32[h * w][4]"""
+    planes = [np.ascontiguousarray(a, np.float32).reshape(-1, 4) for a in (e, ve, normal, albedo, depth)]
+    assert all(len(a) == w * h for a in planes)
+    oe, ov = np.zeros((w * h, 4), np.float32), np.zeros((w * h, 4), np.float32)
+    check(load().er_debug_variance_level_px(w, h, step, float(kc), float(ka), float(kz), *(_fptr(a) for a in planes), _fptr(oe), _fptr(ov)))
+    return oe, ov
+
+
 def _cost_dict(sums, node_terms, tri_terms):
     d = {n: getattr(sums, n) for n in ("node_area", "leaf_area", "tri_area", "cost", "ms")}
     d.update(node_terms=node_terms, tri_terms=tri_terms)
@@ -492,6 +547,10 @@ SYMBOLS = {
     "er_history_info": (C.c_int, [_P, C.POINTER(ErHistoryInfo)]),
     "er_read_history": (C.c_int, [_P, _FP]),
     "er_read_blended": (C.c_int, [_P, _FP]),
+    "er_variance_fold": (C.c_int, [_P]),
+    "er_variance_info": (C.c_int, [_P, C.POINTER(ErVarianceInfo)]),
+    "er_read_variance": (C.c_int, [_P, _FP]),
+    "er_denoise_variance": (C.c_int, [_P, C.POINTER(ErDenoiseVariance)]),
     "er_state_size": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "er_state_export": (C.c_int, [_P, _P, C.c_uint64]),
     "er_state_import": (C.c_int, [_P, _P, C.c_uint64]),
@@ -549,6 +608,11 @@ OPTIONAL_SYMBOLS = {
     "er_debug_history_taps": (C.c_int, [_FP, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, _UP, _UP, _FP, _UP, _FP, _UP, _UP, _FP, _FP, _FP, _UP, _UP]),
     "er_debug_history_capture": (C.c_int, [C.c_uint32, _FP, _UP, _FP, C.c_float, _FP]),
     "er_debug_history_blend": (C.c_int, [C.c_uint32, _FP, _UP, _FP, _FP]),
+    "er_debug_variance_mark": (C.c_int, [C.c_uint32, _FP, _UP, _FP]),
+    "er_debug_variance_fold": (C.c_int, [C.c_uint32, _FP, _UP, _FP, _UP]),
+    "er_debug_variance_value": (C.c_int, [C.c_uint32, _FP, _UP, _FP]),
+    "er_debug_variance_split": (C.c_int, [C.c_uint32, _FP, _FP, _FP]),
+    "er_debug_variance_level_px": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
 }
 
 

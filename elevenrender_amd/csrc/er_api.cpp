@@ -142,6 +142,7 @@ static int begin_open(ErScene* s, const ErRenderParams* p) {
     s->feat_valid = false; // (the feature planes are of the scene state that ends here)
     s->ids_invalidate();   // (and so are the id planes)
     s->history_invalidate();   // (and the reprojection history)
+    s->variance_reset();       // (and the variance moments: the render starts over)
     s->rendered = 0;
     s->params.world = p->world ? p->world : 1;
     if (s->params.max_bounces == 0) s->params.max_bounces = 5;   // the literal of reference src/kernel.cpp:508
@@ -158,6 +159,7 @@ static int begin_open(ErScene* s, const ErRenderParams* p) {
         hipError_t pe = er_probe_kernels(&which);
         if (pe == hipSuccess) pe = er_probe_ids(&which);
         if (pe == hipSuccess) pe = er_probe_history(&which);
+        if (pe == hipSuccess) pe = er_probe_variance(&which);
         if (pe != hipSuccess)
             return fail(ER_ERR_HIP, std::string("er_render_begin: libeleven_hip.so has no usable gfx950 code object for ") + (which ? which : "?") +
                                         " on this device (" + hipGetErrorString(pe) + "); rebuild with `make -C elevenrender_amd/csrc`");
@@ -926,7 +928,7 @@ static int er_state_import_impl(ErScene* s, const void* src, uint64_t bytes) {
     HIP_TRY(hipMemcpyAsync(s->d_rng.p, p, npx * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));      // the caller's buffer may go away
     s->history_invalidate();      // (the planes are another render's: er_history.hip)
-    return ER_OK;
+    return er_variance_mark_imported(s);      // (and the variance starts over from them: er_variance.hip)
 }
 
 static int er_denoise_impl(ErScene* s, uint32_t levels, float colour_sigma) {

@@ -466,6 +466,7 @@ int edit_locked(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, XformL
     for (auto& set : s->unpacked_feat) set.clear();
     s->ids_invalidate();        // (and so do the id planes: er_render_ids)
     if (((e->what & ER_EDIT_GEOMETRY) && !xf) || (e->what & LOOK_BITS)) s->history_invalidate();      // a camera or a pose keeps the history (er_history.hip)
+    s->variance_reset();        // the render starts over: so do the variance moments (er_variance.hip)
     uint32_t stage = 0;
     float stage_ms = 0;
     const bool sparse_geometry = sp && (e->what & ER_EDIT_GEOMETRY);
@@ -749,6 +750,7 @@ static int er_render_topology_impl(ErScene* s, const ErTopologyEdit* t) {
     for (auto& set : s->unpacked_feat) set.clear();
     s->ids_invalidate();
     s->history_invalidate();
+    s->variance_reset();
     s->d_id_map.release();      // the tri -> object map and the table's device form were of the old numbering: the lazy paths make them again
     s->id_map_valid = false;
     s->xform_dev.release();

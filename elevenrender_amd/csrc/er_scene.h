@@ -35,6 +35,7 @@
 #include "er_features.h"
 #include "er_ids.h"
 #include "er_history.h"
+#include "er_variance_state.h"
 #include "er_topology.h"
 
 namespace erh {
@@ -281,6 +282,10 @@ struct ErScene {
     // the look or moves a triangle other than by a pose (history_invalidate)
     ErHistoryState hist;
     void history_invalidate() noexcept { hist.invalidate(); }
+    // the variance plane (er_variance.hip): the batch-mean moments of every pixel since the render last started over (variance_reset:
+    // er_render_begin and every edit; er_state_import snapshots what it brought)
+    ErVarianceState var;
+    void variance_reset() noexcept { var.reset(); }
     std::mutex mtx;
 
     uint32_t tiles_x() const { return (x_res + ER_TILE - 1) / ER_TILE; }      // the frame in tiles of ER_TILE x ER_TILE pixels
@@ -312,6 +317,7 @@ struct ErScene {
         for (auto& u : unpacked_feat) u.clear();
         d_id_planes.release(); d_id_map.release(); d_id_work.release(); d_id_over.release(); ids_valid = id_map_valid = false;
         hist.release();
+        var.release();
         ad_on = false; rendered = 0;
         for (auto& kv : d_rank_tiles) kv.second.release();
         d_rank_tiles.clear();

@@ -27,7 +27,11 @@
 //     gathers the plane to the first of them (er_gather_pass: RCCL send/recv over xGMI, or in-process peer copies);
 //   * --get_pass albedo / depth return the first-hit feature planes (er_render_features, computed once per --start or camera
 //     update, when first asked for); config "denoise_guided": true (optionally "feature_samples": 1 .. 64) makes `denoise: true` /
-//     --get_pass denoise run the filter guided by them (er_denoise_guided) instead of er_denoise.
+//     --get_pass denoise run the filter guided by them (er_denoise_guided) instead of er_denoise;
+//   * config "denoise_variance": true (optionally "variance_batch": b, 0 or absent = 2; gpus 1) makes the render thread fold a batch into
+//     the variance plane whenever the samples reach a multiple of b (er_variance_fold), `denoise: true` / --get_pass denoise run the
+//     filter whose colour stop follows that plane (er_denoise_variance; the guided filter until two folds exist), --get_pass variance
+//     return the plane and --get_info report variance_folds.
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -300,6 +304,7 @@ private:
             j["feature_samples"] = rm.pars.feature_samples ? rm.pars.feature_samples : 4u;      // rays per pixel of a feature pass (--get_pass albedo / depth, denoise_guided)
             if (rm.pars.denoise_guided) j["denoise_guided"] = true;
             if (rm.pars.history) j["history_resolves"] = rm.history_resolves;      // (only with the key: a session without it answers as before)
+            if (rm.pars.denoise_variance) j["variance_folds"] = rm.variance_folds();      // (the same)
             im->write_message(Message::json_data(j));
             return;
         }
@@ -403,6 +408,14 @@ private:
         // temporal reprojection across camera updates (er_history_capture / er_history_resolve): --get_pass blended
         if (const json::Value* v = j.if_contains("history")) rp.history = v->as_bool();
         if (rp.history && rp.gpus > 1) throw std::runtime_error("config history needs gpus 1 (a sharded frame keeps no history)");
+        // the variance plane by batch means and the denoise guided by it (er_variance_fold / er_denoise_variance): --get_pass variance
+        if (const json::Value* v = j.if_contains("denoise_variance")) rp.denoise_variance = v->as_bool();
+        if (const json::Value* v = j.if_contains("variance_batch")) {
+            const long long b = v->as_int64();
+            if (b < 0 || b > 1000000) throw std::runtime_error("config variance_batch out of range (0 .. 1000000)");
+            rp.variance_batch = (unsigned)b;
+        }
+        if (rp.denoise_variance && rp.gpus > 1) throw std::runtime_error("config denoise_variance needs gpus 1 (a sharded frame has no variance plane)");
         stop_render_thread();
         rm.pars = rp;
         scene.x_res = rp.width;
@@ -438,14 +451,19 @@ private:
                 // streaming schedule costs about a millisecond of start-up and tail whatever its length, so each call is given
                 // about 50 ms of work -- long enough to lose ~2 % to that, short enough that --get_pass (a sample-boundary
                 // snapshot, ordered behind the call in flight) and a restart answer within a frame or two of the viewer.
+                // With `denoise_variance` a call also ends at every multiple of the batch and a fold follows it there: the variance
+                // plane then depends on the batch, never on how these calls happened to be sized.
                 unsigned done = 0, n = 1;
                 const bool adaptive = rm.pars.adaptive;
+                const unsigned batch = rm.pars.fold_every();
                 while (done < target && !stop_ && !(adaptive && rm.adaptive_info().active_tiles == 0)) {      // (adaptive: until no rank has an active tile)
                     n = std::min(n, target - done);
+                    if (batch) n = std::min(n, batch - done % batch);
                     const auto t0 = std::chrono::steady_clock::now();
                     rm.render(n);
                     const double per_sample = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / n;
                     done += n;
+                    if (batch && done % batch == 0) rm.variance_fold();
                     samples_per_call_ = n;
                     n = (unsigned)std::min(256.0, std::max(1.0, std::ceil(0.050 / std::max(per_sample, 1e-6))));
                 }
@@ -477,8 +495,17 @@ private:
             im->write_message(Message::float_data(img.data(), img.size(), Message::DataFormat::FLOAT4));
             return;
         }
+        if (lower == "variance") {          // xyz = the variance of BEAUTY as stored, w = the pixel's batches (config "denoise_variance": true)
+            if (!rm.pars.denoise_variance) throw std::runtime_error("get_pass variance needs \"denoise_variance\": true in the config");
+            img = rm.get_variance();
+            im->write_message(Message::float_data(img.data(), img.size(), Message::DataFormat::FLOAT4));
+            return;
+        }
         const bool want_denoise = parsePass(pass) == ER_PASS_DENOISE || (rm.pars.denoise && parsePass(pass) == ER_PASS_BEAUTY);
-        if (want_denoise && rm.pars.denoise_guided) {
+        if (want_denoise && rm.pars.denoise_variance) {
+            img = rm.get_denoised_variance(rm.pars.feature_samples);      // features if there are none yet, er_denoise_variance (the guided filter until two folds exist), read
+            for (size_t i = 3; i < img.size(); i += 4) img[i] = 1.0f;
+        } else if (want_denoise && rm.pars.denoise_guided) {
             img = rm.get_denoised_guided(rm.pars.feature_samples);      // features if there are none yet, gathers, er_denoise_guided, read: one step against the render thread
             for (size_t i = 3; i < img.size(); i += 4) img[i] = 1.0f;
         } else if (want_denoise) {

@@ -137,6 +137,13 @@ struct RenderParameters {   // src/kernel.h:51-69
     // temporal reprojection (extension, off by default): a --start answered by the camera-update path captures the frame before the
     // update and resolves it after (er_history_capture / er_history_resolve); --get_pass blended then answers er_read_blended.  One GPU.
     bool history = false;
+    // the variance plane and the denoise guided by it (extension, off by default): the render thread cuts its calls at multiples of
+    // variance_batch samples (0 = 2) and folds there (er_variance_fold), so the plane depends on the parameters and not on how the thread
+    // sized its calls; `denoise: true` / get_pass denoise then run er_denoise_variance once two folds exist (before that: the guided
+    // filter), and get_pass variance answers er_read_variance.  One GPU.
+    bool denoise_variance = false;
+    unsigned variance_batch = 0;
+    unsigned fold_every() const { return denoise_variance ? (variance_batch ? variance_batch : 2u) : 0u; }
 };
 
 // What a session sent since its last successful --start.  A --start after nothing but --load_camera restarts the render in place
@@ -498,6 +505,35 @@ public:
         return out;
     }
     unsigned history_resolves = 0;      // camera updates whose frame was carried over (reported by --get_info)
+    // er_variance_fold / er_variance_info / er_read_variance (`denoise_variance`; one GPU: a sharded frame has no variance plane)
+    void variance_fold() {
+        if (ers_.empty()) throw std::runtime_error("variance_fold: no render has been started");
+        check(er_variance_fold(ers_[0]));
+    }
+    unsigned variance_folds() {
+        ErVarianceInfo i{};
+        if (ers_.empty() || er_variance_info(ers_[0], &i) != ER_OK) return 0;
+        return i.folds;
+    }
+    std::vector<float> get_variance() {
+        if (ers_.empty()) throw std::runtime_error("get_variance: no render has been started");
+        std::vector<float> out((size_t)pars.width * pars.height * 4);
+        check(er_read_variance(ers_[0], out.data()));
+        return out;
+    }
+    // features if there are none yet + er_denoise_variance + read of the DENOISE plane; until two folds exist (ER_ERR_STATE) the guided
+    // filter answers instead
+    std::vector<float> get_denoised_variance(unsigned feature_samples = 0, unsigned levels = 0, float colour_sigma = 0, float albedo_sigma = 0, float depth_sigma = 0) {
+        if (ers_.empty()) throw std::runtime_error("denoise_variance: no render has been started");
+        std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);
+        if (ers_.size() > 1) lk.lock();
+        if (!features_ready_) render_features_unlocked(feature_samples);
+        const ErDenoiseVariance p{levels, colour_sigma, albedo_sigma, depth_sigma};
+        const int rc = ers_.size() == 1 ? er_denoise_variance(ers_[0], &p) : ER_ERR_STATE;
+        if (rc == ER_ERR_STATE) denoise_guided_unlocked(levels, 0.0f, albedo_sigma, depth_sigma);      // (its own colour_sigma: another unit)
+        else check(rc);
+        return get_pass_unlocked(ER_PASS_DENOISE);
+    }
     std::vector<float> get_pass(const std::string& pass) {   // src/Managers.cpp:287-302
         if (ers_.empty()) throw std::runtime_error("get_pass: no render has been started");
         std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);

@@ -90,8 +90,23 @@ class RenderingManager:
         abi.check(self.lib.er_render_begin(self.handle, C.byref(p)))
 
     # -- reference: kernel_render_enqueue's sample loop (src/kernel.cpp:689-700)
-    def render(self, n_samples, blocking=True):
-        if blocking:
+    def render(self, n_samples, blocking=True, fold_every=0):
+        """fold_every = b > 0 (blocking calls only): the call is cut so that variance_fold() runs whenever the samples done since the
+        render last started over reach a multiple of b -- the variance plane then depends on b, not on how the caller sized its calls."""
+        if fold_every and not blocking:
+            raise ValueError("render: fold_every goes with a blocking call")
+        if fold_every < 0 or int(fold_every) != fold_every:
+            raise ValueError("render: fold_every is a sample count")
+        if blocking and fold_every:
+            left = int(n_samples)
+            while left > 0:
+                done = self.get_render_info().samples - 1      # (the count starts at 1: the setup sample)
+                step = min(left, int(fold_every) - done % int(fold_every))
+                abi.check(self.lib.er_render_samples(self.handle, step))
+                left -= step
+                if (done + step) % int(fold_every) == 0:
+                    self.variance_fold()
+        elif blocking:
             abi.check(self.lib.er_render_samples(self.handle, n_samples))
         else:
             abi.check(self.lib.er_render_samples_async(self.handle, n_samples))
@@ -532,6 +547,27 @@ class RenderingManager:
         out = np.empty((self.scene.y_res, self.scene.x_res, 4), np.float32)
         abi.check(self.lib.er_read_blended(self.handle, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def variance_fold(self):
+        """er_variance_fold: one more batch mean per pixel that received samples since the last fold (or since the render started over)."""
+        abi.check(self.lib.er_variance_fold(self.handle))
+
+    def variance_info(self):
+        a = abi.ErVarianceInfo()
+        abi.check(self.lib.er_variance_info(self.handle, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in abi.ErVarianceInfo._fields_ if n != "reserved"}
+
+    def get_variance(self):
+        """er_read_variance: (H, W, 4) float32 -- rgb = the variance of BEAUTY as stored (0 until a pixel has two batches), a = its batches."""
+        out = np.empty((self.scene.y_res, self.scene.x_res, 4), np.float32)
+        abi.check(self.lib.er_read_variance(self.handle, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def denoise_variance(self, levels=0, colour_sigma=0.0, albedo_sigma=0.0, depth_sigma=0.0):
+        """Fill the DENOISE plane from BEAUTY + NORMAL + the feature planes with the colour stop normalised by the variance plane
+        (er_denoise_variance; render_features and two folds first)."""
+        p = abi.ErDenoiseVariance(levels, colour_sigma, albedo_sigma, depth_sigma)
+        abi.check(self.lib.er_denoise_variance(self.handle, C.byref(p)))
 
     def read_samples(self):
         out = np.empty(self.scene.x_res * self.scene.y_res, np.uint32)

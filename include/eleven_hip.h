@@ -734,6 +734,51 @@ int er_history_info(ErScene* scene, ErHistoryInfo* out);
 int er_read_history(ErScene* scene, float* dst_rgba);
 int er_read_blended(ErScene* scene, float* dst_rgba);
 
+/* A variance plane by batch means and the denoise guided by it (extension; csrc/er_variance.h gives every float32 operation, csrc/
+ * er_variance.hip the kernels).  Stateless with respect to the render like the feature, id and history passes: the render's
+ * planes, sample counts, RNG and ErCounters are read and never written; only DENOISE is written, as the other two filters do.
+ * A pixel's BEAUTY is a running mean with a known count, so the mean of the samples between two read points follows from the two plane
+ * values, and the scatter of those batch means estimates the variance.  Per pixel the library keeps 12 words (48 bytes): a snapshot S
+ * (rgb) with its count m, the weighted mean mu (rgb) of the batch means with the total weight W, M2 (rgb) and the batch count K.
+ * RESET: S, m = the pixel's BEAUTY rgb and sample count as they stand -- (0, 0, 0) and 1 right after er_render_begin or an edit, so the
+ * first fold's batch is everything since the start --, mu = M2 = 0, W = 0, K = 0.  er_render_begin, every successful er_render_update,
+ * er_render_update_sparse, er_render_edit, er_render_transform and er_render_topology, and er_state_import (the snapshot is taken from
+ * the imported planes) reset every pixel and `folds`.  er_render_samples, er_render_features, er_render_ids and the history calls leave
+ * the state alone.
+ * er_variance_fold: waits for pending asynchronous work, then per pixel with I = BEAUTY rgb, M = its sample count, n = M - m:
+ *   n == 0 (a tile the adaptive sampler stopped, a pixel whose samples were all gated): all 12 words stay.  Otherwise per channel
+ *     J = (I * (float)M - S * (float)m) / (float)n;   W' = W + (float)n;   d = J - mu;   mu' = mu + d * ((float)n / W');
+ *     M2' = M2 + (float)n * (d * (J - mu'));   then K' = K + 1, S = I, m = M         (West's weighted update: E[M2] = (K - 1) sigma^2)
+ * er_read_variance: xyz = the variance of BEAUTY as stored, at the current count M: (0, 0, 0) if K < 2, else
+ *   max(0, ((M2 / (float)(K - 1)) * (float)(M - 1)) / ((float)M * (float)M));  w = (float)K.  Row-major like er_read_pass.  Samples
+ *   rendered after the last fold change M but not the moments.
+ * er_denoise_variance: er_denoise_guided's demodulation, stencil, normal, albedo and depth stops, with the colour stop normalised per
+ *   pixel: the squared difference of each channel is divided by the 3 x 3 binomial mean of the demodulated variance v / (albedo + 0.01)^2
+ *   around the centre (+ 1e-8), wc = 1 / (1 + d2 / colour_sigma^2) -- colour_sigma counts standard errors and is not tightened per level,
+ *   because the variance is propagated through the levels instead: ve' = sum(wgt^2 ve_q) / (sum wgt)^2.  A centre with K < 2 takes
+ *   wc = 1.  levels 1..8 (0 -> 5); colour_sigma (0 -> 6), albedo_sigma (0 -> 0.3), depth_sigma (0 -> 0.2, relative).  It needs valid
+ *   feature planes, exactly as er_denoise_guided does, and folds >= 2 since the last reset; otherwise ER_ERR_STATE.
+ * ER_ERR_STATE from all four: the scene is not begun; world > 1 (variance on a sharded frame is not built).  ER_ERR_INVALID_ARG: NULL
+ * arguments; more than 8 levels; a negative or NaN sigma.  Adaptive sampling may be on: the arithmetic is per pixel with per-pixel counts.
+ * Stated limit: J is a difference of two products, its rounding error relative to I about 2^-23 * M / n -- harmless at interactive
+ * counts; a render of thousands of samples should fold in batches that grow with M.  The state is allocated by the first use (48 bytes
+ * per pixel), freed with the scene and not part of er_state_*. */
+typedef struct ErVarianceInfo {
+    uint32_t folds;               /* since the last reset */
+    uint32_t reserved;
+    uint64_t pixels_folded;       /* by the last fold: pixels with n > 0 */
+    uint64_t pixels_known;        /* pixels with K >= 2 after it */
+    float fold_ms, filter_ms;     /* device time of the last fold / er_denoise_variance (HIP events) */
+} ErVarianceInfo;
+typedef struct ErDenoiseVariance {
+    uint32_t levels;
+    float colour_sigma, albedo_sigma, depth_sigma;
+} ErDenoiseVariance;
+int er_variance_fold(ErScene* scene);
+int er_variance_info(ErScene* scene, ErVarianceInfo* out);
+int er_read_variance(ErScene* scene, float* dst_rgba);
+int er_denoise_variance(ErScene* scene, const ErDenoiseVariance* params);
+
 #ifdef __cplusplus
 }
 #endif

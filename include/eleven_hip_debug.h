@@ -310,6 +310,21 @@ int er_debug_history_taps(const float cam[12], uint32_t x_res, uint32_t y_res, f
 int er_debug_history_capture(uint32_t count, const float* beauty, const uint32_t* samples, const float* hist, float max_weight, float* out);
 int er_debug_history_blend(uint32_t count, const float* beauty, const uint32_t* samples, const float* hist, float* out);
 
+/* The arithmetic of the variance plane and of its filter (csrc/er_variance.h, the functions the kernels call), on caller arrays, no
+ * device needed.  A pixel's state is 12 words: S.rgb, m (uint32), mu.rgb, W, M2.rgb, K (uint32).
+ * er_debug_variance_mark / _fold: `count` pixels: beauty [count][4], samples [count], state [count][12] written / updated in place;
+ *   folded [count] (may be NULL): 1 where the pixel had n > 0.
+ * er_debug_variance_value: state [count][12], samples [count] -> out [count][4] = er_read_variance's pixel.
+ * er_debug_variance_split: value [count][4], albedo [count][4] -> ve [count][4], the demodulated variance and the K >= 2 flag.
+ * er_debug_variance_level_px: one level of er_denoise_variance over a whole frame of w x h pixels: planes e, ve, normal, albedo, depth
+ *   [h * w][4] -> out_e, out_ve [h * w][4]; kc = 1 / colour_sigma^2, ka, kz as er_denoise_guided's.  step 1 .. 128. */
+int er_debug_variance_mark(uint32_t count, const float* beauty, const uint32_t* samples, float* state);
+int er_debug_variance_fold(uint32_t count, const float* beauty, const uint32_t* samples, float* state, uint32_t* folded);
+int er_debug_variance_value(uint32_t count, const float* state, const uint32_t* samples, float* out);
+int er_debug_variance_split(uint32_t count, const float* value, const float* albedo, float* ve);
+int er_debug_variance_level_px(uint32_t w, uint32_t h, uint32_t step, float kc, float ka, float kz, const float* e, const float* ve, const float* normal, const float* albedo,
+                               const float* depth, float* out_e, float* out_ve);
+
 #ifdef __cplusplus
 }
 #endif
