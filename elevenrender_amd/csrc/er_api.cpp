@@ -403,8 +403,21 @@ static int begin_textures(ErScene* s, BeginStaging& B, const char* who) {
     if ((rc = upload(s->d_tex_pool, pool.data(), pool.size(), s->stream)) != ER_OK) return rc;
     s->tex_pool_cap = pool.size();
     if ((rc = upload(s->d_cdf, s->hdri_cdf.data(), s->hdri_cdf.size(), s->stream)) != ER_OK) return rc;
+    return upload_hdri_guide(s, B);
+}
+
+// the CDF's guide table and, behind it in the same buffer, the row and column tables of the HDRI's sample directions (er_hdri_trig.h),
+// which one kernel fills on the device from the descriptor s->kept.hdri
+int upload_hdri_guide(ErScene* s, BeginStaging& B) {
+    int rc;
     s->kept.buckets = er_build_cdf_guide(s->hdri_cdf.data(), s->hdri_tex.width * s->hdri_tex.height, B.guide);
-    return upload(s->d_guide, B.guide.data(), B.guide.size(), s->stream);
+    const size_t at = (B.guide.size() + 3) & ~(size_t)3;      // (16-byte aligned)
+    B.guide.resize(at + erd::hdri_trig_words(s->kept.hdri.width, s->kept.hdri.height), 0u);
+    if ((rc = upload(s->d_guide, B.guide.data(), B.guide.size(), s->stream)) != ER_OK) return rc;
+    s->kept.trig_at = at;
+    er_launch_hdri_trig(s->kept.hdri, s->d_guide.p + at, s->stream);
+    HIP_TRY(hipGetLastError());
+    return ER_OK;
 }
 
 // stage 5, ER_FLAG_MESH_LIGHTS: the emitter table, built on the device from the placed triangle records (er_lights.hip).  An empty
@@ -566,6 +579,8 @@ static int begin_descriptor(ErScene* s, uint32_t owned_tiles) {
     D.hdri_guide = s->d_guide.p;
     D.hdri_buckets = s->kept.buckets;
     D.hdri_radiance_sum = s->hdri_radiance_sum;
+    // (A/B and test knob: ER_HDRI_TRIG_ON_DEVICE=1 = the kernels evaluate the sample's sines and cosines themselves)
+    D.hdri_trig = getenv("ER_HDRI_TRIG_ON_DEVICE") ? nullptr : s->d_guide.p + s->kept.trig_at;
     D.cam = s->camera;
     D.x_res = s->x_res;
     D.y_res = s->y_res;

@@ -270,8 +270,7 @@ int edit_pool(ErScene* s, uint32_t what, bool rebuild_pool, BeginStaging& B, con
     }
     if (what & ER_EDIT_HDRI) {
         if ((rc = upload(s->d_cdf, s->hdri_cdf.data(), s->hdri_cdf.size(), s->stream)) != ER_OK) return rc;
-        s->kept.buckets = er_build_cdf_guide(s->hdri_cdf.data(), s->hdri_tex.width * s->hdri_tex.height, B.guide);
-        if ((rc = upload(s->d_guide, B.guide.data(), B.guide.size(), s->stream)) != ER_OK) return rc;
+        if ((rc = upload_hdri_guide(s, B)) != ER_OK) return rc;      // (with the new HDRI's row and column tables behind it)
     }
     return ER_OK;
 }

@@ -4,6 +4,7 @@
 // from the scene (ErScene::kept) and reports a failure under `who`, the entry point that was called.
 #pragma once
 #include "er_scene.h"
+#include "er_hdri_trig.h"
 
 namespace erh {
 
@@ -37,6 +38,9 @@ bool accel_device_first(const ErScene* s);
 void accel_publish(ErScene* s, float up_ms);
 // stage 3 without the point lights: the materials and their precomputed constants
 int upload_materials(ErScene* s, BeginStaging& B);
+// the HDRI's search guide and, behind it, its row and column tables (er_hdri_trig.h) for the descriptor s->kept.hdri: the end of the
+// texture stage, and of an edit's pool stage when the HDRI changes
+int upload_hdri_guide(ErScene* s, BeginStaging& B);
 // the scene's host textures as the texture plan (er_texplan.h) takes them
 void plan_of_scene(const ErScene* s, TexPlan& P);
 // stage 5, ER_FLAG_MESH_LIGHTS: the emitter table from the placed triangle records, materials and texture pool

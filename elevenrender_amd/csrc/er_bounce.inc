@@ -7,6 +7,9 @@
 //   ER_BOUNCE_MESH      macro, optional (default false): a compile-time bool; true compiles ER_FLAG_MESH_LIGHTS in (needs EXT)
 //   ER_BOUNCE_SKIP_EQUAL macro, optional (default true): a compile-time bool; false hands every shadow query to the hooks even when its
 //                       two outcomes are the same addend (the debug pixel trace: its records are compared with the oracle's, which always traces)
+//   ER_BOUNCE_KEEP_LAST macro, optional (default false): a compile-time bool; true computes the continuation -- the BRDF-sampled direction, its
+//                       pdf and BRDF term, `reduction`, `prev_pdf`, the new `ray` -- on the path's last iteration as well, where nothing
+//                       reads it after `done` (the debug pixel trace: its records carry the next direction and the throughput)
 //   S                   the DevScene
 //   Ray      ray        in: the ray that was traced; out: the continuation ray (unchanged when it left the scene)
 //   int      hslot      its closest hit (triangle slot), or < 0
@@ -35,6 +38,9 @@
 #ifndef ER_BOUNCE_SKIP_EQUAL
 #define ER_BOUNCE_SKIP_EQUAL true
 #endif
+#ifndef ER_BOUNCE_KEEP_LAST
+#define ER_BOUNCE_KEEP_LAST false
+#endif
 {
     // A shadow query only selects one of two addends that are both known before it is traced.  Where the two are the same bits the verdict
     // cannot change `light`, and the query is not issued: the addend is added at once.  The common case is a dead path -- `reduction` exactly
@@ -55,7 +61,10 @@
         if (EXT) {
             F3 er_env = tex_filtered(S, S.hdri_tex, u, v);
             if (er_mis && prev_pdf >= 0.0f) {   // balance heuristic for the BRDF-sampled direction that left the scene
-                const float er_ph = hdri_pdf(S, ermath::f2i(u * hw), ermath::f2i(v * hh));
+                // (hdri_pdf; the sine of its row from the row table where there is one and the row lies inside the image)
+                const int er_mx = ermath::f2i(u * hw), er_my = ermath::f2i(v * hh);
+                const float er_ms = (S.hdri_trig != nullptr && (unsigned)er_my < (unsigned)hh) ? hdri_trig_rows(S)[er_my].sin_row : hdri_pdf_sine(S.hdri_tex, er_my);
+                const float er_ph = hdri_pdf_of(S, tex_coords(S, S.hdri_tex, er_mx, er_my), er_ms);
                 er_env = er_env * (1.0f / (1.0f + er_ph / prev_pdf));
                 if (COUNT) c_texels++;
             }
@@ -86,8 +95,9 @@
             int count = er_cdf_search(S.hdri_cdf, hw * hh, S.hdri_guide, S.hdri_buckets, rng_next(rs));   // == HDRI::binarySearch
             // (for a power-of-two width and a non-negative index the division is a shift and a mask -- the same integers)
             const bool hw_pow2 = (hw & (hw - 1)) == 0 && hw > 0 && count >= 0;
-            float tcx = (float)(hw_pow2 ? (int)((unsigned)count & (unsigned)(hw - 1)) : count % hw);
-            float tcy = (float)(hw_pow2 ? (int)((unsigned)count >> (31 - __builtin_clz((unsigned)hw))) : count / hw);
+            const int er_cx = hw_pow2 ? (int)((unsigned)count & (unsigned)(hw - 1)) : count % hw;
+            const int er_cy = hw_pow2 ? (int)((unsigned)count >> (31 - __builtin_clz((unsigned)hw))) : count / hw;
+            float tcx = (float)er_cx, tcy = (float)er_cy;
             float d1 = rng_next(rs), d2 = rng_next(rs), d3 = rng_next(rs);
             const bool er_lights = EXT && !er_mesh && (S.ext_flags & ER_FLAG_POINT_LIGHTS) != 0 && S.light_count > 0;
             float er_rl = 0.0f;
@@ -95,15 +105,35 @@
             float er_mp = 0.0f, er_mu1 = 0.0f, er_mu2 = 0.0f;
             if (er_mesh) { er_mp = rng_next(rs); er_mu1 = rng_next(rs); er_mu2 = rng_next(rs); }   // emitter pick and point: always three
             ER_TP(4);
-            F3 wibrdf = DisneySample(hd, wo, N, d1, d2, d3);
-            float nu = tcx / (float)hw, nv = tcy / (float)hh;
-            float iu, iv;
-            inverse_transform_uv(S.hdri_tex, nu, nv, iu, iv);
-            F3 wihdri = normalized(reverse_spherical_mapping(iu, iv)) * -1.0f;
-            F3 hdriValue = tex_uv(S, S.hdri_tex, iu, iv);
+            // The path's last iteration: the three BRDF draws above are taken, but the continuation they feed -- the sampled direction, its pdf
+            // and BRDF term, `reduction`, `prev_pdf`, the new ray -- goes to variables that nothing reads after `done`, and is not computed.
+            const bool er_last = !(ER_BOUNCE_KEEP_LAST) && bounce + 1u >= S.max_bounces;
+            F3 wibrdf = f3s(0);
+            if (!er_last) wibrdf = DisneySample(hd, wo, N, d1, d2, d3);
+            // The sampled texel's direction and pdf (inverse_transform_uv, reverse_spherical_mapping, tex_uv, hdri_pdf): the transcendentals
+            // depend on the texel's column and row alone and come from the tables of er_hdri_trig.h where there are some -- the bits the
+            // functions below gave when the table was filled with them.  (A search that found nothing, count = -1, is not a texel: evaluated.)
+            float er_px, er_pz, er_py, er_a, er_sin;
+            int er_ix, er_iy;
+            if (S.hdri_trig != nullptr && (unsigned)count < (unsigned)(hw * hh)) {
+                const HdriCol er_c = hdri_trig_cols(S)[er_cx];
+                const HdriRow er_r = hdri_trig_rows(S)[er_cy];
+                er_px = er_c.px; er_pz = er_c.pz; er_ix = er_c.ix;
+                er_py = er_r.py; er_a = er_r.a; er_iy = er_r.iy; er_sin = er_r.sin_pdf;
+            } else {
+                float nu = tcx / (float)hw, nv = tcy / (float)hh;
+                float iu, iv;
+                inverse_transform_uv(S.hdri_tex, nu, nv, iu, iv);
+                rsm_column(iu, er_px, er_pz);
+                rsm_row(iv, er_py, er_a);
+                er_ix = ermath::f2i(iu * hw); er_iy = ermath::f2i(iv * hh);      // (tex_uv's and hdri_pdf's texel: the same one)
+                er_sin = hdri_pdf_sine(S.hdri_tex, er_iy);
+            }
+            F3 wihdri = normalized(f3(er_a * er_px, er_py, er_a * er_pz)) * -1.0f;      // reverse_spherical_mapping's result
+            F3 hdriValue = tex_coords(S, S.hdri_tex, er_ix, er_iy);                     // tex_uv; hdri_pdf reads this texel too: fetched once
             if (COUNT) c_texels += 2;
             F3 evalh = DisneyEval(hd, wo, N, wihdri);
-            float hdripdf = hdri_pdf(S, ermath::f2i(iu * hw), ermath::f2i(iv * hh));
+            float hdripdf = hdri_pdf_of(S, hdriValue, er_sin);
             float absdot = __builtin_fabsf(dot(wihdri, N));
             // The reference always traces the shadow ray (src/kernel.cpp:555-562); a hit on another triangle zeroes
             // hdriValue.  Both outcomes are computed here with the reference's expression; when the BRDF term is
@@ -209,11 +239,13 @@
                 }
             }
             ER_TP(5);
-            float brdfpdf = DisneyPdf(hd, wo, N, wibrdf);
-            reduction = reduction * (DisneyEval(hd, wo, N, wibrdf) * __builtin_fabsf(dot(wibrdf, N)) / brdfpdf);
-            if (er_mis || er_mesh) prev_pdf = brdfpdf;
+            if (!er_last) {
+                float brdfpdf = DisneyPdf(hd, wo, N, wibrdf);
+                reduction = reduction * (DisneyEval(hd, wo, N, wibrdf) * __builtin_fabsf(dot(wibrdf, N)) / brdfpdf);
+                if (er_mis || er_mesh) prev_pdf = brdfpdf;
+                ray = make_ray(hit.position + wibrdf * 0.001f, wibrdf);
+            }
             if (bounce == 0) { ER_BOUNCE_FIRST_HIT(hd.normal, hd.tangent, hd.bitangent); }
-            ray = make_ray(hit.position + wibrdf * 0.001f, wibrdf);
             if (er_mesh) mesh_d = 0.001f;          // (the new ray leaves 0.001 away from the bounce)
         } else {
             if (er_mesh) mesh_d = mesh_d + length(hit.position - ray.o) + 0.001f;      // an opacity pass-through: the segment and the offset

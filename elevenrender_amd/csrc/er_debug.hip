@@ -120,12 +120,14 @@ __global__ __launch_bounds__(64) void er_debug_pixel_kernel(DevScene S, uint32_t
 #define ER_BOUNCE_FIRST_HIT(n, t, b) aov_n = (n); aov_t = (t); aov_b = (b)
 #define ER_BOUNCE_MESH MESH
 #define ER_BOUNCE_SKIP_EQUAL false      // every query the oracle's trace records is traced and recorded here too (its counters are compared with nothing)
+#define ER_BOUNCE_KEEP_LAST true         // the records carry the next direction and the throughput of the last iteration as well
 #include "er_bounce.inc"
 #undef ER_BOUNCE_HDRI_QUERY
 #undef ER_BOUNCE_LIGHT_QUERY
 #undef ER_BOUNCE_FIRST_HIT
 #undef ER_BOUNCE_MESH
 #undef ER_BOUNCE_SKIP_EQUAL
+#undef ER_BOUNCE_KEEP_LAST
         (void)pending; (void)lpending; (void)traced;
         if (rec) {
             // the opacity test passed iff more than its one draw was taken (src/kernel.cpp:539: the opaque branch draws 4+)

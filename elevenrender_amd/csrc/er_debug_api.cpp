@@ -4,6 +4,7 @@
 // and exercise the boundary's failure paths.
 #include "er_scene.h"
 #include "er_debug.h"
+#include "er_hdri_trig.h"
 
 using namespace erh;
 
@@ -402,6 +403,29 @@ static int er_debug_read_light_table_impl(ErScene* s, int32_t* tri_index, float*
     return ER_OK;
 }
 
+static int er_debug_read_hdri_trig_impl(ErScene* s, uint32_t* cols, uint32_t col_cap, uint32_t* rows, uint32_t row_cap) {
+    if (!s) return fail(ER_ERR_INVALID_ARG, "er_debug_read_hdri_trig: NULL scene");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_debug_read_hdri_trig: er_render_begin has not succeeded");
+    const DevTex& t = s->kept.hdri;
+    const size_t nc = std::min<size_t>(col_cap, (size_t)std::max(t.width, 0)), nr = std::min<size_t>(row_cap, (size_t)std::max(t.height, 0));
+    HIP_TRY(hipSetDevice(s->device));
+    const uint32_t* tab = s->d_guide.p + s->kept.trig_at;
+    if (cols && nc) HIP_TRY(hipMemcpyAsync(cols, tab, nc * sizeof(erd::HdriCol), hipMemcpyDeviceToHost, s->stream));
+    if (rows && nr) HIP_TRY(hipMemcpyAsync(rows, tab + erd::hdri_trig_row_offset(t.width), nr * sizeof(erd::HdriRow), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return ER_OK;
+}
+
+static int er_debug_hdri_trig_host_impl(int32_t width, int32_t height, uint32_t* cols, uint32_t* rows) {
+    if (width < 0 || height < 0 || (width && !cols) || (height && !rows)) return fail(ER_ERR_INVALID_ARG, "er_debug_hdri_trig_host: bad argument");
+    std::vector<uint32_t> tab(erd::hdri_trig_words(width, height));
+    er_hdri_trig_host(DevTex{width, height, 3, 0, 0u}, tab.data());
+    if (width) memcpy(cols, tab.data(), (size_t)width * sizeof(erd::HdriCol));
+    if (height) memcpy(rows, tab.data() + erd::hdri_trig_row_offset(width), (size_t)height * sizeof(erd::HdriRow));
+    return ER_OK;
+}
+
 static int er_debug_eval_impl(ErScene* s, int kind, const float* in, uint32_t n, uint32_t in_stride, float* out, uint32_t out_stride) {
     static const uint32_t need_in[ER_FN_COUNT] = {1, 7, 7, 29, 29, 29, 3, 2, 4, 1, 2, 3};
     static const uint32_t need_out[ER_FN_COUNT] = {32, 6, 18, 3, 1, 3, 2, 3, 3, 1, 1, 1};
@@ -543,6 +567,12 @@ int er_debug_trace_pixel(ErScene* s, uint32_t idx, ErTraceRec* recs, int max_rec
 }
 int er_debug_read_light_table(ErScene* s, int32_t* tri_index, float* cdf, uint32_t cap) {
     return guarded("er_debug_read_light_table", [&]() -> int { return er_debug_read_light_table_impl(s, tri_index, cdf, cap); });
+}
+int er_debug_read_hdri_trig(ErScene* s, uint32_t* cols, uint32_t col_cap, uint32_t* rows, uint32_t row_cap) {
+    return guarded("er_debug_read_hdri_trig", [&]() -> int { return er_debug_read_hdri_trig_impl(s, cols, col_cap, rows, row_cap); });
+}
+int er_debug_hdri_trig_host(int32_t width, int32_t height, uint32_t* cols, uint32_t* rows) {
+    return guarded("er_debug_hdri_trig_host", [&]() -> int { return er_debug_hdri_trig_host_impl(width, height, cols, rows); });
 }
 int er_debug_eval(ErScene* s, int kind, const float* in, uint32_t n, uint32_t in_stride, float* out, uint32_t out_stride) {
     return guarded("er_debug_eval", [&]() -> int { return er_debug_eval_impl(s, kind, in, n, in_stride, out, out_stride); });

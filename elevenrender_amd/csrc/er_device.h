@@ -109,6 +109,9 @@ struct DevScene {
     // accumulated sample that drew that many, - 2 for every other one; at 0 the latest count becomes the guess).  A guess, never a
     // result: not part of the progressive state (er_state_export), zeroed by er_render_begin
     uint32_t* px_draws;
+    // row and column tables of the HDRI's next-event sample directions (er_hdri_trig.h): width x 4 words, then height x 6 words, behind
+    // the CDF's guide table in its buffer.  NULL (ER_HDRI_TRIG_ON_DEVICE=1 at er_render_begin: test and A/B knob) = the step evaluates.
+    const uint32_t* hdri_trig;
 };
 
 // Where pass `pass` of pixel `idx` lives in DevScene::passes.  The four planes a finished sample is accumulated into -- beauty, normal,
@@ -157,7 +160,7 @@ ERD float lerpf(float a, float b, float c) { return a + c * (b - a); }          
 ERD F3 lerpv(F3 a, F3 b, float c) { return f3(lerpf(a.x, b.x, c), lerpf(a.y, b.y, c), lerpf(a.z, b.z, c)); }
 ERD float minf(float a, float b) { return a < b ? a : b; }
 ERD float maxf(float a, float b) { return a > b ? a : b; }
-ERD void limitUV(float& u, float& v) {   // src/Math.hpp:48-51
+__host__ __device__ __forceinline__ void limitUV(float& u, float& v) {   // src/Math.hpp:48-51
     u += (float)(-(int)(u > 1) + -(int)(u < 0));
     v += (float)(-(int)(v > 1) + -(int)(v < 0));
 }
@@ -492,20 +495,28 @@ ERD void spherical_mapping(F3 point, float& u, float& v) {   // src/Texture.cpp:
     v = theta / PIF;
     limitUV(u, v);
 }
-ERD void inverse_transform_uv(const DevTex& t, float u, float v, float& nu, float& nv) {   // src/Texture.cpp:267-278
+__host__ __device__ __forceinline__ void inverse_transform_uv(const DevTex& t, float u, float v, float& nu, float& nv) {   // src/Texture.cpp:267-278
     int x = ermath::f2i(u * t.width);
     int y = ermath::f2i(v * t.height);
     nu = (float)x / (float)t.width;
     nv = (float)y / (float)t.height;
     limitUV(nu, nv);
 }
-ERD F3 reverse_spherical_mapping(float u, float v) {   // src/Texture.cpp:280-292
+// (the column's and the row's halves of reverse_spherical_mapping: er_hdri_trig.h tabulates them per texel column and row)
+__host__ __device__ __forceinline__ void rsm_column(float u, float& px, float& pz) {
     float phi = u * 2 * PIF;
+    px = ermath::er_cos(phi - PIF);
+    pz = -ermath::er_sin(phi - PIF);
+}
+__host__ __device__ __forceinline__ void rsm_row(float v, float& py, float& a) {
     float theta = v * PIF;
-    float px = ermath::er_cos(phi - PIF);
-    float py = -ermath::er_cos(theta);
-    float pz = -ermath::er_sin(phi - PIF);
-    float a = __builtin_sqrtf(1 - py * py);
+    py = -ermath::er_cos(theta);
+    a = __builtin_sqrtf(1 - py * py);
+}
+ERD F3 reverse_spherical_mapping(float u, float v) {   // src/Texture.cpp:280-292
+    float px, py, pz, a;
+    rsm_column(u, px, pz);
+    rsm_row(v, py, a);
     return f3(a * px, py, a * pz);
 }
 
@@ -523,10 +534,17 @@ ERD int hdri_binary_search(const float* arr, float value, int length) {
     }
     return to;
 }
+// (the sine HDRI::pdf divides by, for row y; the rest of it from the texel and that sine)
+__host__ __device__ __forceinline__ float hdri_pdf_sine(const DevTex& t, int y) {
+    float theta = (((float)y / (float)t.height)) * PIF;
+    return ermath::er_sin(theta);
+}
+ERD float hdri_pdf_of(const DevScene& S, F3 dv, float sin_theta) {
+    return ((dv.x + dv.y + dv.z) / S.hdri_radiance_sum) * S.hdri_tex.width * S.hdri_tex.height / (2.0f * PIF * sin_theta);
+}
 ERD float hdri_pdf(const DevScene& S, int x, int y) {
     F3 dv = tex_coords(S, S.hdri_tex, x, y);
-    float theta = (((float)y / (float)S.hdri_tex.height)) * PIF;
-    return ((dv.x + dv.y + dv.z) / S.hdri_radiance_sum) * S.hdri_tex.width * S.hdri_tex.height / (2.0f * PIF * ermath::er_sin(theta));
+    return hdri_pdf_of(S, dv, hdri_pdf_sine(S.hdri_tex, y));
 }
 
 // ---- Disney BRDF, src/Disney.cpp:34-230 ---------------------------------------------

@@ -172,6 +172,7 @@ struct ErScene {
         ErGpuBvhDevice accel;      // (its three pointers are null: the scene owns the buffers)
         DevTex hdri{};
         int buckets = 0;
+        size_t trig_at = 0;        // where the HDRI's row and column tables begin in d_guide (words; er_hdri_trig.h)
         uint32_t cus = 0, flags = 0;
     } kept;
     ErRefitTopo refit_topo;      // the trees' nodes by level, from the first refit after an er_render_begin until the next one

@@ -90,6 +90,7 @@
 //   the estimator's mean against the render without it.
 #pragma once
 #include "er_device.h"
+#include "er_hdri_trig.h"
 
 namespace erd {
 

@@ -434,6 +434,15 @@ class RenderingManager:
             abi.check(self.lib.er_debug_read_light_table(self.handle, tri.ctypes.data_as(C.POINTER(C.c_int32)), cdf.ctypes.data_as(C.POINTER(C.c_float)), n))
         return tri, cdf
 
+    def debug_hdri_trig(self, width, height):
+        """include/eleven_hip_debug.h er_debug_read_hdri_trig: (cols uint32[width, 4], rows uint32[height, 6]) of the begun scene's
+        HDRI -- px, pz, ix, iu per column and py, a, iy, sin_pdf, iv, sin_row per row, as raw words."""
+        cols = np.zeros((width, 4), np.uint32)
+        rows = np.zeros((height, 6), np.uint32)
+        up = C.POINTER(C.c_uint32)
+        abi.check(self.lib.er_debug_read_hdri_trig(self.handle, cols.ctypes.data_as(up), width, rows.ctypes.data_as(up), height))
+        return cols, rows
+
     def tile_state(self):
         """(error[tiles_y, tiles_x] float32, samples[tiles_y, tiles_x] uint32): each tile's error at its last test (-1: untested,
         untestable or not owned) and the samples it received (0: not owned)."""

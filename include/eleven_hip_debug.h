@@ -122,6 +122,15 @@ int er_debug_trace_pixel(struct ErScene* scene, uint32_t idx, ErTraceRec* recs, 
  * permutation) and its CDF entry.  Either output may be NULL.  Before er_render_begin: ER_ERR_STATE. */
 int er_debug_read_light_table(struct ErScene* scene, int32_t* tri_index, float* cdf, uint32_t cap);
 
+/* The row and column tables of the HDRI's next-event sample directions (csrc/er_hdri_trig.h), copied as they lie on the device:
+ * `cols` receives 4 words per column -- px, pz, bits(ix), iu --, `rows` 6 words per row -- py, a, bits(iy), sin_pdf, iv, sin_row --
+ * for the first min(width, col_cap) columns and min(height, row_cap) rows of the begun scene's HDRI.  Either output may be NULL.
+ * The tables are there whether or not ER_HDRI_TRIG_ON_DEVICE kept the kernels from reading them.  Before er_render_begin: ER_ERR_STATE. */
+int er_debug_read_hdri_trig(struct ErScene* scene, uint32_t* cols, uint32_t col_cap, uint32_t* rows, uint32_t row_cap);
+/* The same entries evaluated on the HOST for a width x height HDRI (the fill kernel's twin: one implementation of every function for
+ * both sides): `cols` holds 4 * width words, `rows` 6 * height words.  Needs no device. */
+int er_debug_hdri_trig_host(int32_t width, int32_t height, uint32_t* cols, uint32_t* rows);
+
 /* The DEVICE functions of the path, one call per item, for known-answer tests against the oracle's function-level entry
  * points (SURVEY.md section 4 level 1: a1 RNG, a3 camera, a5 Tri::hit record, a6-a8 textures and mappings, a9 HDRI search /
  * pdf, a10-a12 Disney sample / eval / pdf, the transcendentals).  `in` holds n items of in_stride floats, `out` receives n
