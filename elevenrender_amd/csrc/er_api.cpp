@@ -139,7 +139,7 @@ static int begin_open(ErScene* s, const ErRenderParams* p) {
     s->device = p->device;
     s->params = *p;
     s->ad_on = false;      // (adaptive sampling is set per render, after its er_render_begin)
-    s->feat_valid = false; // (the feature planes are of the scene state that ends here)
+    s->feat.valid = false; // (the feature planes are of the scene state that ends here)
     s->ids_invalidate();   // (and so are the id planes)
     s->history_invalidate();   // (and the reprojection history)
     s->variance_reset();       // (and the variance moments: the render starts over)
@@ -1066,11 +1066,6 @@ static int er_accel_info_impl(ErScene* s, ErAccelInfo* out) {
 // tiles into the other); the host keeps a copy, read back with the test's result in one copy, because the streaming schedule's deal
 // is made on the host (stream_redeal, er_stream_host.cpp).  Pack, unpack, gather, denoise and er_samples_done keep working on the whole owned share (s->dev).
 
-static uint32_t tile_pixels(const ErScene* s, uint32_t tile) {      // pixels of a tile inside the frame
-    const uint32_t tiles_x = s->tiles_x(), tx = tile % tiles_x, ty = tile / tiles_x;
-    return std::min<uint32_t>(ER_TILE, s->x_res - tx * ER_TILE) * std::min<uint32_t>(ER_TILE, s->y_res - ty * ER_TILE);
-}
-
 // After a change of the active list (the caller holds the mutex; the stream is idle): the descriptor the wavefront and megakernel
 // schedules are launched with, and -- `redeal` -- the streaming schedule's deal and form for the new share, within the buffers
 // er_render_begin allocated for the owned share (records, spill and pixel rings: a smaller share fits).
@@ -1079,7 +1074,7 @@ static int adaptive_apply_list(ErScene* s, bool redeal) {
     s->ad_dev.owned_tiles = s->d_ad_list[s->ad_cur].p + ER_AD_LIST;
     s->ad_dev.owned_tile_count = (uint32_t)s->ad_active.size();
     s->ad_active_px = 0;
-    for (uint32_t t : s->ad_active) s->ad_active_px += tile_pixels(s, t);
+    for (uint32_t t : s->ad_active) s->ad_active_px += s->tile_pixels(t);
     if (!redeal || !(s->params.flags & ER_FLAG_STREAM) || s->ad_active.empty()) return ER_OK;
     return stream_redeal(s);
 }
@@ -1198,10 +1193,8 @@ static int er_adaptive_info_impl(ErScene* s, ErAdaptiveInfo* out) {
         out->pixel_samples = s->ad_pixel_samples;
         out->max_active_error = s->ad_max_error;
     } else {
-        uint64_t px = 0;
-        for (uint32_t t : s->tiles_of(s->params.rank, s->params.world)) px += tile_pixels(s, t);
         out->active_tiles = s->dev.owned_tile_count;
-        out->pixel_samples = px * s->rendered;
+        out->pixel_samples = s->owned_pixels() * s->rendered;
     }
     return ER_OK;
 }

@@ -461,7 +461,7 @@ int edit_locked(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, XformL
     // the host copy, before any device work: whatever happens below, a later er_render_begin builds the edited scene
     edit_replace(s, e, sp, xf, W);
     if ((e->what & ER_EDIT_GEOMETRY) || ((e->what & ER_EDIT_MATERIALS) && e->material_id)) s->store.release();      // er_render_topology's geometry store does not follow other edits
-    s->feat_valid = false;      // the feature planes show the scene before the edit (er_render_features makes them again)
+    s->feat.valid = false;      // the feature planes show the scene before the edit (er_render_features makes them again)
     for (auto& set : s->unpacked_feat) set.clear();
     s->ids_invalidate();        // (and so do the id planes: er_render_ids)
     if (((e->what & ER_EDIT_GEOMETRY) && !xf) || (e->what & LOOK_BITS)) s->history_invalidate();      // a camera or a pose keeps the history (er_history.hip)
@@ -745,7 +745,7 @@ static int er_render_topology_impl(ErScene* s, const ErTopologyEdit* t) {
     s->tri_count = new_count;
     std::swap(s->objects, table);
     edit_replace(s, &t->rest, nullptr, nullptr, W);      // (rest.material_id has new_count entries: tri_count is the new one)
-    s->feat_valid = false;
+    s->feat.valid = false;
     for (auto& set : s->unpacked_feat) set.clear();
     s->ids_invalidate();
     s->history_invalidate();

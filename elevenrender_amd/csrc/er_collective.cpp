@@ -283,7 +283,7 @@ static int gather_feature_impl(ErScene* s, int feature, ErComm* c, uint32_t root
     if (root >= c->world) return fail(ER_ERR_INVALID_ARG, "er_gather_feature: root >= world");
     std::lock_guard<std::mutex> lk(s->mtx);
     if (!s->begun) return fail(ER_ERR_STATE, "er_gather_feature: er_render_begin has not succeeded");
-    if (!s->feat_valid) return fail(ER_ERR_STATE, "er_gather_feature: no feature planes of this scene state (er_render_features)");
+    if (!s->feat.valid) return fail(ER_ERR_STATE, "er_gather_feature: no feature planes of this scene state (er_render_features)");
     return gather_plane(s, feature, s->d_feat.p + (size_t)feature * s->x_res * s->y_res, "er_gather_feature", &s->unpacked_feat[feature], c, root);
 }
 static int gather_ids_impl(ErScene* s, int kind, ErComm* c, uint32_t root) {
@@ -292,7 +292,7 @@ static int gather_ids_impl(ErScene* s, int kind, ErComm* c, uint32_t root) {
     if (root >= c->world) return fail(ER_ERR_INVALID_ARG, "er_gather_ids: root >= world");
     std::lock_guard<std::mutex> lk(s->mtx);
     if (!s->begun) return fail(ER_ERR_STATE, "er_gather_ids: er_render_begin has not succeeded");
-    if (!s->ids_valid) return fail(ER_ERR_STATE, "er_gather_ids: no id planes of this scene state (er_render_ids)");
+    if (!s->ids.valid) return fail(ER_ERR_STATE, "er_gather_ids: no id planes of this scene state (er_render_ids)");
     float4* const ids = s->d_id_planes.p + (size_t)(2 * kind) * s->x_res * s->y_res;      // (the kind's id plane, then its count plane: er_scene.h)
     const int rc = gather_plane(s, kind, ids, "er_gather_ids", nullptr, c, root);
     return rc != ER_OK ? rc : gather_plane(s, kind, ids + (size_t)s->x_res * s->y_res, "er_gather_ids", nullptr, c, root);

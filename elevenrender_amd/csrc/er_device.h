@@ -207,6 +207,11 @@ __host__ __device__ inline CamTrig camera_trig(const ErCamera& cam) {
     t.cx = er_cos(rx); t.sx = er_sin(rx); t.cy = er_cos(ry); t.sy = er_sin(ry); t.cz = er_cos(rz); t.sz = er_sin(rz);
     return t;
 }
+// the scene's: the host's values or, with cam_trig_valid = 0 (ER_CAM_TRIG_ON_DEVICE), the same bits evaluated here (er_first_hit.h)
+ERD void scene_cam_trig(const DevScene& S, CamTrig& t) {
+    if (S.cam_trig_valid) { t.cx = S.cam_cx; t.sx = S.cam_sx; t.cy = S.cam_cy; t.sy = S.cam_sy; t.cz = S.cam_cz; t.sz = S.cam_sz; }
+    else t = camera_trig(S.cam);
+}
 ERD Ray camera_ray(const ErCamera& cam, int x, int y, uint32_t x_res, uint32_t y_res,
                    float r1, float r2, float r3, float r4, float r5, const CamTrig* pre = nullptr) {
     using namespace ermath;

@@ -6,14 +6,9 @@
 
 struct DevScene;
 
-// Workgroups (one wave each) of the feature pass per CU: the grid is bounded -- the tiles are walked with a grid stride -- so that
-// the traversal's spill area (ER_FEATURE_SPILL_PER_BLOCK uint2 per workgroup, 16 KB) stays at 4 MB per 64 CUs whatever the frame.
-#define ER_FEATURE_BLOCKS_PER_CU 4u
-#define ER_FEATURE_SPILL_PER_BLOCK ((size_t)ER_STACK8 * 64)
-
 hipError_t er_probe_features(const char** which);
 // n camera rays per owned pixel of S through the production traversal: albedo and depth (row-major float4 planes of the frame) of the
-// owned pixels are overwritten.  `spill`: blocks * ER_FEATURE_SPILL_PER_BLOCK uint2.
+// owned pixels are overwritten.  `blocks`, `spill`: the first-hit pass's grid and spill area (er_first_hit_blocks, er_first_hit.h).
 void er_launch_features(const DevScene& S, uint32_t n, float4* albedo, float4* depth, uint32_t blocks, uint2* spill, hipStream_t stream);
 // pixels of the listed tiles <-> compact buffer [tile][64] float4 of a row-major plane (lanes outside the frame: zero / skipped)
 void er_launch_pack_plane(const DevScene& S, const uint32_t* tiles, uint32_t ntiles, const float4* plane, void* dst, hipStream_t stream);

@@ -1,22 +1,21 @@
 // er_features.hip -- first-hit feature planes (albedo, depth) and the a-trous filter guided by them (include/eleven_hip.h
 // er_render_features, er_read_feature, er_gather_feature, er_feature_info, er_denoise_guided).
 //
-// The render kernels are untouched: the planes come from a separate, stateless primary-visibility pass -- n camera rays per owned
-// pixel through the production wide traversal -- which reads the scene descriptor and writes two planes of its own.  It neither
-// reads nor writes the progressive state (passes, samples, RNG, counters), so a render with a feature pass in between is, bit for
-// bit, the render without it.
+// The render kernels are untouched: the planes come from the stateless first-hit camera pass (er_first_hit.h, which the id pass, the
+// pick and the history's key share) -- n camera rays per owned pixel through the production wide traversal -- shaded here into two
+// planes of their own.  The pass neither reads nor writes the progressive state (passes, samples, RNG, counters), so a render with a
+// feature pass in between is, bit for bit, the render without it.
 #include "er_features.h"
 
-#include "er_scene.h"
+#include "er_first_hit.h"
 #include "er_shade.h"
-#include "er_trav.h"
 
 using namespace erd;
 using namespace erh;
 
 // One wave per 8x8 tile, one lane per pixel; a fixed number of workgroups walks the owned tiles with a grid stride (no workgroup
-// waits for or talks to another).  Per pixel idx = py * x_res + px, exactly these operations (-ffp-contract=off;
-// tests/test_gpu_features.py replays them in numpy float32 from the oracle's entry points, bit for bit):
+// waits for or talks to another): first_hit_walk, whose handle gives the ray and its closest hit.  Per pixel idx = py * x_res + px,
+// exactly these operations (-ffp-contract=off; tests/test_gpu_features.py replays them in numpy float32 from the oracle, bit for bit):
 //     rs = jenkins_u32(idx + 1)                                 the value er_setup_kernel gives DevScene::rng -- which is not touched
 //     A = (0, 0, 0), D = 0, hits = 0
 //     for k = 0 .. n - 1:
@@ -32,31 +31,16 @@ using namespace erh;
 // No opacity draw is taken: the first hit counts whatever its opacity (a limit of the pass: a path that passes through a cut-out
 // shades what lies behind it, the feature planes show the cut-out's own albedo and distance).
 __global__ __launch_bounds__(64) void er_features_kernel(DevScene S, uint32_t n, float4* __restrict__ albedo, float4* __restrict__ depth, uint2* spill_base) {
-    __shared__ uint2 s_stack[WF_LDS_STACK * 64];
-    __shared__ int s_stack2[ER_STACK * 64];
-    const uint32_t lane = threadIdx.x;
-    uint2* stack = s_stack + lane;
-    uint2* spill = spill_base + (size_t)blockIdx.x * ER_FEATURE_SPILL_PER_BLOCK + lane;
-    int* stack2 = s_stack2 + lane;
-    CamTrig trig;      // (the camera's six sines and cosines once per lane: camera_trig is what camera_ray would evaluate per sample, the same bits)
-    if (S.cam_trig_valid) { trig.cx = S.cam_cx; trig.sx = S.cam_sx; trig.cy = S.cam_cy; trig.sy = S.cam_sy; trig.cz = S.cam_cz; trig.sz = S.cam_sz; }
-    else trig = camera_trig(S.cam);
     const float fn = (float)n;
-    for (uint32_t t = blockIdx.x; t < S.owned_tile_count; t += gridDim.x) {
-        const uint32_t tile = S.owned_tiles[t];
-        const uint32_t px = (tile % S.tiles_x) * ER_TILE + (lane & 7u), py = (tile / S.tiles_x) * ER_TILE + (lane >> 3);
-        if (px >= S.x_res || py >= S.y_res) continue;
+    first_hit_walk(S, spill_base, [&](uint32_t px, uint32_t py, const FirstHit& fh) {
         const uint32_t idx = py * S.x_res + px;
         uint32_t rs = jenkins_u32(idx + 1u);
         F3 A = f3s(0.0f);
         float D = 0.0f;
         uint32_t hits = 0;
         for (uint32_t k = 0; k < n; k++) {
-            const float c1 = rng_next(rs), c2 = rng_next(rs), c3 = rng_next(rs), c4 = rng_next(rs), c5 = rng_next(rs);
-            const Ray ray = camera_ray(S.cam, (int)px, (int)py, S.x_res, S.y_res, c1, c2, c3, c4, c5, &trig);
-            int info;
-            unsigned cn = 0, ct = 0;
-            const int slot = trav_run_closest<false>(S, stack, spill, stack2, ray, __builtin_inff(), info, cn, ct);
+            const Ray ray = fh.sample_ray(px, py, rs);
+            const int slot = fh.closest(ray);
             F3 a = f3s(1.0f);
             if (slot >= 0) {
                 HitFull hit;
@@ -83,7 +67,7 @@ __global__ __launch_bounds__(64) void er_features_kernel(DevScene S, uint32_t n,
         const float z = hits ? D / (float)hits : 0.0f;
         albedo[idx] = make_float4(A.x / fn, A.y / fn, A.z / fn, cov);
         depth[idx] = make_float4(z, z, z, cov);
-    }
+    });
 }
 
 // pixels of the listed tiles of a row-major plane <-> compact buffer [tile][64] (er_pack_kernel / er_unpack_kernel on a plane pointer)
@@ -215,31 +199,24 @@ int features_impl(ErScene* s, uint32_t n) {
     HIP_TRY(hipStreamSynchronize(s->stream));      // pending asynchronous work first
     int rc;
     const size_t npx = (size_t)s->x_res * s->y_res;
-    const uint32_t blocks = std::max(1u, s->kept.cus) * ER_FEATURE_BLOCKS_PER_CU;
-    s->feat_valid = false;
+    uint32_t blocks;
+    s->feat.valid = false;
     for (auto& u : s->unpacked_feat) u.clear();      // other ranks' pixels gathered earlier are overwritten below
     if (s->d_feat.n < 2 * npx && (rc = upload(s->d_feat, nullptr, 2 * npx, s->stream)) != ER_OK) return rc;
-    if (s->d_feat_spill.n < blocks * ER_FEATURE_SPILL_PER_BLOCK && (rc = upload(s->d_feat_spill, nullptr, blocks * ER_FEATURE_SPILL_PER_BLOCK, s->stream)) != ER_OK) return rc;
+    if ((rc = er_first_hit_blocks(s, &blocks)) != ER_OK) return rc;
     EventPair ev;
     HIP_TRY(hipEventCreate(&ev.a));
     HIP_TRY(hipEventCreate(&ev.b));
     // pixels of other ranks read as zero until they are gathered
     HIP_TRY(hipMemsetAsync(s->d_feat.p, 0, 2 * npx * sizeof(float4), s->stream));
     HIP_TRY(hipEventRecord(ev.a, s->stream));
-    er_launch_features(s->dev, n, feature_plane(s, ER_FEATURE_ALBEDO), feature_plane(s, ER_FEATURE_DEPTH), blocks, s->d_feat_spill.p, s->stream);
+    er_launch_features(s->dev, n, feature_plane(s, ER_FEATURE_ALBEDO), feature_plane(s, ER_FEATURE_DEPTH), blocks, s->d_first_hit_spill.p, s->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev.b, s->stream));
     HIP_TRY(hipEventSynchronize(ev.b));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-    uint64_t px = 0;      // owned pixels inside the frame: one camera ray each per sample
-    const uint32_t tiles_x = s->tiles_x();
-    for (uint32_t t : s->tiles_of(s->params.rank, s->params.world))
-        px += (uint64_t)std::min<uint32_t>(ER_TILE, s->x_res - (t % tiles_x) * ER_TILE) * std::min<uint32_t>(ER_TILE, s->y_res - (t / tiles_x) * ER_TILE);
-    s->feat_samples = n;
-    s->feat_rays = px * n;
-    s->feat_ms = ms;
-    s->feat_valid = true;
+    s->feat = {true, n, s->owned_pixels() * n, ms};      // (one camera ray per sample and owned pixel inside the frame)
     return ER_OK;
 }
 
@@ -248,8 +225,8 @@ int feature_info_impl(ErScene* s, ErFeatureInfo* out) {
     std::lock_guard<std::mutex> lk(s->mtx);
     if (!s->begun) return fail(ER_ERR_STATE, "er_feature_info: er_render_begin has not succeeded");
     *out = ErFeatureInfo{};
-    out->valid = s->feat_valid ? 1u : 0u;
-    if (s->feat_valid) { out->samples = s->feat_samples; out->rays = s->feat_rays; out->ms = s->feat_ms; }
+    out->valid = s->feat.valid ? 1u : 0u;
+    if (s->feat.valid) { out->samples = s->feat.samples; out->rays = s->feat.rays; out->ms = s->feat.ms; }
     return ER_OK;
 }
 
@@ -258,7 +235,7 @@ int read_feature_impl(ErScene* s, int feature, float* dst) {
     if (!s || !dst) return fail(ER_ERR_INVALID_ARG, "er_read_feature: NULL argument");
     std::lock_guard<std::mutex> lk(s->mtx);
     if (!s->begun) return fail(ER_ERR_STATE, "er_read_feature: er_render_begin has not succeeded");
-    if (!s->feat_valid) return fail(ER_ERR_STATE, "er_read_feature: no feature planes of this scene state (er_render_features)");
+    if (!s->feat.valid) return fail(ER_ERR_STATE, "er_read_feature: no feature planes of this scene state (er_render_features)");
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipMemcpyAsync(dst, feature_plane(s, feature), (size_t)s->x_res * s->y_res * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -277,7 +254,7 @@ int denoise_guided_impl(ErScene* s, const ErDenoiseGuided* p) {
     if (sz == 0) sz = 0.2f;
     std::lock_guard<std::mutex> lk(s->mtx);
     if (!s->begun) return fail(ER_ERR_STATE, "er_denoise_guided: er_render_begin has not succeeded");
-    if (!s->feat_valid) return fail(ER_ERR_STATE, "er_denoise_guided: no feature planes of this scene state (er_render_features)");
+    if (!s->feat.valid) return fail(ER_ERR_STATE, "er_denoise_guided: no feature planes of this scene state (er_render_features)");
     if (s->params.world > 1) {      // a sharded frame: only where all four guides are whole (er_denoise)
         std::string missing;
         const uint32_t need = s->params.world - 1;

@@ -1,48 +1,28 @@
 // er_history.hip -- temporal reprojection: the key pass, the capture, the resolve and the blend (include/eleven_hip.h er_history_capture,
 // er_history_resolve, er_history_info, er_read_history, er_read_blended).
 //
-// The key pass is the id pass (er_ids.hip) with one pinhole ray per pixel and the hit's position kept: the same traversal, kernels of its
-// own, nothing of the render written.  The other three kernels are one work item per pixel around the routines of er_reproject.h.  So a
-// render with a capture, a resolve and the reads in between is, bit for bit, the render without them.
+// The key pass is the first-hit camera pass (er_first_hit.h) with one pinhole ray per pixel and the hit's position kept: the walker, the
+// traversal and the id accessors of the feature and id passes, nothing of the render written.  The other three kernels are one work item
+// per pixel around the routines of er_reproject.h.  So a render with a capture, a resolve and the reads in between is, bit for bit, the
+// render without them.
 #include "er_history.h"
 
-#include "er_scene.h"
-#include "er_trav.h"
+#include "er_first_hit.h"
 
 using namespace erd;
 using namespace erh;
 
-// (er_ids.hip's two, restated: a record's triangle and a triangle's object)
-ERD uint32_t hk_slot_triangle(const DevScene& S, uint32_t slot) { return __builtin_bit_cast(uint32_t, S.tri_isect[(size_t)slot * 3].w); }
-ERD uint32_t hk_triangle_object(const DevScene& S, const uint32_t* __restrict__ tri_object, uint32_t tri) {
-    return (tri_object && tri < S.tri_count) ? tri_object[tri] : ER_ID_NONE;
-}
-
-// The geometry of er_ids_kernel: one wave per 8x8 tile, one lane per pixel, a grid stride over the owned tiles (world == 1: all of them),
-// the same LDS stacks and spill area.  One ray per lane: camera_ray with r1 = r2 = 0.5 and bokeh taken as 0.
+// first_hit_walk's geometry (one wave per 8x8 tile, one lane per pixel, a grid stride over the owned tiles; world == 1: all of them).
+// One ray per lane: camera_ray with r1 = r2 = 0.5 and bokeh taken as 0, on the handle's trig.
 // key: [0, npx) hit, [npx, 2 npx) object, [2 npx, 3 npx) dist, then P as [npx][3].
 __global__ __launch_bounds__(64) void er_history_key_kernel(DevScene S, const uint32_t* __restrict__ tri_object, uint32_t* __restrict__ key, size_t npx, uint2* spill_base) {
-    __shared__ uint2 s_stack[WF_LDS_STACK * 64];
-    __shared__ int s_stack2[ER_STACK * 64];
-    const uint32_t lane = threadIdx.x;
-    uint2* stack = s_stack + lane;
-    uint2* spill = spill_base + (size_t)blockIdx.x * ER_FEATURE_SPILL_PER_BLOCK + lane;
-    int* stack2 = s_stack2 + lane;
-    CamTrig trig;
-    if (S.cam_trig_valid) { trig.cx = S.cam_cx; trig.sx = S.cam_sx; trig.cy = S.cam_cy; trig.sy = S.cam_sy; trig.cz = S.cam_cz; trig.sz = S.cam_sz; }
-    else trig = camera_trig(S.cam);
     ErCamera cam = S.cam;
     cam.bokeh = 0;
     float* const kf = (float*)key;
-    for (uint32_t t = blockIdx.x; t < S.owned_tile_count; t += gridDim.x) {
-        const uint32_t tile = S.owned_tiles[t];
-        const uint32_t px = (tile % S.tiles_x) * ER_TILE + (lane & 7u), py = (tile / S.tiles_x) * ER_TILE + (lane >> 3);
-        if (px >= S.x_res || py >= S.y_res) continue;
+    first_hit_walk(S, spill_base, [&](uint32_t px, uint32_t py, const FirstHit& fh) {
         const size_t idx = (size_t)py * S.x_res + px;
-        const Ray ray = camera_ray(cam, (int)px, (int)py, S.x_res, S.y_res, 0.5f, 0.5f, 0.0f, 0.0f, 0.0f, &trig);
-        int info;
-        unsigned cn = 0, ct = 0;
-        const int slot = trav_run_closest<false>(S, stack, spill, stack2, ray, __builtin_inff(), info, cn, ct);
+        const Ray ray = camera_ray(cam, (int)px, (int)py, S.x_res, S.y_res, 0.5f, 0.5f, 0.0f, 0.0f, 0.0f, &fh.trig);
+        const int slot = fh.closest(ray);
         uint32_t hit = 0u, object = ER_ID_NONE;
         float dist = 0.0f;
         F3 P = ray.d;
@@ -50,7 +30,7 @@ __global__ __launch_bounds__(64) void er_history_key_kernel(DevScene S, const ui
             HitFull h;
             full_hit(S, (uint32_t)slot, ray, h);
             hit = 1u;
-            object = hk_triangle_object(S, tri_object, hk_slot_triangle(S, (uint32_t)slot));
+            object = triangle_object(S, tri_object, slot_triangle(S, (uint32_t)slot));
             dist = length(h.position - ray.o);
             P = h.position;
         }
@@ -60,7 +40,7 @@ __global__ __launch_bounds__(64) void er_history_key_kernel(DevScene S, const ui
         kf[3 * npx + idx * 3 + 0] = P.x;
         kf[3 * npx + idx * 3 + 1] = P.y;
         kf[3 * npx + idx * 3 + 2] = P.z;
-    }
+    });
 }
 
 // capture: (C.rgb, W) of every pixel from BEAUTY, the sample counts and, if `hist` is not NULL, the resolved history
@@ -152,11 +132,11 @@ int make_key(ErScene* s) {
     ErHistoryState& H = s->hist;
     int rc;
     const size_t npx = (size_t)s->x_res * s->y_res;
-    const uint32_t blocks = std::max(1u, s->kept.cus) * ER_FEATURE_BLOCKS_PER_CU;
+    uint32_t blocks;
     H.key_valid = false;
-    if ((rc = er_id_prepare(s, blocks)) != ER_OK) return rc;
+    if ((rc = er_first_hit_blocks(s, &blocks)) != ER_OK || (rc = er_id_prepare(s)) != ER_OK) return rc;
     if (s->dev.owned_tile_count)
-        hipLaunchKernelGGL(er_history_key_kernel, dim3(blocks), dim3(64), 0, s->stream, s->dev, er_id_map(s), H.d_key[H.now].p, npx, s->d_feat_spill.p);
+        hipLaunchKernelGGL(er_history_key_kernel, dim3(blocks), dim3(64), 0, s->stream, s->dev, er_id_map(s), H.d_key[H.now].p, npx, s->d_first_hit_spill.p);
     HIP_TRY(hipGetLastError());
     H.key_cam = s->camera;
     H.key_m = s->objects.last_m;

@@ -80,10 +80,9 @@ ER_ID_HD inline uint32_t er_id_object_of(const uint32_t* first, uint32_t objects
 #if defined(__HIPCC__)
 #include <hip/hip_runtime_api.h>
 hipError_t er_probe_ids(const char** which);      // see er_kernels.h; er_render_begin asks it after er_probe_kernels
-// the traversal's spill area for `blocks` workgroups (shared with the feature pass) and the tri -> object map of the current table made
-// current; the map, or NULL without a table.  The scene's mutex is held and its stream idle.
+// the tri -> object map of the current table made current; the map, or NULL without a table.  The scene's mutex is held and its stream idle.
 struct ErScene;
-int er_id_prepare(ErScene* s, uint32_t blocks);
+int er_id_prepare(ErScene* s);
 const uint32_t* er_id_map(ErScene* s);
 #endif
 

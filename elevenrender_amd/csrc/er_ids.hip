@@ -1,30 +1,23 @@
 // er_ids.hip -- the first-hit id pass and its three consumers (include/eleven_hip.h er_render_ids, er_id_info, er_read_ids,
 // er_id_matte, er_pick_rect, er_pick; er_gather_ids is er_collective.cpp's).
 //
-// The pass is the feature pass (er_features.hip) with the shading taken out and the ids kept: the same rays through the same traversal,
-// kernels of its own, nothing of the render read or written.  So a render with an id pass, a matte, a selection or a pick in between
-// is, bit for bit, the render without them.
+// The pass is the first-hit camera pass (er_first_hit.h) with the ids of the hits kept: the rays of the feature pass (er_features.hip),
+// nothing of the render read or written.  So a render with an id pass, a matte, a selection or a pick in between is, bit for bit, the
+// render without them.
 #include "er_ids.h"
 
-#include "er_scene.h"
-#include "er_trav.h"
+#include "er_first_hit.h"
 
 using namespace erd;
 using namespace erh;
 
 #define ER_ID_MAX_RAYS 64u
-static_assert(ER_STACK >= (int)ER_ID_MAX_RAYS, "er_ids_kernel ranks a lane's ids in the exact routine's stack words, one per ray");
 static_assert(ER_ID_SLOTS == 4, "a pixel's slots are one uint4 per plane");
 
-// the three ids of the record in `slot`
-ERD uint32_t slot_triangle(const DevScene& S, uint32_t slot) { return __builtin_bit_cast(uint32_t, S.tri_isect[(size_t)slot * 3].w); }
-ERD uint32_t slot_material(const DevScene& S, uint32_t slot) { return __builtin_bit_cast(uint32_t, S.tri_attr[(size_t)slot * ER_ATTR_PIECES + 6].x); }
-ERD uint32_t triangle_object(const DevScene& S, const uint32_t* __restrict__ tri_object, uint32_t tri) {
-    return (tri_object && tri < S.tri_count) ? tri_object[tri] : ER_ID_NONE;
-}
-
-// The geometry of er_features_kernel: one wave per 8x8 tile, one lane per pixel, a grid stride over the owned tiles, the same LDS stacks
-// and spill area.  Per pixel idx = py * x_res + px the rays are the feature pass's:
+// first_hit_walk and FirstHit's two operations (er_first_hit.h) RESTATED: as a body of the walker this kernel had the same loops,
+// registers and LDS and ran 1.7-2.3 % slower at 1080p (profiles/first_hit_refactor_ab.log; cause not found), so it keeps its own text
+// and shares the trig, the id accessors and the constants.  Whoever changes the walker, sample_ray or closest changes this kernel with
+// them (tests/test_gpu_first_hit.py and test_gpu_ids.py compare them bit for bit).  Per pixel idx = py * x_res + px the feature pass's rays:
 //     rs = jenkins_u32(idx + 1);  for k = 0 .. n - 1:  c1 .. c5 = rng_next(rs);  ray = camera_ray(...);  slot = trav_run_closest(ray)
 // A lane keeps the record slots of its rays that hit in its own column of s_slot ([k][lane]: 16 KB, conflict-free, and no other lane
 // ever touches the column, so no barrier).  Once its n rays are traced the exact routine's stack (s_stack2, ER_STACK words per lane in
@@ -37,13 +30,13 @@ __global__ __launch_bounds__(64) void er_ids_kernel(DevScene S, uint32_t n, cons
     __shared__ uint32_t s_slot[ER_ID_MAX_RAYS * 64];
     const uint32_t lane = threadIdx.x;
     uint2* stack = s_stack + lane;
-    uint2* spill = spill_base + (size_t)blockIdx.x * ER_FEATURE_SPILL_PER_BLOCK + lane;
+    uint2* spill = spill_base + (size_t)blockIdx.x * ER_FIRST_HIT_SPILL_PER_BLOCK + lane;
     int* stack2 = s_stack2 + lane;
     uint32_t* slots = s_slot + lane;
+    static_assert(ER_STACK >= (int)ER_ID_MAX_RAYS, "er_ids_kernel ranks a lane's ids in the exact routine's stack words, one per ray");
     uint32_t* col = (uint32_t*)s_stack2 + lane;
     CamTrig trig;
-    if (S.cam_trig_valid) { trig.cx = S.cam_cx; trig.sx = S.cam_sx; trig.cy = S.cam_cy; trig.sy = S.cam_sy; trig.cz = S.cam_cz; trig.sz = S.cam_sz; }
-    else trig = camera_trig(S.cam);
+    scene_cam_trig(S, trig);
     if (n > ER_ID_MAX_RAYS) n = ER_ID_MAX_RAYS;      // (the entry point refuses more: the columns hold this many)
     for (uint32_t t = blockIdx.x; t < S.owned_tile_count; t += gridDim.x) {
         const uint32_t tile = S.owned_tiles[t];
@@ -84,18 +77,11 @@ __global__ __launch_bounds__(64) void er_ids_kernel(DevScene S, uint32_t n, cons
 
 // er_pick: ray 0 of pixel (px, py) on lane 0 of one wave; `out` takes the ten words of an ErPick
 __global__ __launch_bounds__(64) void er_pick_kernel(DevScene S, uint32_t px, uint32_t py, const uint32_t* __restrict__ tri_object, uint32_t* __restrict__ out, uint2* spill_base) {
-    __shared__ uint2 s_stack[WF_LDS_STACK * 64];
-    __shared__ int s_stack2[ER_STACK * 64];
     if (threadIdx.x != 0 || px >= S.x_res || py >= S.y_res) return;
+    const FirstHit fh = first_hit_lane(S, spill_base);      // (lane 0 of workgroup 0: the first column of the one slice)
     uint32_t rs = jenkins_u32(py * S.x_res + px + 1u);
-    const float c1 = rng_next(rs), c2 = rng_next(rs), c3 = rng_next(rs), c4 = rng_next(rs), c5 = rng_next(rs);
-    CamTrig trig;
-    if (S.cam_trig_valid) { trig.cx = S.cam_cx; trig.sx = S.cam_sx; trig.cy = S.cam_cy; trig.sy = S.cam_sy; trig.cz = S.cam_cz; trig.sz = S.cam_sz; }
-    else trig = camera_trig(S.cam);
-    const Ray ray = camera_ray(S.cam, (int)px, (int)py, S.x_res, S.y_res, c1, c2, c3, c4, c5, &trig);
-    int info;
-    unsigned cn = 0, ct = 0;
-    const int slot = trav_run_closest<false>(S, s_stack, spill_base, s_stack2, ray, __builtin_inff(), info, cn, ct);
+    const Ray ray = fh.sample_ray(px, py, rs);
+    const int slot = fh.closest(ray);
     uint32_t w[10] = {0u, ER_ID_NONE, ER_ID_NONE, ER_ID_NONE, 0u, 0u, 0u, 0u, 0u, 0u};
     if (slot >= 0) {
         HitFull hit;
@@ -217,14 +203,13 @@ bool kind_ok(int kind) { return kind >= 0 && kind < ER_ID_KIND_COUNT; }
 
 int need_planes(ErScene* s, const char* who) {
     if (!s->begun) return fail(ER_ERR_STATE, std::string(who) + ": er_render_begin has not succeeded");
-    if (!s->ids_valid) return fail(ER_ERR_STATE, std::string(who) + ": no id planes of this scene state (er_render_ids)");
+    if (!s->ids.valid) return fail(ER_ERR_STATE, std::string(who) + ": no id planes of this scene state (er_render_ids)");
     return ER_OK;
 }
 
-// the traversal's spill area (shared with the feature pass) and the tri -> object map of the current table; the stream is idle
-int id_prepare(ErScene* s, uint32_t blocks) {
+// the tri -> object map of the current table; the stream is idle
+int id_prepare(ErScene* s) {
     int rc;
-    if (s->d_feat_spill.n < blocks * ER_FEATURE_SPILL_PER_BLOCK && (rc = upload(s->d_feat_spill, nullptr, blocks * ER_FEATURE_SPILL_PER_BLOCK, s->stream)) != ER_OK) return rc;
     const uint32_t objects = s->objects.objects();
     if (s->id_map_valid || objects == 0) return ER_OK;      // (no table: the kernels take a NULL map and answer ER_ID_NONE)
     const uint32_t total = (uint32_t)s->objects.ids.size();
@@ -251,9 +236,9 @@ int render_ids_impl(ErScene* s, uint32_t n) {
     HIP_TRY(hipStreamSynchronize(s->stream));      // pending asynchronous work first
     int rc;
     const size_t npx = (size_t)s->x_res * s->y_res, nplanes = 2 * ER_ID_KIND_COUNT;
-    const uint32_t blocks = std::max(1u, s->kept.cus) * ER_FEATURE_BLOCKS_PER_CU;
-    s->ids_valid = false;
-    if ((rc = id_prepare(s, blocks)) != ER_OK) return rc;
+    uint32_t blocks;
+    s->ids.valid = false;
+    if ((rc = er_first_hit_blocks(s, &blocks)) != ER_OK || (rc = id_prepare(s)) != ER_OK) return rc;
     if (s->d_id_planes.n < nplanes * npx && (rc = upload(s->d_id_planes, nullptr, nplanes * npx, s->stream)) != ER_OK) return rc;
     if (s->d_id_over.n < ER_ID_KIND_COUNT && (rc = upload(s->d_id_over, nullptr, ER_ID_KIND_COUNT, s->stream)) != ER_OK) return rc;
     EventPair ev;
@@ -267,22 +252,15 @@ int render_ids_impl(ErScene* s, uint32_t n) {
     HIP_TRY(hipMemsetAsync(s->d_id_over.p, 0, ER_ID_KIND_COUNT * 4, s->stream));
     HIP_TRY(hipEventRecord(ev.a, s->stream));
     if (s->dev.owned_tile_count)
-        hipLaunchKernelGGL(er_ids_kernel, dim3(blocks), dim3(64), 0, s->stream, s->dev, n, id_map(s), (uint4*)s->d_id_planes.p, npx, s->d_id_over.p, s->d_feat_spill.p);
+        hipLaunchKernelGGL(er_ids_kernel, dim3(blocks), dim3(64), 0, s->stream, s->dev, n, id_map(s), (uint4*)s->d_id_planes.p, npx, s->d_id_over.p, s->d_first_hit_spill.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev.b, s->stream));
     HIP_TRY(hipMemcpyAsync(s->ids_overflow, s->d_id_over.p, ER_ID_KIND_COUNT * 4, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-    uint64_t px = 0;      // owned pixels inside the frame: one camera ray each per sample
-    const uint32_t tiles_x = s->tiles_x();
-    for (uint32_t t : s->tiles_of(s->params.rank, s->params.world))
-        px += (uint64_t)std::min<uint32_t>(ER_TILE, s->x_res - (t % tiles_x) * ER_TILE) * std::min<uint32_t>(ER_TILE, s->y_res - (t / tiles_x) * ER_TILE);
-    s->ids_samples = n;
-    s->ids_rays = px * n;
-    s->ids_ms = ms;
+    s->ids = {true, n, s->owned_pixels() * n, ms};      // (one camera ray per sample and owned pixel inside the frame)
     s->ids_objects = s->objects.objects();
-    s->ids_valid = true;
     return ER_OK;
 }
 
@@ -291,9 +269,9 @@ int id_info_impl(ErScene* s, ErIdInfo* out) {
     std::lock_guard<std::mutex> lk(s->mtx);
     if (!s->begun) return fail(ER_ERR_STATE, "er_id_info: er_render_begin has not succeeded");
     *out = ErIdInfo{};
-    out->valid = s->ids_valid ? 1u : 0u;
-    if (s->ids_valid) {
-        out->samples = s->ids_samples; out->rays = s->ids_rays; out->ms = s->ids_ms; out->objects = s->ids_objects;
+    out->valid = s->ids.valid ? 1u : 0u;
+    if (s->ids.valid) {
+        out->samples = s->ids.samples; out->rays = s->ids.rays; out->ms = s->ids.ms; out->objects = s->ids_objects;
         for (int k = 0; k < ER_ID_KIND_COUNT; k++) out->overflow_pixels[k] = s->ids_overflow[k];
     }
     return ER_OK;
@@ -332,7 +310,7 @@ int id_matte_impl(ErScene* s, int kind, const uint32_t* ids, uint32_t count, flo
     HIP_TRY(hipMemcpyAsync(d_list, list.data(), list.size() * 4, hipMemcpyHostToDevice, s->stream));
     if (npx)
         hipLaunchKernelGGL(k_id_matte, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, s->stream, (const uint4*)id_plane(s, kind, 0), (const uint4*)id_plane(s, kind, 1), npx,
-                           (const uint32_t*)d_list, (uint32_t)list.size(), s->ids_samples, d_dst);
+                           (const uint32_t*)d_list, (uint32_t)list.size(), s->ids.samples, d_dst);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(dst, d_dst, npx * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));      // (`list` goes out of scope)
@@ -379,9 +357,9 @@ int pick_impl(ErScene* s, uint32_t x, uint32_t y, ErPick* out) {
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));      // pending asynchronous work first
     int rc;
-    if ((rc = id_prepare(s, 1)) != ER_OK) return rc;
+    if ((rc = er_first_hit_spill(s, 1)) != ER_OK || (rc = id_prepare(s)) != ER_OK) return rc;
     if (s->d_id_work.n < sizeof(ErPick) / 4 && (rc = upload(s->d_id_work, nullptr, sizeof(ErPick) / 4, s->stream)) != ER_OK) return rc;
-    hipLaunchKernelGGL(er_pick_kernel, dim3(1), dim3(64), 0, s->stream, s->dev, x, y, id_map(s), s->d_id_work.p, s->d_feat_spill.p);
+    hipLaunchKernelGGL(er_pick_kernel, dim3(1), dim3(64), 0, s->stream, s->dev, x, y, id_map(s), s->d_id_work.p, s->d_first_hit_spill.p);
     HIP_TRY(hipGetLastError());
     ErPick got{};
     HIP_TRY(hipMemcpyAsync(&got, s->d_id_work.p, sizeof(ErPick), hipMemcpyDeviceToHost, s->stream));
@@ -392,8 +370,8 @@ int pick_impl(ErScene* s, uint32_t x, uint32_t y, ErPick* out) {
 
 }  // namespace
 
-// what er_history.hip shares with the pass: the spill area and the tri -> object map
-int er_id_prepare(ErScene* s, uint32_t blocks) { return id_prepare(s, blocks); }
+// what er_history.hip shares with the pass: the tri -> object map
+int er_id_prepare(ErScene* s) { return id_prepare(s); }
 const uint32_t* er_id_map(ErScene* s) { return id_map(s); }
 
 extern "C" {

@@ -256,29 +256,27 @@ struct ErScene {
     // which ranks' pixels of each plane were unpacked into this scene since the last sample was enqueued: er_denoise on a
     // sharded frame needs the whole BEAUTY and NORMAL planes (the rank the frame was gathered to)
     std::set<uint32_t> unpacked[ER_PASS_COUNT];
-    // the feature pass (er_features.hip): the ALBEDO and DEPTH planes back to back (row-major, allocated by the first er_render_features)
-    // and the traversal's spill area of its bounded grid; valid from a pass until the next er_render_begin or er_render_update.
-    // Recomputable, so not part of the progressive state.  unpacked_feat: as `unpacked`, since the last pass.
+    // the first-hit camera pass (er_first_hit.h) of er_render_features, er_render_ids, er_pick and the history's key: the traversal's
+    // spill area of its bounded grid (the consumers run one at a time on the scene's stream), and what a whole-frame pass reports
+    DevBuf<uint2> d_first_hit_spill;
+    struct PassInfo { bool valid = false; uint32_t samples = 0; uint64_t rays = 0; float ms = 0; };
+    // the feature pass (er_features.hip): the ALBEDO and DEPTH planes back to back (row-major, allocated by the first er_render_features);
+    // valid from a pass until the next er_render_begin or er_render_update.  Recomputable, so not part of the progressive state.
+    // unpacked_feat: as `unpacked`, since the last pass.
     DevBuf<float4> d_feat;
-    DevBuf<uint2> d_feat_spill;
-    bool feat_valid = false;
-    uint32_t feat_samples = 0;
-    uint64_t feat_rays = 0;
-    float feat_ms = 0;
+    PassInfo feat;
     std::set<uint32_t> unpacked_feat[ER_FEATURE_COUNT];
     // the id pass (er_ids.hip): per kind an id plane and a count plane, 16 bytes per pixel each, back to back -- plane 2 * kind + 0 /
-    // + 1, row-major, allocated by the first er_render_ids; ids_valid from a pass until the next er_render_begin, edit of any kind or
+    // + 1, row-major, allocated by the first er_render_ids; ids.valid from a pass until the next er_render_begin, edit of any kind or
     // er_objects_set (ids_invalidate).  d_id_map: tri -> object of the current table (tri_count words), made again when the table
     // changed.  d_id_work: the words the consumers work in, grown on demand and kept (er_pick_rect: marks, block counts, offsets, the
-    // selection; er_id_matte: the plane and the list; er_pick: one ErPick).  d_id_over: the pass's three overflow counters.  The
-    // traversal's spill area is the feature pass's (d_feat_spill): both passes run alone on the scene's stream.
+    // selection; er_id_matte: the plane and the list; er_pick: one ErPick).  d_id_over: the pass's three overflow counters.
     DevBuf<float4> d_id_planes;
     DevBuf<uint32_t> d_id_map, d_id_work, d_id_over;
-    bool ids_valid = false, id_map_valid = false;
-    uint32_t ids_samples = 0, ids_objects = 0, ids_overflow[ER_ID_KIND_COUNT] = {0, 0, 0};
-    uint64_t ids_rays = 0;
-    float ids_ms = 0;
-    void ids_invalidate() noexcept { ids_valid = false; }
+    PassInfo ids;
+    bool id_map_valid = false;
+    uint32_t ids_objects = 0, ids_overflow[ER_ID_KIND_COUNT] = {0, 0, 0};
+    void ids_invalidate() noexcept { ids.valid = false; }
     // the temporal reprojection (er_history.hip): key planes, the captured colours and the resolved history; dropped by whatever changes
     // the look or moves a triangle other than by a pose (history_invalidate)
     ErHistoryState hist;
@@ -304,6 +302,15 @@ struct ErScene {
                 if ((tx + ty) % world == rank) t.push_back(ty * nx + tx);
         return t;
     }
+    uint32_t tile_pixels(uint32_t tile) const {      // pixels of a tile inside the frame
+        const uint32_t nx = tiles_x(), tx = tile % nx, ty = tile / nx;
+        return std::min<uint32_t>(ER_TILE, x_res - tx * ER_TILE) * std::min<uint32_t>(ER_TILE, y_res - ty * ER_TILE);
+    }
+    uint64_t owned_pixels() const {      // ... and of this rank's share of the frame
+        uint64_t px = 0;
+        for (uint32_t t : tiles_of(params.rank, params.world)) px += tile_pixels(t);
+        return px;
+    }
     void release_device() {
         d_nodes.release(); d_nodes8.release(); d_attr.release(); d_passes.release(); d_plane.release(); d_materials.release();
         d_textures.release(); d_tex_pool.release(); tex_pool_cap = 0; d_lights.release(); d_cdf.release(); d_samples.release(); d_rng.release();
@@ -314,9 +321,10 @@ struct ErScene {
         refit_topo.release();
         xform_dev.release();
         store.release();
-        d_feat.release(); d_feat_spill.release(); feat_valid = false;
+        d_first_hit_spill.release();
+        d_feat.release(); feat.valid = false;
         for (auto& u : unpacked_feat) u.clear();
-        d_id_planes.release(); d_id_map.release(); d_id_work.release(); d_id_over.release(); ids_valid = id_map_valid = false;
+        d_id_planes.release(); d_id_map.release(); d_id_work.release(); d_id_over.release(); ids.valid = id_map_valid = false;
         hist.release();
         var.release();
         ad_on = false; rendered = 0;

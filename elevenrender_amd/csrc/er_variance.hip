@@ -230,7 +230,7 @@ int denoise_impl(ErScene* s, const ErDenoiseVariance* p) {
     std::lock_guard<std::mutex> lk(s->mtx);
     int rc;
     if ((rc = need_begun(s, "er_denoise_variance")) != ER_OK) return rc;
-    if (!s->feat_valid) return fail(ER_ERR_STATE, "er_denoise_variance: no feature planes of this scene state (er_render_features)");
+    if (!s->feat.valid) return fail(ER_ERR_STATE, "er_denoise_variance: no feature planes of this scene state (er_render_features)");
     ErVarianceState& V = s->var;
     if (V.folds < 2) return fail(ER_ERR_STATE, "er_denoise_variance: fewer than two folds since the render last started over (er_variance_fold)");
     HIP_TRY(hipSetDevice(s->device));
