@@ -13,6 +13,8 @@ into a temporary directory wherever oracle/_ref/ exists and requires identical a
                                        tests/test_gpu_function_kat.py (scene `rig_*`) plus rays on the 300-triangle scene of the existing golden
   reference_cornell_32x32.npz          whole path, 4 samples per pixel, the reference's compiled-in MAXBOUNCES: the five planes, the
   reference_torture_300tri_32x24.npz   sample counts and the final RNG states; the scene inputs are those of the two existing goldens
+  reference_trihit_uv.npz              Tri::hit on the 300-triangle scene with per-triangle uvs and mirrored tangent signs
+                                       (tests/uv_scenes.py): reference_functions.npz pins it under the unit triangle's uvs and sign +1 only
 
 Usage: python tests/golden/make_golden_reference.py [output directory]
 """
@@ -289,6 +291,44 @@ def make_functions():
     return out
 
 
+# ---------------------------------------------------------------- Tri::hit under varied uvs and signs
+TRIHIT_UV_SEED, TRIHIT_UV_RAYS = 19, 1000
+TRI_ARRAYS = ("vertices", "normals", "tangents", "uvs", "tangent_sign")
+
+
+def trihit_uv_scene():
+    """the 300-triangle scene of the existing golden with the uvs and signs of tests/uv_scenes.py"""
+    import uv_scenes
+    trace, _, _, _ = load(TRACE_SCENE)
+    return uv_scenes.varied(trace, TRIHIT_UV_SEED)
+
+
+def make_trihit_uv():
+    """1 000 rays aimed like function_inputs' (through a vertex, along an edge, from both sides, misses); the five per-triangle arrays
+    Tri::hit reads are stored next to the outputs as rig_*"""
+    sc = trihit_uv_scene()
+    r = np.random.default_rng(12)
+    n = TRIHIT_UV_RAYS
+    tri = r.integers(0, sc.tri_count, n)
+    tri[:70] = np.repeat(np.arange(7), 10)                       # uv_scenes.SPECIAL: ten rays at each
+    v = sc.vertices.reshape(-1, 3, 3)[tri]
+    w = r.dirichlet([1, 1, 1], n).astype(np.float32)
+    w[::10] = [1, 0, 0]
+    w[::11, 2] = 0
+    target = (v * w[:, :, None]).sum(1).astype(np.float32)
+    origin = (target + r.normal(size=(n, 3)).astype(np.float32) * np.float32(0.7)).astype(np.float32)
+    d = target - origin
+    d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+    items = np.concatenate([ibits(tri.astype(np.int32)).reshape(-1, 1), origin, d], 1)
+    res = run_reference({**job_scene(sc), "trihit_items": items})
+    out = {"rig_" + k: getattr(sc, k) for k in TRI_ARRAYS}
+    out["trihit_items"] = items
+    for m in MODES:
+        out["trihit_ok_" + m] = res[m]["trihit_ok"]
+        out["trihit_rec_" + m] = res[m]["trihit_rec"].reshape(-1, 17)
+    return out
+
+
 # ---------------------------------------------------------------- whole path
 def make_render(golden_name):
     sc, _, _, _ = load(golden_name)
@@ -306,7 +346,8 @@ def make_render(golden_name):
 
 FIXTURES = {"reference_functions": make_functions,
             "reference_cornell_32x32": lambda: make_render("cornell_32x32_4spp"),
-            "reference_torture_300tri_32x24": lambda: make_render("torture_300tri_32x24_4spp")}
+            "reference_torture_300tri_32x24": lambda: make_render("torture_300tri_32x24_4spp"),
+            "reference_trihit_uv": make_trihit_uv}
 MAX_BYTES = 1 << 20      # of one committed file
 
 

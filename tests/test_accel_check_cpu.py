@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import accel_check
+import uv_scenes
 from elevenrender_amd import abi, scenes
 
 
@@ -72,12 +73,17 @@ def flat_grid(g=37):
                          hdri=scenes.sky_hdri(32, 16), camera=cam, x_res=32, y_res=24)
 
 
+def varied_soup(n):
+    """per-triangle uvs and tangent signs (tests/uv_scenes.py): r_attr and r_sign can tell one triangle's record from another's"""
+    return uv_scenes.varied(small_soup(n), 29)
+
+
 def empty_scene():
     return abi.SceneData(None, None, None, None, None, None, [abi.default_material()], x_res=8, y_res=8)
 
 
 SPECIAL = {"cornell": lambda: scenes.cornell(32, 24), "same-centroid": same_centroid, "duplicates": duplicates, "clusters": clusters,
-           "translated": translated_soup, "flat-grid": flat_grid}
+           "translated": translated_soup, "flat-grid": flat_grid, "varied-257": lambda: varied_soup(257), "varied-6000": lambda: varied_soup(6000)}
 
 
 def host_dump(sc, threads=0):

@@ -19,7 +19,7 @@ BUILDERS = {"host": abi.FLAG_HOST_BUILD, "device": abi.FLAG_GPU_BUILD, "default"
 # soups: one 256-thread block and less (3, 64), one triangle over a block (257), the global-atomic and the per-wave-LDS binning of k_sah_bin
 # at several widths, triangle counts that are no multiple of 64 (20001), the default builder's threshold (20000) from above
 CASES = ["soup-3", "soup-64", "soup-257", "soup-6000", "soup-20001", "soup-30000", "torture", "blobs",
-         "same-centroid", "duplicates", "clusters", "translated", "flat-grid"]
+         "same-centroid", "duplicates", "clusters", "translated", "flat-grid", "varied-257", "varied-6000"]
 ASSERT_BUILDER_FROM = 6000        # tests/test_gpu_build.py asserts accel_info()["builder"] from this size up
 
 
@@ -27,7 +27,7 @@ ASSERT_BUILDER_FROM = 6000        # tests/test_gpu_build.py asserts accel_info()
 def scene(case):
     if case.startswith("soup-"):
         return small_soup(int(case[5:]))
-    if case == "torture":       # materials, uvs and tangents that are not constant
+    if case == "torture":       # materials and tangents that are not constant (uvs and signs that are not: the "varied" cases)
         return scenes.torture(6000, 32, 24, seed=6, n_materials=8, tex_size=16, hdri_size=(32, 16))
     if case == "blobs":
         return scenes.blob_instances(n_instances=30, tris_per_blob=300, x_res=32, y_res=24, grid=(5, 3, 2), spacing=0.45)

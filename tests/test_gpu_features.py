@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import oracle as orc
+import uv_scenes
 from elevenrender_amd import abi, client, render, scenes
 from test_gpu_denoise import atrous_numpy
 from test_gpu_update import assert_same_outputs, edit_J, moved_camera, outputs, with_arrays
@@ -43,6 +44,8 @@ def scene(name):
         sc.materials[1] = abi.default_material(albedo=(0.3, 0.6, 0.2), roughness_tex=4, metallic_tex=5)
         sc._desc = None
         return sc
+    if name in uv_scenes.KINDS:     # varied, tiled and negative uvs on a frame of 48 x 32: the fused and the plain albedo fetch outside [0, 1]^2
+        return uv_scenes.tiled(name, 48, 32)
     if name == "torture-filter":
         return scenes.torture(4000, 70, 45, n_materials=8, tex_size=32)
     raise KeyError(name)
@@ -113,10 +116,10 @@ def planes_numpy(name, n):
 
 
 @pytest.mark.parametrize("builder", list(BUILDERS))
-@pytest.mark.parametrize("name", ["torture-600", "torture-4000"])
+@pytest.mark.parametrize("name", ["torture-600", "torture-4000"] + list(uv_scenes.KINDS))
 def test_planes_equal_the_replay_from_the_oracles_entry_points(name, builder):
     sc = scene(name)
-    if name == "torture-4000":
+    if name == "torture-4000" or name in uv_scenes.KINDS:
         assert oracle_samples(name)[3] == {"constant", "bilinear", "unfiltered"}
     rm = render.RenderingManager(render.RenderParameters(max_bounces=1, flags=BUILDERS[builder]))
     rm.start_rendering(sc)

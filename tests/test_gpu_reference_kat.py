@@ -70,6 +70,30 @@ def test_tri_hit_records(rm, fx):
     assert ok.all(), first_bad(ok)
 
 
+def test_tri_hit_records_with_varied_uvs_and_signs():
+    """reference_trihit_uv.npz: the reference's Tri::hit on per-triangle uvs (mirrored, several periods wide, negative) and tangent
+    signs of both kinds -- full_hit's uv interpolation and its signed bitangent (csrc/er_device.h) against src/Tri.h:76,136 itself"""
+    import copy
+    z = np.load(os.path.join(GOLDEN_DIR, "reference_trihit_uv.npz"), allow_pickle=False)
+    sc = copy.copy(load(TRACE_SCENE)[0])
+    sc._desc = None
+    for k in ("vertices", "normals", "tangents", "uvs", "tangent_sign"):
+        a = np.ascontiguousarray(z["rig_" + k])
+        assert a.shape == getattr(sc, k).shape, k
+        setattr(sc, k, a)
+    m = render.RenderingManager(render.RenderParameters(max_bounces=5))
+    m.start_rendering(sc)
+    try:
+        out = m.debug_eval(FN["TRI_HIT"], z["trihit_items"], 18)
+    finally:
+        m.close()
+    hit = z["trihit_ok_er"] == 1
+    assert ((out[:, 0] == 1.0) == hit).all(), first_bad((out[:, 0] == 1.0) == hit)
+    ok = same(out[hit, 1:], z["trihit_rec_er"][hit]).all(1)
+    assert ok.all(), (first_bad(ok), out[hit][~ok][:2], z["trihit_rec_er"][hit][~ok][:2])
+    assert hit.sum() > len(hit) // 2
+
+
 def test_disney_eval_pdf_sample(rm, fx):
     it = fx["disney_items"]
     for kind, items, ref in (("DISNEY_EVAL", it, fx["disney_eval_er"]), ("DISNEY_PDF", it, fx["disney_pdf_er"].reshape(-1, 1)),

@@ -108,6 +108,35 @@ def test_tri_hit_records(oracle_mod, fx, rig):
     assert len(items) // 2 < hit.sum() < len(items)        # hits and misses both
 
 
+def test_tri_hit_records_with_varied_uvs_and_signs(oracle_mod):
+    """reference_trihit_uv.npz: the reference's Tri::hit where uv0 + (uv1 - uv0) * u + (uv2 - uv0) * v (src/Tri.h:76) rounds and
+    tangentsSign (src/Tri.h:136) is -1 on half of the triangles -- under the unit triangle's uvs every partial sum above is exact"""
+    z = np.load(os.path.join(GOLDEN_DIR, "reference_trihit_uv.npz"), allow_pickle=False)
+    L = oracle_mod.lib()
+    items = z["trihit_items"]
+    tri = items[:, 0].copy().view(np.int32)
+    V, N, T, U, S = (np.ascontiguousarray(z["rig_" + k]).reshape(len(z["rig_tangent_sign"]), -1) for k in gen.TRI_ARRAYS)
+    sc = gen.trihit_uv_scene()      # the recorded inputs are what the generator makes today (the rays follow from them)
+    for k, a in zip(gen.TRI_ARRAYS, (V, N, T, U, S)):
+        assert a.tobytes() == getattr(sc, k).tobytes(), k
+    assert len(items) == gen.TRIHIT_UV_RAYS and set(np.unique(S).tolist()) == {-1.0, 1.0} and (U.reshape(-1, 3, 2) != [[0, 0], [1, 0], [0, 1]]).any((1, 2)).mean() > 0.99
+    okf = np.zeros(len(items), np.int32)
+    rec = np.zeros((len(items), 17), np.float32)
+    for k in range(len(items)):
+        t = int(tri[k])
+        okf[k] = L.oracle_tri_hit(fp(V[t]), fp(N[t]), fp(T[t]), fp(U[t]), float(S[t, 0]), fp(np.ascontiguousarray(items[k, 1:4])),
+                                  fp(np.ascontiguousarray(items[k, 4:7])), fp(rec[k]))
+    for m in MODES:
+        assert (okf == z["trihit_ok_" + m]).all(), (m, first_bad(okf == z["trihit_ok_" + m]))
+        hit = okf == 1
+        ok = same(rec[hit], z["trihit_rec_" + m][hit]).all(1)
+        assert ok.all(), (m, first_bad(ok))
+    assert len(items) // 2 < hit.sum() < len(items)
+    assert (S[tri[hit], 0] < 0).sum() > 200 and (S[tri[hit], 0] > 0).sum() > 200
+    uv = rec[hit, 15:17]
+    assert ((uv < 0) | (uv > 1)).any(1).mean() > 0.5 and (np.abs(uv) > 900).any()      # outside the unit square; the far tile
+
+
 @pytest.mark.parametrize("m", MODES)
 def test_closest_hit_of_throw_ray(oracle_mod, fx, m):
     sc, _, _, _ = load(gen.TRACE_SCENE)
