@@ -568,6 +568,7 @@ SYMBOLS = {
     "er_debug_trace_rays": (C.c_int, [_P, _FP, _FP, C.c_uint32, _IP, _FP, _IP, _IP, _FP, _FP, _IP]),
     "er_debug_trace_pixel": (C.c_int, [_P, C.c_uint32, C.POINTER(ErTraceRec), C.c_int, C.POINTER(C.c_int)]),
     "er_debug_read_light_table": (C.c_int, [_P, _IP, _FP, C.c_uint32]),
+    "er_debug_read_light_table_prob": (C.c_int, [_P, _IP, _FP, _FP, C.c_uint32]),
     "er_debug_read_hdri_trig": (C.c_int, [_P, _UP, C.c_uint32, _UP, C.c_uint32]),
     "er_debug_hdri_trig_host": (C.c_int, [C.c_int32, C.c_int32, _UP, _UP]),
     "er_debug_set_host_alloc_limit": (None, [C.c_uint64]),

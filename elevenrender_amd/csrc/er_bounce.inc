@@ -16,7 +16,8 @@
 //   uint32_t rs         the pixel's RNG state
 //   F3       light, reduction;  uint32_t bounce      the path state of src/kernel.cpp:496-506
 //   float    prev_pdf   ER_FLAG_MIS / ER_FLAG_MESH_LIGHTS: brdfpdf of the last opaque bounce, < 0 before the first one (read only if EXT)
-//   float    mesh_d     ER_FLAG_MESH_LIGHTS: distance from the last opaque bounce to ray.o (read and written only if ER_BOUNCE_MESH)
+//   float    mesh_d     ER_FLAG_MESH_LIGHTS: distance from the last opaque bounce to ray.o, < 0 once the ray has gone through a hit that failed its
+//                       opacity draw (read and written only if ER_BOUNCE_MESH)
 //   bool     done       set when the path ends with this step (left the scene, or the bounce limit is reached)
 //   bool     pending, lpending   set when an HDRI / a point-light shadow query was handed to the hooks
 //   unsigned c_shaded, c_texels, c_hdri   counters
@@ -141,8 +142,9 @@
             float er_wnee = 1.0f;
             if (er_mis) er_wnee = 1.0f / (1.0f + DisneyPdf(hd, wo, N, wihdri) / hdripdf);   // balance heuristic, NEE direction
             F3 er_em = hd.emission;
-            if (er_mesh && prev_pdf >= 0.0f) {
-                // emission found by a BRDF-sampled ray: balance heuristic against the emitter sample (rule 7)
+            if (er_mesh && prev_pdf >= 0.0f && mesh_d >= 0.0f) {
+                // emission found by a BRDF-sampled ray: balance heuristic against the emitter sample (rule 7); weight 1 after an opacity
+                // pass-through, a connection the emitter sample never makes (its shadow ray treats every triangle as opaque)
                 const float er_ph = mesh_prob(S)[hslot];
                 if (er_ph > 0.0f) {
                     F3 er_a, er_b, er_c, er_ng;
@@ -248,7 +250,7 @@
             if (bounce == 0) { ER_BOUNCE_FIRST_HIT(hd.normal, hd.tangent, hd.bitangent); }
             if (er_mesh) mesh_d = 0.001f;          // (the new ray leaves 0.001 away from the bounce)
         } else {
-            if (er_mesh) mesh_d = mesh_d + length(hit.position - ray.o) + 0.001f;      // an opacity pass-through: the segment and the offset
+            if (er_mesh) mesh_d = -1.0f;           // an opacity pass-through: no emitter sample reaches what this ray finds (rule 7)
             ray = make_ray(hit.position + ray.d * 0.001f, ray.d);
         }
         ER_TP(6);

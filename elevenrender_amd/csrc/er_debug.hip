@@ -254,6 +254,12 @@ __global__ __launch_bounds__(64) void er_debug_eval_kernel(DevScene S, int kind,
                  : op == 4 ? ermath::er_pow(x, y) : ermath::er_atan2(x, y);
             break;
         }
+        case ER_FN_MESH_PICK: {      // (the host refuses this kind without a table)
+            const uint32_t k = mesh_pick(S, a[0]);
+            o[0] = fbits(k);
+            o[1] = fbits(__builtin_bit_cast(uint32_t, S.tri_isect[(size_t)mesh_slot(S, k) * 3].w));
+            break;
+        }
         default: break;
     }
 }

@@ -383,7 +383,7 @@ static int er_debug_trace_pixel_impl(ErScene* s, uint32_t idx, ErTraceRec* recs,
     return ER_OK;
 }
 
-static int er_debug_read_light_table_impl(ErScene* s, int32_t* tri_index, float* cdf, uint32_t cap) {
+static int er_debug_read_light_table_impl(ErScene* s, int32_t* tri_index, float* cdf, float* prob, uint32_t cap) {
     if (!s) return fail(ER_ERR_INVALID_ARG, "er_debug_read_light_table: NULL scene");
     std::lock_guard<std::mutex> lk(s->mtx);
     if (!s->begun) return fail(ER_ERR_STATE, "er_debug_read_light_table: er_render_begin has not succeeded");
@@ -395,8 +395,11 @@ static int er_debug_read_light_table_impl(ErScene* s, int32_t* tri_index, float*
     int rc;
     if ((rc = upload(d_tri, (const int32_t*)nullptr, m, s->stream)) != ER_OK) return rc;
     if ((rc = upload(d_cdf, (const float*)nullptr, m, s->stream)) != ER_OK) return rc;
-    er_launch_light_table_read(s->dev.tri_isect, s->d_light_tab.p, s->tri_count, s->light_emitters, m, d_tri.p, d_cdf.p, s->stream);
+    ScopedDevBuf<float> d_prob;
+    if (prob && (rc = upload(d_prob, (const float*)nullptr, m, s->stream)) != ER_OK) return rc;
+    er_launch_light_table_read(s->dev.tri_isect, s->d_light_tab.p, s->tri_count, s->light_emitters, m, d_tri.p, d_cdf.p, prob ? d_prob.p : nullptr, s->stream);
     HIP_TRY(hipGetLastError());
+    if (prob) HIP_TRY(hipMemcpyAsync(prob, d_prob.p, sizeof(float) * m, hipMemcpyDeviceToHost, s->stream));
     if (tri_index) HIP_TRY(hipMemcpyAsync(tri_index, d_tri.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, s->stream));
     if (cdf) HIP_TRY(hipMemcpyAsync(cdf, d_cdf.p, sizeof(float) * m, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -427,13 +430,15 @@ static int er_debug_hdri_trig_host_impl(int32_t width, int32_t height, uint32_t*
 }
 
 static int er_debug_eval_impl(ErScene* s, int kind, const float* in, uint32_t n, uint32_t in_stride, float* out, uint32_t out_stride) {
-    static const uint32_t need_in[ER_FN_COUNT] = {1, 7, 7, 29, 29, 29, 3, 2, 4, 1, 2, 3};
-    static const uint32_t need_out[ER_FN_COUNT] = {32, 6, 18, 3, 1, 3, 2, 3, 3, 1, 1, 1};
+    static const uint32_t need_in[ER_FN_COUNT] = {1, 7, 7, 29, 29, 29, 3, 2, 4, 1, 2, 3, 1};
+    static const uint32_t need_out[ER_FN_COUNT] = {32, 6, 18, 3, 1, 3, 2, 3, 3, 1, 1, 1, 2};
     if (!s || !in || !out) return fail(ER_ERR_INVALID_ARG, "er_debug_eval: NULL argument");
     if (kind < 0 || kind >= ER_FN_COUNT) return fail(ER_ERR_INVALID_ARG, "er_debug_eval: unknown kind");
     if (in_stride < need_in[kind] || out_stride < need_out[kind]) return fail(ER_ERR_INVALID_ARG, "er_debug_eval: stride smaller than the kind's item");
     std::lock_guard<std::mutex> lk(s->mtx);
     if (!s->begun) return fail(ER_ERR_STATE, "er_debug_eval: er_render_begin has not succeeded");
+    if (kind == ER_FN_MESH_PICK && ((s->dev.ext_flags & ER_FLAG_MESH_LIGHTS) == 0 || s->light_emitters == 0))
+        return fail(ER_ERR_STATE, "er_debug_eval: ER_FN_MESH_PICK needs a render begun with ER_FLAG_MESH_LIGHTS and a non-empty emitter table");
     if (kind == ER_FN_TEXTURE)
         for (uint32_t i = 0; i < n; i++) {
             int32_t id;
@@ -566,7 +571,10 @@ int er_debug_trace_pixel(ErScene* s, uint32_t idx, ErTraceRec* recs, int max_rec
     return guarded("er_debug_trace_pixel", [&]() -> int { return er_debug_trace_pixel_impl(s, idx, recs, max_recs, count); });
 }
 int er_debug_read_light_table(ErScene* s, int32_t* tri_index, float* cdf, uint32_t cap) {
-    return guarded("er_debug_read_light_table", [&]() -> int { return er_debug_read_light_table_impl(s, tri_index, cdf, cap); });
+    return guarded("er_debug_read_light_table", [&]() -> int { return er_debug_read_light_table_impl(s, tri_index, cdf, nullptr, cap); });
+}
+int er_debug_read_light_table_prob(ErScene* s, int32_t* tri_index, float* cdf, float* prob, uint32_t cap) {
+    return guarded("er_debug_read_light_table_prob", [&]() -> int { return er_debug_read_light_table_impl(s, tri_index, cdf, prob, cap); });
 }
 int er_debug_read_hdri_trig(ErScene* s, uint32_t* cols, uint32_t col_cap, uint32_t* rows, uint32_t row_cap) {
     return guarded("er_debug_read_hdri_trig", [&]() -> int { return er_debug_read_hdri_trig_impl(s, cols, col_cap, rows, row_cap); });

@@ -22,6 +22,6 @@ hipError_t er_lights_build(const float4* isect, const float4* attr, uint32_t tri
                            const float* tex_pool, const int32_t* emission_textures, uint32_t n_etex, uint32_t texture_count,
                            float** table, uint32_t* count, float* total, hipStream_t stream);
 // out[i] <- the input triangle index of the i-th emitter (the builder's permutation is in the triangle records), cdf_out[i] <- its CDF
-// entry, for i < min(count, cap)
+// entry, prob_out[i] (may be NULL) <- P at its slot, for i < min(count, cap)
 void er_launch_light_table_read(const float4* isect, const float* table, uint32_t tri_count, uint32_t count, uint32_t cap,
-                                int32_t* out, float* cdf_out, hipStream_t stream);
+                                int32_t* out, float* cdf_out, float* prob_out, hipStream_t stream);

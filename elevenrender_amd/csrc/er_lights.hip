@@ -10,7 +10,7 @@
 //      emitters come out in ascending slot order (the leaf order of the traversal);
 //   5. the CDF over the compacted weights and P = w / W per slot.
 //
-// Float arithmetic, in this exact order (tests/test_gpu_mesh_lights.py replays it):
+// Float arithmetic, in this exact order (tests/mesh_light_scenes.py replays it for tests/test_gpu_mesh_lights.py, and so does the oracle):
 //   lum(r, g, b) = (0.2126f * r + 0.7152f * g) + 0.0722f * b, no fused multiply-add (the Makefile's -ffp-contract=off);
 //   texel values as tex_coords reads them: one channel c -> (c, c, c), two -> (r, g, 0), three or more -> the first three;
 //   texture mean: thread t of 256 sums the luminances of texels t, t + 256, t + 512, ... in ascending order starting from 0.0f; the
@@ -151,12 +151,15 @@ __global__ __launch_bounds__(256) void er_lights_prob_kernel(const float* __rest
 }
 
 __global__ __launch_bounds__(256) void er_lights_read_kernel(const float4* __restrict__ isect, const float* __restrict__ table, uint32_t tri_count,
-                                                             uint32_t count, uint32_t m, int32_t* __restrict__ out, float* __restrict__ cdf_out) {
+                                                             uint32_t count, uint32_t m, int32_t* __restrict__ out, float* __restrict__ cdf_out,
+                                                             float* __restrict__ prob_out) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= m) return;
     const uint32_t slot = __builtin_bit_cast(uint32_t, table[(size_t)tri_count + count + i]);
-    out[i] = __builtin_bit_cast(int32_t, isect[(size_t)slot * 3].w);
+    // (a slot that is none -- a table that a defect left unwritten -- is reported as triangle -1 and P NaN, not followed)
+    out[i] = slot < tri_count ? __builtin_bit_cast(int32_t, isect[(size_t)slot * 3].w) : -1;
     cdf_out[i] = table[(size_t)tri_count + i];
+    if (prob_out) prob_out[i] = slot < tri_count ? table[slot] : __builtin_nanf("");      // (P at the emitter's slot, what mesh_prob reads)
 }
 
 }  // namespace
@@ -206,8 +209,8 @@ hipError_t er_lights_build(const float4* isect, const float4* attr, uint32_t tri
 }
 
 void er_launch_light_table_read(const float4* isect, const float* table, uint32_t tri_count, uint32_t count, uint32_t cap,
-                                int32_t* out, float* cdf_out, hipStream_t stream) {
+                                int32_t* out, float* cdf_out, float* prob_out, hipStream_t stream) {
     const uint32_t m = count < cap ? count : cap;
     if (m == 0 || !table) return;
-    hipLaunchKernelGGL(er_lights_read_kernel, dim3((m + 255u) / 256u), dim3(256), 0, stream, isect, table, tri_count, count, m, out, cdf_out);
+    hipLaunchKernelGGL(er_lights_read_kernel, dim3((m + 255u) / 256u), dim3(256), 0, stream, isect, table, tri_count, count, m, out, cdf_out, prob_out);
 }

@@ -77,17 +77,22 @@
 //            term, as the point-light term is.
 //         7. Emission found by a BRDF-sampled ray: the hd.emission term of c_vis / c_occ is multiplied by w_bsdf = 1 / (1 +
 //            p_L(hit) / prev_pdf), p_L(hit) with the hit triangle's P, area and cos_l and the distance from the last opaque bounce
-//            (the segments of opacity pass-throughs in between summed: path state `mesh_d`, the distance from that bounce to the
-//            current ray's origin, kept in ray_o.w of the wavefront and streaming records).  Weight 1 for camera rays, for paths
-//            without an opaque bounce yet and for triangles not in the table.  prev_pdf is carried whenever the table is non-empty.
+//            (path state `mesh_d`, the distance from that bounce to the current ray's origin, kept in ray_o.w of the wavefront and
+//            streaming records).  Weight 1 for camera rays, for paths without an opaque bounce yet, for triangles not in the table,
+//            and for a ray that has gone through a hit that failed its opacity draw since the last opaque bounce (mesh_d < 0 marks
+//            it): the emitter sample's shadow ray treats every triangle as opaque, so it never makes a connection through a cut-out
+//            and the BRDF-sampled ray carries that light alone.  (Until this was tested on a scene with cut-outs the weight was
+//            applied there too, with the segments summed, and lost that light's w_nee share: DESIGN.md 3c.)  prev_pdf is carried
+//            whenever the table is non-empty.
 //         8. ER_FLAG_MIS (the HDRI weights) is independent of this flag.  A scene with an empty table renders exactly as without the
 //            flag (the MESH = false instances run).  ER_FLAG_POINT_LIGHTS with this flag on a scene that has point lights and
 //            emitters: er_render_begin returns ER_ERR_INVALID_ARG (both would need the one light-query record per slot).
 //       Like the HDRI's next-event estimate, the shadow ray treats every triangle as opaque.
-//   Parity for the extensions is UNPINNED by construction (the reference defines no result); the oracle mirrors the first two
-//   operation for operation (oracle/er_oracle.cpp) and the GPU tests require bit-equality with it.  The oracle does not mirror
-//   ER_FLAG_MESH_LIGHTS: tests/test_gpu_mesh_lights.py replays its table in numpy and checks the schedules against each other and
-//   the estimator's mean against the render without it.
+//   Parity for the extensions is UNPINNED by construction (the reference defines no result); the oracle mirrors all three
+//   operation for operation (oracle/er_oracle.cpp) and the GPU tests require bit-equality with it.  For ER_FLAG_MESH_LIGHTS the oracle
+//   takes the emitter order from the device (oracle_set_emitters), builds the table itself and answers the emitter shadow query by
+//   brute force (tests/test_gpu_mesh_light_parity.py); tests/test_gpu_mesh_lights.py replays the table in numpy float32 bit for bit and
+//   checks the schedules against each other and the estimator's mean against the render without the flag.
 #pragma once
 #include "er_device.h"
 #include "er_hdri_trig.h"

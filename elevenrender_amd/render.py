@@ -425,14 +425,19 @@ class RenderingManager:
         abi.check(self.lib.er_light_info(self.handle, C.byref(li)))
         return {n: getattr(li, n) for n, _ in abi.ErLightInfo._fields_}
 
-    def debug_light_table(self):
-        """include/eleven_hip_debug.h er_debug_read_light_table: (input triangle index int32[n], cdf float32[n]) of the emitter table."""
+    def debug_light_table(self, prob=False):
+        """include/eleven_hip_debug.h er_debug_read_light_table: (input triangle index int32[n], cdf float32[n]) of the emitter table;
+        with prob=True (er_debug_read_light_table_prob) a third array, P float32[n]: the table's value at each emitter's triangle slot."""
         n = self.light_info()["emitters"]
         tri = np.zeros(n, np.int32)
         cdf = np.zeros(n, np.float32)
-        if n:
-            abi.check(self.lib.er_debug_read_light_table(self.handle, tri.ctypes.data_as(C.POINTER(C.c_int32)), cdf.ctypes.data_as(C.POINTER(C.c_float)), n))
-        return tri, cdf
+        p = np.zeros(n, np.float32)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        if n and prob:
+            abi.check(self.lib.er_debug_read_light_table_prob(self.handle, tri.ctypes.data_as(C.POINTER(C.c_int32)), fp(cdf), fp(p), n))
+        elif n:
+            abi.check(self.lib.er_debug_read_light_table(self.handle, tri.ctypes.data_as(C.POINTER(C.c_int32)), fp(cdf), n))
+        return (tri, cdf, p) if prob else (tri, cdf)
 
     def debug_hdri_trig(self, width, height):
         """include/eleven_hip_debug.h er_debug_read_hdri_trig: (cols uint32[width, 4], rows uint32[height, 6]) of the begun scene's

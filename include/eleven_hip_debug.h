@@ -97,8 +97,8 @@ int er_debug_closest_hit(struct ErScene* scene, const float* origins, const floa
 int er_debug_trace_rays(struct ErScene* scene, const float* origins, const float* dirs, uint32_t n, const int32_t* self_slots,
                         const float* limits, int32_t* tri_ids, int32_t* slots, float* positions, float* distances, int32_t* info);
 
-/* One record per executed bounce-loop iteration (reference src/kernel.cpp:508-592); same layout as the oracle's
- * OracleTraceRec (oracle/er_oracle.h). */
+/* One record per executed bounce-loop iteration (reference src/kernel.cpp:508-592); the same fields, in the same order, as the oracle's
+ * OracleTraceRec begins with (oracle/er_oracle.h; the oracle's record goes on with fields of its own). */
 typedef struct ErTraceRec {
     int32_t bounce;
     int32_t tri;            /* ORIGINAL triangle id of the closest hit, -1 = miss */
@@ -121,6 +121,9 @@ int er_debug_trace_pixel(struct ErScene* scene, uint32_t idx, ErTraceRec* recs, 
  * order (ascending triangle slot), the emitter's INPUT triangle index (ErSceneDesc order, mapped back through the BVH builder's
  * permutation) and its CDF entry.  Either output may be NULL.  Before er_render_begin: ER_ERR_STATE. */
 int er_debug_read_light_table(struct ErScene* scene, int32_t* tri_index, float* cdf, uint32_t cap);
+/* The same, and in `prob` P of each entry: the value the table holds at the emitter's triangle slot (w / W), which the shading step
+ * reads for p_L of an emitter sample and of a BRDF-sampled hit (csrc/er_shade.h rules 5 and 7).  Any output may be NULL. */
+int er_debug_read_light_table_prob(struct ErScene* scene, int32_t* tri_index, float* cdf, float* prob, uint32_t cap);
 
 /* The row and column tables of the HDRI's next-event sample directions (csrc/er_hdri_trig.h), copied as they lie on the device:
  * `cols` receives 4 words per column -- px, pz, bits(ix), iu --, `rows` 6 words per row -- py, a, bits(iy), sin_pdf, iv, sin_row --
@@ -153,9 +156,12 @@ int er_debug_hdri_trig_host(int32_t width, int32_t height, uint32_t* cols, uint3
  *                        begin the render with ER_TEX_COMPACT=0 in the environment to evaluate such a texture)
  *   ER_FN_HDRI_SEARCH    in [value]                                    out [bits(index)]                          (1)
  *   ER_FN_HDRI_PDF       in [bits(x), bits(y)]                         out [pdf]                                  (1)
- *   ER_FN_MATH           in [bits(op: 0 sin 1 cos 2 acos 3 log 4 pow 5 atan2), x, y]   out [value]                (1) */
+ *   ER_FN_MATH           in [bits(op: 0 sin 1 cos 2 acos 3 log 4 pow 5 atan2), x, y]   out [value]                (1)
+ *   ER_FN_MESH_PICK      in [r]                                        out [bits(table index), bits(input triangle)] (2)
+ *                        (mesh_pick and mesh_slot of csrc/er_shade.h on the begun scene's emitter table; ER_ERR_STATE unless the
+ *                        render was begun with ER_FLAG_MESH_LIGHTS and the table is non-empty) */
 enum { ER_FN_RNG = 0, ER_FN_CAMERA_RAY, ER_FN_TRI_HIT, ER_FN_DISNEY_EVAL, ER_FN_DISNEY_PDF, ER_FN_DISNEY_SAMPLE, ER_FN_SPHERICAL,
-       ER_FN_REV_SPHERICAL, ER_FN_TEXTURE, ER_FN_HDRI_SEARCH, ER_FN_HDRI_PDF, ER_FN_MATH, ER_FN_COUNT };
+       ER_FN_REV_SPHERICAL, ER_FN_TEXTURE, ER_FN_HDRI_SEARCH, ER_FN_HDRI_PDF, ER_FN_MATH, ER_FN_MESH_PICK, ER_FN_COUNT };
 int er_debug_eval(struct ErScene* scene, int kind, const float* in, uint32_t n, uint32_t in_stride, float* out, uint32_t out_stride);
 
 /* Loopback transport for er_gather_pass: `world` communicators that live in ONE process and move the packed buffers

@@ -586,6 +586,13 @@ struct Oracle {
     Hdri hdri;
     RefBVH bvh;
     double build_s = 0;
+    // ER_FLAG_MESH_LIGHTS: the emitter table (rules: elevenrender_amd/csrc/er_shade.h; float order: the header of csrc/er_lights.hip),
+    // built by oracle_set_emitters in the order the caller hands over
+    std::vector<int> mesh_ids;        // table entry -> input triangle
+    std::vector<float> mesh_w;        // its weight
+    std::vector<float> mesh_cdf;      // its CDF entry
+    std::vector<float> mesh_prob;     // per input triangle: w / W, 0 for a triangle without an entry
+    float mesh_total = 0.0f;          // W
     std::vector<float> passes;
     std::vector<uint32_t> samples;
     std::vector<uint32_t> rng;
@@ -731,6 +738,116 @@ struct Oracle {
         }
     }
 
+    // ---- ER_FLAG_MESH_LIGHTS (er_shade.h rules 1-7) ----
+    static float lumf(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
+    // er_lights_tex_mean_kernel: 256 strided partial sums from 0.0f, then the pairwise tree h = 128 .. 1
+    static float texMean(const Tex& t) {
+        const size_t texels = (size_t)t.width * (size_t)t.height;
+        const float* d = t.data.data();
+        float s[256];
+        for (size_t th = 0; th < 256; th++) {
+            float acc = 0.0f;
+            for (size_t i = th; i < texels; i += 256) {
+                float r = 0.0f, g = 0.0f, b = 0.0f;
+                if (t.channels == 1) { r = g = b = d[i]; }
+                else if (t.channels == 2) { r = d[2 * i]; g = d[2 * i + 1]; }
+                else if (t.channels >= 3) { r = d[(size_t)t.channels * i]; g = d[(size_t)t.channels * i + 1]; b = d[(size_t)t.channels * i + 2]; }
+                acc = acc + lumf(r, g, b);
+            }
+            s[th] = acc;
+        }
+        for (size_t h = 128; h >= 1; h >>= 1)
+            for (size_t th = 0; th < h; th++) s[th] = s[th] + s[th + h];
+        return s[0] / (float)texels;
+    }
+    // mesh_tri: c = cross(v1 - v0, v2 - v0), A = 0.5 |c|, n = c / |c|
+    void meshTri(int id, V3& ng, float& area) const {
+        const Tri& T = tris[id];
+        V3 cr = cross(T.v[1] - T.v[0], T.v[2] - T.v[0]);
+        float len = length(cr);
+        area = 0.5f * len;
+        ng = cr / len;
+    }
+    // er_lights_weight_kernel: the weight of a triangle, 0 = no entry
+    float meshWeight(int id, const std::vector<float>& mean) const {
+        const ErMaterial& mat = materials[tris[id].material];
+        float lum = 0.0f;
+        bool emitter = false;
+        if (mat.emission_tex >= 0) { lum = mean[mat.emission_tex]; emitter = true; }
+        else { lum = lumf(mat.emission.x, mat.emission.y, mat.emission.z); emitter = lum > 0.0f; }
+        if (!emitter) return 0.0f;
+        V3 ng; float area;
+        meshTri(id, ng, area);
+        float weight = area * lum;
+        if (!(area > 0.0f) || !(weight > 0.0f)) weight = 0.0f;
+        return weight;
+    }
+    // the table over `ids` in that order; -1 if the list is not exactly the set of triangles with a weight > 0, each once
+    int setEmitters(const int32_t* ids, uint32_t n) {
+        mesh_ids.clear(); mesh_w.clear(); mesh_cdf.clear(); mesh_total = 0.0f;
+        mesh_prob.assign(tris.size(), 0.0f);
+        std::vector<float> mean(textures.size() + 1, 0.0f);
+        for (const ErMaterial& mat : materials)
+            if (mat.emission_tex >= 0 && (size_t)mat.emission_tex < textures.size()) mean[mat.emission_tex] = texMean(textures[mat.emission_tex]);
+        std::vector<float> w(tris.size(), 0.0f);
+        uint32_t own = 0;
+        for (size_t t = 0; t < tris.size(); t++) { w[t] = meshWeight((int)t, mean); own += w[t] > 0.0f; }
+        if (own != n) return -1;
+        std::vector<char> seen(tris.size(), 0);
+        for (uint32_t i = 0; i < n; i++) {
+            if (ids[i] < 0 || (size_t)ids[i] >= tris.size() || seen[ids[i]] || !(w[ids[i]] > 0.0f)) return -1;
+            seen[ids[i]] = 1;
+        }
+        if (n == 0) return 0;
+        mesh_ids.assign(ids, ids + n);
+        mesh_w.resize(n);
+        for (uint32_t i = 0; i < n; i++) mesh_w[i] = w[ids[i]];
+        // er_lights_cdf_kernel: 1024 threads, chunk = ceil(n / 1024), clamped ranges, the serial offsets, cdf_i = run / W
+        mesh_cdf = mesh_w;
+        std::vector<float> s(1025, 0.0f);
+        const uint32_t chunk = (n + 1023u) / 1024u;
+        for (uint32_t t = 0; t < 1024u; t++) {
+            const uint32_t lo = t * chunk < n ? t * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
+            float sum = 0.0f;
+            for (uint32_t i = lo; i < hi; i++) sum = sum + mesh_cdf[i];
+            s[t + 1] = sum;
+        }
+        s[0] = 0.0f;
+        for (uint32_t x = 1; x <= 1024u; x++) s[x] = s[x - 1] + s[x];
+        const float W = s[1024];
+        mesh_total = W;
+        for (uint32_t t = 0; t < 1024u; t++) {
+            const uint32_t lo = t * chunk < n ? t * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
+            float run = s[t];
+            for (uint32_t i = lo; i < hi; i++) { run = run + mesh_cdf[i]; mesh_cdf[i] = run / W; }
+        }
+        for (size_t t = 0; t < tris.size(); t++) mesh_prob[t] = w[t] / W;      // er_lights_prob_kernel
+        return 0;
+    }
+    // mesh_pick: the first k with cdf[k] > r, clamped to n - 1
+    uint32_t meshPick(float r) const {
+        const float* cdf = mesh_cdf.data();
+        const uint32_t n = (uint32_t)mesh_cdf.size();
+        uint32_t lo = 0, hi = n;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (cdf[mid] > r) hi = mid; else lo = mid + 1;
+        }
+        return lo < n ? lo : n - 1;
+    }
+    // rule 3, stated as plainly as it can be: occluded iff some triangle other than k is hit nearer than `limit`, both distances from
+    // the shadow ray's origin, by brute force over all triangles (nothing shared with either traversal)
+    bool meshOccluded(const Ray& sr, int k, float limit, OracleCounters& c) const {
+        c.rays++;
+        for (size_t id = 0; id < tris.size(); id++) {
+            if ((int)id == k) continue;
+            Hit h;
+            c.tri_tests++;
+            if (tri_hit(tris[id], sr, h) && length(h.position - sr.origin) < limit) return true;
+        }
+        return false;
+    }
+
     // kernel.cpp:477-646 ; the literal 5 of :508 is the max_bounces parameter
     void renderingKernel(uint32_t idx, OracleCounters& c, OracleTraceRec* recs, int max_recs, int* nrec) {
         if (idx >= x_res * y_res) return;
@@ -745,14 +862,17 @@ struct Oracle {
         V3 light(0.0f), normal(0.0f), tangent(0.0f), bitangent(0.0f), reduction(1.0f);
         // the two build-defined extensions (rules: elevenrender_amd/csrc/er_shade.h; off = the reference)
         const bool mis = (flags & ER_FLAG_MIS) != 0;
-        const bool use_lights = (flags & ER_FLAG_POINT_LIGHTS) != 0 && !lights.empty();
-        float prev_pdf = -1.0f;     // ER_FLAG_MIS: brdfpdf of the last opaque bounce
+        const bool mesh = (flags & ER_FLAG_MESH_LIGHTS) != 0 && !mesh_ids.empty();     // (an empty table renders as without the flag, rule 8)
+        const bool use_lights = !mesh && (flags & ER_FLAG_POINT_LIGHTS) != 0 && !lights.empty();
+        float prev_pdf = -1.0f;     // ER_FLAG_MIS / ER_FLAG_MESH_LIGHTS: brdfpdf of the last opaque bounce
+        float mesh_d = 0.0f;        // ER_FLAG_MESH_LIGHTS: distance from the last opaque bounce to the ray's origin, < 0 after an opacity pass-through
         for (int i = 0; i < max_bounces; i++) {
             c.bounce_samples++;
             HitData hd;
             Hit nearestHit = throwRay(ray, c);
             OracleTraceRec* rec = (recs && *nrec < max_recs) ? &recs[(*nrec)++] : nullptr;
-            if (rec) { memset(rec, 0, sizeof(*rec)); rec->bounce = i; rec->tri = nearestHit.valid ? nearestHit.tri : -1; rec->shadow_tri = -1; rec->shadow_occ = -1; rec->light_occ = -1; }
+            if (rec) { memset(rec, 0, sizeof(*rec)); rec->bounce = i; rec->tri = nearestHit.valid ? nearestHit.tri : -1; rec->shadow_tri = -1; rec->shadow_occ = -1; rec->light_occ = -1;
+                       rec->mesh_sample = -1; rec->mesh_k = -1; rec->mesh_le_tex = -1; }
             if (!nearestHit.valid) {
                 float u, v;
                 sphericalMapping(m, V3(), -1 * ray.direction, 1, u, v);
@@ -781,6 +901,8 @@ struct Oracle {
                 float d1 = rnd.next(), d2 = rnd.next(), d3 = rnd.next();
                 float rl = 0.0f;
                 if (use_lights) rl = rnd.next();     // the light pick: one extra draw, right after DisneySample's three
+                float mp = 0.0f, mu1 = 0.0f, mu2 = 0.0f;
+                if (mesh) { mp = rnd.next(); mu1 = rnd.next(); mu2 = rnd.next(); }   // rule 2: emitter pick and point, always three
                 V3 wibrdf = DisneySample(m, hd, wo, hd.normal, d1, d2, d3);
                 float nu = textCoordinate.x / (float)hdri.texture.width;
                 float nv = textCoordinate.y / (float)hdri.texture.height;
@@ -795,7 +917,22 @@ struct Oracle {
                 V3 hdriInt = hdriValue * DisneyEval(m, hd, wo, hd.normal, wihdri) * std::fabs(dot(wihdri, hd.normal)) / hdripdf;
                 if (mis) hdriInt = hdriInt * (1.0f / (1.0f + DisneyPdf(m, hd, wo, hd.normal, wihdri) / hdripdf));   // balance heuristic, NEE direction
                 float brdfpdf = DisneyPdf(m, hd, wo, hd.normal, wibrdf);
-                light = light + reduction * (hd.emission + hdriInt);
+                V3 em = hd.emission;
+                if (mesh && prev_pdf >= 0.0f) {
+                    // rule 7: emission found by a BRDF-sampled ray, balance heuristic against the emitter sample
+                    float ph = mesh_prob[nearestHit.tri];
+                    if (ph > 0.0f && !(mesh_d >= 0.0f) && rec) rec->mesh_hit = 2;       // after a pass-through: weight 1
+                    if (ph > 0.0f && mesh_d >= 0.0f) {
+                        V3 ng;
+                        float area;
+                        meshTri(nearestHit.tri, ng, area);
+                        float dh = mesh_d + length(nearestHit.position - ray.origin);
+                        float pl = ph * (dh * dh) / (area * std::fabs(dot(ng, ray.direction)));
+                        em = em * (1.0f / (1.0f + pl / prev_pdf));
+                        if (rec) { rec->mesh_hit = 1; rec->mesh_d = mesh_d; }
+                    }
+                }
+                light = light + reduction * (em + hdriInt);
                 if (use_lights) {
                     // the author's sketch pointLight(), kernel.cpp:269-301
                     int count = (int)lights.size();
@@ -820,13 +957,56 @@ struct Oracle {
                         light = light + reduction * pl;
                     }
                 }
+                if (mesh && !(i + 1 < max_bounces) && rec) rec->mesh_sample = 2;      // rule 6: none at the last bounce
+                if (mesh && i + 1 < max_bounces) {
+                    // an emitter sample (rules 3-6)
+                    const int k = mesh_ids[meshPick(mp)];
+                    if (rec) { rec->mesh_k = k; rec->mesh_sample = 1; }
+                    if (k != nearestHit.tri) {
+                        const Tri& K = tris[k];
+                        V3 ng;
+                        float area;
+                        meshTri(k, ng, area);
+                        float su = std::sqrt(mu1);
+                        float b1 = su * (1.0f - mu2), b2 = su * mu2;
+                        V3 p = K.v[0] * (1.0f - su) + K.v[1] * b1 + K.v[2] * b2;
+                        V3 toL = p - hd.position;
+                        V3 dir = normalized(toL);
+                        float dist = length(toL);
+                        float cosl = dot(ng, dir);
+                        V3 evall = cosl != 0.0f ? DisneyEval(m, hd, wo, hd.normal, dir) : V3(0.0f);
+                        if (rec) rec->mesh_sample = cosl != 0.0f ? 4 : 3;
+                        if (evall.x != 0.0f || evall.y != 0.0f || evall.z != 0.0f) {
+                            // rule 4: Le at p's interpolated uv, times the opacity there clamped to [0, 1]
+                            const ErMaterial& km = materials[K.material];
+                            float tu = K.uvx[0] + (K.uvx[1] - K.uvx[0]) * b1 + (K.uvx[2] - K.uvx[0]) * b2;
+                            float tv = K.uvy[0] + (K.uvy[1] - K.uvy[0]) * b1 + (K.uvy[2] - K.uvy[0]) * b2;
+                            V3 le = km.emission_tex < 0 ? V3(km.emission.x, km.emission.y, km.emission.z)
+                                                        : texFiltered(textures[km.emission_tex], tu, tv, &c.texel_fetches);
+                            float op = km.opacity_tex < 0 ? km.opacity : texFiltered(textures[km.opacity_tex], tu, tv, &c.texel_fetches).x;
+                            le = le * clampf(op, 0.0f, 1.0f);
+                            // rule 5
+                            float lpdf = mesh_prob[k] * (dist * dist) / (area * std::fabs(cosl));
+                            // rule 6
+                            float wl = 1.0f / (1.0f + DisneyPdf(m, hd, wo, hd.normal, dir) / lpdf);
+                            V3 ml = le * evall * std::fabs(dot(dir, hd.normal)) / lpdf * wl;
+                            Ray lr(hd.position + dir * 0.001f, dir);
+                            const bool locc = meshOccluded(lr, k, length(p - lr.origin), c);
+                            if (locc) ml = V3();
+                            if (rec) { rec->light_occ = locc ? 1 : 0; rec->mesh_sample = 0; rec->mesh_le_tex = km.emission_tex; rec->mesh_opacity = op; }
+                            light = light + reduction * ml;
+                        }
+                    }
+                }
                 reduction = reduction * (DisneyEval(m, hd, wo, hd.normal, wibrdf) * std::fabs(dot(wibrdf, hd.normal)) / brdfpdf);
-                if (mis) prev_pdf = brdfpdf;
+                if (mis || mesh) prev_pdf = brdfpdf;
                 if (i == 0) { normal = hd.normal; tangent = hd.tangent; bitangent = hd.bitangent; }
                 ray = Ray(nearestHit.position + wibrdf * 0.001f, wibrdf);
+                if (mesh) mesh_d = 0.001f;          // (the new ray leaves 0.001 away from the bounce)
                 if (rec) { rec->opaque = 1; rec->shadow_tri = shadowHit.valid ? shadowHit.tri : -1;
                            rec->shadow_occ = (shadowHit.valid && shadowHit.triIdx != hd.triIdx) ? 1 : 0; }
             } else {
+                if (mesh) mesh_d = -1.0f;          // an opacity pass-through: no emitter sample reaches what this ray finds (rule 7)
                 ray = Ray(nearestHit.position + ray.direction * 0.001f, ray.direction);
             }
             if (rec) {
@@ -929,6 +1109,20 @@ Oracle* oracle_create(const ErSceneDesc* d, const OracleOpts* opts) {
     return o;
 }
 void oracle_destroy(Oracle* o) { delete o; }
+int oracle_set_emitters(Oracle* o, const int32_t* tri_ids, uint32_t n) { return o->setEmitters(tri_ids, n); }
+uint32_t oracle_read_emitters(const Oracle* o, int32_t* tri_ids, float* weight, float* cdf, float* prob, float* total, uint32_t cap) {
+    const uint32_t n = (uint32_t)o->mesh_ids.size(), mcap = n < cap ? n : cap;
+    for (uint32_t i = 0; i < mcap; i++) {
+        if (tri_ids) tri_ids[i] = o->mesh_ids[i];
+        if (weight) weight[i] = o->mesh_w[i];
+        if (cdf) cdf[i] = o->mesh_cdf[i];
+        if (prob) prob[i] = o->mesh_prob[o->mesh_ids[i]];
+    }
+    if (total) *total = o->mesh_total;
+    return n;
+}
+float oracle_texture_mean_luminance(const ErTexture* tex) { return Oracle::texMean(make_tex(*tex)); }
+uint32_t oracle_mesh_pick(const Oracle* o, float r) { return o->mesh_ids.empty() ? 0xFFFFFFFFu : o->meshPick(r); }
 double oracle_build_seconds(const Oracle* o) { return o->build_s; }
 
 void oracle_render(Oracle* o, uint32_t n_samples, uint32_t idx0, uint32_t idx1) {

@@ -27,8 +27,9 @@ typedef struct OracleOpts {
     int32_t max_bounces;  /* 0 -> 5 (src/kernel.cpp:508) */
     int32_t traversal;    /* 0 = reference BVH (fixed depth 18, src/BVH.cpp), 1 = brute force over all tris */
     int32_t threads;      /* worker threads over pixel rows; <=0 -> 1 */
-    uint32_t flags;       /* ER_FLAG_POINT_LIGHTS | ER_FLAG_MIS: the two build-defined extensions, mirrored operation for
-                             operation from elevenrender_amd/csrc/er_shade.h (the reference defines no result for either) */
+    uint32_t flags;       /* ER_FLAG_POINT_LIGHTS | ER_FLAG_MIS | ER_FLAG_MESH_LIGHTS: the three build-defined extensions, mirrored
+                             operation for operation from elevenrender_amd/csrc/er_shade.h (the reference defines no result for any).
+                             ER_FLAG_MESH_LIGHTS takes effect after oracle_set_emitters has made a non-empty table */
 } OracleOpts;
 
 typedef struct OracleCounters {
@@ -48,13 +49,34 @@ typedef struct OracleTraceRec {
     float light[3];
     float reduction[3];
     int32_t shadow_occ;     /* HDRI shadow query: 1 if shadowHit.valid && shadowHit.triIdx != hitdata.triIdx, 0 if not, -1 not traced */
-    int32_t light_occ;      /* point-light query (extension): 1 occluded, 0 visible, -1 none */
+    int32_t light_occ;      /* point-light / emitter query (extensions): 1 occluded, 0 visible, -1 none */
+    /* ER_FLAG_MESH_LIGHTS, the oracle's own (the library's ErTraceRec ends above): what the bounce did, for counting what a scene exercises */
+    int32_t mesh_sample;    /* -1 no opaque bounce with a table; 0 emitter sample evaluated and its shadow query traced; 1 skipped: k is the
+                               shaded triangle; 2 skipped: the last bounce; 3 skipped: cos_l == 0; 4 skipped: DisneyEval exactly zero */
+    int32_t mesh_k;         /* the picked emitter's input triangle, -1 none */
+    int32_t mesh_le_tex;    /* mesh_sample 0: the texture Le came from, -1 a constant */
+    float mesh_opacity;     /* mesh_sample 0: the opacity at the sampled point BEFORE the clamp */
+    int32_t mesh_hit;       /* a table triangle reached with prev_pdf >= 0 (rule 7): 1 reached directly, its emission weighted by w_bsdf;
+                               2 reached after at least one opacity pass-through, weight 1 */
+    float mesh_d;           /* mesh_hit 1: mesh_d at the hit (0.001f: the ray left that far from the bounce) */
 } OracleTraceRec;
 
 typedef struct Oracle Oracle;
 
 Oracle* oracle_create(const ErSceneDesc* desc, const OracleOpts* opts);
 void oracle_destroy(Oracle* o);
+
+/* ER_FLAG_MESH_LIGHTS: hands the oracle the emitter ORDER -- input triangle ids in the library's table order (ascending triangle slot of
+ * ITS acceleration structure; the oracle's tree has another leaf order, and the order decides which emitter a draw picks).  From it the
+ * oracle builds weights, CDF and P itself, in the float order the header of elevenrender_amd/csrc/er_lights.hip documents.  Returns 0, or
+ * -1 (and an empty table) if the list is not exactly the oracle's own set of emitters, each once.  n = 0: an empty table. */
+int oracle_set_emitters(Oracle* o, const int32_t* tri_ids, uint32_t n);
+/* the table as built: per entry the input triangle, weight, CDF entry and P; *total = W.  Any output may be NULL; returns the entry count. */
+uint32_t oracle_read_emitters(const Oracle* o, int32_t* tri_ids, float* weight, float* cdf, float* prob, float* total, uint32_t cap);
+/* the mean luminance of a texture in the texture-mean kernel's summation order */
+float oracle_texture_mean_luminance(const ErTexture* tex);
+/* mesh_pick on the oracle's table (0xFFFFFFFF for an empty one) */
+uint32_t oracle_mesh_pick(const Oracle* o, float r);
 double oracle_build_seconds(const Oracle* o);
 
 /* n_samples calls of renderingKernel for every pixel idx in [idx0, idx1) (idx1 = 0 -> all). */

@@ -30,7 +30,10 @@ class OracleCounters(C.Structure):
 class OracleTraceRec(C.Structure):
     _fields_ = [("bounce", C.c_int32), ("tri", C.c_int32), ("shadow_tri", C.c_int32), ("opaque", C.c_int32),
                 ("position", C.c_float * 3), ("wi", C.c_float * 3), ("light", C.c_float * 3), ("reduction", C.c_float * 3),
-                ("shadow_occ", C.c_int32), ("light_occ", C.c_int32)]
+                ("shadow_occ", C.c_int32), ("light_occ", C.c_int32),
+                # ER_FLAG_MESH_LIGHTS, the oracle's own (er_oracle.h)
+                ("mesh_sample", C.c_int32), ("mesh_k", C.c_int32), ("mesh_le_tex", C.c_int32), ("mesh_opacity", C.c_float),
+                ("mesh_hit", C.c_int32), ("mesh_d", C.c_float)]
 
 
 MATH_LIBM, MATH_ER = 0, 1
@@ -54,6 +57,14 @@ def lib():
     L.oracle_create.restype = C.c_void_p
     L.oracle_create.argtypes = [C.POINTER(abi.ErSceneDesc), C.POINTER(OracleOpts)]
     L.oracle_destroy.argtypes = [C.c_void_p]
+    L.oracle_set_emitters.restype = C.c_int
+    L.oracle_set_emitters.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_uint32]
+    L.oracle_read_emitters.restype = C.c_uint32
+    L.oracle_read_emitters.argtypes = [C.c_void_p, C.POINTER(C.c_int32), _FP, _FP, _FP, _FP, C.c_uint32]
+    L.oracle_texture_mean_luminance.restype = C.c_float
+    L.oracle_texture_mean_luminance.argtypes = [C.POINTER(abi.ErTexture)]
+    L.oracle_mesh_pick.restype = C.c_uint32
+    L.oracle_mesh_pick.argtypes = [C.c_void_p, C.c_float]
     L.oracle_build_seconds.restype = C.c_double
     L.oracle_build_seconds.argtypes = [C.c_void_p]
     L.oracle_render.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
@@ -102,7 +113,7 @@ class Oracle:
     def __init__(self, scene, math_mode=MATH_ER, max_bounces=5, traversal=TRAV_REFERENCE_BVH, threads=1, flags=0):
         self.scene = scene
         self.L = lib()
-        opts = OracleOpts(math_mode, max_bounces, traversal, threads, flags & (abi.FLAG_POINT_LIGHTS | abi.FLAG_MIS))
+        opts = OracleOpts(math_mode, max_bounces, traversal, threads, flags & (abi.FLAG_POINT_LIGHTS | abi.FLAG_MIS | abi.FLAG_MESH_LIGHTS))
         self.h = self.L.oracle_create(C.byref(scene.desc()), C.byref(opts))
         self.npx = scene.x_res * scene.y_res
 
@@ -116,6 +127,26 @@ class Oracle:
             self.close()
         except Exception:
             pass
+
+    def set_emitters(self, tri_ids):
+        """ER_FLAG_MESH_LIGHTS: the emitter order -- input triangle ids in the library's table order (render.debug_light_table()[0]).
+        The oracle builds weights, CDF and P from it; it refuses a list that is not exactly its own set of emitters."""
+        ids = np.ascontiguousarray(tri_ids, np.int32)
+        rc = self.L.oracle_set_emitters(self.h, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids))
+        if rc != 0:
+            raise ValueError("oracle_set_emitters: the list is not the oracle's own set of emitters, each once")
+
+    def emitters(self):
+        """the oracle's table: dict of tri int32[n], weight, cdf, prob float32[n] and total (W)"""
+        n = self.L.oracle_read_emitters(self.h, None, None, None, None, None, 0)
+        tri = np.zeros(n, np.int32)
+        w, cdf, prob = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+        total = C.c_float(0.0)
+        self.L.oracle_read_emitters(self.h, tri.ctypes.data_as(C.POINTER(C.c_int32)), fp(w), fp(cdf), fp(prob), C.byref(total), n)
+        return dict(tri=tri, weight=w, cdf=cdf, prob=prob, total=np.float32(total.value))
+
+    def mesh_pick(self, r):
+        return int(self.L.oracle_mesh_pick(self.h, float(r)))
 
     @property
     def build_seconds(self):

@@ -15,7 +15,7 @@ from elevenrender_amd import abi, render, scenes
 pytestmark = pytest.mark.gpu
 
 FN = dict(RNG=0, CAMERA_RAY=1, TRI_HIT=2, DISNEY_EVAL=3, DISNEY_PDF=4, DISNEY_SAMPLE=5, SPHERICAL=6, REV_SPHERICAL=7,
-          TEXTURE=8, HDRI_SEARCH=9, HDRI_PDF=10, MATH=11)
+          TEXTURE=8, HDRI_SEARCH=9, HDRI_PDF=10, MATH=11, MESH_PICK=12)
 
 
 def ibits(v):
@@ -242,3 +242,30 @@ def test_texture_fetch_refuses_entries_the_library_keeps_compacted(oracle_mod):
         assert np.isfinite(rm.debug_eval(FN["TEXTURE"], item(-1), 3)).all()
     finally:
         rm.close()
+
+
+@pytest.mark.parametrize("n_tris,share", [(1, "all"), (2049, "all"), (3000, 1 / 97)], ids=["1", "2049", "3000-97th"])
+def test_mesh_pick_known_answers(n_tris, share):
+    """mesh_pick and mesh_slot of csrc/er_shade.h (ER_FN_MESH_PICK) on the device's own emitter table: the first entry with cdf > r,
+    clamped to n - 1 -- min(searchsorted(cdf, r, side="right"), n - 1) -- at every CDF entry, its float32 neighbours on both sides, 0,
+    1.0 (rng_next can return it), values above a last entry that rounds below 1, and 2 000 uniform draws; on a table of one entry,
+    of 2 049 and of 30 among 3 000 triangles.  Without a table the kind is refused."""
+    import mesh_light_scenes as mls
+    from test_mesh_light_scenes_cpu import pick_inputs, pick_reference
+    sc = mls.emitters(n_tris, share)
+    rm = render.RenderingManager(render.RenderParameters(flags=abi.FLAG_MESH_LIGHTS))
+    rm.start_rendering(sc)
+    tri, cdf = rm.debug_light_table()
+    assert len(cdf) == mls.emitter_count(n_tris, share)
+    r = pick_inputs(cdf)
+    out = rm.debug_eval(FN["MESH_PICK"], r.reshape(-1, 1), 2).view(np.uint32)
+    rm.close()
+    ref = pick_reference(cdf, r)
+    assert (out[:, 0] == ref).all(), np.nonzero(out[:, 0] != ref)[0][:10]
+    assert (out[:, 1] == tri[ref].astype(np.uint32)).all()
+    assert set(np.unique(ref).tolist()) == set(range(len(cdf)))         # every entry is some input's answer
+    plain = render.RenderingManager(render.RenderParameters())
+    plain.start_rendering(sc)
+    with pytest.raises(abi.ErError):
+        plain.debug_eval(FN["MESH_PICK"], r[:4].reshape(-1, 1), 2)
+    plain.close()
