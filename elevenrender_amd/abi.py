@@ -21,6 +21,7 @@ PASS_NAMES = {"beauty": 0, "denoise": 1, "normal": 2, "tangent": 3, "bitangent":
 FLAG_POINT_LIGHTS, FLAG_COUNTERS, FLAG_MEGAKERNEL, FLAG_PROFILE, FLAG_FUSED, FLAG_WAVEFRONT, FLAG_GPU_BUILD, FLAG_MIS, FLAG_STREAM = 1, 2, 4, 8, 16, 32, 64, 128, 256
 FLAG_HOST_BUILD = 512
 FLAG_MESH_LIGHTS = 1024     # next-event estimation of emissive triangles (csrc/er_shade.h)
+MAX_BOUNCES = 65535         # ER_MAX_BOUNCES: er_render_begin refuses a larger ErRenderParams.max_bounces
 UPDATE_CAMERA, UPDATE_GEOMETRY = 1, 2     # ErSceneUpdate.what
 EDIT_CAMERA, EDIT_GEOMETRY, EDIT_MATERIALS, EDIT_TEXTURES, EDIT_HDRI = 1, 2, 4, 8, 16     # ErSceneEdit.what
 REBUILD_NEVER, REBUILD_ALWAYS, REBUILD_AUTO = 0, 1, 2     # ErUpdatePolicy.mode

@@ -119,6 +119,9 @@ namespace erh {
 static int begin_check(const ErRenderParams* p, ErDeviceInfo& info) {
     const uint32_t world = p->world ? p->world : 1;
     if (p->rank >= world) return fail(ER_ERR_INVALID_ARG, "er_render_begin: rank >= world");
+    // (the schedules keep a path's bounce count in 16 bits of a packed word: one more would read back as a flag, and the path would never end)
+    if (p->max_bounces > ER_MAX_BOUNCES)
+        return fail(ER_ERR_INVALID_ARG, "er_render_begin: max_bounces " + std::to_string(p->max_bounces) + " is above ER_MAX_BOUNCES (" + std::to_string(ER_MAX_BOUNCES) + ")");
     int ndev = er_device_count();
     if (ndev <= 0) return fail(ER_ERR_NO_DEVICE, "er_render_begin: no HIP device available (there is no CPU fallback)");
     if (p->device < 0 || p->device >= ndev) return fail(ER_ERR_NO_DEVICE, "er_render_begin: device ordinal out of range");
@@ -673,7 +676,11 @@ static int er_render_begin_impl(ErScene* s, const ErRenderParams* p) {
 // n more samples of the wavefront schedule: trace and shade launches of every slot pool, on the pools' streams
 static int wavefront_enqueue(ErScene* s, const DevScene& D, uint32_t n, bool count) {
     // a path takes at most max_bounces ray steps plus one finalize-only step
-    const uint32_t iters = n * (s->params.max_bounces + 1);
+    const uint64_t iters64 = (uint64_t)n * ((uint64_t)s->params.max_bounces + 1u);
+    if (iters64 > 0xFFFFFFFFull)      // (refused before anything is launched: a wrapped count would render fewer iterations than the samples need)
+        return fail(ER_ERR_INVALID_ARG, "er_render_samples: " + std::to_string(n) + " samples of " + std::to_string(s->params.max_bounces) +
+                                            " bounces are more than 4294967295 iterations of the wavefront schedule in one call");
+    const uint32_t iters = (uint32_t)iters64;
     const uint32_t pools = (uint32_t)s->wf.size();
     const bool prof = (s->params.flags & ER_FLAG_PROFILE) != 0;
     if (prof) {
@@ -768,8 +775,9 @@ static int er_render_samples_async_impl(ErScene* s, uint32_t n) {
     }
     if (n > 0) for (auto& u : s->unpacked) u.clear();     // other ranks' pixels gathered earlier are stale from here on
     if (s->ad_on) return adaptive_render(s, n);
-    s->rendered += n;
-    return enqueue_samples(s, n);
+    const int rc = enqueue_samples(s, n);
+    if (rc == ER_OK) s->rendered += n;      // (a refused call rendered nothing)
+    return rc;
 }
 
 static int er_wait_impl(ErScene* s, float* elapsed_ms) {

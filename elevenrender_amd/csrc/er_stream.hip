@@ -182,6 +182,8 @@ enum { C_LIVE = 0, C_DONE, C_INIT, C_WORDS };
 #define ST_WATCHDOG 300000u      // idle polls (>= 1000 cycles each) without any ring activity in the workgroup before a wave gives up
 #define WF_PENDING_BIT 0x10000u  // per-slot flags in reduc.w, as in er_wavefront.hip: bounce (bits 0-15) | pending HDRI shadow query
 #define WF_LPENDING_BIT 0x20000u //   | pending point-light query
+static_assert(ER_MAX_BOUNCES < WF_PENDING_BIT && (WF_PENDING_BIT & (WF_PENDING_BIT - 1u)) == 0u && WF_LPENDING_BIT == 2u * WF_PENDING_BIT,
+              "a bounce count of up to ER_MAX_BOUNCES (er_render_begin refuses more) must fit below the flag bits of reduc.w");
 // status word bits (er_wait turns any of them into ER_ERR_STATE): 1 tracer watchdog, 2 shader watchdog, 4 pixel ring, 8 shade
 // ring, 16 ray ring, 32 context queues -- the last four mean a ring wait outlasted its guard, which no correct run can see
 #define ST_ERR_PIXEL 4u

@@ -69,6 +69,8 @@ __device__ __forceinline__ void slot_pixel(const DevScene& S, uint32_t slot, uin
 // packed per-slot flags in reduc.w: bounce (bits 0-15) | pending shadow (bit 16)
 #define WF_PENDING 0x10000u
 #define WF_LPENDING 0x20000u   // ... | pending point-light shadow (bit 17)
+static_assert(ER_MAX_BOUNCES < WF_PENDING && (WF_PENDING & (WF_PENDING - 1u)) == 0u && WF_LPENDING == 2u * WF_PENDING,
+              "a bounce count of up to ER_MAX_BOUNCES (er_render_begin refuses more) must fit below the flag bits of reduc.w");
 
 // ---- begin: first camera ray of every slot, queue 0 = all valid slots ----
 __global__ __launch_bounds__(64) void er_wf_begin(DevScene S, WfState W, uint32_t n_samples) {
@@ -472,12 +474,18 @@ __global__ __launch_bounds__(64, WF_SHADE_WAVES) void er_wf_shade(DevScene S, Wf
     queue_flush(&W.counts[WF_NS + WF_PAR(parity ^ 1)], qsn, s_qs, n_qs);
     unsigned t0 = wave_sum_u(c_paths), t1 = wave_sum_u(c_bounce), t3 = wave_sum_u(c_shaded), t4 = wave_sum_u(c_hdri);
     unsigned t7 = COUNT ? wave_sum_u(c_texels) : 0;
+    // (the exact re-traces of overflowed rays above visit nodes and test triangles too: the streaming kernel's shader waves count theirs)
+    unsigned t5 = COUNT ? wave_sum_u(c_nodes) : 0, t6 = COUNT ? wave_sum_u(c_tris) : 0;
     if (lane == 0 && t1 + t0) {
         atomicAdd(&S.counters->paths, (unsigned long long)t0);
         atomicAdd(&S.counters->bounce_samples, (unsigned long long)t1);
         atomicAdd(&S.counters->shaded_hits, (unsigned long long)t3);
         atomicAdd(&S.counters->hdri_samples, (unsigned long long)t4);
         if (COUNT) atomicAdd(&S.counters->texel_fetches, (unsigned long long)t7);
+        if (COUNT && t5 + t6) {
+            atomicAdd(&S.counters->node_visits, (unsigned long long)t5);
+            atomicAdd(&S.counters->tri_tests, (unsigned long long)t6);
+        }
     }
 }
 

@@ -137,11 +137,15 @@ typedef struct ErSceneDesc {
 #define ER_FLAG_GPU_BUILD    64u  /* force the device build whatever the triangle count (an error of it is then the call's error) */
 #define ER_FLAG_HOST_BUILD   512u /* force the host build (er_bvh.cpp) */
 
+/* The largest ErRenderParams::max_bounces: every schedule keeps a path's bounce count in 16 bits of a packed word, below its flag bits
+ * (csrc/er_wavefront.hip WF_PENDING, csrc/er_stream.hip WF_PENDING_BIT).  er_render_begin refuses a larger value. */
+#define ER_MAX_BOUNCES 65535u
+
 /* reference RenderParameters (src/kernel.h:51-69) + what the MI355X build adds. */
 typedef struct ErRenderParams {
     uint32_t sample_target;   /* informational, as in the reference */
     uint32_t block_size;      /* accepted for protocol compatibility; launch geometry is ours */
-    uint32_t max_bounces;     /* 0 -> 5, the literal of src/kernel.cpp:508 */
+    uint32_t max_bounces;     /* 0 -> 5, the literal of src/kernel.cpp:508; at most ER_MAX_BOUNCES (more: ER_ERR_INVALID_ARG) */
     int32_t device;           /* HIP device ordinal */
     uint32_t rank, world;     /* pixel-tile shard: this process renders tiles t with t % world == rank; world 0 -> 1 */
     uint32_t flags;

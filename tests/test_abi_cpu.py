@@ -70,6 +70,31 @@ def test_argument_validation_and_error_text():
     lib.er_scene_destroy(None)
 
 
+def test_max_bounces_is_bounded_by_er_max_bounces():
+    """The schedules keep a path's bounce count in 16 bits of a packed word, below its flag bits: er_render_begin refuses more than
+    ER_MAX_BOUNCES, beside its rank check and before it looks for a device.  65 535 and 0 (which means 5: tests/test_gpu_long_paths.py)
+    pass that check -- without a device the call then ends with ER_ERR_NO_DEVICE, with one it begins a render (nothing is rendered)."""
+    lib = abi.load()
+    header = open(os.path.join(ROOT, "include", "eleven_hip.h")).read()
+    assert re.search(r"#define\s+ER_MAX_BOUNCES\s+65535u\b", header) and abi.MAX_BOUNCES == 65535
+    sc = scenes.cornell(16, 16)
+    h = C.c_void_p()
+    assert lib.er_scene_create(C.byref(sc.desc()), C.byref(h)) == abi.ER_OK
+    for mb in (abi.MAX_BOUNCES + 1, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF):
+        p = abi.ErRenderParams(16, 8, mb, 0, 0, 1, 0)
+        assert lib.er_render_begin(h, C.byref(p)) == abi.ER_ERR_INVALID_ARG, mb
+        msg = lib.er_last_error()
+        assert b"max_bounces" in msg and b"65535" in msg and str(mb).encode() in msg, msg
+        assert lib.er_render_samples(h, 1) == abi.ER_ERR_STATE          # (the refused call began nothing)
+    p = abi.ErRenderParams(16, 8, abi.MAX_BOUNCES + 1, 0, 3, 2, 0)      # both wrong: an argument error either way
+    assert lib.er_render_begin(h, C.byref(p)) == abi.ER_ERR_INVALID_ARG
+    have_device = lib.er_device_count() > 0
+    for mb in (abi.MAX_BOUNCES, 0, 1):
+        p = abi.ErRenderParams(16, 8, mb, 0, 0, 1, 0)
+        assert lib.er_render_begin(h, C.byref(p)) == (abi.ER_OK if have_device else abi.ER_ERR_NO_DEVICE), (mb, lib.er_last_error())
+    lib.er_scene_destroy(h)
+
+
 def test_no_cpu_fallback_without_a_device():
     lib = abi.load()
     if lib.er_device_count() > 0:

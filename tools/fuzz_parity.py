@@ -1,4 +1,5 @@
-"""Randomised parity run on an MI355X: random small scenes (soup / textured soup / smooth blobs / Cornell), random
+"""Randomised parity run on an MI355X: random small scenes (soup / textured soup / smooth blobs / Cornell / blobs in concentric shells,
+whose paths live as long as the bounce limit says: tests/long_path_scenes.py), random
 frame sizes, bounce limits and sample counts; every schedule (the streaming one included) and both acceleration-structure builders against the
 oracle, bit for bit; half of the textured scenes with textures and an HDRI whose sides are not powers of two.  Usage: python tools/fuzz_parity.py [cases] [seed].  Prints MISMATCH lines and a summary.
 Known source of single-pixel mismatches: an exact distance tie between two triangles, e.g. a ray
@@ -12,6 +13,7 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
     sys.path.insert(0, p)
 import numpy as np
 
+import long_path_scenes
 import oracle
 from elevenrender_amd import abi, scenes
 from test_gpu_parity import gpu_render, oracle_render
@@ -22,9 +24,9 @@ cases = int(sys.argv[1]) if len(sys.argv) > 1 else 24
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 2026)
 bad, t0 = 0, time.time()
 for it in range(cases):
-    kind, seed = it % 4, int(rng.integers(1, 1 << 30))
+    kind, seed = it % 5, int(rng.integers(1, 1 << 30))
     w, h = int(rng.integers(9, 90)), int(rng.integers(7, 70))
-    mb, spp = int(rng.choice([1, 2, 5, 8, 16])), int(rng.integers(1, 6))
+    mb, spp = int(rng.choice([1, 2, 5, 8, 16, 32, 64])), int(rng.integers(1, 6))
     if kind == 0:
         sc = scenes.soup(int(rng.integers(1, 40000)), w, h, seed=seed, hdri_size=(int(rng.choice([16, 64, 256])), int(rng.choice([8, 32, 128]))))
     elif kind == 1:
@@ -39,8 +41,10 @@ for it in range(cases):
     elif kind == 2:
         sc = scenes.blob_instances(n_instances=int(rng.integers(1, 30)), tris_per_blob=int(rng.choice([8, 72, 200, 512])), x_res=w, y_res=h, grid=(5, 3, 2),
                                    spacing=float(rng.choice([0.2, 0.45])))
-    else:
+    elif kind == 3:
         sc = scenes.cornell(w, h)
+    else:
+        sc = long_path_scenes.shells(w, h, int(rng.choice([1, 2, 8, 64])), seed=seed)
     o = oracle_render(oracle, sc, spp, max_bounces=mb, threads=16)
     for flags in FLAG_SETS:
         g = gpu_render(sc, spp, max_bounces=mb, flags=flags)
