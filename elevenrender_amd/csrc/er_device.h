@@ -732,4 +732,38 @@ ERD void generate_hit_data(const DevScene& S, const ErMaterial& mat, const HitFu
     hd.position = hit.position;
 }
 
+// ---- the event counters: a kernel counts per lane and adds each wave's sums once, at its end ----
+ERD unsigned wave_sum(unsigned v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+// One lane of a wave adds the wave's sums to S.counters.  GATED: a sum of zero costs no atomic (the persistent kernels: most waves see
+// few kinds of event; and a kernel that never counts a kind passes the constant 0 -- ungated, an add of constant 0 compiles to an atomic
+// LOAD of the counter, which the wave waits for: -18 % on the wavefront schedule); the megakernel, whose every wave counts everything,
+// adds ungated.  Node visits and triangle tests are counted only with ER_FLAG_COUNTERS (COUNT).  Text, not a function: behind a
+// reference parameter the streaming kernel's descriptor loads are hoisted, and its code is held byte for byte.
+#define ER_FLUSH_COUNTERS(GATED, n_paths, n_bounce, n_rays, n_shaded, n_hdri, n_nodes, n_tris)                                    \
+    do {                                                                                                                          \
+        if (!(GATED) || (n_paths)) atomicAdd(&S.counters->paths, (unsigned long long)(n_paths));                                  \
+        if (!(GATED) || (n_bounce)) atomicAdd(&S.counters->bounce_samples, (unsigned long long)(n_bounce));                       \
+        if (!(GATED) || (n_rays)) atomicAdd(&S.counters->rays, (unsigned long long)(n_rays));                                     \
+        if (!(GATED) || (n_shaded)) atomicAdd(&S.counters->shaded_hits, (unsigned long long)(n_shaded));                          \
+        if (!(GATED) || (n_hdri)) atomicAdd(&S.counters->hdri_samples, (unsigned long long)(n_hdri));                             \
+        if (COUNT) {                                                                                                              \
+            atomicAdd(&S.counters->node_visits, (unsigned long long)(n_nodes));                                                   \
+            atomicAdd(&S.counters->tri_tests, (unsigned long long)(n_tris));                                                      \
+        }                                                                                                                         \
+    } while (0)
+// (COUNT) the lane occupancy of a tracer loop: wave-uniform counts
+#define ER_FLUSH_TRACE_LANES(wsteps, busy, node_lanes, tri_lanes)                                                                 \
+    do {                                                                                                                          \
+        if (COUNT) {                                                                                                              \
+            atomicAdd(&S.counters->trace_wave_steps, (unsigned long long)(wsteps));                                               \
+            atomicAdd(&S.counters->trace_busy_lanes, (unsigned long long)(busy));                                                 \
+            atomicAdd(&S.counters->trace_node_lanes, (unsigned long long)(node_lanes));                                           \
+            atomicAdd(&S.counters->trace_tri_lanes, (unsigned long long)(tri_lanes));                                             \
+        }                                                                                                                         \
+    } while (0)
+
 }  // namespace erd

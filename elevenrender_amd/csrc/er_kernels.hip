@@ -16,12 +16,6 @@
 
 using namespace erd;
 
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // setupKernel, reference src/kernel.cpp:176-213 -- for EVERY pixel (the reference's launch
 // rounds the range down to a multiple of the block size, leaving edge pixels uninitialised;
 // that defect is not reproduced).
@@ -112,16 +106,8 @@ __global__ __launch_bounds__(64) void er_render_kernel(DevScene S, uint32_t n_sa
     unsigned t5 = 0, t6 = 0, t7 = 0;
     if (COUNT) { t5 = wave_sum(c_nodes); t6 = wave_sum(c_tris); t7 = wave_sum(c_texels); }
     if (lane == 0) {
-        atomicAdd(&S.counters->paths, (unsigned long long)t0);
-        atomicAdd(&S.counters->bounce_samples, (unsigned long long)t1);
-        atomicAdd(&S.counters->rays, (unsigned long long)t2);
-        atomicAdd(&S.counters->shaded_hits, (unsigned long long)t3);
-        atomicAdd(&S.counters->hdri_samples, (unsigned long long)t4);
-        if (COUNT) {
-            atomicAdd(&S.counters->node_visits, (unsigned long long)t5);
-            atomicAdd(&S.counters->tri_tests, (unsigned long long)t6);
-            atomicAdd(&S.counters->texel_fetches, (unsigned long long)t7);
-        }
+        ER_FLUSH_COUNTERS(false, t0, t1, t2, t3, t4, t5, t6);
+        if (COUNT) atomicAdd(&S.counters->texel_fetches, (unsigned long long)t7);
     }
 }
 

@@ -1,5 +1,5 @@
 // er_shade.h + er_bounce.inc -- ONE iteration of the bounce loop of renderingKernel (reference src/kernel.cpp:508-593),
-// shared by every schedule of this library (er_kernels.hip megakernel, er_wavefront.hip, er_fused.hip) and by the
+// shared by every schedule of this library (er_kernels.hip megakernel, er_wavefront.hip, er_stream.hip) and by the
 // per-bounce debug trace (er_debug.hip).  The schedules differ only in WHEN they trace the rays this step asks for; the
 // arithmetic -- and with it every bit of the image -- is written once: the statement sequence lives in er_bounce.inc,
 // which each kernel #includes at the point where it shades (hooks below), this header holds what it calls.

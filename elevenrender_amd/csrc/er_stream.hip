@@ -180,10 +180,6 @@ enum { C_LIVE = 0, C_DONE, C_INIT, C_WORDS };
 #define ST_BATCH_SLEEP 8         // ... of a wave waiting for a fuller batch
 #endif
 #define ST_WATCHDOG 300000u      // idle polls (>= 1000 cycles each) without any ring activity in the workgroup before a wave gives up
-#define WF_PENDING_BIT 0x10000u  // per-slot flags in reduc.w, as in er_wavefront.hip: bounce (bits 0-15) | pending HDRI shadow query
-#define WF_LPENDING_BIT 0x20000u //   | pending point-light query
-static_assert(ER_MAX_BOUNCES < WF_PENDING_BIT && (WF_PENDING_BIT & (WF_PENDING_BIT - 1u)) == 0u && WF_LPENDING_BIT == 2u * WF_PENDING_BIT,
-              "a bounce count of up to ER_MAX_BOUNCES (er_render_begin refuses more) must fit below the flag bits of reduc.w");
 // status word bits (er_wait turns any of them into ER_ERR_STATE): 1 tracer watchdog, 2 shader watchdog, 4 pixel ring, 8 shade
 // ring, 16 ray ring, 32 context queues -- the last four mean a ring wait outlasted its guard, which no correct run can see
 #define ST_ERR_PIXEL 4u
@@ -192,12 +188,6 @@ static_assert(ER_MAX_BOUNCES < WF_PENDING_BIT && (WF_PENDING_BIT & (WF_PENDING_B
 #define ST_ERR_CTX 32u
 // the pixel ring's "previous entry has been read" bits (er_ring.h): one per cell, so ring_cap <= ER_STREAM_MAX_RING (er_stream_host.cpp checks)
 #define ST_PXBITS_WORDS (ER_STREAM_MAX_RING / 32u)
-
-__device__ __forceinline__ unsigned st_wave_sum(unsigned v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // wave-aggregated reservation on a plain LDS counter: returns this lane's rank-ordered value (valid only if `want`)
 __device__ __forceinline__ uint32_t st_reserve(uint32_t* counter, bool want) {
@@ -301,6 +291,7 @@ struct StState {
         return (const float4*)(base + (size_t)(g * stride + (kind == 0u ? 0u : (kind == 1u ? 32u : 256u))));
     }
 };
+#define ER_SLOT(field, i) W.field(i)      // how the shared slot protocol (er_wavefront.h, er_slot_bounce.inc) names a field of record i here
 
 // Pixel-ring cells carry the LAP of their position in the top byte of .y (1 .. 128; 0 = never written): a consumer waits for the
 // entry of ITS lap.  Whether the previous lap's entry of a cell has been read is one bit per cell in LDS (er_bits_acquire /
@@ -355,13 +346,7 @@ __device__ __forceinline__ uint32_t st_begin_sample(const DevScene& S, const StS
     const CamTrig trig = {S.cam_cx, S.cam_sx, S.cam_cy, S.cam_sy, S.cam_cz, S.cam_sz};      // (evaluated once on the host: er_api.cpp)
     const Ray ray = camera_ray(S.cam, (int)px, (int)py, S.x_res, S.y_res, c1, c2, c3, c4, c5, S.cam_trig_valid ? &trig : nullptr);
     W.pix(g) = pxy;
-    W.ray_o(g) = make_float4(ray.o.x, ray.o.y, ray.o.z, 0.0f);
-    W.ray_d(g) = make_float4(ray.d.x, ray.d.y, ray.d.z, -1.0f);
-    W.light(g) = make_float4(0.0f, 0.0f, 0.0f, __builtin_bit_cast(float, rs));
-    W.reduc(g) = make_float4(1.0f, 1.0f, 1.0f, __builtin_bit_cast(float, 0u));
-    W.aov_n(g) = make_float4(0, 0, 0, 0);
-    W.aov_t(g) = make_float4(0, 0, 0, 0);
-    W.aov_b(g) = make_float4(0, 0, 0, 0);
+    ER_SLOT_RESET(g, ray, rs);
     W.left(g) = left;
     if (SPECB) {      // (the 16-wave form of the kernel writes none of this: it is the code it was)
         W.spec_word(g) = spec ? (uint32_t)SP_PENDING : (uint32_t)SP_NONE;
@@ -372,18 +357,6 @@ __device__ __forceinline__ uint32_t st_begin_sample(const DevScene& S, const StS
     }
     ER_SP(W.stamp(g) = sp_now(); W.stamp0(g) = W.stamp(g);)
     return rs0;
-}
-
-// what a finished traversal leaves in the slot's record (closest: winner + second candidate; shadow: verdict + candidates)
-__device__ __forceinline__ void st_write_result(const StState& W, uint32_t rec, bool shadow, bool occluded, bool overflow, int s0, int s1) {
-    if (shadow) {
-        W.occluded(rec) = occluded ? 1 : (overflow ? 3 : (s0 >= 0 ? 2 : 0));     // a certain occluder ends the query at once
-        W.occ_a(rec) = s0;
-        W.occ_b(rec) = s1;
-    } else {
-        W.hit(rec) = s0 >= 0 ? s0 : s1;
-        W.hit2(rec) = overflow ? -2 : ((s0 >= 0 && s1 >= 0) ? s1 : -1);
-    }
 }
 
 // the verdict of a slot's shadow query (record rec) as the shader reads it: from the flags the tracers left in the slot's s_wait word when it is
@@ -609,14 +582,14 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                     const uint32_t ls = lsk & ST_SLOT_MASK, kind = lsk >> ST_SLOT_BITS;
                     if (done) {
                         const uint32_t rec = g0 + ls + (kind == 2u ? W.slots : 0u);
-                        if (!HANDOFF) st_write_result(W, rec, T.shadow, done_occl, T.overflow, T.s0, T.s1);
+                        if (!HANDOFF) { ER_SLOT_WRITE_RESULT(rec, T, done_occl) }
                         else if (T.shadow) {
                             // a certain verdict is a flag; an ambiguous one (2, 3) leaves what it left before, for the shader's exact test
-                            if (!done_occl && (T.overflow || T.s0 >= 0)) st_write_result(W, rec, true, false, T.overflow, T.s0, T.s1);
+                            if (!done_occl && (T.overflow || T.s0 >= 0)) { ER_SLOT_WRITE_RESULT(rec, T, false) }
                         } else {
-                            // (st_write_result's hit and hit2)
-                            s_hit[ls] = T.s0 >= 0 ? T.s0 : T.s1;
-                            if (T.overflow || (T.s0 >= 0 && T.s1 >= 0)) W.hit2(rec) = T.overflow ? -2 : T.s1;
+                            // (ER_SLOT_WRITE_RESULT's hit and hit2)
+                            s_hit[ls] = trav_hit(T);
+                            if (T.overflow || (T.s0 >= 0 && T.s1 >= 0)) W.hit2(rec) = trav_hit2(T);
                         }
                     }
                     if (SPEC && COUNT && done) {      // this ray's visits and tests belong to its sample (counted if and when that is accumulated)
@@ -630,7 +603,7 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                     uint32_t fin = 0;
                     if (done) {
                         const bool esc = !T.shadow && !T.overflow && T.s0 < 0 && T.s1 < 0;
-                        const bool amb = T.shadow && !done_occl && (T.overflow || T.s0 >= 0);       // (st_write_result's verdicts 2 and 3)
+                        const bool amb = T.shadow && !done_occl && (T.overflow || T.s0 >= 0);       // (trav_shadow_code's verdicts 2 and 3)
                         // (HANDOFF) a certain occluder and a second candidate in the record are flags too (worked out here, from the ray's state: no register across the fence)
                         const bool occf = HANDOFF && T.shadow && done_occl, hit2f = HANDOFF && !T.shadow && (T.overflow || (T.s0 >= 0 && T.s1 >= 0));
                         const uint32_t add = (esc ? ST_ESC : 0u) + (amb ? (kind == 1u ? ST_AMB1 : ST_AMB2) : 0u) + (occf ? (kind == 1u ? ST_OCC1 : ST_OCC2) : 0u) +
@@ -758,7 +731,7 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
             }
             ER_MARK("tracer_loop_end");
 #ifdef ER_TRACER_PROBE
-            const unsigned trp_rays = st_wave_sum(c_rays);
+            const unsigned trp_rays = wave_sum(c_rays);
             if (lane == 0) {
                 unsigned long long* c = (unsigned long long*)&S.counters->node_visits;      // node_visits ... trace_tri_lanes: nine 64-bit sums
                 for (int i = 0; i < 7; i++) atomicAdd(&c[i], (unsigned long long)trp[i]);
@@ -893,36 +866,10 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                 unsigned &c_texels = SPEC ? t_texels : o_texels, &c_nodes = SPEC ? t_nodes : o_nodes, &c_tris = SPEC ? t_tris : o_tris;
                 (void)c_texels;
                 const bool fin_only = (e >> ST_SLOT_BITS) != 0;
-                float4 L4 = W.light(slot), R4 = W.reduc(slot);
-                F3 light = f3(L4.x, L4.y, L4.z), reduction = f3(R4.x, R4.y, R4.z);
-                rs = __builtin_bit_cast(uint32_t, L4.w);
-                uint32_t packed = __builtin_bit_cast(uint32_t, R4.w);
-                uint32_t bounce = packed & 0xFFFFu;
-                if (packed & WF_PENDING_BIT) {   // resolve the previous bounce's shadow query
-                    int occ = st_verdict<HANDOFF>(W, slot, wflags, ST_AMB1, ST_OCC1);
-                    if (occ >= 2) {
-                        float4 so = W.sh_o(slot), sd = W.sh_d(slot);
-                        Ray sr;
-                        sr.o = f3(so.x, so.y, so.z);
-                        sr.d = f3(sd.x, sd.y, sd.z);
-                        occ = resolve_shadow<COUNT>(S, stack, sr, __builtin_bit_cast(int, so.w), sd.w, occ, W.occ_a(slot), W.occ_b(slot), c_nodes, c_tris) ? 1 : 0;
-                    }
-                    float4 c = occ ? W.c_occ(slot) : W.c_vis(slot);
-                    light = light + f3(c.x, c.y, c.z);
-                }
-                if (EXT && (packed & WF_LPENDING_BIT)) {   // ... then its point-light query (second half of the shadow records)
-                    const uint32_t q = slot + W.slots;
-                    int occ = st_verdict<HANDOFF>(W, q, wflags, ST_AMB2, ST_OCC2);
-                    if (occ >= 2) {
-                        float4 so = W.sh_o(q), sd = W.sh_d(q);
-                        Ray sr;
-                        sr.o = f3(so.x, so.y, so.z);
-                        sr.d = f3(sd.x, sd.y, sd.z);
-                        occ = resolve_shadow<COUNT>(S, stack, sr, __builtin_bit_cast(int, so.w), sd.w, occ, W.occ_a(q), W.occ_b(q), c_nodes, c_tris) ? 1 : 0;
-                    }
-                    float4 c = occ ? W.c_occ(q) : W.c_vis(q);
-                    light = light + f3(c.x, c.y, c.z);
-                }
+                ER_SLOT_LOAD(slot);
+                // the previous bounce's shadow query, then its point-light query (second half of the shadow records)
+                if (packed & ER_SLOT_PENDING) ER_SLOT_RESOLVE_QUERY(slot, st_verdict<HANDOFF>(W, slot, wflags, ST_AMB1, ST_OCC1))
+                if (EXT && (packed & ER_SLOT_LPENDING)) ER_SLOT_RESOLVE_QUERY(slot + W.slots, st_verdict<HANDOFF>(W, slot + W.slots, wflags, ST_AMB2, ST_OCC2))
                 bool pending = false, lpending = false;
                 bool done = fin_only;
                 Ray ray;
@@ -931,45 +878,19 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                 float prev_pdf = -1.0f;
                 float mesh_d = 0.0f;       // (MESH: ray_o.w)
                 if (!fin_only) {
-                    float4 o = W.ray_o(slot), d = W.ray_d(slot);
-                    ray.o = f3(o.x, o.y, o.z);
-                    ray.d = f3(d.x, d.y, d.z);
-                    if (MESH) mesh_d = o.w;
+                    ER_SLOT_LOAD_RAY(slot)
                     int hslot = resolve_closest<COUNT>(S, stack, ray, HANDOFF ? s_hit[ls] : W.hit(slot), (!HANDOFF || (wflags & ST_HIT2) != 0u) ? W.hit2(slot) : -1, c_nodes, c_tris);
                     c_bounce++;
-                    if (EXT) prev_pdf = d.w;
-#define ER_BOUNCE_HDRI_QUERY(sr, self_slot, d_self, cv, co)                                                     \
-    W.sh_o(slot) = make_float4((sr).o.x, (sr).o.y, (sr).o.z, __builtin_bit_cast(float, (int)(self_slot)));      \
-    W.sh_d(slot) = make_float4((sr).d.x, (sr).d.y, (sr).d.z, (d_self));                                          \
-    W.c_vis(slot) = make_float4((cv).x, (cv).y, (cv).z, 0.0f);                                                   \
-    W.c_occ(slot) = make_float4((co).x, (co).y, (co).z, 0.0f)
-#define ER_BOUNCE_LIGHT_QUERY(lr, self_slot, limit, lv, lo)                                                     \
-    {                                                                                                            \
-        const uint32_t lq = slot + W.slots;                                                                      \
-        const F3 lv_ = (lv), lo_ = (lo);                                                                         \
-        W.sh_o(lq) = make_float4((lr).o.x, (lr).o.y, (lr).o.z, __builtin_bit_cast(float, (int)(self_slot)));     \
-        W.sh_d(lq) = make_float4((lr).d.x, (lr).d.y, (lr).d.z, (limit));                                         \
-        W.c_vis(lq) = make_float4(lv_.x, lv_.y, lv_.z, 0.0f);                                                    \
-        W.c_occ(lq) = make_float4(lo_.x, lo_.y, lo_.z, 0.0f);                                                    \
-    }
-#define ER_BOUNCE_FIRST_HIT(n, t, b)                                                                            \
-    W.aov_n(slot) = make_float4((n).x, (n).y, (n).z, 0.0f);                                                      \
-    W.aov_t(slot) = make_float4((t).x, (t).y, (t).z, 0.0f);                                                      \
-    W.aov_b(slot) = make_float4((b).x, (b).y, (b).z, 0.0f)
 #define ER_BOUNCE_FUSE FUSE
 #define ER_BOUNCE_MESH MESH
-#include "er_bounce.inc"
-#undef ER_BOUNCE_HDRI_QUERY
-#undef ER_BOUNCE_LIGHT_QUERY
-#undef ER_BOUNCE_FIRST_HIT
-#undef ER_BOUNCE_MESH
+#include "er_slot_bounce.inc"
                 }
                 bool alive = true, fin_next = false;
                 if (done && (pending || lpending)) {
                     fin_next = true;          // the path is over but a shadow query is in flight: come back once, without a ray
                 } else if (done) {
                     // the path is over and nothing is pending: its sample goes to the finish ring (light and RNG state through the record)
-                    W.light(slot) = make_float4(light.x, light.y, light.z, __builtin_bit_cast(float, rs));
+                    ER_SLOT_STORE_LIGHT(slot);
                     alive = false;
                     to_finish = true;
                     ER_SP(W.stamp(slot) = sp_now();)      // G: handed to the finish ring by a shading step
@@ -979,13 +900,7 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                 push_shadow = pending;
                 push_light = EXT && lpending;
                 if (alive) {
-                    if (!fin_next) {
-                        W.ray_o(slot) = make_float4(ray.o.x, ray.o.y, ray.o.z, MESH ? mesh_d : 0.0f);
-                        W.ray_d(slot) = make_float4(ray.d.x, ray.d.y, ray.d.z, EXT ? prev_pdf : -1.0f);
-                    }
-                    W.light(slot) = make_float4(light.x, light.y, light.z, __builtin_bit_cast(float, rs));
-                    W.reduc(slot) = make_float4(reduction.x, reduction.y, reduction.z,
-                                                __builtin_bit_cast(float, bounce | (pending ? WF_PENDING_BIT : 0u) | ((EXT && lpending) ? WF_LPENDING_BIT : 0u)));
+                    ER_SLOT_STORE(slot, !fin_next);
                     s_wait[ls] = (push_closest ? 1u : 0u) + (push_shadow ? 1u : 0u) + (push_light ? 1u : 0u) + (fin_next ? ST_FIN : 0u);
                 }
                 if (SPEC) {
@@ -1022,21 +937,14 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
                 const uint32_t packed = __builtin_bit_cast(uint32_t, R4.w);
                 // while the host has not yet decided which deal of tiles the frame gets, the path's length goes to its tile's sum (a count of
                 // work, not a time: the decision is the same on every run of the same frame; one fire-and-forget atomic per finished sample)
-                if (S.tile_cost) __hip_atomic_fetch_add(&S.tile_cost[(pxy >> 19) * S.tiles_x + ((pxy & 0xFFFFu) >> 3)], (packed & 0xFFFFu) + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (S.tile_cost) __hip_atomic_fetch_add(&S.tile_cost[(pxy >> 19) * S.tiles_x + ((pxy & 0xFFFFu) >> 3)], (packed & ER_SLOT_BOUNCE_MASK) + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if ((e >> ST_SLOT_BITS) != 0) {
                     // straight from the tracers: the path's last ray left the scene.  What the shading step does for such a slot --
                     // the previous bounce's shadow verdicts (certain ones: the tracers checked), then the miss branch of the bounce.
                     F3 reduction = f3(R4.x, R4.y, R4.z);
-                    uint32_t bounce = packed & 0xFFFFu;
-                    if (packed & WF_PENDING_BIT) {
-                        const float4 c = st_verdict<HANDOFF>(W, slot, wflags, 0u, ST_OCC1) ? W.c_occ(slot) : W.c_vis(slot);      // (certain: the tracers checked)
-                        light = light + f3(c.x, c.y, c.z);
-                    }
-                    if (EXT && (packed & WF_LPENDING_BIT)) {
-                        const uint32_t q = slot + W.slots;
-                        const float4 c = st_verdict<HANDOFF>(W, q, wflags, 0u, ST_OCC2) ? W.c_occ(q) : W.c_vis(q);
-                        light = light + f3(c.x, c.y, c.z);
-                    }
+                    uint32_t bounce = packed & ER_SLOT_BOUNCE_MASK;
+                    if (packed & ER_SLOT_PENDING) ER_SLOT_ADD_QUERY(slot, st_verdict<HANDOFF>(W, slot, wflags, 0u, ST_OCC1))      // (certain: the tracers checked)
+                    if (EXT && (packed & ER_SLOT_LPENDING)) ER_SLOT_ADD_QUERY(slot + W.slots, st_verdict<HANDOFF>(W, slot + W.slots, wflags, 0u, ST_OCC2))
                     const float4 d = W.ray_d(slot);
                     Ray ray;
                     ray.o = f3s(0);
@@ -1302,27 +1210,16 @@ __global__ __launch_bounds__(ST_THREADS) void er_stream_kernel(const DevScene __
             if (q0 | q1 | q2) { atomicAdd(status + ER_SC_SPEC, q0); atomicAdd(status + ER_SC_SPEC + 1, q1); atomicAdd(status + ER_SC_SPEC + 2, q2); }
         }
     }
-    unsigned t0 = st_wave_sum(c_paths), t1 = st_wave_sum(c_bounce), t2 = st_wave_sum(c_rays), t3 = st_wave_sum(c_shaded), t4 = st_wave_sum(c_hdri);
+    unsigned t0 = wave_sum(c_paths), t1 = wave_sum(c_bounce), t2 = wave_sum(c_rays), t3 = wave_sum(c_shaded), t4 = wave_sum(c_hdri);
     unsigned t5 = 0, t6 = 0, t7 = 0;
-    if (COUNT) { t5 = st_wave_sum(c_nodes); t6 = st_wave_sum(c_tris); t7 = st_wave_sum(c_texels); }
+    if (COUNT) { t5 = wave_sum(c_nodes); t6 = wave_sum(c_tris); t7 = wave_sum(c_texels); }
     if (lane == 0) {
         const unsigned long long t_end = (unsigned long long)wall_clock64();
         atomicMax((unsigned long long*)(status + ER_SC_END + 2 * (blockIdx.x & 7u)), t_end);
         atomicMax((unsigned long long*)(status + ER_SC_WG_END + 2 * blockIdx.x), t_end);      // ... and each workgroup's (er_debug_stream_balance: printed and logged, nothing is decided on it)
-        if (t0) atomicAdd(&S.counters->paths, (unsigned long long)t0);
-        if (t1) atomicAdd(&S.counters->bounce_samples, (unsigned long long)t1);
-        if (t2) atomicAdd(&S.counters->rays, (unsigned long long)t2);
-        if (t3) atomicAdd(&S.counters->shaded_hits, (unsigned long long)t3);
-        if (t4) atomicAdd(&S.counters->hdri_samples, (unsigned long long)t4);
-        if (COUNT) {
-            atomicAdd(&S.counters->node_visits, (unsigned long long)t5);
-            atomicAdd(&S.counters->tri_tests, (unsigned long long)t6);
-            atomicAdd(&S.counters->texel_fetches, (unsigned long long)t7);
-            atomicAdd(&S.counters->trace_wave_steps, (unsigned long long)c_wsteps);
-            atomicAdd(&S.counters->trace_busy_lanes, (unsigned long long)c_busy);
-            atomicAdd(&S.counters->trace_node_lanes, (unsigned long long)c_nl);
-            atomicAdd(&S.counters->trace_tri_lanes, (unsigned long long)c_tl);
-        }
+        ER_FLUSH_COUNTERS(true, t0, t1, t2, t3, t4, t5, t6);
+        if (COUNT) atomicAdd(&S.counters->texel_fetches, (unsigned long long)t7);
+        ER_FLUSH_TRACE_LANES(c_wsteps, c_busy, c_nl, c_tl);
     }
 }
 

@@ -362,6 +362,16 @@ ERD int trace_cold(const DevScene& S, int* stack, const Ray& ray, int skip_slot,
     return trace<COUNT, ANY>(S, stack, ray, skip_slot, limit, dd, node_visits, tri_tests);
 }
 
+// What a finished traversal leaves for the step that shades it (the records of er_wavefront.h, the streaming kernel's hand-off, the
+// debug hooks below); resolve_closest / resolve_shadow turn it into the reference's answer.
+//   closest: hit = the surviving candidate, -1 = miss; hit2 = a second survivor (the exact metric decides), -1 none, -2 = more than
+//            two inside one t-interval: re-trace exactly
+//   shadow:  0 not occluded, 1 occluded (`certain`: a step found an occluder and ended the query), 2 = decide among the candidates
+//            s0 / s1 by the exact metric, 3 = re-trace exactly
+ERD int trav_hit(const Trav& T) { return T.s0 >= 0 ? T.s0 : T.s1; }
+ERD int trav_hit2(const Trav& T) { return T.overflow ? -2 : ((T.s0 >= 0 && T.s1 >= 0) ? T.s1 : -1); }
+ERD int trav_shadow_code(const Trav& T, bool certain) { return certain ? 1 : (T.overflow ? 3 : (T.s0 >= 0 ? 2 : 0)); }
+
 // closest-hit result of a finished traversal: the winning slot (or -1) under the reference's exact metric
 template <bool COUNT>
 ERD int resolve_closest(const DevScene& S, int* stack2, const Ray& ray, int hslot, int h2, unsigned& c_nodes, unsigned& c_tris) {
@@ -408,9 +418,9 @@ ERD int trav_run_closest(const DevScene& S, uint2* stack, uint2* spill, int* sta
         trav_fetch(S, st, D);
         trav_apply<COUNT>(T, S, st, D, c_nodes, c_tris);
     }
-    const int h2 = T.overflow ? -2 : ((T.s0 >= 0 && T.s1 >= 0) ? T.s1 : -1);
+    const int h2 = trav_hit2(T);
     info = T.overflow ? 2 : (h2 >= 0 ? 1 : 0);     // 0 one survivor (or none), 1 two survivors -> exact metric, 2 -> exact re-trace
-    return resolve_closest<COUNT>(S, stack2, ray, T.s0 >= 0 ? T.s0 : T.s1, h2, c_nodes, c_tris);
+    return resolve_closest<COUNT>(S, stack2, ray, trav_hit(T), h2, c_nodes, c_tris);
 }
 template <bool COUNT>
 ERD bool trav_run_shadow(const DevScene& S, uint2* stack, uint2* spill, int* stack2, const Ray& ray, int self_slot, float limit, int& info,
@@ -424,10 +434,10 @@ ERD bool trav_run_shadow(const DevScene& S, uint2* stack, uint2* spill, int* sta
     while (trav_choose(T, S, stack, spill, st)) {
         TravData D;
         trav_fetch(S, st, D);
-        if (trav_apply<COUNT>(T, S, st, D, c_nodes, c_tris)) { code = 1; break; }
+        if (trav_apply<COUNT>(T, S, st, D, c_nodes, c_tris)) { code = trav_shadow_code(T, true); break; }
     }
-    if (code < 0) code = T.overflow ? 3 : (T.s0 >= 0 ? 2 : 0);
-    info = code;                                   // 0 / 1 decided by the t-intervals, 2 exact metric of <= 2 candidates, 3 exact re-trace
+    if (code < 0) code = trav_shadow_code(T, false);
+    info = code;                                  // 0 / 1 decided by the t-intervals, 2 exact metric of <= 2 candidates, 3 exact re-trace
     return resolve_shadow<COUNT>(S, stack2, ray, self_slot, limit, code, T.s0, T.s1, c_nodes, c_tris);
 }
 

@@ -27,11 +27,7 @@
 
 using namespace erd;
 
-__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
+#define ER_SLOT(field, i) W.field[i]      // how the shared slot protocol (er_wavefront.h, er_slot_bounce.inc) names a field of record i here
 
 // wave-aggregated queue append: returns this lane's position (valid only if `want`)
 __device__ __forceinline__ unsigned queue_push(uint32_t* counter, bool want) {
@@ -66,12 +62,6 @@ __device__ __forceinline__ void slot_pixel(const DevScene& S, uint32_t slot, uin
     py = ty * ER_TILE + (lane >> 3);
 }
 
-// packed per-slot flags in reduc.w: bounce (bits 0-15) | pending shadow (bit 16)
-#define WF_PENDING 0x10000u
-#define WF_LPENDING 0x20000u   // ... | pending point-light shadow (bit 17)
-static_assert(ER_MAX_BOUNCES < WF_PENDING && (WF_PENDING & (WF_PENDING - 1u)) == 0u && WF_LPENDING == 2u * WF_PENDING,
-              "a bounce count of up to ER_MAX_BOUNCES (er_render_begin refuses more) must fit below the flag bits of reduc.w");
-
 // ---- begin: first camera ray of every slot, queue 0 = all valid slots ----
 __global__ __launch_bounds__(64) void er_wf_begin(DevScene S, WfState W, uint32_t n_samples) {
     uint32_t slot = (blockIdx.x * W.pools + W.pool) * 64 + threadIdx.x;   // this pool's share of the owned tiles
@@ -83,13 +73,7 @@ __global__ __launch_bounds__(64) void er_wf_begin(DevScene S, WfState W, uint32_
         uint32_t rs = S.rng[idx];
         float c1 = rng_next(rs), c2 = rng_next(rs), c3 = rng_next(rs), c4 = rng_next(rs), c5 = rng_next(rs);
         Ray ray = camera_ray(S.cam, (int)px, (int)py, S.x_res, S.y_res, c1, c2, c3, c4, c5);
-        W.ray_o[slot] = make_float4(ray.o.x, ray.o.y, ray.o.z, 0.0f);
-        W.ray_d[slot] = make_float4(ray.d.x, ray.d.y, ray.d.z, -1.0f);   // w: brdfpdf of the last opaque bounce (ER_FLAG_MIS)
-        W.light[slot] = make_float4(0.0f, 0.0f, 0.0f, __builtin_bit_cast(float, rs));
-        W.reduc[slot] = make_float4(1.0f, 1.0f, 1.0f, __builtin_bit_cast(float, 0u));
-        W.aov_n[slot] = make_float4(0, 0, 0, 0);
-        W.aov_t[slot] = make_float4(0, 0, 0, 0);
-        W.aov_b[slot] = make_float4(0, 0, 0, 0);
+        ER_SLOT_RESET(slot, ray, rs);
         W.left[slot] = n_samples;
     }
     unsigned pos = queue_push(&W.counts[WF_NC], valid);
@@ -184,8 +168,8 @@ __global__ __launch_bounds__(64, WF_TRACE_WAVES) void er_wf_trace(DevScene S, Wf
                                    shadow ? rd.w : __builtin_inff());
                         c_rays++;
                         busy = S.node_count != 0;
-                        if (!busy) {   // empty scene: every ray misses
-                            if (shadow) W.occluded[entry] = 0; else { W.hit[entry] = -1; W.hit2[entry] = -1; }
+                        if (!busy) {   // empty scene: every ray misses (T is fresh from trav_begin: no candidate, no overflow)
+                            if (shadow) W.occluded[entry] = trav_shadow_code(T, false); else { W.hit[entry] = trav_hit(T); W.hit2[entry] = trav_hit2(T); }
                         }
                     }
                 }
@@ -222,37 +206,30 @@ __global__ __launch_bounds__(64, WF_TRACE_WAVES) void er_wf_trace(DevScene S, Wf
         if (busy) {
             if (do_step) {
                 if (trav_apply<COUNT>(T, S, st, D, c_nodes, c_tris)) {
-                    W.occluded[entry] = 1;   // a certain occluder ends the shadow query
+                    W.occluded[entry] = trav_shadow_code(T, true);   // a certain occluder ends the shadow query
                     finished = true;
                 }
             } else if (T.shadow) {
-                W.occluded[entry] = T.overflow ? 3 : (T.s0 >= 0 ? 2 : 0);
+                W.occluded[entry] = trav_shadow_code(T, false);
             }
             if (finished) {
                 if (T.shadow) {
                     W.occ_a[entry] = T.s0;
                     W.occ_b[entry] = T.s1;
                 } else {
-                    W.hit[entry] = T.s0 >= 0 ? T.s0 : T.s1;
-                    W.hit2[entry] = T.overflow ? -2 : ((T.s0 >= 0 && T.s1 >= 0) ? T.s1 : -1);
+                    W.hit[entry] = trav_hit(T);
+                    W.hit2[entry] = trav_hit2(T);
                 }
                 busy = false;
             }
         }
     }
-    unsigned t0 = wave_sum_u(c_rays);
+    unsigned t0 = wave_sum(c_rays);
     unsigned t1 = 0, t2 = 0;
-    if (COUNT) { t1 = wave_sum_u(c_nodes); t2 = wave_sum_u(c_tris); }
+    if (COUNT) { t1 = wave_sum(c_nodes); t2 = wave_sum(c_tris); }
     if (lane == 0 && t0) {
-        atomicAdd(&S.counters->rays, (unsigned long long)t0);
-        if (COUNT) {
-            atomicAdd(&S.counters->node_visits, (unsigned long long)t1);
-            atomicAdd(&S.counters->tri_tests, (unsigned long long)t2);
-            atomicAdd(&S.counters->trace_wave_steps, (unsigned long long)c_wsteps);
-            atomicAdd(&S.counters->trace_busy_lanes, (unsigned long long)c_busy);
-            atomicAdd(&S.counters->trace_node_lanes, (unsigned long long)c_nl);
-            atomicAdd(&S.counters->trace_tri_lanes, (unsigned long long)c_tl);
-        }
+        ER_FLUSH_COUNTERS(true, 0, 0, t0, 0, 0, t1, t2);
+        ER_FLUSH_TRACE_LANES(c_wsteps, c_busy, c_nl, c_tl);
     }
 }
 
@@ -279,7 +256,6 @@ __global__ __launch_bounds__(64, WF_SHADE_WAVES) void er_wf_shade(DevScene S, Wf
     const uint32_t* qc = W.q[parity];
     uint32_t* qn = W.q[parity ^ 1];
     uint32_t* qsn = W.qs[parity ^ 1];
-    const size_t npx = (size_t)S.x_res * S.y_res;
     unsigned c_paths = 0, c_bounce = 0, c_shaded = 0, c_texels = 0, c_hdri = 0;
     // tickets (64 slots each) are taken several at a time: one atomic per chunk
     uint32_t tchunk = wC / (gridDim.x * 4u);
@@ -313,14 +289,13 @@ __global__ __launch_bounds__(64, WF_SHADE_WAVES) void er_wf_shade(DevScene S, Wf
             uint32_t px, py;
             slot_pixel(S, slot, px, py);
             const uint32_t idx = py * S.x_res + px;
-            float4 L4 = W.light[slot], R4 = W.reduc[slot];
-            F3 light = f3(L4.x, L4.y, L4.z), reduction = f3(R4.x, R4.y, R4.z);
-            uint32_t rs = __builtin_bit_cast(uint32_t, L4.w);
-            uint32_t packed = __builtin_bit_cast(uint32_t, R4.w);
-            uint32_t bounce = packed & 0xFFFFu;
-            if (packed & WF_PENDING) {   // resolve the previous bounce's shadow query
+            uint32_t rs;
+            ER_SLOT_LOAD(slot);
+            // the previous bounce's shadow query, then its point-light query (second half of the shadow records); a verdict the
+            // trace kernel could not decide from t-intervals (2, 3) is settled by the exact metric
+            if (packed & ER_SLOT_PENDING) {   // (resolve_shadow's body by hand: the call spills more registers here, C2 -0.8 % against a run-to-run spread of 0.5 %)
                 int occ = W.occluded[slot];
-                if (occ >= 2) {          // the trace kernel could not decide from t-intervals: exact metric
+                if (occ >= 2) {
                     float4 so = W.sh_o[slot], sd = W.sh_d[slot];
                     Ray sr;
                     sr.o = f3(so.x, so.y, so.z);
@@ -335,127 +310,50 @@ __global__ __launch_bounds__(64, WF_SHADE_WAVES) void er_wf_shade(DevScene S, Wf
                         occ = nearer ? 1 : 0;
                     }
                 }
-                float4 c = occ ? W.c_occ[slot] : W.c_vis[slot];
-                light = light + f3(c.x, c.y, c.z);
+                ER_SLOT_ADD_QUERY(slot, occ)
             }
-            if (EXT && (packed & WF_LPENDING)) {   // ... then its point-light query (second half of the shadow records)
-                const uint32_t q = slot + W.slots;
-                int occ = W.occluded[q];
-                if (occ >= 2) {
-                    float4 so = W.sh_o[q], sd = W.sh_d[q];
-                    Ray sr;
-                    sr.o = f3(so.x, so.y, so.z);
-                    sr.d = f3(sd.x, sd.y, sd.z);
-                    occ = resolve_shadow<COUNT>(S, stack, sr, __builtin_bit_cast(int, so.w), sd.w, occ, W.occ_a[q], W.occ_b[q], c_nodes, c_tris) ? 1 : 0;
-                }
-                float4 c = occ ? W.c_occ[q] : W.c_vis[q];
-                light = light + f3(c.x, c.y, c.z);
-            }
+            if (EXT && (packed & ER_SLOT_LPENDING)) ER_SLOT_RESOLVE_QUERY(slot + W.slots, W.occluded[slot + W.slots])
             bool pending = false, lpending = false;
             bool done = fin_only;
             Ray ray;
             float prev_pdf = -1.0f;
             float mesh_d = 0.0f;       // (MESH: ray_o.w)
             if (!fin_only) {
-                float4 o = W.ray_o[slot], d = W.ray_d[slot];
-                if (MESH) mesh_d = o.w;
-                ray.o = f3(o.x, o.y, o.z);
-                ray.d = f3(d.x, d.y, d.z);
-                int hslot = W.hit[slot];
-                int h2 = W.hit2[slot];
-                if (h2 == -2) {          // more than two candidates inside one t-interval: exact scalar traversal
-                    float dd;
-                    hslot = trace<COUNT, false>(S, stack, ray, -1, __builtin_inff(), dd, c_nodes, c_tris);
-                } else if (h2 >= 0) {    // two candidates: the reference's strict '<' on the exact metric
-                    if (exact_distance(S, (uint32_t)h2, ray) < exact_distance(S, (uint32_t)hslot, ray)) hslot = h2;
-                }
+                ER_SLOT_LOAD_RAY(slot)
+                int hslot = resolve_closest<COUNT>(S, stack, ray, W.hit[slot], W.hit2[slot], c_nodes, c_tris);
                 c_bounce++;
-                if (EXT) prev_pdf = d.w;
-#define ER_BOUNCE_HDRI_QUERY(sr, self_slot, d_self, cv, co)                                                     \
-    W.sh_o[slot] = make_float4((sr).o.x, (sr).o.y, (sr).o.z, __builtin_bit_cast(float, (int)(self_slot)));      \
-    W.sh_d[slot] = make_float4((sr).d.x, (sr).d.y, (sr).d.z, (d_self));                                          \
-    W.c_vis[slot] = make_float4((cv).x, (cv).y, (cv).z, 0.0f);                                                   \
-    W.c_occ[slot] = make_float4((co).x, (co).y, (co).z, 0.0f)
-#define ER_BOUNCE_LIGHT_QUERY(lr, self_slot, limit, lv, lo)                                                     \
-    {   /* the light query of a slot lives in the second half of the shadow records */                          \
-        const uint32_t lq = slot + W.slots;                                                                      \
-        const F3 lv_ = (lv), lo_ = (lo);                                                                         \
-        W.sh_o[lq] = make_float4((lr).o.x, (lr).o.y, (lr).o.z, __builtin_bit_cast(float, (int)(self_slot)));     \
-        W.sh_d[lq] = make_float4((lr).d.x, (lr).d.y, (lr).d.z, (limit));                                         \
-        W.c_vis[lq] = make_float4(lv_.x, lv_.y, lv_.z, 0.0f);                                                    \
-        W.c_occ[lq] = make_float4(lo_.x, lo_.y, lo_.z, 0.0f);                                                    \
-    }
-#define ER_BOUNCE_FIRST_HIT(n, t, b)                                                                            \
-    W.aov_n[slot] = make_float4((n).x, (n).y, (n).z, 0.0f);                                                      \
-    W.aov_t[slot] = make_float4((t).x, (t).y, (t).z, 0.0f);                                                      \
-    W.aov_b[slot] = make_float4((b).x, (b).y, (b).z, 0.0f)
 #define ER_BOUNCE_MESH MESH
-#include "er_bounce.inc"
-#undef ER_BOUNCE_HDRI_QUERY
-#undef ER_BOUNCE_LIGHT_QUERY
-#undef ER_BOUNCE_FIRST_HIT
-#undef ER_BOUNCE_MESH
+#include "er_slot_bounce.inc"
             }
-            bool alive = true;
+            bool store = true;
             if (done && (pending || lpending)) {
                 // the path is over but its last shadow query is in flight: come back once, without a ray
                 next_entry = slot | ER_WF_FINALIZE_ONLY;
                 push_closest = true;
             } else if (done) {
-                // src/kernel.cpp:597-645
-                light = f3(clampf(light.x, 0, 10), clampf(light.y, 0, 10), clampf(light.z, 0, 10));
-                uint32_t sa = S.samples[idx];
-                if (!(light.x != light.x) && !(light.y != light.y) && !(light.z != light.z)) {
-                    float k = ((float)sa) / ((float)(sa + 1));
-                    float inv = (float)(sa + 1);
-                    float4 an = W.aov_n[slot], at = W.aov_t[slot], ab = W.aov_b[slot];
-                    const F3 vals[4] = {light, f3(an.x, an.y, an.z), f3(at.x, at.y, at.z), f3(ab.x, ab.y, ab.z)};
-                    const int planes[4] = {ER_PASS_BEAUTY, ER_PASS_NORMAL, ER_PASS_TANGENT, ER_PASS_BITANGENT};
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        float4* pp = S.passes + er_pass_index(npx, planes[q], idx);
-                        float4 p = *pp;
-                        if (sa > 0) { p.x *= k; p.y *= k; p.z *= k; }
-                        p.x += vals[q].x / inv; p.y += vals[q].y / inv; p.z += vals[q].z / inv;
-                        *pp = p;
-                    }
-                    S.samples[idx] = sa + 1;
-                }
+                const float4 an = W.aov_n[slot], at = W.aov_t[slot], ab = W.aov_b[slot];
+                const uint32_t sa = S.samples[idx];
+                const uint32_t sa2 = accumulate_sample(S, idx, sa, light, f3(an.x, an.y, an.z), f3(at.x, at.y, at.z), f3(ab.x, ab.y, ab.z));
+                if (sa2 != sa) S.samples[idx] = sa2;
                 S.rng[idx] = rs;
                 c_paths++;
                 uint32_t left = W.left[slot] - 1;
                 W.left[slot] = left;
-                if (left > 0) {
+                if (left > 0) {   // the pixel's next sample starts in the same slot
                     float c1 = rng_next(rs), c2 = rng_next(rs), c3 = rng_next(rs), c4 = rng_next(rs), c5 = rng_next(rs);
                     ray = camera_ray(S.cam, (int)px, (int)py, S.x_res, S.y_res, c1, c2, c3, c4, c5);
-                    light = f3s(0);
-                    reduction = f3s(1);
-                    bounce = 0;
-                    prev_pdf = -1.0f;
-                    mesh_d = 0.0f;
-                    W.aov_n[slot] = make_float4(0, 0, 0, 0);
-                    W.aov_t[slot] = make_float4(0, 0, 0, 0);
-                    W.aov_b[slot] = make_float4(0, 0, 0, 0);
+                    ER_SLOT_RESET(slot, ray, rs);
                     next_entry = slot;
                     push_closest = true;
-                } else {
-                    alive = false;
                 }
+                store = false;
             } else {
                 next_entry = slot;
                 push_closest = true;
             }
             push_shadow = pending;
             push_light = EXT && lpending;
-            if (alive) {
-                if (!(next_entry & ER_WF_FINALIZE_ONLY)) {
-                    W.ray_o[slot] = make_float4(ray.o.x, ray.o.y, ray.o.z, MESH ? mesh_d : 0.0f);
-                    W.ray_d[slot] = make_float4(ray.d.x, ray.d.y, ray.d.z, EXT ? prev_pdf : -1.0f);
-                }
-                W.light[slot] = make_float4(light.x, light.y, light.z, __builtin_bit_cast(float, rs));
-                W.reduc[slot] = make_float4(reduction.x, reduction.y, reduction.z,
-                                            __builtin_bit_cast(float, bounce | (pending ? WF_PENDING : 0u) | ((EXT && lpending) ? WF_LPENDING : 0u)));
-            }
+            if (store) { ER_SLOT_STORE(slot, !(next_entry & ER_WF_FINALIZE_ONLY)); }
         }
         const unsigned long long mc = __ballot(push_closest), ms = __ballot(push_shadow);
         const unsigned long long below = (1ull << lane) - 1ull;
@@ -472,20 +370,14 @@ __global__ __launch_bounds__(64, WF_SHADE_WAVES) void er_wf_shade(DevScene S, Wf
     __syncthreads();
     queue_flush(&W.counts[WF_NC + WF_PAR(parity ^ 1)], qn, s_qc, n_qc);
     queue_flush(&W.counts[WF_NS + WF_PAR(parity ^ 1)], qsn, s_qs, n_qs);
-    unsigned t0 = wave_sum_u(c_paths), t1 = wave_sum_u(c_bounce), t3 = wave_sum_u(c_shaded), t4 = wave_sum_u(c_hdri);
-    unsigned t7 = COUNT ? wave_sum_u(c_texels) : 0;
+    unsigned t0 = wave_sum(c_paths), t1 = wave_sum(c_bounce), t3 = wave_sum(c_shaded), t4 = wave_sum(c_hdri);
     // (the exact re-traces of overflowed rays above visit nodes and test triangles too: the streaming kernel's shader waves count theirs)
-    unsigned t5 = COUNT ? wave_sum_u(c_nodes) : 0, t6 = COUNT ? wave_sum_u(c_tris) : 0;
-    if (lane == 0 && t1 + t0) {
-        atomicAdd(&S.counters->paths, (unsigned long long)t0);
-        atomicAdd(&S.counters->bounce_samples, (unsigned long long)t1);
-        atomicAdd(&S.counters->shaded_hits, (unsigned long long)t3);
-        atomicAdd(&S.counters->hdri_samples, (unsigned long long)t4);
+    unsigned t5 = 0, t6 = 0, t7 = 0;
+    if (COUNT) { t5 = wave_sum(c_nodes); t6 = wave_sum(c_tris); t7 = wave_sum(c_texels); }
+    // (gated: this kernel counts no rays, er_device.h)
+    if (lane == 0 && t0 + t1) {
+        ER_FLUSH_COUNTERS(true, t0, t1, 0, t3, t4, t5, t6);
         if (COUNT) atomicAdd(&S.counters->texel_fetches, (unsigned long long)t7);
-        if (COUNT && t5 + t6) {
-            atomicAdd(&S.counters->node_visits, (unsigned long long)t5);
-            atomicAdd(&S.counters->tri_tests, (unsigned long long)t6);
-        }
     }
 }
 

@@ -138,7 +138,7 @@ typedef struct ErSceneDesc {
 #define ER_FLAG_HOST_BUILD   512u /* force the host build (er_bvh.cpp) */
 
 /* The largest ErRenderParams::max_bounces: every schedule keeps a path's bounce count in 16 bits of a packed word, below its flag bits
- * (csrc/er_wavefront.hip WF_PENDING, csrc/er_stream.hip WF_PENDING_BIT).  er_render_begin refuses a larger value. */
+ * (csrc/er_wavefront.h ER_SLOT_PENDING).  er_render_begin refuses a larger value. */
 #define ER_MAX_BOUNCES 65535u
 
 /* reference RenderParameters (src/kernel.h:51-69) + what the MI355X build adds. */
