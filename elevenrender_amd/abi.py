@@ -315,6 +315,16 @@ def debug_bvh_dump(vertices, normals, threads=0):
     return accel_dump_dict(info, nodes=nodes, nodes8=nodes8, slot_to_tri=s2t, tri_lift=lift)
 
 
+def debug_spill_levels(spilled, n, usable):
+    """include/eleven_hip_debug.h er_debug_spill_levels: what er_debug_trace_rays_levels says about a spill area read back, on a caller's
+    buffer (uint32 [ceil(n / 64)][stack levels][64][2], 0xFFFFFFFF where nothing was written; no device needed).  Returns uint32[n]
+    levels; raises ErError(ER_ERR_STATE) for an entry that should not be there."""
+    buf = np.ascontiguousarray(spilled, np.uint32)
+    levels = np.zeros(n, np.uint32)
+    check(load().er_debug_spill_levels(buf.ctypes.data_as(C.c_void_p), buf.nbytes, n, usable, levels.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return levels
+
+
 def debug_transform_apply(m, vertices, normals, tangents):
     """include/eleven_hip_debug.h er_debug_transform_apply: the host form of er_render_transform's arithmetic (csrc/er_xform.h; no device
     needed) on [n][3][3] rest arrays: the posed (vertices, normals, tangents)."""
@@ -606,6 +616,8 @@ OPTIONAL_SYMBOLS = {
     "er_debug_transform_apply": (C.c_int, [_FP, C.c_uint32, _FP, _FP, _FP, _FP, _FP, _FP]),
     "er_debug_accel_cost_host": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(ErCostSumsDebug), C.POINTER(C.c_double), C.c_uint64, _FP, C.c_uint64]),
     "er_debug_id_rank": (C.c_int, [_UP, C.c_uint32, _UP, _UP, _UP]),
+    "er_debug_spill_levels": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32, _UP]),
+    "er_debug_trace_rays_levels": (C.c_int, [_P, _FP, _FP, C.c_uint32, _IP, _FP, _IP, _IP, _FP, _FP, _IP, _UP, _UP, _UP]),
     "er_debug_history_camera": (C.c_int, [_P, _FP]),
     "er_debug_history_project": (C.c_int, [_FP, C.c_uint32, C.c_uint32, C.c_uint32, _FP, _FP, _UP]),
     "er_debug_history_back_matrix": (C.c_int, [_FP, _FP, _FP]),

@@ -19,6 +19,8 @@
 // Stack levels of the WIDE traversal (one entry per level of the 8-wide tree at most): the first WF_LDS_STACK (er_trav.h) of them in LDS, the others in the HBM spill
 // area, which is sized for all of them.  The wide tree is far shallower than the binary one it is collapsed from (C2: 9 levels, C4: 11; the binary
 // routines' own stacks stay ER_BVH_MAX_DEPTH deep, ER_STACK in er_device.h); er_render_begin refuses a scene whose wide tree is deeper.
+// The levels beyond the LDS ones are tested, not only sized: tests/test_gpu_deep_tree.py holds every kernel that addresses the area to the oracle on a
+// 648-triangle scene whose camera rays keep 14 entries (6 levels of the area; a stride wrong by fewer levels than the 32 - 6 unused ones would still pass).
 #ifndef ER_STACK8
 #define ER_STACK8 32
 #endif

@@ -13,6 +13,8 @@ struct DevScene;
 // nearer than limit[i]).  spill: blocks x ER_STACK8 x 64 uint2 (er_trav.h).
 void er_launch_debug_trace(const DevScene& S, const float* o, const float* d, uint32_t n, const int32_t* self, const float* limit,
                            int32_t* tri, int32_t* slot, float* pos, float* dist, int32_t* info, void* spill, hipStream_t stream);
+// WF_LDS_STACK (er_trav.h) as the kernels were compiled: the stack levels that stay in LDS, for host code that reads a spill buffer back
+uint32_t er_debug_lds_stack_levels();
 // ONE more sample of pixel idx, one record per executed bounce-loop iteration.  spill: ER_DEBUG_PIXEL_SCRATCH uint2.
 // (derived from the depth bounds: the wide traversal's spill levels occupy entries [0, ER_STACK8 x 64), the exact routine's int stack
 // -- ER_BVH_MAX_DEPTH levels x 64 ints = half as many uint2 -- follows them; er_debug.hip asserts the two agree)

@@ -54,6 +54,7 @@ void er_launch_debug_trace(const DevScene& S, const float* o, const float* d, ui
     if (n == 0) return;
     hipLaunchKernelGGL(er_debug_trace_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, S, o, d, n, self, limit, tri, slot, pos, dist, info, (uint2*)spill);
 }
+uint32_t er_debug_lds_stack_levels() { return WF_LDS_STACK; }
 
 // ---- per-bounce trace of one pixel-sample: er_bounce.inc over the production traversal, queries traced at once ----
 template <bool EXT, bool MESH>

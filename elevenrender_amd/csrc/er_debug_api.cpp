@@ -324,8 +324,37 @@ static int er_debug_bvh_dump_impl(const float* vertices, const float* normals, u
     return dump_put(who, tri_lift, lift_cap, b.tri_lift.data(), (uint64_t)tri_count * 4, false, nullptr);
 }
 
+// What a spill buffer of er_launch_debug_trace, filled with 0xFF bytes before the launch, says after it: levels[i] = the leading levels of
+// ray i's own column that hold an entry.  Returns what is wrong ("" = nothing): an entry above an unwritten level of its column, at or
+// above level `usable`, or in the column of a lane that had no ray.
+static std::string spill_levels_of(const uint2* spilled, uint32_t n, uint32_t usable, uint32_t* levels) {
+    const uint32_t blocks = (n + 63) / 64;
+    auto written = [](const uint2& e) { return e.x != 0xFFFFFFFFu || e.y != 0xFFFFFFFFu; };
+    auto where = [](uint32_t b, uint32_t l, uint32_t k) { return "block " + std::to_string(b) + " lane " + std::to_string(l) + " level " + std::to_string(k); };
+    for (uint32_t b = 0; b < blocks; b++)
+        for (uint32_t l = 0; l < 64; l++) {
+            const uint2* col = spilled + (size_t)b * ER_STACK8 * 64 + l;
+            const uint32_t ray = b * 64 + l;
+            uint32_t lead = 0;
+            while (lead < (uint32_t)ER_STACK8 && written(col[(size_t)lead * 64])) lead++;
+            for (uint32_t k = lead; k < (uint32_t)ER_STACK8; k++)
+                if (written(col[(size_t)k * 64])) return where(b, l, k) + " holds an entry above the unwritten level " + std::to_string(lead);
+            if (ray >= n) {
+                if (lead) return where(b, l, 0) + " holds an entry, and the lane had no ray";
+                continue;
+            }
+            if (lead > usable) return where(b, l, lead - 1) + " holds an entry, and the wide tree has only " + std::to_string(usable) + " levels beyond the LDS ones";
+            levels[ray] = lead;
+        }
+    return "";
+}
+
+// spill_levels != nullptr: er_debug_trace_rays_levels.  The spill buffer is filled with 0xFF bytes before the launch -- a pushed entry's
+// second word is nmask | imask << 8 (trav_choose), at most 0xFFFF, so the fill can never be an entry -- and read back after it: block b's
+// region is ER_STACK8 levels of 64 columns, lane l's column the entries l, 64 + l, ...  (er_debug.hip: spill_base + b * ER_STACK8 * 64 + l).
 static int er_debug_trace_rays_impl(ErScene* s, const float* origins, const float* dirs, uint32_t n, const int32_t* self_slots, const float* limits,
-                                    int32_t* tri_ids, int32_t* slots, float* positions, float* distances, int32_t* info) {
+                                    int32_t* tri_ids, int32_t* slots, float* positions, float* distances, int32_t* info,
+                                    uint32_t* spill_levels = nullptr) {
     if (!s || !origins || !dirs || !tri_ids || !slots || !positions || !distances || !info || (self_slots && !limits))
         return fail(ER_ERR_INVALID_ARG, "er_debug_trace_rays: NULL argument");
     std::lock_guard<std::mutex> lk(s->mtx);
@@ -349,7 +378,9 @@ static int er_debug_trace_rays_impl(ErScene* s, const float* origins, const floa
     if ((rc = upload(d_tri, (const int32_t*)nullptr, (size_t)n, s->stream)) != ER_OK) return rc;
     if ((rc = upload(d_slot, (const int32_t*)nullptr, (size_t)n, s->stream)) != ER_OK) return rc;
     if ((rc = upload(d_info, (const int32_t*)nullptr, (size_t)n, s->stream)) != ER_OK) return rc;
-    if ((rc = upload(d_spill, (const uint2*)nullptr, (size_t)((n + 63) / 64) * ER_STACK8 * 64, s->stream)) != ER_OK) return rc;
+    const size_t spill_entries = (size_t)((n + 63) / 64) * ER_STACK8 * 64;
+    if ((rc = upload(d_spill, (const uint2*)nullptr, spill_entries, s->stream)) != ER_OK) return rc;
+    if (spill_levels && spill_entries) HIP_TRY(hipMemsetAsync(d_spill.p, 0xFF, spill_entries * sizeof(uint2), s->stream));
     er_launch_debug_trace(s->dev, d_o.p, d_d.p, n, self_slots ? d_self.p : nullptr, self_slots ? d_lim.p : nullptr, d_tri.p, d_slot.p, d_pos.p,
                           d_dist.p, d_info.p, d_spill.p, s->stream);
     HIP_TRY(hipGetLastError());
@@ -358,7 +389,16 @@ static int er_debug_trace_rays_impl(ErScene* s, const float* origins, const floa
     HIP_TRY(hipMemcpyAsync(info, d_info.p, (size_t)n * 4, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipMemcpyAsync(positions, d_pos.p, (size_t)n * 12, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipMemcpyAsync(distances, d_dist.p, (size_t)n * 4, hipMemcpyDeviceToHost, s->stream));
+    std::vector<uint2> spilled(spill_levels ? spill_entries : 0);
+    if (!spilled.empty()) HIP_TRY(hipMemcpyAsync(spilled.data(), d_spill.p, spill_entries * sizeof(uint2), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
+    if (spill_levels) {
+        // a level of the area can hold an entry only if the tree has a level for it: sp stays below the wide depth (er_trav.h)
+        const uint32_t depth8 = s->accel.max_depth, lds = er_debug_lds_stack_levels();
+        const uint32_t usable = depth8 > lds ? std::min<uint32_t>(depth8 - lds, ER_STACK8) : 0u;
+        const std::string bad = spill_levels_of(spilled.data(), n, usable, spill_levels);
+        if (!bad.empty()) return fail(ER_ERR_STATE, "er_debug_trace_rays_levels: " + bad);
+    }
     return ER_OK;
 }
 
@@ -566,6 +606,24 @@ int er_debug_bvh_check(const float* vertices, const float* normals, uint32_t tri
 int er_debug_trace_rays(ErScene* s, const float* origins, const float* dirs, uint32_t n, const int32_t* self_slots, const float* limits, int32_t* tri_ids,
                         int32_t* slots, float* positions, float* distances, int32_t* info) {
     return guarded("er_debug_trace_rays", [&]() -> int { return er_debug_trace_rays_impl(s, origins, dirs, n, self_slots, limits, tri_ids, slots, positions, distances, info); });
+}
+int er_debug_trace_rays_levels(ErScene* s, const float* origins, const float* dirs, uint32_t n, const int32_t* self_slots, const float* limits, int32_t* tri_ids,
+                               int32_t* slots, float* positions, float* distances, int32_t* info, uint32_t* spill_levels, uint32_t* lds_levels, uint32_t* stack_levels) {
+    return guarded("er_debug_trace_rays_levels", [&]() -> int {
+        if (!spill_levels || !lds_levels || !stack_levels) return fail(ER_ERR_INVALID_ARG, "er_debug_trace_rays_levels: NULL argument");
+        *lds_levels = er_debug_lds_stack_levels();
+        *stack_levels = ER_STACK8;
+        return er_debug_trace_rays_impl(s, origins, dirs, n, self_slots, limits, tri_ids, slots, positions, distances, info, spill_levels);
+    });
+}
+int er_debug_spill_levels(const void* spilled, uint64_t spilled_bytes, uint32_t n, uint32_t usable, uint32_t* levels) {
+    return guarded("er_debug_spill_levels", [&]() -> int {
+        if (!spilled || !levels) return fail(ER_ERR_INVALID_ARG, "er_debug_spill_levels: NULL argument");
+        if (spilled_bytes != (uint64_t)((n + 63) / 64) * ER_STACK8 * 64 * sizeof(uint2)) return fail(ER_ERR_INVALID_ARG, "er_debug_spill_levels: the buffer is not ceil(n / 64) regions of ER_STACK8 x 64 entries");
+        const std::string bad = spill_levels_of((const uint2*)spilled, n, usable, levels);
+        if (!bad.empty()) return fail(ER_ERR_STATE, "er_debug_spill_levels: " + bad);
+        return ER_OK;
+    });
 }
 int er_debug_trace_pixel(ErScene* s, uint32_t idx, ErTraceRec* recs, int max_recs, int* count) {
     return guarded("er_debug_trace_pixel", [&]() -> int { return er_debug_trace_pixel_impl(s, idx, recs, max_recs, count); });

@@ -657,9 +657,11 @@ class RenderingManager:
         abi.check(self.lib.er_debug_closest_hit(self.handle, fp(o), fp(d), n, tri.ctypes.data_as(C.POINTER(C.c_int32)), fp(pos), fp(dist)))
         return tri, pos, dist
 
-    def debug_trace_rays(self, origins, dirs, self_slots=None, limits=None):
+    def debug_trace_rays(self, origins, dirs, self_slots=None, limits=None, levels=False):
         """include/eleven_hip_debug.h: rays through the PRODUCTION traversal (er_trav.h + resolve_closest/resolve_shadow).
-        Closest queries return (tri, slot, pos, dist, info); shadow queries (self_slots given) return (occluded, info)."""
+        Closest queries return (tri, slot, pos, dist, info); shadow queries (self_slots given) return (occluded, info).
+        levels=True (er_debug_trace_rays_levels) appends a dict: spill_levels uint32[n] (the levels of its column of the HBM spill area each
+        ray wrote), lds_levels (WF_LDS_STACK) and stack_levels (ER_STACK8) as compiled."""
         o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
         n = len(o)
@@ -667,13 +669,20 @@ class RenderingManager:
         pos, dist = np.empty((n, 3), np.float32), np.empty(n, np.float32)
         fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        ss = None if self_slots is None else np.ascontiguousarray(self_slots, np.int32)
+        lim = None if self_slots is None else np.ascontiguousarray(limits, np.float32)
+        args = (self.handle, fp(o), fp(d), n, None if ss is None else ip(ss), None if ss is None else fp(lim), ip(tri), ip(slot), fp(pos), fp(dist), ip(info))
+        extra = ()
+        if levels:
+            spill = np.zeros(n, np.uint32)
+            lds, stack = C.c_uint32(), C.c_uint32()
+            abi.check(self.lib.er_debug_trace_rays_levels(*args, spill.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(lds), C.byref(stack)))
+            extra = ({"spill_levels": spill, "lds_levels": lds.value, "stack_levels": stack.value},)
+        else:
+            abi.check(self.lib.er_debug_trace_rays(*args))
         if self_slots is None:
-            abi.check(self.lib.er_debug_trace_rays(self.handle, fp(o), fp(d), n, None, None, ip(tri), ip(slot), fp(pos), fp(dist), ip(info)))
-            return tri, slot, pos, dist, info
-        ss = np.ascontiguousarray(self_slots, np.int32)
-        lim = np.ascontiguousarray(limits, np.float32)
-        abi.check(self.lib.er_debug_trace_rays(self.handle, fp(o), fp(d), n, ip(ss), fp(lim), ip(tri), ip(slot), fp(pos), fp(dist), ip(info)))
-        return tri.astype(bool), info
+            return (tri, slot, pos, dist, info) + extra
+        return (tri.astype(bool), info) + extra
 
     def debug_eval(self, kind, items, out_width):
         """include/eleven_hip_debug.h er_debug_eval: one DEVICE function of the path per row of `items` ([n, in_width] float32;

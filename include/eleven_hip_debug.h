@@ -97,6 +97,21 @@ int er_debug_closest_hit(struct ErScene* scene, const float* origins, const floa
 int er_debug_trace_rays(struct ErScene* scene, const float* origins, const float* dirs, uint32_t n, const int32_t* self_slots,
                         const float* limits, int32_t* tri_ids, int32_t* slots, float* positions, float* distances, int32_t* info);
 
+/* er_debug_trace_rays, and what the queries left in the traversal's HBM spill area.  A lane's stack keeps its first *lds_levels entries
+ * (WF_LDS_STACK as compiled) in LDS and the deeper ones in its own column of the spill area, *stack_levels (ER_STACK8 as compiled)
+ * levels in all.  The call fills the area with 0xFF bytes before the launch (no entry has that value) and reads it back after it:
+ * spill_levels[i] = the leading levels of ray i's column that were written, so ray i's stack reached *lds_levels + spill_levels[i]
+ * entries.  ER_ERR_STATE (the rays' results are delivered all the same) if an entry lies above an unwritten level of its column, at
+ * level (wide depth - *lds_levels) or above, or in the column of a lane that had no ray. */
+int er_debug_trace_rays_levels(struct ErScene* scene, const float* origins, const float* dirs, uint32_t n, const int32_t* self_slots,
+                               const float* limits, int32_t* tri_ids, int32_t* slots, float* positions, float* distances, int32_t* info,
+                               uint32_t* spill_levels, uint32_t* lds_levels, uint32_t* stack_levels);
+
+/* The judgement er_debug_trace_rays_levels passes on the spill area it read back, on a caller's buffer (host code, no device): `spilled`
+ * holds ceil(n / 64) regions of *stack_levels levels x 64 lanes x 2 words, filled with 0xFF bytes where nothing was written; `usable` is
+ * the wide depth minus *lds_levels.  levels[i] = the leading written levels of ray i's column; ER_ERR_STATE as described above. */
+int er_debug_spill_levels(const void* spilled, uint64_t spilled_bytes, uint32_t n, uint32_t usable, uint32_t* levels);
+
 /* One record per executed bounce-loop iteration (reference src/kernel.cpp:508-592); the same fields, in the same order, as the oracle's
  * OracleTraceRec begins with (oracle/er_oracle.h; the oracle's record goes on with fields of its own). */
 typedef struct ErTraceRec {
