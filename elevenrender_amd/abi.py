@@ -243,6 +243,11 @@ class ErDenoiseVariance(C.Structure):
     _fields_ = [("levels", C.c_uint32), ("colour_sigma", C.c_float), ("albedo_sigma", C.c_float), ("depth_sigma", C.c_float)]
 
 
+class ErHistoryVarianceInfo(C.Structure):
+    _fields_ = [("captured", C.c_uint32), ("resolved", C.c_uint32), ("pixels_known_captured", C.c_uint64), ("pixels_known_history", C.c_uint64),
+                ("pixels_known_blended", C.c_uint64), ("filter_ms", C.c_float)]
+
+
 class ErPick(C.Structure):
     _fields_ = [("hit", C.c_uint32), ("triangle", C.c_uint32), ("object", C.c_uint32), ("material", C.c_uint32), ("distance", C.c_float),
                 ("position", C.c_float * 3), ("uv", C.c_float * 2)]
@@ -409,6 +414,83 @@ def debug_history_blend(beauty, samples, hist):
     return out
 
 
+def _opt4(a, width=4):
+    return None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1, width)
+
+
+def _optp(a):
+    return None if a is None else _fptr(a)
+
+
+def debug_history_variance_current(state):
+    """include/eleven_hip_debug.h er_debug_history_variance_current: (s2.rgb, K >= 2) float32[n][4] of states [n][12]
+    (csrc/er_history_variance.h; no device needed) -- elevenrender_amd/history_variance.py current() restates it"""
+    st = _opt4(state, 12)
+    out = np.zeros((len(st), 4), np.float32)
+    check(load().er_debug_history_variance_current(len(st), _fptr(st), _fptr(out)))
+    return out
+
+
+def debug_history_variance_pool(s_h, w, s_c, n):
+    """er_debug_history_variance_pool: (pool.rgb, flag) float32[n][4]"""
+    a, b = _opt4(s_h), _opt4(s_c)
+    w, n = np.ascontiguousarray(w, np.float32).reshape(-1), np.ascontiguousarray(n, np.float32).reshape(-1)
+    out = np.zeros((len(a), 4), np.float32)
+    check(load().er_debug_history_variance_pool(len(a), _fptr(a), _fptr(w), _fptr(b), _fptr(n), _fptr(out)))
+    return out
+
+
+def debug_history_variance_capture(state, samples, hist, hv):
+    """er_debug_history_variance_capture: SV float32[n][4]; state None = K 0, hist None = w 0, hv None = no carried variance"""
+    st, h, v = _opt4(state, 12), _opt4(hist), _opt4(hv)
+    s = np.ascontiguousarray(samples, np.uint32).reshape(-1)
+    out = np.zeros((len(s), 4), np.float32)
+    check(load().er_debug_history_variance_capture(len(s), _optp(st), s.ctypes.data_as(_UP), _optp(h), _optp(v), _fptr(out)))
+    return out
+
+
+def debug_history_variance_mean(tap_state, tap_w, tap_sv):
+    """er_debug_history_variance_mean: HV float32[n][4] from tap states [n][4], tap weights [n][4] and the taps' SV [n][4][4]"""
+    st = np.ascontiguousarray(tap_state, np.uint32).reshape(-1, 4)
+    tw, sv = _opt4(tap_w), _opt4(tap_sv, 16)
+    out = np.zeros((len(st), 4), np.float32)
+    check(load().er_debug_history_variance_mean(len(st), st.ctypes.data_as(_UP), _fptr(tw), _fptr(sv), _fptr(out)))
+    return out
+
+
+def debug_history_variance_taps(cam, x_res, y_res, tol, hit, obj, P, moved, back, old_hit, old_obj, old_dist, old_cw, old_sv):
+    """er_debug_history_variance_taps: (rgbw, hv float32[n][4], state uint32[n][4], class uint32[n]) -- history_variance.py resolve()"""
+    u32 = lambda a: np.ascontiguousarray(a, np.uint32).reshape(-1)
+    f32 = lambda a: np.ascontiguousarray(a, np.float32).reshape(-1)
+    c, hit, obj, P, moved, back = f32(cam), u32(hit), u32(obj), f32(P), u32(moved), f32(back)
+    old_hit, old_obj, old_dist, old_cw, old_sv = u32(old_hit), u32(old_obj), f32(old_dist), f32(old_cw), f32(old_sv)
+    n = len(hit)
+    assert len(P) == 3 * n and len(back) == 12 * n and len(moved) == n and len(obj) == n
+    assert len(old_hit) == len(old_obj) == len(old_dist) == x_res * y_res and len(old_cw) == len(old_sv) == 4 * x_res * y_res
+    rgbw, hv, state, cls = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32), np.zeros((n, 4), np.uint32), np.zeros(n, np.uint32)
+    up = lambda a: a.ctypes.data_as(_UP)
+    check(load().er_debug_history_variance_taps(_fptr(c), x_res, y_res, float(tol), n, up(hit), up(obj), _fptr(P), up(moved), _fptr(back), up(old_hit), up(old_obj),
+                                                _fptr(old_dist), _fptr(old_cw), _fptr(old_sv), _fptr(rgbw), _fptr(hv), up(state), up(cls)))
+    return rgbw, hv, state, cls
+
+
+def debug_history_variance_blend(state, samples, hist, hv):
+    """er_debug_history_variance_blend: VB float32[n][4]"""
+    st, h, v = _opt4(state, 12), _opt4(hist), _opt4(hv)
+    s = np.ascontiguousarray(samples, np.uint32).reshape(-1)
+    out = np.zeros((len(s), 4), np.float32)
+    check(load().er_debug_history_variance_blend(len(s), _optp(st), s.ctypes.data_as(_UP), _fptr(h), _optp(v), _fptr(out)))
+    return out
+
+
+def debug_history_variance_split(blend, vb, albedo):
+    """er_debug_history_variance_split: (e, ve) float32[n][4]"""
+    b, v, a = _opt4(blend), _opt4(vb), _opt4(albedo)
+    e, ve = np.zeros_like(b), np.zeros_like(b)
+    check(load().er_debug_history_variance_split(len(b), _fptr(b), _fptr(v), _fptr(a), _fptr(e), _fptr(ve)))
+    return e, ve
+
+
 def debug_variance_mark(beauty, samples):
     """include/eleven_hip_debug.h er_debug_variance_mark: the state float32[n][12] of a reset (csrc/er_variance.h; no device needed) --
     elevenrender_amd/variance.py mark() restates it"""
@@ -562,6 +644,10 @@ SYMBOLS = {
     "er_variance_info": (C.c_int, [_P, C.POINTER(ErVarianceInfo)]),
     "er_read_variance": (C.c_int, [_P, _FP]),
     "er_denoise_variance": (C.c_int, [_P, C.POINTER(ErDenoiseVariance)]),
+    "er_history_variance_info": (C.c_int, [_P, C.POINTER(ErHistoryVarianceInfo)]),
+    "er_read_history_variance": (C.c_int, [_P, _FP]),
+    "er_read_blended_variance": (C.c_int, [_P, _FP]),
+    "er_denoise_blended": (C.c_int, [_P, C.POINTER(ErDenoiseVariance)]),
     "er_state_size": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "er_state_export": (C.c_int, [_P, _P, C.c_uint64]),
     "er_state_import": (C.c_int, [_P, _P, C.c_uint64]),
@@ -629,6 +715,13 @@ OPTIONAL_SYMBOLS = {
     "er_debug_variance_value": (C.c_int, [C.c_uint32, _FP, _UP, _FP]),
     "er_debug_variance_split": (C.c_int, [C.c_uint32, _FP, _FP, _FP]),
     "er_debug_variance_level_px": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
+    "er_debug_history_variance_current": (C.c_int, [C.c_uint32, _FP, _FP]),
+    "er_debug_history_variance_pool": (C.c_int, [C.c_uint32, _FP, _FP, _FP, _FP, _FP]),
+    "er_debug_history_variance_capture": (C.c_int, [C.c_uint32, _FP, _UP, _FP, _FP, _FP]),
+    "er_debug_history_variance_mean": (C.c_int, [C.c_uint32, _UP, _FP, _FP, _FP]),
+    "er_debug_history_variance_taps": (C.c_int, [_FP, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, _UP, _UP, _FP, _UP, _FP, _UP, _UP, _FP, _FP, _FP, _FP, _FP, _UP, _UP]),
+    "er_debug_history_variance_blend": (C.c_int, [C.c_uint32, _FP, _UP, _FP, _FP, _FP]),
+    "er_debug_history_variance_split": (C.c_int, [C.c_uint32, _FP, _FP, _FP, _FP, _FP]),
 }
 
 

@@ -162,6 +162,7 @@ static int begin_open(ErScene* s, const ErRenderParams* p) {
         hipError_t pe = er_probe_kernels(&which);
         if (pe == hipSuccess) pe = er_probe_ids(&which);
         if (pe == hipSuccess) pe = er_probe_history(&which);
+        if (pe == hipSuccess) pe = er_probe_history_variance(&which);
         if (pe == hipSuccess) pe = er_probe_variance(&which);
         if (pe != hipSuccess)
             return fail(ER_ERR_HIP, std::string("er_render_begin: libeleven_hip.so has no usable gfx950 code object for ") + (which ? which : "?") +

@@ -127,6 +127,9 @@ int need_begun(ErScene* s, const char* who) {
 
 size_t key_words(size_t npx) { return 6 * npx; }
 
+// k_variance_fold's grid: four workgroups per CU, a grid stride beyond
+unsigned bounded_blocks(const ErScene* s, size_t npx) { return std::min((unsigned)((npx + 255) / 256), std::max(1u, s->kept.cus) * 4u); }
+
 // the key plane of the scene as it is now into key[now]; the stream is idle
 int make_key(ErScene* s) {
     ErHistoryState& H = s->hist;
@@ -165,19 +168,41 @@ int capture_impl(ErScene* s, const ErHistoryParams* p) {
     if (H.d_cw.n < npx && (rc = upload(H.d_cw, nullptr, npx, s->stream)) != ER_OK) return rc;
     if (H.d_hist.n < npx && (rc = upload(H.d_hist, nullptr, npx, s->stream)) != ER_OK) return rc;
     if (H.d_counts.n < ER_HC_COUNT && (rc = upload(H.d_counts, nullptr, ER_HC_COUNT, s->stream)) != ER_OK) return rc;
+    // the carried variance (er_history_variance.hip): only a scene whose variance state exists pays for the two planes and the kernel
+    const bool carry = s->var.d_state.n >= 3 * npx && npx > 0;
+    if (carry) {
+        if (H.d_sv.n < npx && (rc = upload(H.d_sv, nullptr, npx, s->stream)) != ER_OK) return rc;
+        if (H.d_hv.n < npx && (rc = upload(H.d_hv, nullptr, npx, s->stream)) != ER_OK) return rc;
+        if (H.d_known.n < ER_HV_KNOWN_COUNT * ER_HV_COUNT_STRIDE && (rc = upload(H.d_known, nullptr, ER_HV_KNOWN_COUNT * ER_HV_COUNT_STRIDE, s->stream)) != ER_OK) return rc;
+    }
     EventPair ev;
     HIP_TRY(hipEventCreate(&ev.a));
     HIP_TRY(hipEventCreate(&ev.b));
     H.captured = false;
+    H.sv_captured = false;
     HIP_TRY(hipEventRecord(ev.a, s->stream));
     if (!key_current(s) && (rc = make_key(s)) != ER_OK) return rc;
     if (npx)
         hipLaunchKernelGGL(k_history_capture, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, s->stream, (const float4*)s->d_passes.p, (const uint32_t*)s->d_samples.p,
                            H.resolved ? (const float4*)H.d_hist.p : (const float4*)nullptr, p->max_weight > 0 ? p->max_weight : 32.0f, npx, H.d_cw.p);
+    uint32_t known = 0;
+    if (carry) {
+        // a pending restart has not reached the planes yet: they hold the moments of the frame before the edit, and K = 0 is what counts
+        const float4* m2k = s->var.restarted ? (const float4*)nullptr : (const float4*)s->var.d_state.p + 2 * npx;
+        uint32_t* d_known = H.d_known.p + ER_HV_KNOWN_CAPTURED * ER_HV_COUNT_STRIDE;
+        HIP_TRY(hipMemsetAsync(d_known, 0, sizeof(uint32_t), s->stream));
+        er_launch_history_variance_capture(m2k, (const uint32_t*)s->d_samples.p, H.resolved ? (const float4*)H.d_hist.p : (const float4*)nullptr,
+                                           H.resolved && H.hv_resolved ? (const float4*)H.d_hv.p : (const float4*)nullptr, npx, H.d_sv.p, d_known, bounded_blocks(s, npx), s->stream);
+        HIP_TRY(hipMemcpyAsync(&known, d_known, sizeof(known), hipMemcpyDeviceToHost, s->stream));
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev.b, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     HIP_TRY(hipEventElapsedTime(&H.capture_ms, ev.a, ev.b));
+    H.sv_captured = carry;
+    H.known_captured = known;
+    H.hv_resolved = false;
+    H.known_history = H.known_blended = 0;
     // the key made for "now" becomes the captured one: the next resolve writes the other plane
     H.now = 1 - H.now;
     H.key_valid = false;
@@ -218,22 +243,35 @@ int resolve_impl(ErScene* s) {
     HIP_TRY(hipEventCreate(&ev.a));
     HIP_TRY(hipEventCreate(&ev.b));
     H.resolved = false;
+    H.hv_resolved = false;
+    const bool carry = H.sv_captured && npx > 0;      // the held capture carries SV: one kernel takes the taps once for both planes
+    uint32_t* d_known = carry ? H.d_known.p + ER_HV_KNOWN_HISTORY * ER_HV_COUNT_STRIDE : nullptr;
     HIP_TRY(hipEventRecord(ev.a, s->stream));
     if (objects) HIP_TRY(hipMemcpyAsync(H.d_back.p, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemsetAsync(H.d_counts.p, 0, ER_HC_COUNT * sizeof(unsigned long long), s->stream));
+    if (carry) HIP_TRY(hipMemsetAsync(d_known, 0, sizeof(uint32_t), s->stream));
     if ((rc = make_key(s)) != ER_OK) return rc;
-    if (npx)
+    if (carry)
+        er_launch_history_resolve_variance((const uint32_t*)H.d_key[H.now].p, (const uint32_t*)H.d_key[1 - H.now].p, (const float4*)H.d_cw.p, (const float4*)H.d_sv.p,
+                                           (const float*)H.d_back.p, objects, reproj_cam(H.cap_cam), s->x_res, s->y_res, H.tol, H.d_hist.p, H.d_hv.p, H.d_counts.p, d_known,
+                                           bounded_blocks(s, npx), s->stream);
+    else if (npx)
         hipLaunchKernelGGL(k_history_resolve, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, s->stream, (const uint32_t*)H.d_key[H.now].p, (const uint32_t*)H.d_key[1 - H.now].p,
                            (const float4*)H.d_cw.p, (const float*)H.d_back.p, objects, reproj_cam(H.cap_cam), s->x_res, s->y_res, H.tol, H.d_hist.p, H.d_counts.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev.b, s->stream));
     unsigned long long counts[ER_HC_COUNT] = {0, 0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(counts, H.d_counts.p, sizeof(counts), hipMemcpyDeviceToHost, s->stream));
+    uint32_t known = 0;
+    if (carry) HIP_TRY(hipMemcpyAsync(&known, d_known, sizeof(known), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));      // (`table` goes out of scope)
     HIP_TRY(hipEventElapsedTime(&H.resolve_ms, ev.a, ev.b));
     for (int c = 0; c < ER_HC_COUNT; c++) H.classes[c] = counts[c];
     H.moved_objects = moved_objects;
     H.resolved = true;
+    H.hv_resolved = carry;
+    H.known_history = known;
+    H.known_blended = 0;
     return er_scene_stream_status(s, "er_history_resolve");
 }
 

@@ -164,24 +164,35 @@ ER_RP_HD inline void er_history_blend_px(const float* beauty_rgb, uint32_t sampl
     out[3] = 1.0f;
 }
 
+// The four taps of one pixel of a resolve: their states, their bilinear weights and their pixels in the captured frame (q: 0 for a tap
+// outside it, which is never read).  What every plane carried beside the colour is gathered through (er_history_variance.h).
+ER_RP_HD inline void er_history_tap_set(const ErHistoryKey& k, const float* back, uint32_t moved, const ErReprojCam& cam, uint32_t x_res, uint32_t y_res, float tol,
+                                        const uint32_t* old_hit, const uint32_t* old_object, const float* old_dist, int* state /*[4]*/, float* tw /*[4]*/, size_t* q /*[4]*/) {
+    float Po[3], fx, fy;
+    er_history_old_point(k, back, moved, cam.pos, Po);
+    const bool projected = er_history_project(cam, x_res, y_res, Po, &fx, &fy);
+    const float d_exp = er_rp_length(Po[0] - cam.pos[0], Po[1] - cam.pos[1], Po[2] - cam.pos[2]);
+    int tx[4], ty[4];
+    bool inside[4];
+    er_history_tap_geometry(projected, fx, fy, x_res, y_res, tx, ty, tw, inside);
+    for (int t = 0; t < 4; t++) {
+        q[t] = inside[t] ? (size_t)ty[t] * x_res + (size_t)tx[t] : 0;
+        state[t] = er_history_tap_state(inside[t], k.hit, k.object, d_exp, tol, inside[t] ? old_hit[q[t]] : 0u, inside[t] ? old_object[q[t]] : 0u, inside[t] ? old_dist[q[t]] : 0.0f);
+    }
+}
+
 // One pixel of a resolve, from plain arrays: the new key k, the object's back matrix, the captured camera, the captured key plane
 // (old_hit / old_object / old_dist, row-major) and the captured (C, W) plane.  out = (H.rgb, w); returns the pixel's class.  What the
 // device kernel runs per work item and what er_debug_history_taps runs per query.
 ER_RP_HD inline int er_history_resolve_px(const ErHistoryKey& k, const float* back, uint32_t moved, const ErReprojCam& cam, uint32_t x_res, uint32_t y_res, float tol,
                                           const uint32_t* old_hit, const uint32_t* old_object, const float* old_dist, const float* old_cw /*[npx][4]*/, float* out,
                                           int* state_out /*[4] or NULL*/) {
-    float Po[3], fx, fy;
-    er_history_old_point(k, back, moved, cam.pos, Po);
-    const bool projected = er_history_project(cam, x_res, y_res, Po, &fx, &fy);
-    const float d_exp = er_rp_length(Po[0] - cam.pos[0], Po[1] - cam.pos[1], Po[2] - cam.pos[2]);
-    int tx[4], ty[4], state[4];
+    int state[4];
     float tw[4], cw[4][4];
-    bool inside[4];
-    er_history_tap_geometry(projected, fx, fy, x_res, y_res, tx, ty, tw, inside);
+    size_t q[4];
+    er_history_tap_set(k, back, moved, cam, x_res, y_res, tol, old_hit, old_object, old_dist, state, tw, q);
     for (int t = 0; t < 4; t++) {
-        const size_t q = inside[t] ? (size_t)ty[t] * x_res + (size_t)tx[t] : 0;
-        state[t] = er_history_tap_state(inside[t], k.hit, k.object, d_exp, tol, inside[t] ? old_hit[q] : 0u, inside[t] ? old_object[q] : 0u, inside[t] ? old_dist[q] : 0.0f);
-        for (int c = 0; c < 4; c++) cw[t][c] = state[t] == ER_TAP_VALID ? old_cw[q * 4 + c] : 0.0f;
+        for (int c = 0; c < 4; c++) cw[t][c] = state[t] == ER_TAP_VALID ? old_cw[q[t] * 4 + c] : 0.0f;
         if (state_out) state_out[t] = state[t];
     }
     er_history_mean(state, tw, cw, out);

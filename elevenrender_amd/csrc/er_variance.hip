@@ -219,14 +219,10 @@ int read_impl(ErScene* s, float* dst) {
 
 int denoise_impl(ErScene* s, const ErDenoiseVariance* p) {
     if (!s || !p) return fail(ER_ERR_INVALID_ARG, "er_denoise_variance: NULL argument");
-    uint32_t levels = p->levels;
-    float sc = p->colour_sigma, sa = p->albedo_sigma, sz = p->depth_sigma;
-    if (levels > 8) return fail(ER_ERR_INVALID_ARG, "er_denoise_variance: at most 8 levels");
-    if (!(sc >= 0) || !(sa >= 0) || !(sz >= 0)) return fail(ER_ERR_INVALID_ARG, "er_denoise_variance: the sigmas must be >= 0 (and not NaN)");
-    if (levels == 0) levels = 5;
-    if (sc == 0) sc = 6.0f;      // (in standard errors of the pixel: the colour difference is divided by the variance; DESIGN.md 3m has the sweep)
-    if (sa == 0) sa = 0.3f;
-    if (sz == 0) sz = 0.2f;
+    uint32_t levels;
+    float kc, ka, kz;      // kc is NOT tightened per level: the propagated variance shrinks instead
+    int prc;
+    if ((prc = er_variance_filter_params(p, "er_denoise_variance", &levels, &kc, &ka, &kz)) != ER_OK) return prc;
     std::lock_guard<std::mutex> lk(s->mtx);
     int rc;
     if ((rc = need_begun(s, "er_denoise_variance")) != ER_OK) return rc;
@@ -243,7 +239,6 @@ int denoise_impl(ErScene* s, const ErDenoiseVariance* p) {
     const float4* normal = s->d_passes.p + er_pass_index(npx, ER_PASS_NORMAL, 0);
     float4* out = s->d_passes.p + er_pass_index(npx, ER_PASS_DENOISE, 0);
     const float4 *alb = s->d_feat.p + (size_t)ER_FEATURE_ALBEDO * npx, *dep = s->d_feat.p + (size_t)ER_FEATURE_DEPTH * npx;
-    const float kc = 1.0f / (sc * sc), ka = 1.0f / (sa * sa), kz = 1.0f / (sz * sz);      // kc is NOT tightened per level: the propagated variance shrinks instead
     float4 *bufs[2] = {tmp.p, tmp.p + npx}, *vbufs[2] = {tmp.p + 2 * npx, tmp.p + 3 * npx};
     EventPair ev;
     HIP_TRY(hipEventCreate(&ev.a));
@@ -252,9 +247,7 @@ int denoise_impl(ErScene* s, const ErDenoiseVariance* p) {
     if (npx) {
         hipLaunchKernelGGL(er_variance_split_kernel, dim3(px_blocks(npx)), dim3(256), 0, s->stream, beauty, 4, alb, (const float4*)V.d_state.p, (const uint32_t*)s->d_samples.p, bufs[0],
                            vbufs[0], npx);
-        for (uint32_t k = 0; k < levels; k++)
-            hipLaunchKernelGGL(er_variance_level_kernel, dim3((w + 15) / 16, (h + 15) / 16), dim3(256), 0, s->stream, (const float4*)bufs[k & 1u], (const float4*)vbufs[k & 1u], normal, 4,
-                               alb, dep, bufs[(k + 1) & 1u], vbufs[(k + 1) & 1u], w, h, 1 << k, kc, ka, kz);
+        er_launch_variance_levels(bufs, vbufs, normal, 4, alb, dep, w, h, levels, kc, ka, kz, s->stream);
         er_launch_guided_join(bufs[levels & 1u], alb, beauty, 4, out, w, h, s->stream);
     }
     HIP_TRY(hipGetLastError());
@@ -265,6 +258,27 @@ int denoise_impl(ErScene* s, const ErDenoiseVariance* p) {
 }
 
 }  // namespace
+
+int er_variance_filter_params(const ErDenoiseVariance* p, const char* who, uint32_t* levels_out, float* kc, float* ka, float* kz) {
+    uint32_t levels = p->levels;
+    float sc = p->colour_sigma, sa = p->albedo_sigma, sz = p->depth_sigma;
+    if (levels > 8) return fail(ER_ERR_INVALID_ARG, std::string(who) + ": at most 8 levels");
+    if (!(sc >= 0) || !(sa >= 0) || !(sz >= 0)) return fail(ER_ERR_INVALID_ARG, std::string(who) + ": the sigmas must be >= 0 (and not NaN)");
+    if (levels == 0) levels = 5;
+    if (sc == 0) sc = 6.0f;      // (in standard errors of the pixel: the colour difference is divided by the variance; DESIGN.md 3m has the sweep)
+    if (sa == 0) sa = 0.3f;
+    if (sz == 0) sz = 0.2f;
+    *levels_out = levels;
+    *kc = 1.0f / (sc * sc); *ka = 1.0f / (sa * sa); *kz = 1.0f / (sz * sz);
+    return ER_OK;
+}
+
+void er_launch_variance_levels(float4* const bufs[2], float4* const vbufs[2], const float4* normal, int normal_stride, const float4* albedo, const float4* depth, int w, int h,
+                               uint32_t levels, float kc, float ka, float kz, hipStream_t stream) {
+    for (uint32_t k = 0; k < levels; k++)
+        hipLaunchKernelGGL(er_variance_level_kernel, dim3((w + 15) / 16, (h + 15) / 16), dim3(256), 0, stream, (const float4*)bufs[k & 1u], (const float4*)vbufs[k & 1u], normal,
+                           normal_stride, albedo, depth, bufs[(k + 1) & 1u], vbufs[(k + 1) & 1u], w, h, 1 << k, kc, ka, kz);
+}
 
 int er_variance_mark_imported(ErScene* s) {
     ErVarianceState& V = s->var;

@@ -25,6 +25,11 @@ struct ErVarianceState {
 };
 
 struct ErScene;
+// er_denoise_variance's argument checks and defaults, for every filter of this family: levels, kc = 1 / colour_sigma^2, ka, kz
+int er_variance_filter_params(const ErDenoiseVariance* p, const char* who, uint32_t* levels, float* kc, float* ka, float* kz);
+// the a-trous levels on demodulated planes: bufs[0] / vbufs[0] hold (e, ve) of er_variance.h; the result is in bufs[levels & 1]
+void er_launch_variance_levels(float4* const bufs[2], float4* const vbufs[2], const float4* normal, int normal_stride, const float4* albedo, const float4* depth, int w, int h,
+                               uint32_t levels, float kc, float ka, float kz, hipStream_t stream);
 hipError_t er_probe_variance(const char** which);      // see er_kernels.h; er_render_begin asks it beside er_probe_history
 // er_state_import's reset: the snapshot is taken from the planes as they lie now (the stream is idle, the scene's mutex held)
 int er_variance_mark_imported(ErScene* s);

@@ -32,6 +32,9 @@
 //     the variance plane whenever the samples reach a multiple of b (er_variance_fold), `denoise: true` / --get_pass denoise run the
 //     filter whose colour stop follows that plane (er_denoise_variance; the guided filter until two folds exist), --get_pass variance
 //     return the plane and --get_info report variance_folds.
+//   * config "denoise_blended": true (needs "history" and "denoise_variance" both true and gpus 1) makes `denoise: true` / --get_pass
+//     denoise answer er_denoise_blended -- the blended frame filtered by the variance the history carried -- whenever a camera update left
+//     a resolved history, the feature planes made for the new camera if they are missing; --get_info reports blended_denoises.
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -305,6 +308,7 @@ private:
             if (rm.pars.denoise_guided) j["denoise_guided"] = true;
             if (rm.pars.history) j["history_resolves"] = rm.history_resolves;      // (only with the key: a session without it answers as before)
             if (rm.pars.denoise_variance) j["variance_folds"] = rm.variance_folds();      // (the same)
+            if (rm.pars.denoise_blended) j["blended_denoises"] = rm.blended_denoises;      // (the same)
             im->write_message(Message::json_data(j));
             return;
         }
@@ -416,6 +420,10 @@ private:
             rp.variance_batch = (unsigned)b;
         }
         if (rp.denoise_variance && rp.gpus > 1) throw std::runtime_error("config denoise_variance needs gpus 1 (a sharded frame has no variance plane)");
+        // the denoise of the blended frame (er_denoise_blended) wherever a camera update left a resolved history
+        if (const json::Value* v = j.if_contains("denoise_blended")) rp.denoise_blended = v->as_bool();
+        if (rp.denoise_blended && !(rp.history && rp.denoise_variance && rp.gpus == 1))
+            throw std::runtime_error("config denoise_blended needs \"history\": true, \"denoise_variance\": true and gpus 1");
         stop_render_thread();
         rm.pars = rp;
         scene.x_res = rp.width;
@@ -502,7 +510,9 @@ private:
             return;
         }
         const bool want_denoise = parsePass(pass) == ER_PASS_DENOISE || (rm.pars.denoise && parsePass(pass) == ER_PASS_BEAUTY);
-        if (want_denoise && rm.pars.denoise_variance) {
+        if (want_denoise && rm.pars.denoise_blended && rm.get_denoised_blended(img, rm.pars.feature_samples)) {      // a resolved history exists: the blend, filtered by its own variance
+            for (size_t i = 3; i < img.size(); i += 4) img[i] = 1.0f;
+        } else if (want_denoise && rm.pars.denoise_variance) {
             img = rm.get_denoised_variance(rm.pars.feature_samples);      // features if there are none yet, er_denoise_variance (the guided filter until two folds exist), read
             for (size_t i = 3; i < img.size(); i += 4) img[i] = 1.0f;
         } else if (want_denoise && rm.pars.denoise_guided) {

@@ -144,6 +144,9 @@ struct RenderParameters {   // src/kernel.h:51-69
     bool denoise_variance = false;
     unsigned variance_batch = 0;
     unsigned fold_every() const { return denoise_variance ? (variance_batch ? variance_batch : 2u) : 0u; }
+    // with `history` and `denoise_variance`: `denoise: true` / get_pass denoise answer er_denoise_blended -- the blended frame filtered by
+    // its own variance, which the history carried across the camera update -- whenever a resolved history exists
+    bool denoise_blended = false;
 };
 
 // What a session sent since its last successful --start.  A --start after nothing but --load_camera restarts the render in place
@@ -534,6 +537,20 @@ public:
         else check(rc);
         return get_pass_unlocked(ER_PASS_DENOISE);
     }
+    // features if there are none yet + er_denoise_blended + read of the DENOISE plane (`denoise_blended`); false, and nothing done, while
+    // no resolved history exists: the caller answers as it does without the key
+    bool get_denoised_blended(std::vector<float>& out, unsigned feature_samples = 0, unsigned levels = 0, float colour_sigma = 0, float albedo_sigma = 0, float depth_sigma = 0) {
+        if (ers_.size() != 1) return false;
+        ErHistoryInfo hi{};
+        if (er_history_info(ers_[0], &hi) != ER_OK || !hi.resolved) return false;
+        if (!features_ready_) render_features_unlocked(feature_samples);
+        const ErDenoiseVariance p{levels, colour_sigma, albedo_sigma, depth_sigma};
+        check(er_denoise_blended(ers_[0], &p));
+        out = get_pass_unlocked(ER_PASS_DENOISE);
+        blended_denoises++;
+        return true;
+    }
+    unsigned blended_denoises = 0;      // answers er_denoise_blended gave (reported by --get_info)
     std::vector<float> get_pass(const std::string& pass) {   // src/Managers.cpp:287-302
         if (ers_.empty()) throw std::runtime_error("get_pass: no render has been started");
         std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);

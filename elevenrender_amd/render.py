@@ -583,6 +583,29 @@ class RenderingManager:
         p = abi.ErDenoiseVariance(levels, colour_sigma, albedo_sigma, depth_sigma)
         abi.check(self.lib.er_denoise_variance(self.handle, C.byref(p)))
 
+    def history_variance_info(self):
+        a = abi.ErHistoryVarianceInfo()
+        abi.check(self.lib.er_history_variance_info(self.handle, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in abi.ErHistoryVarianceInfo._fields_}
+
+    def get_history_variance(self):
+        """er_read_history_variance: (H, W, 4) float32 -- rgb = the per-sample variance carried by the history, a = 1 where it is known."""
+        out = np.empty((self.scene.y_res, self.scene.x_res, 4), np.float32)
+        abi.check(self.lib.er_read_history_variance(self.handle, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def get_blended_variance(self):
+        """er_read_blended_variance: (H, W, 4) float32 -- rgb = the variance of get_blended()'s colour, a = 1 where it is known."""
+        out = np.empty((self.scene.y_res, self.scene.x_res, 4), np.float32)
+        abi.check(self.lib.er_read_blended_variance(self.handle, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def denoise_blended(self, levels=0, colour_sigma=0.0, albedo_sigma=0.0, depth_sigma=0.0):
+        """Fill the DENOISE plane from the blended frame, the colour stop normalised by the blend's variance (er_denoise_blended; a
+        history_resolve and render_features first -- no folds are needed)."""
+        p = abi.ErDenoiseVariance(levels, colour_sigma, albedo_sigma, depth_sigma)
+        abi.check(self.lib.er_denoise_blended(self.handle, C.byref(p)))
+
     def read_samples(self):
         out = np.empty(self.scene.x_res * self.scene.y_res, np.uint32)
         abi.check(self.lib.er_read_samples(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint32))))

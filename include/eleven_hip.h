@@ -783,6 +783,46 @@ int er_variance_info(ErScene* scene, ErVarianceInfo* out);
 int er_read_variance(ErScene* scene, float* dst_rgba);
 int er_denoise_variance(ErScene* scene, const ErDenoiseVariance* params);
 
+/* The variance carried through the history, the variance of the blend and the denoise of the blended frame (extension; csrc/
+ * er_history_variance.h gives every float32 operation, csrc/er_history_variance.hip the kernels).  Display-side like both
+ * parents: the render's planes, sample counts, RNG and ErCounters are read and never written; only DENOISE is written.  Every output of
+ * every other entry point is, bit for bit, what it is without these calls.
+ * West's moments give the variance of ONE sample of a pixel, s2 = M2 / (float)(K - 1) per channel (values not > 0, a NaN too, become 0),
+ * known where K >= 2; a pending reset of the variance state or a state that was never allocated is K = 0 everywhere.
+ * POOL of (s2_H, k_H, w) and (s2_C, k_C, n), n = (float)(samples - 1):  useH = k_H && w > 0, useC = k_C && n > 0;  both:
+ * (w * s2_H + n * s2_C) / (w + n) per channel;  one: that one, bit for bit;  none: 0 and flag 0.
+ * er_history_capture also writes, if the scene's variance state is allocated (an er_variance_fold or er_read_variance has run), a plane
+ * SV = (pool.rgb, flag) per pixel: the pixel's resolved history variance HV with the history weight w, pooled with its current variance
+ * with n; without a resolved history w = 0 and k_H = 0.  er_history_resolve, when the held capture carries SV, takes the colour's four
+ * taps once and also writes HV = (rgb, flag): the mean of SV.rgb over the taps that are valid and whose SV flag is set, with the
+ * colour's tap weights renormalised over those taps (a plain mean, accumulated in the colour's order); flag 1 if their weights sum to
+ * more than 0, else all four words 0.  The history plane and the five class counts are the same bits with and without SV.
+ * er_read_history_variance: HV; a plane of zeros if the capture carried nothing.
+ * er_read_blended_variance: VB, the variance of er_read_blended's colour:  (s2, k) = pool(HV, w, current, n);  VB.rgb = s2 / (w + n)
+ *   where k is set and w + n > 0, else 0;  a = k.
+ * er_denoise_blended: fills DENOISE from the blend.  e = blend.rgb / (albedo + 0.01), ve = VB.rgb / ((albedo + 0.01) * (albedo + 0.01))
+ *   with ve.w = VB's flag, then er_denoise_variance's levels unchanged and its join with the blend's alpha (1).  It needs a resolved
+ *   history and valid feature planes of the current scene state, NOT two folds: a pixel whose flag is 0 is filtered with wc = 1.
+ *   Parameters, defaults and argument checks are er_denoise_variance's.
+ * The two planes (32 bytes per pixel) live and die with the capture: whatever drops a capture drops them.  They are allocated by the
+ * first capture that carries variance, freed with the scene and not part of er_state_*.
+ * ER_ERR_STATE: the scene is not begun; world > 1; a read or the filter without a resolved history; the filter without feature planes.
+ * ER_ERR_INVALID_ARG: NULL arguments; more than 8 levels; a negative or NaN sigma.
+ * Stated limits: the cap W = min(w + n, max_weight) makes s2 / w overstate the variance of a long history, and bilinear taps average up
+ * to four pixels, which the carried variance ignores: both err towards smoothing.  A per-sample variance is view-dependent and goes stale
+ * as the colour does. */
+typedef struct ErHistoryVarianceInfo {
+    uint32_t captured, resolved;          /* the held capture carries SV / the resolved history carries HV */
+    uint64_t pixels_known_captured;       /* SV flag set, last capture */
+    uint64_t pixels_known_history;        /* HV flag set, last resolve */
+    uint64_t pixels_known_blended;        /* VB flag set, last er_denoise_blended or er_read_blended_variance */
+    float filter_ms;                      /* device time of the last er_denoise_blended (HIP events) */
+} ErHistoryVarianceInfo;
+int er_history_variance_info(ErScene* scene, ErHistoryVarianceInfo* out);
+int er_read_history_variance(ErScene* scene, float* dst_rgba);
+int er_read_blended_variance(ErScene* scene, float* dst_rgba);
+int er_denoise_blended(ErScene* scene, const ErDenoiseVariance* params);
+
 #ifdef __cplusplus
 }
 #endif

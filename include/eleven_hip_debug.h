@@ -355,6 +355,28 @@ int er_debug_variance_split(uint32_t count, const float* value, const float* alb
 int er_debug_variance_level_px(uint32_t w, uint32_t h, uint32_t step, float kc, float ka, float kz, const float* e, const float* ve, const float* normal, const float* albedo,
                                const float* depth, float* out_e, float* out_ve);
 
+/* The arithmetic of the variance carried through the history (csrc/er_history_variance.h, the functions the kernels call), on caller
+ * arrays, no device needed.  Planes are [count][4]: rgb and a flag word (0.0 or 1.0).
+ * er_debug_history_variance_current: state [count][12] (er_debug_variance_*'s) -> out = (M2 / (K - 1) clamped at 0, K >= 2).
+ * er_debug_history_variance_pool: (s_h, w [count]) and (s_c, n [count]) -> out = (pool.rgb, flag).
+ * er_debug_history_variance_capture: state [count][12] (NULL: K = 0), samples [count], hist [count][4] = (H.rgb, w) (NULL: w = 0), hv
+ *   (NULL: none) -> out = SV.
+ * er_debug_history_variance_mean: tap states [count][4] (er_debug_history_taps's), tap weights [count][4], the taps' SV [count][4][4]
+ *   -> out = HV.
+ * er_debug_history_variance_taps: er_debug_history_taps with the captured SV plane old_sv [y_res * x_res][4] beside old_cw: out_rgbw is
+ *   the colour's, out_hv = HV.
+ * er_debug_history_variance_blend: as _capture -> out = VB.
+ * er_debug_history_variance_split: blend (er_debug_history_blend's), vb, albedo [count][4] -> e, ve [count][4]. */
+int er_debug_history_variance_current(uint32_t count, const float* state, float* out);
+int er_debug_history_variance_pool(uint32_t count, const float* s_h, const float* w, const float* s_c, const float* n, float* out);
+int er_debug_history_variance_capture(uint32_t count, const float* state, const uint32_t* samples, const float* hist, const float* hv, float* out);
+int er_debug_history_variance_mean(uint32_t count, const uint32_t* tap_state, const float* tap_w, const float* tap_sv, float* out);
+int er_debug_history_variance_taps(const float cam[12], uint32_t x_res, uint32_t y_res, float depth_tolerance, uint32_t count, const uint32_t* hit, const uint32_t* object,
+                                   const float* P, const uint32_t* moved, const float* back, const uint32_t* old_hit, const uint32_t* old_object, const float* old_dist,
+                                   const float* old_cw, const float* old_sv, float* out_rgbw, float* out_hv, uint32_t* out_state, uint32_t* out_class);
+int er_debug_history_variance_blend(uint32_t count, const float* state, const uint32_t* samples, const float* hist, const float* hv, float* out);
+int er_debug_history_variance_split(uint32_t count, const float* blend, const float* vb, const float* albedo, float* e, float* ve);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,26 @@ For quality the blend carries up to 32 samples' weight against 4: where the hist
 partial and rejected pixels).
 
     python tools/history_bench.py [--quick] > profiles/history_bench.log
+
+--variance: what carrying the variance through the history costs and what er_denoise_blended buys.  The same soup and
+frames, two handles per frame -- one that folds, so that its captures carry the variance plane, and one that never does --, frames and
+handles alternated in one session, medians of 7: resolve_ms and capture_ms with and without the carried plane, and the device time of
+er_denoise_blended beside er_denoise_variance on the handle that folds.  Quality: the same two frames and moves as above with 64 spp in
+folds of 2; blend, denoised blend, and the plain 4 spp through er_denoise_guided, each against 1 024 spp.
+
+EXPECTATION, written before the first run: the per-pixel part of the combined resolve moves about 1.5 x the bytes of the plain one --
+four more 16-byte tap reads and one more 16-byte store (80 B) against 24 B of key, 4 x 32 B of taps and 16 B out (168 B) -- so at 1080p
+166 MB more, some 0.04 - 0.08 ms at the bandwidth such kernels reach here; resolve_ms also holds the key pass (one traced ray per
+pixel), which does not change, so the ratio of the two resolve_ms should be well below 1.5 and their DIFFERENCE is what to compare with
+the per-pixel kernel (capture_current_ms is such a kernel alone).  The combined kernel counts in registers with a bounded grid where the
+plain one adds once per wave and class, so it may even gain there.  A capture that carries adds one kernel of 16 B in, up to 48 B more in
+and 16 B out per pixel: about the plain capture kernel again.  er_denoise_blended runs er_denoise_variance's levels on planes of the
+same size; its split reads three more planes and writes one more: a few per cent above er_denoise_variance.  Quality: the blend's
+variance is small where the history is valid, so the colour stop is tight there and the filter mostly removes the noise of the
+disoccluded and rejected pixels, which carry only 4 spp: the denoised blend should beat the blend clearly, and beat the guided filter of
+the plain 4 spp where most pixels have a history.
+
+    python tools/history_bench.py --variance [--quick] > profiles/history_variance_bench.log
 """
 import argparse
 import os
@@ -97,11 +117,97 @@ def quality(label, sc, dpos, rot):
     print(f"     classes: valid {info['pixels_valid']} partial {info['pixels_partial']} offscreen {info['pixels_offscreen']} rejected {info['pixels_rejected']} sky {info['pixels_sky']} of {npx}")
 
 
+def cost_variance(n_tris, rounds):
+    frames = {"720p": (1280, 720), "1080p": (1920, 1080)}
+    keys = ("capture_ms", "capture_current_ms", "resolve_ms", "denoise_blended_ms", "denoise_variance_ms")
+    rms, rows, last = {}, {}, {}
+    for name, (w, h) in frames.items():
+        sc = scenes.soup(n_tris, w, h)
+        for mode in ("carried", "plain"):
+            rm = render.RenderingManager(render.RenderParameters())
+            rm.start_rendering(sc)
+            t = np.arange(sc.tri_count, dtype=np.uint32)
+            rm.set_objects([t[t % 64 == o] for o in range(64)])
+            rm.render(2)
+            if mode == "carried":
+                rm.variance_fold()
+            rms[name, mode], rows[name, mode] = (rm, sc), {k: [] for k in keys}
+    for r in range(rounds + 1):      # (round 0 warms up and allocates)
+        for (name, mode), (rm, sc) in rms.items():
+            cam = moved(sc, (0.002 * (r + 1), 0.001, 0.0), (0.0, 0.1 * (r + 1), 0.0))
+            rm.history_capture()
+            c0 = rm.history_info()["capture_ms"]
+            rm.update(camera=cam)
+            rm.history_resolve()
+            res = rm.history_info()["resolve_ms"]
+            for _ in range(2):
+                rm.render(1)
+                if mode == "carried":
+                    rm.variance_fold()
+            rm.render_features()
+            rm.denoise_blended()
+            last[name, mode] = rm.history_variance_info()
+            fb = last[name, mode]["filter_ms"]
+            fv = float("nan")
+            if mode == "carried":
+                rm.denoise_variance()
+                fv = rm.variance_info()["filter_ms"]
+            rm.history_capture()      # the resolve's key plane is current: the per-pixel kernels alone
+            c1 = rm.history_info()["capture_ms"]
+            if r:
+                for k, v in zip(keys, (c0, c1, res, fb, fv)):
+                    rows[name, mode][k].append(v)
+    for (name, mode), (rm, _) in rms.items():
+        rm.close()
+        print(f"cost {name} {mode} soup {n_tris} triangles, 64 objects, medians of {rounds}: " + ", ".join(f"{k} {statistics.median(v):.3f}" for k, v in rows[name, mode].items()))
+        print(f"     last: {last[name, mode]}")
+    for name in frames:
+        a, b = rows[name, "carried"], rows[name, "plain"]
+        med = lambda v: statistics.median(v)
+        print(f"cost {name}: resolve carried / plain {med(a['resolve_ms']) / med(b['resolve_ms']):.3f} (difference {med(a['resolve_ms']) - med(b['resolve_ms']):+.3f} ms), "
+              f"capture with a current key carried / plain {med(a['capture_current_ms']) / med(b['capture_current_ms']):.3f} "
+              f"(difference {med(a['capture_current_ms']) - med(b['capture_current_ms']):+.3f} ms), "
+              f"er_denoise_blended / er_denoise_variance {med(a['denoise_blended_ms']) / med(a['denoise_variance_ms']):.3f}")
+
+
+def quality_variance(label, sc, dpos, rot):
+    npx = sc.x_res * sc.y_res
+    none = np.zeros((npx, 4), np.float32)
+    mean_of = lambda rm, plane: history.blend(plane, rm.read_samples(), none).reshape(sc.y_res, sc.x_res, 4)[..., :3].astype(np.float64)      # (without the setup sample)
+    cam = moved(sc, dpos, rot)
+    rm = render.RenderingManager(render.RenderParameters())
+    rm.start_rendering(sc)
+    rm.render(64, fold_every=2)
+    rm.update(camera=cam, keep_history=True)
+    rm.render(4)
+    rm.render_features()
+    rm.denoise_blended()
+    denoised, info = rm.get_pass("denoise")[..., :3].astype(np.float64), rm.history_variance_info()
+    blended, plain = rm.get_blended()[..., :3].astype(np.float64), mean_of(rm, rm.get_pass("beauty"))
+    rm.denoise_guided()
+    guided = mean_of(rm, rm.get_pass("denoise"))
+    rm.update(camera=cam)
+    rm.render(1024)
+    truth = mean_of(rm, rm.get_pass("beauty"))
+    rm.close()
+    err = lambda a: float(np.abs(a - truth).mean())
+    eb, ed, ep, eg = err(blended), err(denoised), err(plain), err(guided)
+    print(f"quality {label}: mean absolute error against 1024 spp: blend {eb:.5f}, er_denoise_blended {ed:.5f} (x{ed / eb:.3f} of the blend), plain 4 spp {ep:.5f}, "
+          f"er_denoise_guided of it {eg:.5f} (x{eg / ep:.3f} of the plain); denoised blend / guided {ed / eg:.3f}")
+    print(f"     known pixels: history {info['pixels_known_history']} blended {info['pixels_known_blended']} of {npx}; filter {info['filter_ms']:.3f} ms")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="20 000 triangles and 3 rounds: a check that the tool runs")
+    ap.add_argument("--variance", action="store_true", help="the carried variance and er_denoise_blended (DESIGN.md 3n) instead of the history alone")
     args = ap.parse_args()
     n = 20_000 if args.quick else 1_000_000
+    if args.variance:
+        cost_variance(n, 3 if args.quick else 7)
+        quality_variance("cornell_textured 256x256", scenes.cornell_textured(256, 256), (0.02, 0.01, 0.0), (0.0, 1.0, 0.0))
+        quality_variance(f"C5-style torture {n} triangles 1280x720", scenes.torture(n, 1280, 720), (0.01, 0.005, 0.0), (0.0, 0.5, 0.0))
+        return
     cost(n, 3 if args.quick else 7)
     quality("cornell_textured 256x256", scenes.cornell_textured(256, 256), (0.02, 0.01, 0.0), (0.0, 1.0, 0.0))
     quality(f"C5-style torture {n} triangles 1280x720", scenes.torture(n, 1280, 720), (0.01, 0.005, 0.0), (0.0, 0.5, 0.0))
