@@ -248,6 +248,15 @@ class ErHistoryVarianceInfo(C.Structure):
                 ("pixels_known_blended", C.c_uint64), ("filter_ms", C.c_float)]
 
 
+class ErFirstHitParams(C.Structure):
+    _fields_ = [("cutouts", C.c_uint32), ("opacity_threshold", C.c_float)]
+
+
+class ErFirstHitInfo(C.Structure):
+    _fields_ = [("cutouts", C.c_uint32), ("opacity_threshold", C.c_float), ("rays", C.c_uint64), ("rays_through", C.c_uint64), ("layers_skipped", C.c_uint64),
+                ("rays_capped", C.c_uint64), ("rays_through_to_miss", C.c_uint64)]
+
+
 class ErPick(C.Structure):
     _fields_ = [("hit", C.c_uint32), ("triangle", C.c_uint32), ("object", C.c_uint32), ("material", C.c_uint32), ("distance", C.c_float),
                 ("position", C.c_float * 3), ("uv", C.c_float * 2)]
@@ -491,6 +500,31 @@ def debug_history_variance_split(blend, vb, albedo):
     return e, ve
 
 
+def debug_cutout_threshold(t):
+    """include/eleven_hip_debug.h er_debug_cutout_threshold: (ok uint32[n], resolved float32[n]) of thresholds as er_first_hit_set takes them
+    (csrc/er_cutout.h; no device needed) -- elevenrender_amd/first_hit.py restates it"""
+    t = np.ascontiguousarray(t, np.float32).reshape(-1)
+    ok, res = np.zeros(len(t), np.uint32), np.zeros(len(t), np.float32)
+    check(load().er_debug_cutout_threshold(len(t), _fptr(t), ok.ctypes.data_as(_UP), _fptr(res)))
+    return ok, res
+
+
+def debug_cutout_stops(opacity, threshold):
+    """er_debug_cutout_stops: uint32[n], 1 where a hit of this opacity stops the ray"""
+    a, t = np.ascontiguousarray(opacity, np.float32).reshape(-1), np.ascontiguousarray(threshold, np.float32).reshape(-1)
+    out = np.zeros(len(a), np.uint32)
+    check(load().er_debug_cutout_stops(len(a), _fptr(a), _fptr(t), out.ctypes.data_as(_UP)))
+    return out
+
+
+def debug_cutout_continue(position, d):
+    """er_debug_cutout_continue: (origin, direction) float32[n][3] of the ray that goes on past a hit at `position` along `d`"""
+    p, d = np.ascontiguousarray(position, np.float32).reshape(-1, 3), np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+    o2, d2 = np.zeros_like(p), np.zeros_like(p)
+    check(load().er_debug_cutout_continue(len(p), _fptr(p), _fptr(d), _fptr(o2), _fptr(d2)))
+    return o2, d2
+
+
 def debug_variance_mark(beauty, samples):
     """include/eleven_hip_debug.h er_debug_variance_mark: the state float32[n][12] of a reset (csrc/er_variance.h; no device needed) --
     elevenrender_amd/variance.py mark() restates it"""
@@ -648,6 +682,8 @@ SYMBOLS = {
     "er_read_history_variance": (C.c_int, [_P, _FP]),
     "er_read_blended_variance": (C.c_int, [_P, _FP]),
     "er_denoise_blended": (C.c_int, [_P, C.POINTER(ErDenoiseVariance)]),
+    "er_first_hit_set": (C.c_int, [_P, C.POINTER(ErFirstHitParams)]),
+    "er_first_hit_info": (C.c_int, [_P, C.POINTER(ErFirstHitInfo)]),
     "er_state_size": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "er_state_export": (C.c_int, [_P, _P, C.c_uint64]),
     "er_state_import": (C.c_int, [_P, _P, C.c_uint64]),
@@ -722,6 +758,10 @@ OPTIONAL_SYMBOLS = {
     "er_debug_history_variance_taps": (C.c_int, [_FP, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, _UP, _UP, _FP, _UP, _FP, _UP, _UP, _FP, _FP, _FP, _FP, _FP, _UP, _UP]),
     "er_debug_history_variance_blend": (C.c_int, [C.c_uint32, _FP, _UP, _FP, _FP, _FP]),
     "er_debug_history_variance_split": (C.c_int, [C.c_uint32, _FP, _FP, _FP, _FP, _FP]),
+    "er_debug_cutout_threshold": (C.c_int, [C.c_uint32, _FP, _UP, _FP]),
+    "er_debug_cutout_stops": (C.c_int, [C.c_uint32, _FP, _FP, _UP]),
+    "er_debug_cutout_continue": (C.c_int, [C.c_uint32, _FP, _FP, _FP, _FP]),
+    "er_debug_first_hit_rays": (C.c_int, [_P, _FP, _FP, C.c_uint32, C.c_float, _IP, _UP, _FP, _FP]),
 }
 
 

@@ -161,6 +161,7 @@ static int begin_open(ErScene* s, const ErRenderParams* p) {
         const char* which = nullptr;
         hipError_t pe = er_probe_kernels(&which);
         if (pe == hipSuccess) pe = er_probe_ids(&which);
+        if (pe == hipSuccess) pe = er_probe_first_hit(&which);
         if (pe == hipSuccess) pe = er_probe_history(&which);
         if (pe == hipSuccess) pe = er_probe_history_variance(&which);
         if (pe == hipSuccess) pe = er_probe_variance(&which);

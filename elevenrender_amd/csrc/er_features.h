@@ -10,6 +10,10 @@ hipError_t er_probe_features(const char** which);
 // n camera rays per owned pixel of S through the production traversal: albedo and depth (row-major float4 planes of the frame) of the
 // owned pixels are overwritten.  `blocks`, `spill`: the first-hit pass's grid and spill area (er_first_hit_blocks, er_first_hit.h).
 void er_launch_features(const DevScene& S, uint32_t n, float4* albedo, float4* depth, uint32_t blocks, uint2* spill, hipStream_t stream);
+// ... with the pass seeing through cut-outs (er_first_hit_set): the resolved threshold and the mode's counter words (er_first_hit.h)
+void er_launch_features_cutouts(const DevScene& S, uint32_t n, float4* albedo, float4* depth, uint32_t blocks, uint2* spill, float threshold, unsigned long long* counts,
+                                hipStream_t stream);
+hipError_t er_probe_first_hit(const char** which);      // er_first_hit.hip; er_render_begin asks it beside er_probe_ids
 // pixels of the listed tiles <-> compact buffer [tile][64] float4 of a row-major plane (lanes outside the frame: zero / skipped)
 void er_launch_pack_plane(const DevScene& S, const uint32_t* tiles, uint32_t ntiles, const float4* plane, void* dst, hipStream_t stream);
 void er_launch_unpack_plane(const DevScene& S, const uint32_t* tiles, uint32_t ntiles, float4* plane, const void* src, hipStream_t stream);

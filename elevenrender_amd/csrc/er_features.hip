@@ -28,9 +28,14 @@ using namespace erh;
 //         A_c = A_c + a_c                                        c = R, G, B
 //     albedo[idx] = (A_R / (float)n, A_G / (float)n, A_B / (float)n, (float)hits / (float)n)
 //     z = hits ? D / (float)hits : 0;  depth[idx] = (z, z, z, (float)hits / (float)n)
-// No opacity draw is taken: the first hit counts whatever its opacity (a limit of the pass: a path that passes through a cut-out
-// shades what lies behind it, the feature planes show the cut-out's own albedo and distance).
-__global__ __launch_bounds__(64) void er_features_kernel(DevScene S, uint32_t n, float4* __restrict__ albedo, float4* __restrict__ depth, uint2* spill_base) {
+// No opacity draw is taken.  CUTOUTS = false (the default mode): the first hit counts whatever its opacity -- a path that passes
+// through a cut-out shades what lies behind it, the feature planes show the cut-out's own albedo and distance.  CUTOUTS = true
+// (er_first_hit_set): `slot` and `hit` are FirstHit::visible's -- the first hit whose opacity reaches the threshold x =
+// (threshold, counters), or a miss -- and d is still measured from the camera ray's origin; everything else above is unchanged.
+template <bool CUTOUTS, class... X>
+__global__ __launch_bounds__(64) void er_features_kernel(DevScene S, uint32_t n, float4* __restrict__ albedo, float4* __restrict__ depth, uint2* spill_base, X... x) {
+    static_assert(sizeof...(X) == (CUTOUTS ? 2 : 0), "the mode's threshold and counters are arguments of the mode-on instance only");
+    Cutouts<CUTOUTS> co{x...};
     const float fn = (float)n;
     first_hit_walk(S, spill_base, [&](uint32_t px, uint32_t py, const FirstHit& fh) {
         const uint32_t idx = py * S.x_res + px;
@@ -40,11 +45,13 @@ __global__ __launch_bounds__(64) void er_features_kernel(DevScene S, uint32_t n,
         uint32_t hits = 0;
         for (uint32_t k = 0; k < n; k++) {
             const Ray ray = fh.sample_ray(px, py, rs);
-            const int slot = fh.closest(ray);
+            HitFull hit;
+            int slot;
+            if constexpr (CUTOUTS) slot = co.visible(fh, ray, hit);
+            else slot = fh.closest(ray);
             F3 a = f3s(1.0f);
             if (slot >= 0) {
-                HitFull hit;
-                full_hit(S, (uint32_t)slot, ray, hit);
+                if constexpr (!CUTOUTS) full_hit(S, (uint32_t)slot, ray, hit);
                 const ErMaterial& mat = S.materials[hit.material];
                 // the albedo branch of generate_hit_data (er_device.h) ...
                 DevFused fu = {0, 0, 0, 0};
@@ -68,6 +75,7 @@ __global__ __launch_bounds__(64) void er_features_kernel(DevScene S, uint32_t n,
         albedo[idx] = make_float4(A.x / fn, A.y / fn, A.z / fn, cov);
         depth[idx] = make_float4(z, z, z, cov);
     });
+    co.flush();      // (every lane arrives: the walk has no early return)
 }
 
 // pixels of the listed tiles of a row-major plane <-> compact buffer [tile][64] (er_pack_kernel / er_unpack_kernel on a plane pointer)
@@ -150,14 +158,21 @@ hipError_t er_probe_features(const char** which) {
     hipFuncAttributes a;
     hipError_t e;
     *which = "er_features_kernel";
-    if ((e = hipFuncGetAttributes(&a, (const void*)er_features_kernel)) != hipSuccess) return e;
+    if ((e = hipFuncGetAttributes(&a, (const void*)er_features_kernel<false>)) != hipSuccess) return e;
+    *which = "er_features_kernel (cut-outs)";
+    if ((e = hipFuncGetAttributes(&a, (const void*)er_features_kernel<true, float, unsigned long long*>)) != hipSuccess) return e;
     *which = "er_guided_level_kernel";
     return hipFuncGetAttributes(&a, (const void*)er_guided_level_kernel);
 }
 
 void er_launch_features(const DevScene& S, uint32_t n, float4* albedo, float4* depth, uint32_t blocks, uint2* spill, hipStream_t stream) {
     if (S.owned_tile_count == 0 || n == 0 || blocks == 0) return;
-    hipLaunchKernelGGL(er_features_kernel, dim3(blocks), dim3(64), 0, stream, S, n, albedo, depth, spill);
+    hipLaunchKernelGGL(er_features_kernel<false>, dim3(blocks), dim3(64), 0, stream, S, n, albedo, depth, spill);
+}
+void er_launch_features_cutouts(const DevScene& S, uint32_t n, float4* albedo, float4* depth, uint32_t blocks, uint2* spill, float threshold, unsigned long long* counts,
+                                hipStream_t stream) {
+    if (S.owned_tile_count == 0 || n == 0 || blocks == 0) return;
+    hipLaunchKernelGGL((er_features_kernel<true, float, unsigned long long*>), dim3(blocks), dim3(64), 0, stream, S, n, albedo, depth, spill, threshold, counts);
 }
 void er_launch_pack_plane(const DevScene& S, const uint32_t* tiles, uint32_t ntiles, const float4* plane, void* dst, hipStream_t stream) {
     if (ntiles == 0) return;
@@ -209,11 +224,18 @@ int features_impl(ErScene* s, uint32_t n) {
     HIP_TRY(hipEventCreate(&ev.b));
     // pixels of other ranks read as zero until they are gathered
     HIP_TRY(hipMemsetAsync(s->d_feat.p, 0, 2 * npx * sizeof(float4), s->stream));
+    const bool cutouts = er_first_hit_cutouts(s);
+    if (cutouts && (rc = er_first_hit_counts_begin(s)) != ER_OK) return rc;
     HIP_TRY(hipEventRecord(ev.a, s->stream));
-    er_launch_features(s->dev, n, feature_plane(s, ER_FEATURE_ALBEDO), feature_plane(s, ER_FEATURE_DEPTH), blocks, s->d_first_hit_spill.p, s->stream);
+    if (cutouts)
+        er_launch_features_cutouts(s->dev, n, feature_plane(s, ER_FEATURE_ALBEDO), feature_plane(s, ER_FEATURE_DEPTH), blocks, s->d_first_hit_spill.p, s->first_hit.threshold,
+                                   s->d_first_hit_counts.p, s->stream);
+    else
+        er_launch_features(s->dev, n, feature_plane(s, ER_FEATURE_ALBEDO), feature_plane(s, ER_FEATURE_DEPTH), blocks, s->d_first_hit_spill.p, s->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev.b, s->stream));
     HIP_TRY(hipEventSynchronize(ev.b));
+    if (cutouts && (rc = er_first_hit_counts_end(s)) != ER_OK) return rc;
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
     s->feat = {true, n, s->owned_pixels() * n, ms};      // (one camera ray per sample and owned pixel inside the frame)

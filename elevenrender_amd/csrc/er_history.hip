@@ -15,20 +15,27 @@ using namespace erh;
 // first_hit_walk's geometry (one wave per 8x8 tile, one lane per pixel, a grid stride over the owned tiles; world == 1: all of them).
 // One ray per lane: camera_ray with r1 = r2 = 0.5 and bokeh taken as 0, on the handle's trig.
 // key: [0, npx) hit, [npx, 2 npx) object, [2 npx, 3 npx) dist, then P as [npx][3].
-__global__ __launch_bounds__(64) void er_history_key_kernel(DevScene S, const uint32_t* __restrict__ tri_object, uint32_t* __restrict__ key, size_t npx, uint2* spill_base) {
+// CUTOUTS = true (er_first_hit_set): x = (threshold, counters); the hit is FirstHit::visible's, dist still from the camera ray's origin, and
+// a ray that passes and then leaves the scene (or is capped) is keyed as a miss: P = the camera ray's direction.
+template <bool CUTOUTS, class... X>
+__global__ __launch_bounds__(64) void er_history_key_kernel(DevScene S, const uint32_t* __restrict__ tri_object, uint32_t* __restrict__ key, size_t npx, uint2* spill_base, X... x) {
+    static_assert(sizeof...(X) == (CUTOUTS ? 2 : 0), "the mode's threshold and counters are arguments of the mode-on instance only");
+    Cutouts<CUTOUTS> co{x...};
     ErCamera cam = S.cam;
     cam.bokeh = 0;
     float* const kf = (float*)key;
     first_hit_walk(S, spill_base, [&](uint32_t px, uint32_t py, const FirstHit& fh) {
         const size_t idx = (size_t)py * S.x_res + px;
         const Ray ray = camera_ray(cam, (int)px, (int)py, S.x_res, S.y_res, 0.5f, 0.5f, 0.0f, 0.0f, 0.0f, &fh.trig);
-        const int slot = fh.closest(ray);
+        HitFull h;
+        int slot;
+        if constexpr (CUTOUTS) slot = co.visible(fh, ray, h);
+        else slot = fh.closest(ray);
         uint32_t hit = 0u, object = ER_ID_NONE;
         float dist = 0.0f;
         F3 P = ray.d;
         if (slot >= 0) {
-            HitFull h;
-            full_hit(S, (uint32_t)slot, ray, h);
+            if constexpr (!CUTOUTS) full_hit(S, (uint32_t)slot, ray, h);
             hit = 1u;
             object = triangle_object(S, tri_object, slot_triangle(S, (uint32_t)slot));
             dist = length(h.position - ray.o);
@@ -41,6 +48,7 @@ __global__ __launch_bounds__(64) void er_history_key_kernel(DevScene S, const ui
         kf[3 * npx + idx * 3 + 1] = P.y;
         kf[3 * npx + idx * 3 + 2] = P.z;
     });
+    co.flush();      // (every lane arrives: the walk has no early return)
 }
 
 // capture: (C.rgb, W) of every pixel from BEAUTY, the sample counts and, if `hist` is not NULL, the resolved history
@@ -102,7 +110,9 @@ hipError_t er_probe_history(const char** which) {
     hipFuncAttributes a;
     hipError_t e;
     *which = "er_history_key_kernel";
-    if ((e = hipFuncGetAttributes(&a, (const void*)er_history_key_kernel)) != hipSuccess) return e;
+    if ((e = hipFuncGetAttributes(&a, (const void*)er_history_key_kernel<false>)) != hipSuccess) return e;
+    *which = "er_history_key_kernel (cut-outs)";
+    if ((e = hipFuncGetAttributes(&a, (const void*)er_history_key_kernel<true, float, unsigned long long*>)) != hipSuccess) return e;
     *which = "k_history_resolve (er_history.hip)";
     return hipFuncGetAttributes(&a, (const void*)k_history_resolve);
 }
@@ -138,9 +148,17 @@ int make_key(ErScene* s) {
     uint32_t blocks;
     H.key_valid = false;
     if ((rc = er_first_hit_blocks(s, &blocks)) != ER_OK || (rc = er_id_prepare(s)) != ER_OK) return rc;
-    if (s->dev.owned_tile_count)
-        hipLaunchKernelGGL(er_history_key_kernel, dim3(blocks), dim3(64), 0, s->stream, s->dev, er_id_map(s), H.d_key[H.now].p, npx, s->d_first_hit_spill.p);
+    const bool cutouts = er_first_hit_cutouts(s);
+    if (cutouts && (rc = er_first_hit_counts_begin(s)) != ER_OK) return rc;
+    if (s->dev.owned_tile_count) {
+        if (cutouts)
+            hipLaunchKernelGGL((er_history_key_kernel<true, float, unsigned long long*>), dim3(blocks), dim3(64), 0, s->stream, s->dev, er_id_map(s), H.d_key[H.now].p, npx,
+                               s->d_first_hit_spill.p, s->first_hit.threshold, s->d_first_hit_counts.p);
+        else
+            hipLaunchKernelGGL(er_history_key_kernel<false>, dim3(blocks), dim3(64), 0, s->stream, s->dev, er_id_map(s), H.d_key[H.now].p, npx, s->d_first_hit_spill.p);
+    }
     HIP_TRY(hipGetLastError());
+    if (cutouts && (rc = er_first_hit_counts_end(s)) != ER_OK) return rc;      // (waits for the pass; with the mode off nothing waits here)
     H.key_cam = s->camera;
     H.key_m = s->objects.last_m;
     H.key_valid = true;

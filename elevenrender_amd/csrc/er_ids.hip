@@ -23,8 +23,13 @@ static_assert(ER_ID_SLOTS == 4, "a pixel's slots are one uint4 per plane");
 // ever touches the column, so no barrier).  Once its n rays are traced the exact routine's stack (s_stack2, ER_STACK words per lane in
 // the same [k][lane] layout) is idle: the lane writes the ids of one kind there and ranks them with er_id_rank (er_ids.h), kind after
 // kind.  planes: [2 * kind] ids, [2 * kind + 1] counts, npx uint4 each.
+// CUTOUTS = true (er_first_hit_set): x = (threshold, counters) and FirstHit::visible RESTATED too -- the ray goes on through hits whose
+// opacity is below the threshold by er_cutout.h's two routines, at most S.max_bounces hits; the slot kept is the stopping hit's.
+template <bool CUTOUTS, class... X>
 __global__ __launch_bounds__(64) void er_ids_kernel(DevScene S, uint32_t n, const uint32_t* __restrict__ tri_object, uint4* __restrict__ planes, size_t npx,
-                                                    uint32_t* __restrict__ overflow, uint2* spill_base) {
+                                                    uint32_t* __restrict__ overflow, uint2* spill_base, X... x) {
+    static_assert(sizeof...(X) == (CUTOUTS ? 2 : 0), "the mode's threshold and counters are arguments of the mode-on instance only");
+    Cutouts<CUTOUTS> co{x...};
     __shared__ uint2 s_stack[WF_LDS_STACK * 64];
     __shared__ int s_stack2[ER_STACK * 64];
     __shared__ uint32_t s_slot[ER_ID_MAX_RAYS * 64];
@@ -50,7 +55,25 @@ __global__ __launch_bounds__(64) void er_ids_kernel(DevScene S, uint32_t n, cons
             const Ray ray = camera_ray(S.cam, (int)px, (int)py, S.x_res, S.y_res, c1, c2, c3, c4, c5, &trig);
             int info;
             unsigned cn = 0, ct = 0;
-            const int slot = trav_run_closest<false>(S, stack, spill, stack2, ray, __builtin_inff(), info, cn, ct);
+            int slot;
+            if constexpr (CUTOUTS) {
+                Ray seg = ray;
+                uint32_t layers = 0;
+                bool capped = true;
+                slot = -1;
+                for (uint32_t b = 0; b < S.max_bounces; b++) {
+                    const int found = trav_run_closest<false>(S, stack, spill, stack2, seg, __builtin_inff(), info, cn, ct);
+                    if (found < 0) { capped = false; break; }
+                    HitFull hit;
+                    full_hit(S, (uint32_t)found, seg, hit);
+                    if (er_cutout_stops(hit_opacity(S, hit), co.threshold)) { slot = found; capped = false; break; }
+                    layers++;
+                    seg = cutout_continue(hit, seg);
+                }
+                co.tally(slot, layers, capped);
+            } else {
+                slot = trav_run_closest<false>(S, stack, spill, stack2, ray, __builtin_inff(), info, cn, ct);
+            }
             if (slot >= 0) { slots[m * 64] = (uint32_t)slot; m++; }
         }
         uint32_t oi[ER_ID_SLOTS], oc[ER_ID_SLOTS];
@@ -73,19 +96,30 @@ __global__ __launch_bounds__(64) void er_ids_kernel(DevScene S, uint32_t n, cons
         planes[(size_t)(2 * ER_ID_MATERIAL + 1) * npx + idx] = make_uint4(oc[0], oc[1], oc[2], oc[3]);
         if (distinct > ER_ID_SLOTS) atomicAdd(overflow + ER_ID_MATERIAL, 1u);
     }
+    co.flush();      // (every lane arrives: the loop above has no early return)
 }
 
-// er_pick: ray 0 of pixel (px, py) on lane 0 of one wave; `out` takes the ten words of an ErPick
-__global__ __launch_bounds__(64) void er_pick_kernel(DevScene S, uint32_t px, uint32_t py, const uint32_t* __restrict__ tri_object, uint32_t* __restrict__ out, uint2* spill_base) {
+// er_pick: ray 0 of pixel (px, py) on lane 0 of one wave; `out` takes the ten words of an ErPick.  CUTOUTS = true: x = (threshold), the
+// hit is FirstHit::visible's, the distance still from the camera ray's origin; nothing is counted.
+template <bool CUTOUTS, class... X>
+__global__ __launch_bounds__(64) void er_pick_kernel(DevScene S, uint32_t px, uint32_t py, const uint32_t* __restrict__ tri_object, uint32_t* __restrict__ out, uint2* spill_base,
+                                                     X... x) {
+    static_assert(sizeof...(X) == (CUTOUTS ? 1 : 0), "the mode's threshold is an argument of the mode-on instance only");
     if (threadIdx.x != 0 || px >= S.x_res || py >= S.y_res) return;
     const FirstHit fh = first_hit_lane(S, spill_base);      // (lane 0 of workgroup 0: the first column of the one slice)
     uint32_t rs = jenkins_u32(py * S.x_res + px + 1u);
     const Ray ray = fh.sample_ray(px, py, rs);
-    const int slot = fh.closest(ray);
+    HitFull hit;
+    int slot;
+    if constexpr (CUTOUTS) {
+        Cutouts<true> co{x...};
+        slot = co.visible(fh, ray, hit);
+    } else {
+        slot = fh.closest(ray);
+    }
     uint32_t w[10] = {0u, ER_ID_NONE, ER_ID_NONE, ER_ID_NONE, 0u, 0u, 0u, 0u, 0u, 0u};
     if (slot >= 0) {
-        HitFull hit;
-        full_hit(S, (uint32_t)slot, ray, hit);
+        if constexpr (!CUTOUTS) full_hit(S, (uint32_t)slot, ray, hit);
         w[0] = 1u;
         w[1] = slot_triangle(S, (uint32_t)slot);
         w[2] = triangle_object(S, tri_object, w[1]);
@@ -185,9 +219,13 @@ hipError_t er_probe_ids(const char** which) {
     hipFuncAttributes a;
     hipError_t e;
     *which = "er_ids_kernel";
-    if ((e = hipFuncGetAttributes(&a, (const void*)er_ids_kernel)) != hipSuccess) return e;
+    if ((e = hipFuncGetAttributes(&a, (const void*)er_ids_kernel<false>)) != hipSuccess) return e;
+    *which = "er_ids_kernel (cut-outs)";
+    if ((e = hipFuncGetAttributes(&a, (const void*)er_ids_kernel<true, float, unsigned long long*>)) != hipSuccess) return e;
     *which = "er_pick_kernel";
-    if ((e = hipFuncGetAttributes(&a, (const void*)er_pick_kernel)) != hipSuccess) return e;
+    if ((e = hipFuncGetAttributes(&a, (const void*)er_pick_kernel<false>)) != hipSuccess) return e;
+    *which = "er_pick_kernel (cut-outs)";
+    if ((e = hipFuncGetAttributes(&a, (const void*)er_pick_kernel<true, float>)) != hipSuccess) return e;
     *which = "k_id_write (er_ids.hip)";
     return hipFuncGetAttributes(&a, (const void*)k_id_write);
 }
@@ -250,13 +288,21 @@ int render_ids_impl(ErScene* s, uint32_t n) {
         HIP_TRY(hipMemsetAsync(id_plane(s, k, 1), 0, npx * sizeof(uint4), s->stream));
     }
     HIP_TRY(hipMemsetAsync(s->d_id_over.p, 0, ER_ID_KIND_COUNT * 4, s->stream));
+    const bool cutouts = er_first_hit_cutouts(s);
+    if (cutouts && (rc = er_first_hit_counts_begin(s)) != ER_OK) return rc;
     HIP_TRY(hipEventRecord(ev.a, s->stream));
-    if (s->dev.owned_tile_count)
-        hipLaunchKernelGGL(er_ids_kernel, dim3(blocks), dim3(64), 0, s->stream, s->dev, n, id_map(s), (uint4*)s->d_id_planes.p, npx, s->d_id_over.p, s->d_first_hit_spill.p);
+    if (s->dev.owned_tile_count) {
+        if (cutouts)
+            hipLaunchKernelGGL((er_ids_kernel<true, float, unsigned long long*>), dim3(blocks), dim3(64), 0, s->stream, s->dev, n, id_map(s), (uint4*)s->d_id_planes.p, npx,
+                               s->d_id_over.p, s->d_first_hit_spill.p, s->first_hit.threshold, s->d_first_hit_counts.p);
+        else
+            hipLaunchKernelGGL(er_ids_kernel<false>, dim3(blocks), dim3(64), 0, s->stream, s->dev, n, id_map(s), (uint4*)s->d_id_planes.p, npx, s->d_id_over.p, s->d_first_hit_spill.p);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev.b, s->stream));
     HIP_TRY(hipMemcpyAsync(s->ids_overflow, s->d_id_over.p, ER_ID_KIND_COUNT * 4, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
+    if (cutouts && (rc = er_first_hit_counts_end(s)) != ER_OK) return rc;
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
     s->ids = {true, n, s->owned_pixels() * n, ms};      // (one camera ray per sample and owned pixel inside the frame)
@@ -359,7 +405,10 @@ int pick_impl(ErScene* s, uint32_t x, uint32_t y, ErPick* out) {
     int rc;
     if ((rc = er_first_hit_spill(s, 1)) != ER_OK || (rc = id_prepare(s)) != ER_OK) return rc;
     if (s->d_id_work.n < sizeof(ErPick) / 4 && (rc = upload(s->d_id_work, nullptr, sizeof(ErPick) / 4, s->stream)) != ER_OK) return rc;
-    hipLaunchKernelGGL(er_pick_kernel, dim3(1), dim3(64), 0, s->stream, s->dev, x, y, id_map(s), s->d_id_work.p, s->d_first_hit_spill.p);
+    if (er_first_hit_cutouts(s))
+        hipLaunchKernelGGL((er_pick_kernel<true, float>), dim3(1), dim3(64), 0, s->stream, s->dev, x, y, id_map(s), s->d_id_work.p, s->d_first_hit_spill.p, s->first_hit.threshold);
+    else
+        hipLaunchKernelGGL(er_pick_kernel<false>, dim3(1), dim3(64), 0, s->stream, s->dev, x, y, id_map(s), s->d_id_work.p, s->d_first_hit_spill.p);
     HIP_TRY(hipGetLastError());
     ErPick got{};
     HIP_TRY(hipMemcpyAsync(&got, s->d_id_work.p, sizeof(ErPick), hipMemcpyDeviceToHost, s->stream));

@@ -259,6 +259,11 @@ struct ErScene {
     // the first-hit camera pass (er_first_hit.h) of er_render_features, er_render_ids, er_pick and the history's key: the traversal's
     // spill area of its bounded grid (the consumers run one at a time on the scene's stream), and what a whole-frame pass reports
     DevBuf<uint2> d_first_hit_spill;
+    // its mode (er_first_hit_set, er_first_hit.hip): set after er_render_begin and kept through every edit and a later er_render_begin;
+    // threshold as resolved (0 -> 0.5).  counts: ErFirstHitInfo's five, of the last whole-frame pass run with the mode on, through
+    // d_first_hit_counts (five words 64 bytes apart, allocated by the first such pass).
+    struct FirstHitMode { uint32_t cutouts = 0; float threshold = 0.5f; uint64_t counts[5] = {0, 0, 0, 0, 0}; } first_hit;
+    DevBuf<unsigned long long> d_first_hit_counts;
     struct PassInfo { bool valid = false; uint32_t samples = 0; uint64_t rays = 0; float ms = 0; };
     // the feature pass (er_features.hip): the ALBEDO and DEPTH planes back to back (row-major, allocated by the first er_render_features);
     // valid from a pass until the next er_render_begin or er_render_update.  Recomputable, so not part of the progressive state.
@@ -321,7 +326,8 @@ struct ErScene {
         refit_topo.release();
         xform_dev.release();
         store.release();
-        d_first_hit_spill.release();
+        d_first_hit_spill.release(); d_first_hit_counts.release();
+        for (auto& c : first_hit.counts) c = 0;      // (the mode itself stays: er_first_hit_set)
         d_feat.release(); feat.valid = false;
         for (auto& u : unpacked_feat) u.clear();
         d_id_planes.release(); d_id_map.release(); d_id_work.release(); d_id_over.release(); ids.valid = id_map_valid = false;

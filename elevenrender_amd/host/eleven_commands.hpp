@@ -35,6 +35,9 @@
 //   * config "denoise_blended": true (needs "history" and "denoise_variance" both true and gpus 1) makes `denoise: true` / --get_pass
 //     denoise answer er_denoise_blended -- the blended frame filtered by the variance the history carried -- whenever a camera update left
 //     a resolved history, the feature planes made for the new camera if they are missing; --get_info reports blended_denoises.
+//   * config "cutouts": true (optionally "cutout_threshold": 0 for 0.5, or in (0, 1]) makes the first-hit passes behind albedo, depth
+//     and the history's key see through hits whose opacity is below the threshold (er_first_hit_set, on every rank); --get_info reports
+//     cutouts, cutout_threshold and the five counters of the last such pass, summed over the ranks, as cutout_*.
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -306,6 +309,16 @@ private:
             j["topology_edits"] = topology_edits_;
             j["feature_samples"] = rm.pars.feature_samples ? rm.pars.feature_samples : 4u;      // rays per pixel of a feature pass (--get_pass albedo / depth, denoise_guided)
             if (rm.pars.denoise_guided) j["denoise_guided"] = true;
+            if (rm.pars.cutouts) {      // (only with the key: a session without it answers as before)
+                const ErFirstHitInfo fh = rm.first_hit_info();
+                j["cutouts"] = fh.cutouts != 0;
+                j["cutout_threshold"] = (double)fh.opacity_threshold;
+                j["cutout_rays"] = fh.rays;
+                j["cutout_rays_through"] = fh.rays_through;
+                j["cutout_layers_skipped"] = fh.layers_skipped;
+                j["cutout_rays_capped"] = fh.rays_capped;
+                j["cutout_rays_through_to_miss"] = fh.rays_through_to_miss;
+            }
             if (rm.pars.history) j["history_resolves"] = rm.history_resolves;      // (only with the key: a session without it answers as before)
             if (rm.pars.denoise_variance) j["variance_folds"] = rm.variance_folds();      // (the same)
             if (rm.pars.denoise_blended) j["blended_denoises"] = rm.blended_denoises;      // (the same)
@@ -408,6 +421,13 @@ private:
             const long long n = v->as_int64();
             if (n < 1 || n > 64) throw std::runtime_error("config feature_samples out of range (1 .. 64)");
             rp.feature_samples = (unsigned)n;
+        }
+        // the first-hit passes (albedo, depth, the history's key) see through cut-outs (er_first_hit_set), on every rank
+        if (const json::Value* v = j.if_contains("cutouts")) rp.cutouts = v->as_bool();
+        if (const json::Value* v = j.if_contains("cutout_threshold")) {
+            const double t = v->as_double();
+            if (!(t >= 0.0 && t <= 1.0)) throw std::runtime_error("config cutout_threshold out of range (0 for the default 0.5, or in (0, 1])");
+            rp.cutout_threshold = (float)t;
         }
         // temporal reprojection across camera updates (er_history_capture / er_history_resolve): --get_pass blended
         if (const json::Value* v = j.if_contains("history")) rp.history = v->as_bool();

@@ -134,6 +134,10 @@ struct RenderParameters {   // src/kernel.h:51-69
     // er_denoise_guided on feature planes of feature_samples camera rays per pixel (0 = the library's default, 4)
     bool denoise_guided = false;
     unsigned feature_samples = 0;
+    // the first-hit passes see through cut-outs (extension, off by default): applied to every rank after er_render_begin
+    // (er_first_hit_set; the library keeps it through every edit in place); cutout_threshold 0 = the library's default, 0.5
+    bool cutouts = false;
+    float cutout_threshold = 0;
     // temporal reprojection (extension, off by default): a --start answered by the camera-update path captures the frame before the
     // update and resolves it after (er_history_capture / er_history_resolve); --get_pass blended then answers er_read_blended.  One GPU.
     bool history = false;
@@ -312,6 +316,10 @@ public:
         mats_sent_ = mat;
         if (pars.adaptive)
             for (ErScene* e : ers_) if (er_adaptive_set(e, &pars.adaptive_params) != ER_OK) { std::string m = er_last_error(); release(); throw std::runtime_error(m); }
+        if (pars.cutouts) {
+            const ErFirstHitParams fh{1u, pars.cutout_threshold};
+            for (ErScene* e : ers_) if (er_first_hit_set(e, &fh) != ER_OK) { std::string m = er_last_error(); release(); throw std::runtime_error(m); }
+        }
         // ---- the combine's communicators ----
         if (multi) {
             bool distinct = true;
@@ -608,6 +616,29 @@ public:
             sum.samples = i.samples;
             sum.rays += i.rays;
             sum.ms = std::max(sum.ms, i.ms);
+        }
+        return sum;
+    }
+    // er_first_hit_set on every rank of a begun render (a change invalidates the feature planes: the next ensure_features runs a pass)
+    void set_first_hit(bool cutouts = true, float opacity_threshold = 0) {
+        if (ers_.empty()) throw std::runtime_error("set_first_hit: no render has been started");
+        std::unique_lock<std::mutex> lk(frame_mtx_, std::defer_lock);
+        if (ers_.size() > 1) lk.lock();
+        const ErFirstHitParams p{cutouts ? 1u : 0u, opacity_threshold};
+        for (ErScene* e : ers_) check(er_first_hit_set(e, &p));
+        pars.cutouts = cutouts;
+        pars.cutout_threshold = opacity_threshold;
+        features_ready_ = false;
+    }
+    ErFirstHitInfo first_hit_info() {      // over the ranks: the counters summed (each rank counts its own rays)
+        ErFirstHitInfo sum{};
+        for (ErScene* e : ers_) {
+            ErFirstHitInfo i{};
+            check(er_first_hit_info(e, &i));
+            sum.cutouts = i.cutouts;
+            sum.opacity_threshold = i.opacity_threshold;
+            sum.rays += i.rays; sum.rays_through += i.rays_through; sum.layers_skipped += i.layers_skipped;
+            sum.rays_capped += i.rays_capped; sum.rays_through_to_miss += i.rays_through_to_miss;
         }
         return sum;
     }

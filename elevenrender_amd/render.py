@@ -478,6 +478,18 @@ class RenderingManager:
         abi.check(self.lib.er_feature_info(self.handle, C.byref(a)))
         return {n: getattr(a, n) for n, _ in abi.ErFeatureInfo._fields_}
 
+    def set_first_hit(self, cutouts=True, opacity_threshold=0.0):
+        """er_first_hit_set: with cutouts the first-hit passes (features, ids, pick, the history's key) see through hits whose opacity is
+        below the threshold (0 -> 0.5) and report the first surface that stops the ray; a change invalidates their planes."""
+        p = abi.ErFirstHitParams(1 if cutouts else 0, opacity_threshold)
+        abi.check(self.lib.er_first_hit_set(self.handle, C.byref(p)))
+
+    def first_hit_info(self):
+        """er_first_hit_info: the mode and the five counters of the last whole-frame pass run in it"""
+        a = abi.ErFirstHitInfo()
+        abi.check(self.lib.er_first_hit_info(self.handle, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in abi.ErFirstHitInfo._fields_}
+
     def denoise_guided(self, levels=0, colour_sigma=0.0, albedo_sigma=0.0, depth_sigma=0.0):
         """Fill the DENOISE plane from BEAUTY + NORMAL + the feature planes (er_denoise_guided; render_features first)."""
         p = abi.ErDenoiseGuided(levels, colour_sigma, albedo_sigma, depth_sigma)
@@ -706,6 +718,19 @@ class RenderingManager:
         if self_slots is None:
             return (tri, slot, pos, dist, info) + extra
         return (tri.astype(bool), info) + extra
+
+    def debug_first_hit_rays(self, origins, dirs, threshold=0.0):
+        """include/eleven_hip_debug.h er_debug_first_hit_rays: FirstHit::visible for arbitrary rays, whatever the scene's mode.  Returns
+        (tri int32[n], layers uint32[n], dist float32[n], pos float32[n][3])."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        n = len(o)
+        tri, layers = np.empty(n, np.int32), np.empty(n, np.uint32)
+        pos, dist = np.empty((n, 3), np.float32), np.empty(n, np.float32)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        abi.check(self.lib.er_debug_first_hit_rays(self.handle, fp(o), fp(d), n, threshold, tri.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                   layers.ctypes.data_as(C.POINTER(C.c_uint32)), fp(dist), fp(pos)))
+        return tri, layers, dist, pos
 
     def debug_eval(self, kind, items, out_width):
         """include/eleven_hip_debug.h er_debug_eval: one DEVICE function of the path per row of `items` ([n, in_width] float32;

@@ -114,6 +114,26 @@ def cornell_textured(x_res=256, y_res=256):
     return sc
 
 
+def cornell_cards(x_res=256, y_res=256, cells=6):
+    """cornell_textured with a card in front of its back wall (z = 3.7, 1.7 wide and high): two triangles whose opacity comes from an
+    unfiltered `cells` x `cells` checker of 0 and 1 (uv cells of 8 x 8 texels) and whose albedo is a constant orange -- a fence of
+    opaque squares with the textured wall seen through the holes.  The scene on which the first-hit passes that see through cut-outs
+    (er_first_hit_set) are measured: without them the albedo, depth and id planes show one flat card."""
+    sc = cornell_textured(x_res, y_res)
+    z, a = 3.7, 0.85
+    card = np.array([[[-a, -a, z], [-a, a, z], [a, a, z]], [[-a, -a, z], [a, a, z], [a, -a, z]]], np.float32)      # normal -z, as the back wall
+    uv = np.array([[[0, 0], [0, 1], [1, 1]], [[0, 0], [1, 1], [1, 0]]], np.float32)
+    v = np.concatenate([sc.vertices, card])
+    normals, tangents = face_frame(v)
+    n = 8 * cells
+    holes = ((np.arange(n)[:, None] // 8 + np.arange(n)[None, :] // 8) % 2).astype(np.float32)[:, :, None]
+    out = abi.SceneData(v, normals, tangents, np.concatenate([sc.uvs, uv]), np.ones(len(v), np.float32),
+                        np.concatenate([sc.material_id, np.array([4, 4], np.int32)]),
+                        list(sc.materials) + [abi.default_material(albedo=(0.9, 0.45, 0.1), opacity_tex=1)],
+                        textures=list(sc.textures) + [(abi._f32(holes), n, n, 1, 0)], camera=sc.camera, x_res=x_res, y_res=y_res)
+    return out
+
+
 def soup_geometry(n_tris, seed=12345):
     """C2 distribution: centroid c ~ U([-1,1]^2 x [2,4]); v0 = c, v1,v2 = c + U([-1,1]^3) * e, e = 2/cbrt(N)."""
     r = Rand(seed, 1)

@@ -823,6 +823,41 @@ int er_read_history_variance(ErScene* scene, float* dst_rgba);
 int er_read_blended_variance(ErScene* scene, float* dst_rgba);
 int er_denoise_blended(ErScene* scene, const ErDenoiseVariance* params);
 
+/* ---- Seeing through cut-outs in the first-hit passes.  The render passes a path straight through a hit that fails its
+ * opacity draw and shades what lies behind; the first-hit camera pass (er_render_features, er_render_ids, er_pick, the key plane of
+ * er_history_capture / er_history_resolve) by default reports the first hit whatever its opacity.  With `cutouts` set a camera ray of
+ * these four goes on through hits the render would mostly pass through and reports the first surface that stops it:
+ *   along the ray take the closest hit; its opacity is the material's constant or the first channel of the opacity texture through its
+ *   filter at the hit's uv (what the render shades with); the hit STOPS the ray iff opacity >= threshold (a NaN opacity passes);
+ *   otherwise the ray goes on as the render's does, from position + d * 0.001 along d, with no self-exclusion.  At most max_bounces
+ *   hits are examined (a path of the render ends there): if all of them pass, the ray is a miss (rays_capped).  A ray that passes and
+ *   then leaves the scene is a miss (rays_through_to_miss).  Distances (DEPTH, the key's dist, ErPick::distance) are measured from the
+ *   CAMERA ray's origin.  Each consumer does with the surviving hit what it does with the first hit otherwise.
+ * The rule is deterministic -- a threshold, not the render's draw, because a guide plane must be free of noise -- and takes no RNG
+ * draw: binary cut-outs are exact under it, a semi-transparent sheet goes to the majority.
+ * opacity_threshold: 0 means 0.5; otherwise in (0, 1].  cutouts: 0 (the default: every output is bit for bit what it is without this
+ * call) or 1; any other value is refused.
+ * A successful er_first_hit_set that changes either field invalidates the feature planes, the id planes and the history (a capture
+ * keyed under one rule cannot be resolved under the other); one that changes nothing invalidates nothing.  The setting survives
+ * er_render_update, _edit, _transform, _topology and a second er_render_begin.  The render itself (BEAUTY, samples, RNG, ErCounters) is
+ * the same with and without the mode.
+ * ErFirstHitInfo: the setting (the threshold as resolved: 0.5 for 0) and five counters of the last whole-frame pass run in this mode
+ * (features, ids or key, whichever ran last; on a sharded frame the rank's own rays): rays traced; rays_through, those that passed at
+ * least one hit; layers_skipped, the hits passed, summed; rays_capped; rays_through_to_miss.  All five are 0 while the mode is off.
+ * ER_ERR_STATE: the scene is not begun.  ER_ERR_INVALID_ARG: NULL arguments; cutouts > 1; a NaN, negative or > 1 threshold (the scene
+ * is left untouched). */
+typedef struct ErFirstHitParams {
+    uint32_t cutouts;
+    float opacity_threshold;
+} ErFirstHitParams;
+typedef struct ErFirstHitInfo {
+    uint32_t cutouts;
+    float opacity_threshold;
+    uint64_t rays, rays_through, layers_skipped, rays_capped, rays_through_to_miss;
+} ErFirstHitInfo;
+int er_first_hit_set(ErScene* scene, const ErFirstHitParams* params);
+int er_first_hit_info(ErScene* scene, ErFirstHitInfo* out);
+
 #ifdef __cplusplus
 }
 #endif

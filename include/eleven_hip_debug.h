@@ -377,6 +377,20 @@ int er_debug_history_variance_taps(const float cam[12], uint32_t x_res, uint32_t
 int er_debug_history_variance_blend(uint32_t count, const float* state, const uint32_t* samples, const float* hist, const float* hv, float* out);
 int er_debug_history_variance_split(uint32_t count, const float* blend, const float* vb, const float* albedo, float* e, float* ve);
 
+/* The cut-out rule of the first-hit pass (csrc/er_cutout.h, the functions the kernels call), on caller arrays, no device needed.
+ * er_debug_cutout_threshold: t [count] -> ok [count] (1: er_first_hit_set takes it) and resolved [count] (0 -> 0.5).
+ * er_debug_cutout_stops: opacity [count], threshold [count] -> out [count] (1: the hit stops the ray).
+ * er_debug_cutout_continue: position, d [count][3] -> the continuation ray's origin and direction [count][3]. */
+int er_debug_cutout_threshold(uint32_t count, const float* t, uint32_t* ok, float* resolved);
+int er_debug_cutout_stops(uint32_t count, const float* opacity, const float* threshold, uint32_t* out);
+int er_debug_cutout_continue(uint32_t count, const float* position, const float* d, float* o_out, float* d_out);
+/* FirstHit::visible (csrc/er_first_hit.h) for n arbitrary rays of a begun scene, whatever its er_first_hit_set: `threshold` as
+ * er_first_hit_set takes it, at most max_bounces hits examined.  tri_out: the triangle id of the hit that stopped the ray, or -1;
+ * layers_out: the hits passed (of a capped ray: max_bounces); dist_out: length(position - origin), 0 of a miss; pos_out [n][3]: the
+ * hit's position, zeros of a miss.  The directions are taken as given (normalise them as the camera does). */
+int er_debug_first_hit_rays(struct ErScene* scene, const float* origins, const float* dirs, uint32_t n, float threshold, int32_t* tri_out, uint32_t* layers_out,
+                            float* dist_out, float* pos_out);
+
 #ifdef __cplusplus
 }
 #endif
