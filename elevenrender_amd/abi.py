@@ -152,6 +152,24 @@ class ErTransformInfo(C.Structure):
                 ("dirty_nodes8", C.c_uint32), ("reserved", C.c_uint32), ("bytes_uploaded", C.c_uint64), ("refit_ms", C.c_float)]
 
 
+class ErSkin(C.Structure):   # [size_of(object)][3][4] bones and weights, the object's tri_ids order
+    _fields_ = [("object", C.c_uint32), ("bone_count", C.c_uint32), ("bones", C.POINTER(C.c_uint16)), ("weights", C.POINTER(C.c_float))]
+
+
+class ErSkinPose(C.Structure):   # palette: [bone_count][12], row-major 3x4 each
+    _fields_ = [("object", C.c_uint32), ("bone_count", C.c_uint32), ("palette", C.POINTER(C.c_float))]
+
+
+class ErSkinUpdate(C.Structure):
+    _fields_ = [("what", C.c_uint32), ("camera", ErCamera), ("count", C.c_uint32), ("poses", C.POINTER(ErSkinPose))]
+
+
+class ErSkinInfo(C.Structure):
+    _fields_ = [("calls", C.c_uint32), ("skinned", C.c_uint32), ("objects", C.c_uint32), ("bones", C.c_uint32), ("moved", C.c_uint32), ("path", C.c_uint32),
+                ("why_full", C.c_uint32), ("dirty_nodes2", C.c_uint32), ("dirty_nodes8", C.c_uint32), ("refit_ms", C.c_float), ("bytes_uploaded", C.c_uint64),
+                ("influence_bytes", C.c_uint64)]
+
+
 class ErSceneEdit(C.Structure):
     _fields_ = [("what", C.c_uint32), ("camera", ErCamera), ("vertices", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)),
                 ("tangents", C.POINTER(C.c_float)), ("material_count", C.c_uint32), ("materials", C.POINTER(ErMaterial)),
@@ -348,6 +366,20 @@ def debug_transform_apply(m, vertices, normals, tangents):
     assert v.shape == n.shape == t.shape
     out = [np.empty_like(v) for _ in range(3)]
     check(lib.er_debug_transform_apply(_fptr(mm), len(v), _fptr(v), _fptr(n), _fptr(t), *(_fptr(o) for o in out)))
+    return tuple(out)
+
+
+def debug_skin_apply(palette, bones, weights, vertices, normals, tangents):
+    """include/eleven_hip_debug.h er_debug_skin_apply: the host form of er_render_skin's arithmetic (csrc/er_skin.h; no device needed) on
+    [n][3][3] rest arrays with [n][3][4] bones and weights: the skinned (vertices, normals, tangents)."""
+    lib = load()
+    P = np.ascontiguousarray(palette, np.float32).reshape(-1, 12)
+    v, n, t = (np.ascontiguousarray(a, np.float32).reshape(-1, 3, 3) for a in (vertices, normals, tangents))
+    b = np.ascontiguousarray(bones, np.uint16).reshape(-1, 3, 4)
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1, 3, 4)
+    assert v.shape == n.shape == t.shape and len(b) == len(w) == len(v)
+    out = [np.empty_like(v) for _ in range(3)]
+    check(lib.er_debug_skin_apply(_fptr(P), len(P), len(v), b.ctypes.data_as(C.POINTER(C.c_uint16)), _fptr(w), _fptr(v), _fptr(n), _fptr(t), *(_fptr(o) for o in out)))
     return tuple(out)
 
 
@@ -644,6 +676,9 @@ SYMBOLS = {
     "er_objects_set": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "er_render_transform": (C.c_int, [_P, C.POINTER(ErTransformUpdate)]),
     "er_transform_info": (C.c_int, [_P, C.POINTER(ErTransformInfo)]),
+    "er_skin_set": (C.c_int, [_P, C.POINTER(ErSkin)]),
+    "er_render_skin": (C.c_int, [_P, C.POINTER(ErSkinUpdate)]),
+    "er_skin_info": (C.c_int, [_P, C.POINTER(ErSkinInfo)]),
     "er_render_edit": (C.c_int, [_P, C.POINTER(ErSceneEdit)]),
     "er_edit_info": (C.c_int, [_P, C.POINTER(ErEditInfo)]),
     "er_accel_cost": (C.c_int, [_P, C.POINTER(ErAccelCost)]),
@@ -736,6 +771,7 @@ OPTIONAL_SYMBOLS = {
                                     _FP, C.c_uint64]),
     "er_debug_accel_cost_terms": (C.c_int, [_P, C.POINTER(ErCostSumsDebug), C.POINTER(C.c_double), C.c_uint64, _FP, C.c_uint64]),
     "er_debug_transform_apply": (C.c_int, [_FP, C.c_uint32, _FP, _FP, _FP, _FP, _FP, _FP]),
+    "er_debug_skin_apply": (C.c_int, [_FP, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint16), _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
     "er_debug_accel_cost_host": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(ErCostSumsDebug), C.POINTER(C.c_double), C.c_uint64, _FP, C.c_uint64]),
     "er_debug_id_rank": (C.c_int, [_UP, C.c_uint32, _UP, _UP, _UP]),
     "er_debug_spill_levels": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32, _UP]),

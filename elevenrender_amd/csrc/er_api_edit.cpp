@@ -7,6 +7,8 @@
 // er_render_transform is the same function a third time: its list of posed OBJECTS (er_xform.h) takes the place of the sparse list in the
 // same three places -- checked in O(objects), the host copy only marked (ErScene::flush_poses applies the marks where the arrays are
 // read), the listed triangles posed on the device by the refit itself.  Also here: er_objects_set.
+// er_render_skin is er_render_transform with palettes in place of matrices (er_skin.h): the same list type with its `skin` half filled, a
+// branch in each of the same three places.  Also here: er_skin_set.
 // er_render_topology (at the end) changes WHICH triangles there are: its own checks and renumbering (er_topology_host.h), the checks and
 // the replacement of edit_locked for its `rest`, the geometry store (er_topology.h) in front of begin_accel, then the same stages.
 #include <algorithm>
@@ -31,7 +33,14 @@ struct XformList {
     const ErObjectTransform* x = nullptr;
     std::vector<ErXformEntry> entries;
     uint32_t moved = 0;
+    // er_render_skin: the caller's poses in place of `x`, and the entries and the palettes that go up in place of `entries`
+    const ErSkinPose* poses = nullptr;
+    bool skin = false;
+    std::vector<ErSkinEntry> skin_entries;
+    std::vector<float> palette;
 };
+
+static_assert(ER_SKIN_INFLUENCES == ER_SKIN_K && ER_SKIN_MAX_BONES == ER_SKIN_BONES_MAX, "er_skin.h restates the two constants");
 
 // The pieces below run with the mutex held, the device set, the stream idle and the host copy already edited.
 
@@ -56,12 +65,20 @@ int edit_refit(ErScene* s, bool new_normals, bool new_tangents, const ErSparseLi
             frc = er_refit_sparse(s->refit_topo, b, *sp, s->stream, &sr, why);
         } else {
             frc = s->xform_dev.valid ? 0 : er_xform_table_build(s->xform_dev, s->objects, s->stream, why);      // once per er_objects_set / er_render_begin
-            ErXformCall c;
-            c.table = &s->xform_dev; c.entries = (uint32_t)xf->entries.size(); c.list = xf->entries.data(); c.moved = xf->moved;
-            if (frc == 0) frc = er_refit_xform(s->refit_topo, b, c, s->stream, &sr, why);
+            if (!xf->skin) {
+                ErXformCall c;
+                c.table = &s->xform_dev; c.entries = (uint32_t)xf->entries.size(); c.list = xf->entries.data(); c.moved = xf->moved;
+                if (frc == 0) frc = er_refit_xform(s->refit_topo, b, c, s->stream, &sr, why);
+            } else {
+                if (frc == 0 && !s->skin_dev.valid) frc = er_skin_table_build(s->skin_dev, s->objects, s->skins, s->stream, &s->skin_influence_bytes, why);      // once per er_skin_set / er_render_begin
+                ErSkinCall c;
+                c.table = &s->xform_dev; c.skin = &s->skin_dev; c.entries = (uint32_t)xf->skin_entries.size(); c.list = xf->skin_entries.data();
+                c.bones = (uint32_t)(xf->palette.size() / 12); c.palette = xf->palette.data(); c.moved = xf->moved;
+                if (frc == 0) frc = er_refit_skin(s->refit_topo, b, c, s->stream, &sr, why);
+            }
         }
         r = sr.refit;
-        ErSparseInfo& I = sp ? s->sparse : s->xform;
+        ErSparseInfo& I = sp ? s->sparse : xf->skin ? s->skin : s->xform;
         I.path = sr.path; I.why_full = sr.why_full;
         I.dirty_nodes2 = sr.dirty_nodes2; I.dirty_nodes8 = sr.dirty_nodes8;
         I.bytes_uploaded = sr.bytes_uploaded; I.refit_ms = r.refit_ms;
@@ -326,6 +343,10 @@ int edit_check(const ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, X
     if ((what & ER_EDIT_GEOMETRY) && sp) {
         std::string why;
         if (!er_sparse_check(s->tri_count, *sp, why)) return fail(ER_ERR_INVALID_ARG, pre + why);
+    } else if ((what & ER_EDIT_GEOMETRY) && xf && xf->skin) {
+        std::string why;
+        const int src = er_skin_pose_check(s->objects, s->skins, xf->count, xf->poses, xf->skin_entries, xf->palette, xf->moved, why);
+        if (src != 0) return fail(src == 2 ? ER_ERR_STATE : ER_ERR_INVALID_ARG, pre + why);
     } else if ((what & ER_EDIT_GEOMETRY) && xf) {
         std::string why;
         if (!er_xform_check(s->objects, xf->count, xf->x, xf->entries, xf->moved, why)) return fail(ER_ERR_INVALID_ARG, pre + why);
@@ -424,6 +445,8 @@ void edit_replace(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, cons
     if ((what & ER_EDIT_GEOMETRY) && sp) {
         s->flush_poses();
         er_sparse_patch(*sp, s->vertices.data(), s->normals.data(), s->tangents.data());
+    } else if ((what & ER_EDIT_GEOMETRY) && xf && xf->skin) {
+        er_skin_mark(s->objects, s->skins, xf->skin_entries.data(), (uint32_t)xf->skin_entries.size(), xf->palette.data());
     } else if ((what & ER_EDIT_GEOMETRY) && xf) {
         er_objects_mark(s->objects, xf->entries.data(), (uint32_t)xf->entries.size());
     } else if (what & ER_EDIT_GEOMETRY) {
@@ -460,11 +483,13 @@ int edit_locked(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, XformL
     HIP_TRY(hipStreamSynchronize(s->stream));
     // the host copy, before any device work: whatever happens below, a later er_render_begin builds the edited scene
     edit_replace(s, e, sp, xf, W);
+    // a deformation has no back matrix: a palette pose drops the history, and so does the matrix pose that takes an object out of one
+    const bool deformed = xf && (e->what & ER_EDIT_GEOMETRY) && (xf->skin || er_skin_mark_matrix(s->skins, xf->entries.data(), (uint32_t)xf->entries.size()));
     if ((e->what & ER_EDIT_GEOMETRY) || ((e->what & ER_EDIT_MATERIALS) && e->material_id)) s->store.release();      // er_render_topology's geometry store does not follow other edits
     s->feat.valid = false;      // the feature planes show the scene before the edit (er_render_features makes them again)
     for (auto& set : s->unpacked_feat) set.clear();
     s->ids_invalidate();        // (and so do the id planes: er_render_ids)
-    if (((e->what & ER_EDIT_GEOMETRY) && !xf) || (e->what & LOOK_BITS)) s->history_invalidate();      // a camera or a pose keeps the history (er_history.hip)
+    if (((e->what & ER_EDIT_GEOMETRY) && (!xf || deformed)) || (e->what & LOOK_BITS)) s->history_invalidate();      // a camera or a pose keeps the history (er_history.hip)
     s->variance_reset();        // the render starts over: so do the variance moments (er_variance.hip)
     uint32_t stage = 0;
     float stage_ms = 0;
@@ -476,9 +501,11 @@ int edit_locked(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, XformL
     }
     const bool xform_geometry = xf && (e->what & ER_EDIT_GEOMETRY);
     if (xform_geometry) {
-        const uint32_t calls = s->xform.calls;
-        s->xform = ErSparseInfo{};
-        s->xform.calls = calls;
+        ErSparseInfo& I = xf->skin ? s->skin : s->xform;
+        const uint32_t calls = I.calls;
+        I = ErSparseInfo{};
+        I.calls = calls;
+        if (xf->skin) s->skin_influence_bytes = 0;
     }
     if ((rc = edit_device(s, e, sp, xf, W.rebuild_pool, who, stage, stage_ms)) != ER_OK) {
         s->begun = false;      // (er_render_begin releases what is left and rebuilds from the edited host copy)
@@ -493,11 +520,18 @@ int edit_locked(ErScene* s, const ErSceneEdit* e, const ErSparseList* sp, XformL
         s->sparse.moved = sp->count;
         if (s->accel.builder != 2u) s->sparse.path = 3u;      // the policy ended the call in a build: the refit's figures, if one ran, stay
     }
-    if (xform_geometry) {
+    if (xform_geometry && !xf->skin) {
         s->xform.calls++;
         s->xform.moved = xf->moved;
         s->xform_objects = xf->count;
         if (s->accel.builder != 2u) s->xform.path = 3u;
+    }
+    if (xform_geometry && xf->skin) {
+        s->skin.calls++;
+        s->skin.moved = xf->moved;
+        s->skin_objects = xf->count;
+        s->skin_bones = (uint32_t)(xf->palette.size() / 12);
+        if (s->accel.builder != 2u) s->skin.path = 3u;
     }
     if ((e->what & ER_EDIT_GEOMETRY) && s->accel.builder == 2u) s->upd.refits++;      // (under a rebuild policy the call may have ended in a build)
     const float wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -552,10 +586,12 @@ static int er_objects_set_impl(ErScene* s, uint32_t object_count, const uint32_t
     if (object_count) host_reserve((uint64_t)first[object_count] * (27 + 1) * 4 + (uint64_t)object_count * 20 * 4);
     s->flush_poses();      // the rest pose is the CURRENT pose
     er_objects_take(s->objects, object_count, first, tri_ids, s->vertices.data(), s->normals.data(), s->tangents.data());
-    if (s->xform_dev.valid || s->xform_dev.d_rest) {      // the device form was the old table's: the next transform builds the new one
+    er_skin_drop(s->skins);      // (skins do not survive a new table)
+    if (s->xform_dev.valid || s->xform_dev.d_rest || s->skin_dev.valid || s->skin_dev.d_w) {      // the device forms were the old table's: the next transform or skin builds the new ones
         (void)hipSetDevice(s->device);
         if (s->stream) (void)hipStreamSynchronize(s->stream);
         s->xform_dev.release();
+        s->skin_dev.release();
     }
     s->ids_invalidate();      // the OBJECT plane and the tri -> object map were the old table's (er_ids.hip)
     s->history_invalidate();      // (and the captured poses)
@@ -581,6 +617,45 @@ static int er_transform_info_impl(ErScene* s, ErTransformInfo* out) {
     std::lock_guard<std::mutex> lk(s->mtx);
     const ErSparseInfo& x = s->xform;
     *out = ErTransformInfo{x.calls, s->xform_objects, x.moved, x.path, x.why_full, x.dirty_nodes2, x.dirty_nodes8, 0u, x.bytes_uploaded, x.refit_ms};
+    return ER_OK;
+}
+
+static int er_skin_set_impl(ErScene* s, const ErSkin* k) {
+    if (!s || !k || (k->bone_count && (!k->bones || !k->weights))) return fail(ER_ERR_INVALID_ARG, "er_skin_set: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (s->objects.objects() == 0) return fail(ER_ERR_STATE, "er_skin_set: no object table (er_objects_set)");
+    std::string why;
+    if (!er_skin_check(s->objects, *k, why)) return fail(ER_ERR_INVALID_ARG, "er_skin_set: " + why);
+    if (k->bone_count) host_reserve((uint64_t)s->objects.size_of(k->object) * 72 + (uint64_t)k->bone_count * 48 + (uint64_t)s->objects.objects() * 64);
+    s->flush_poses();      // (a palette pose of this object that is still pending is applied with the skin it was given for)
+    er_skin_take(s->skins, s->objects, *k);
+    if (s->skin_dev.valid || s->skin_dev.d_w) {      // the device form was of the old skins: the next er_render_skin builds the new one
+        (void)hipSetDevice(s->device);
+        if (s->stream) (void)hipStreamSynchronize(s->stream);
+        s->skin_dev.release();
+    }
+    return ER_OK;
+}
+
+static int er_render_skin_impl(ErScene* s, const ErSkinUpdate* u) {
+    if (!s || !u) return fail(ER_ERR_INVALID_ARG, "er_render_skin: NULL argument");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->begun) return fail(ER_ERR_STATE, "er_render_skin: er_render_begin has not succeeded");
+    if ((u->what & ER_UPDATE_GEOMETRY) && s->objects.objects() == 0) return fail(ER_ERR_STATE, "er_render_skin: the geometry bit without an object table (er_objects_set, er_skin_set)");
+    ErSceneEdit e{};      // (its arrays stay NULL: the listed objects stand for them)
+    e.what = u->what; e.camera = u->camera;
+    XformList l;
+    l.count = u->count; l.poses = u->poses; l.skin = true;
+    return edit_locked(s, &e, nullptr, &l, ER_UPDATE_CAMERA | ER_UPDATE_GEOMETRY, "er_render_skin", t0);
+}
+
+static int er_skin_info_impl(ErScene* s, ErSkinInfo* out) {
+    if (!s || !out) return fail(ER_ERR_INVALID_ARG, "er_skin_info: NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    const ErSparseInfo& x = s->skin;
+    *out = ErSkinInfo{x.calls, s->skins.skinned, s->skin_objects, s->skin_bones, x.moved, x.path, x.why_full, x.dirty_nodes2, x.dirty_nodes8, x.refit_ms, x.bytes_uploaded,
+                      s->skin_influence_bytes};
     return ER_OK;
 }
 
@@ -753,6 +828,8 @@ static int er_render_topology_impl(ErScene* s, const ErTopologyEdit* t) {
     s->d_id_map.release();      // the tri -> object map and the table's device form were of the old numbering: the lazy paths make them again
     s->id_map_valid = false;
     s->xform_dev.release();
+    er_skin_drop(s->skins);      // (skins do not survive a renumbering; their pending poses were flushed above)
+    s->skin_dev.release();
     if ((t->rest.what & ER_EDIT_MATERIALS) && t->rest.material_id) s->store.release();      // (the store's material ids would be stale: filled again below)
     const uint32_t calls = s->topo.calls;
     s->topo = ErTopologyInfo{};
@@ -786,6 +863,9 @@ int er_sparse_info(ErScene* s, ErSparseInfo* out) { return guarded("er_sparse_in
 int er_objects_set(ErScene* s, uint32_t object_count, const uint32_t* first, const uint32_t* tri_ids) { return guarded("er_objects_set", [&]() -> int { return er_objects_set_impl(s, object_count, first, tri_ids); }); }
 int er_render_transform(ErScene* s, const ErTransformUpdate* u) { return guarded("er_render_transform", [&]() -> int { return er_render_transform_impl(s, u); }); }
 int er_transform_info(ErScene* s, ErTransformInfo* out) { return guarded("er_transform_info", [&]() -> int { return er_transform_info_impl(s, out); }); }
+int er_skin_set(ErScene* s, const ErSkin* k) { return guarded("er_skin_set", [&]() -> int { return er_skin_set_impl(s, k); }); }
+int er_render_skin(ErScene* s, const ErSkinUpdate* u) { return guarded("er_render_skin", [&]() -> int { return er_render_skin_impl(s, u); }); }
+int er_skin_info(ErScene* s, ErSkinInfo* out) { return guarded("er_skin_info", [&]() -> int { return er_skin_info_impl(s, out); }); }
 int er_render_edit(ErScene* s, const ErSceneEdit* e) { return guarded("er_render_edit", [&]() -> int { return er_render_edit_impl(s, e); }); }
 int er_edit_info(ErScene* s, ErEditInfo* out) { return guarded("er_edit_info", [&]() -> int { return er_edit_info_impl(s, out); }); }
 int er_accel_cost(ErScene* s, ErAccelCost* out) { return guarded("er_accel_cost", [&]() -> int { return er_accel_cost_impl(s, out); }); }

@@ -653,6 +653,15 @@ int er_debug_transform_apply(const float* m, uint32_t count, const float* v, con
         return ER_OK;
     });
 }
+int er_debug_skin_apply(const float* palette, uint32_t bone_count, uint32_t count, const uint16_t* bones, const float* weights, const float* v, const float* n, const float* t,
+                        float* ov, float* on, float* ot) {
+    return guarded("er_debug_skin_apply", [&]() -> int {
+        if (!palette || (count && (!bones || !weights || !v || !n || !t || !ov || !on || !ot))) return fail(ER_ERR_INVALID_ARG, "er_debug_skin_apply: NULL argument");
+        std::string why;
+        if (!er_skin_apply(palette, bone_count, count, bones, weights, v, n, t, ov, on, ot, why)) return fail(ER_ERR_INVALID_ARG, "er_debug_skin_apply: " + why);
+        return ER_OK;
+    });
+}
 int er_debug_id_rank(const uint32_t* ids, uint32_t count, uint32_t* out_ids, uint32_t* out_counts, uint32_t* distinct) {
     return guarded("er_debug_id_rank", [&]() -> int {
         if ((count && !ids) || !out_ids || !out_counts || !distinct) return fail(ER_ERR_INVALID_ARG, "er_debug_id_rank: NULL argument");

@@ -14,6 +14,7 @@ hipError_t er_probe_gpu_build(const char** which);
 hipError_t er_probe_refit(const char** which);
 hipError_t er_probe_refit_sparse(const char** which);
 hipError_t er_probe_xform(const char** which);
+hipError_t er_probe_skin(const char** which);
 hipError_t er_probe_cost(const char** which);
 void er_launch_atrous(const float4* src, int src_stride, const float4* normal, int normal_stride, float4* dst, int w, int h, int step, float kc, hipStream_t stream);
 void er_launch_plane(const DevScene& S, int pass, float4* dst, hipStream_t stream);      // DevScene::passes -> one contiguous plane

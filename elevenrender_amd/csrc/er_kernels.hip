@@ -170,6 +170,7 @@ hipError_t er_probe_kernels(const char** which) {
     if ((e = er_probe_refit(which)) != hipSuccess) return e;
     if ((e = er_probe_refit_sparse(which)) != hipSuccess) return e;
     if ((e = er_probe_xform(which)) != hipSuccess) return e;
+    if ((e = er_probe_skin(which)) != hipSuccess) return e;
     if ((e = er_probe_cost(which)) != hipSuccess) return e;
     if ((e = er_probe_features(which)) != hipSuccess) return e;
     if ((e = er_probe_texstage(which)) != hipSuccess) return e;

@@ -11,6 +11,7 @@
 #include "er_bvh.h"
 #include "er_sparse_host.h"      // ErSparseList: the listed triangles of er_render_update_sparse, already checked
 #include "er_xform.h"            // ErXformEntry, ErObjectTable: the listed objects of er_render_transform, already checked
+#include "er_skin.h"             // ErSkinEntry, ErSkinTable: the listed objects of er_render_skin, already checked
 
 // Per topology: the nodes of either tree by level, as index lists on the device (level L of a tree = entries [off[L], off[L + 1])),
 // and what the sparse refit needs to find its way UP from a triangle: the slot of every triangle id, the binary and the wide node that
@@ -108,6 +109,43 @@ int er_xform_table_build(ErXformDev& dev, const ErObjectTable& t, hipStream_t st
 // er_refit_sparse with the listed triangles posed ON THE DEVICE from the rest copy (k_xform_scatter): nothing but the entries is uploaded.
 // The same structure, byte for byte, as er_refit_sparse given the listed objects' ids with their posed vertices, normals and tangents.
 int er_refit_xform(ErRefitTopo& topo, const ErRefitBuffers& b, const ErXformCall& x, hipStream_t stream, ErSparseResult* out, std::string& err);
+
+// The influences of er_skin_set on the device, beside the rest copy, built at the first er_render_skin after an er_skin_set or an
+// er_render_begin: the rows of the SKINNED objects only, in object order (ErSkinTable::row_first), 72 bytes per triangle as six pieces,
+// piece-major like the rest copy -- corner c of row r has its four weights at d_w[c * rows + r] (16 bytes) and its four 16-bit bone
+// indices at d_b[c * rows + r] (8 bytes, as they lie in the caller's array: bone k in the low or high half, by k & 1, of word k / 2) --
+// so the 64 lanes of a wave load 1 KiB and 512 consecutive bytes per piece.
+struct ErSkinDev {
+    bool valid = false;
+    float4* d_w = nullptr;           // [3][rows]
+    uint2* d_b = nullptr;            // [3][rows]
+    uint32_t rows = 0;
+    void release() {
+        if (d_w) (void)hipFree(d_w);
+        if (d_b) (void)hipFree(d_b);
+        d_w = nullptr; d_b = nullptr;
+        rows = 0;
+        valid = false;
+    }
+};
+
+struct ErSkinCall {                  // one er_render_skin: the listed objects' entries and palettes (host) over the two device tables
+    const ErXformDev* table = nullptr;
+    const ErSkinDev* skin = nullptr;
+    uint32_t entries = 0;
+    const ErSkinEntry* list = nullptr;
+    uint32_t bones = 0;              // matrices in `palette`: the listed objects' bone counts added up
+    const float* palette = nullptr;  // [bones][12]
+    uint32_t moved = 0;              // triangles of the listed objects
+};
+
+// `dev` from the host tables (one upload of 72 bytes per triangle of a skinned object; *bytes gets that figure).  Blocks until done.
+int er_skin_table_build(ErSkinDev& dev, const ErObjectTable& t, const ErSkinTable& k, hipStream_t stream, uint64_t* bytes, std::string& err);
+// er_refit_sparse with the listed triangles skinned ON THE DEVICE from the rest copy (k_skin_scatter): 32 bytes per listed object and 48
+// per listed bone are uploaded.  The same structure, byte for byte, as er_refit_sparse given the listed objects' ids with their posed
+// vertices, normals and tangents.
+int er_refit_skin(ErRefitTopo& topo, const ErRefitBuffers& b, const ErSkinCall& x, hipStream_t stream, ErSparseResult* out, std::string& err);
+hipError_t er_probe_skin(const char** which);
 hipError_t er_probe_refit(const char** which);          // see er_kernels.h
 hipError_t er_probe_xform(const char** which);
 hipError_t er_probe_refit_sparse(const char** which);

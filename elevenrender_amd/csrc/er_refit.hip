@@ -21,7 +21,8 @@
 //
 // The transform refit (er_refit_xform) is the sparse refit with one kernel exchanged: the listed triangles are not uploaded
 // but posed by k_xform_scatter from a rest copy that lies on the device (er_xform.h has the arithmetic), which also writes the id list
-// that everything behind the scatter runs over.  refit_listed is the one body of both.
+// that everything behind the scatter runs over.  The skin refit (er_refit_skin) exchanges the same kernel once more:
+// k_skin_scatter blends each corner's matrix from a palette (er_skin.h).  refit_listed is the one body of all three.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -282,6 +283,57 @@ __global__ __launch_bounds__(256) void k_xform_scatter(uint32_t moved, uint32_t 
     for (int a = 0; a < 9; a++) { N[a] = e->N[a]; T[a] = e->T[a]; }
     float v[9], o[18];
     er_xform_triangle(m, N, T, r, r + 9, r + 18, v, o, o + 9);
+    float4* q = (float4*)(isect + k);
+    const float* w = (const float*)q;
+    q[0] = make_float4(v[0], v[1], v[2], w[3]);
+    q[1] = make_float4(v[3], v[4], v[5], w[7]);
+    q[2] = make_float4(v[6], v[7], v[8], w[11]);
+    float4* a4 = (float4*)(attr + k);      // n[3][3] and t[3][3] lie first in the record, back to back
+    for (int p = 0; p < 4; p++) a4[p] = make_float4(o[4 * p], o[4 * p + 1], o[4 * p + 2], o[4 * p + 3]);
+    ((float2*)a4)[8] = make_float2(o[16], o[17]);
+}
+
+// er_render_skin: k_xform_scatter with the pose of each CORNER blended from a palette (er_skin.h has the arithmetic).  The same work
+// items, the same reads of the rest copy, slot_of and the record's w words, the same stores.  New per triangle: its 72 bytes of
+// influences, six pieces laid out piece-major over the rows of the skinned objects (ErSkinDev: consecutive lanes, consecutive
+// addresses), and per corner up to four matrices of the listed object's palette -- 48 bytes each, the same few for every lane of the
+// object, read through the cache.  A bone index is clamped to the entry's bone count (er_skin_set checked it: the clamp changes
+// nothing, and no index can reach past the palette).  Plain vector stores; one writer per record; no atomics.
+__global__ __launch_bounds__(256) void k_skin_scatter(uint32_t moved, uint32_t entries, const ErSkinEntry* __restrict__ ent, const uint32_t* __restrict__ first,
+                                                       const float4* __restrict__ rest, uint32_t total, const float4* __restrict__ inf_w, const uint2* __restrict__ inf_b,
+                                                       uint32_t rows, const float* __restrict__ palette, uint32_t bones, const uint32_t* __restrict__ slot_of, uint32_t n,
+                                                       ErTriIsect* isect, ErTriAttr* attr, uint32_t* __restrict__ ids_out) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= moved) return;
+    uint32_t lo = 0, hi = entries;      // the LAST entry that starts at or before t
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (ent[mid].start <= t) lo = mid; else hi = mid;
+    }
+    const ErSkinEntry e = ent[lo];
+    const uint32_t j = first[e.object] + (t - e.start), row = e.row + (t - e.start);
+    ids_out[t] = 0xffffffffu;           // (names no triangle: the kernels behind this one skip it)
+    if (j >= total || row >= rows || e.bones == 0 || e.pal >= bones || e.bones > bones - e.pal) return;      // cannot happen with a checked list
+    float r[4 * ER_XFORM_PIECES];
+    for (uint32_t p = 0; p < ER_XFORM_PIECES; p++) {
+        const float4 q = rest[(size_t)p * total + j];
+        r[4 * p] = q.x; r[4 * p + 1] = q.y; r[4 * p + 2] = q.z; r[4 * p + 3] = q.w;
+    }
+    const uint32_t id = __float_as_uint(r[27]);
+    if (id >= n) return;
+    ids_out[t] = id;
+    const uint32_t k = slot_of[id];
+    if (k >= n) return;
+    const float* P = palette + (size_t)e.pal * 12;
+    const uint32_t last = e.bones - 1;
+    float v[9], o[18];
+    for (uint32_t c = 0; c < 3; c++) {
+        const float4 w4 = inf_w[(size_t)c * rows + row];
+        const uint2 b2 = inf_b[(size_t)c * rows + row];
+        const float w[ER_SKIN_K] = {w4.x, w4.y, w4.z, w4.w};
+        const uint32_t b[ER_SKIN_K] = {min(b2.x & 0xffffu, last), min(b2.x >> 16, last), min(b2.y & 0xffffu, last), min(b2.y >> 16, last)};
+        er_skin_corner(P, b, w, r + 3 * c, r + 9 + 3 * c, r + 18 + 3 * c, v + 3 * c, o + 3 * c, o + 9 + 3 * c);
+    }
     float4* q = (float4*)(isect + k);
     const float* w = (const float*)q;
     q[0] = make_float4(v[0], v[1], v[2], w[3]);
@@ -635,7 +687,34 @@ struct DeviceListed {    // er_render_transform: the rest copy lies on the devic
     }
 };
 
-// The sparse refit over `L`'s triangles (its arguments checked by the caller): er_refit_sparse and er_refit_xform
+struct SkinListed {      // er_render_skin: rest copy and influences lie on the device; entries and palettes go up and k_skin_scatter poses and scatters
+    const ErSkinCall& x;
+    uint32_t count;
+    Tmp<uint32_t> d_ids;
+    Tmp<ErSkinEntry> d_ent;
+    Tmp<float> d_pal;
+    explicit SkinListed(const ErSkinCall& c) : x(c), count(c.moved) {}
+    const uint32_t* ids() const { return d_ids.p; }
+    int allocate(std::string& err) {
+        RF_OK(hipMalloc((void**)&d_ids.p, (size_t)count * 4));
+        RF_OK(hipMalloc((void**)&d_ent.p, (size_t)x.entries * sizeof(ErSkinEntry)));
+        RF_OK(hipMalloc((void**)&d_pal.p, (size_t)x.bones * 48));
+        return 0;
+    }
+    int upload(hipStream_t st, uint64_t* bytes, std::string& err) {
+        RF_OK(hipMemcpyAsync(d_ent.p, x.list, (size_t)x.entries * sizeof(ErSkinEntry), hipMemcpyHostToDevice, st));
+        RF_OK(hipMemcpyAsync(d_pal.p, x.palette, (size_t)x.bones * 48, hipMemcpyHostToDevice, st));
+        *bytes = (uint64_t)x.entries * sizeof(ErSkinEntry) + (uint64_t)x.bones * 48;
+        return 0;
+    }
+    void scatter(const ErRefitTopo& topo, const ErRefitBuffers& b, hipStream_t st) {
+        hipLaunchKernelGGL(k_skin_scatter, dim3((count + 255) / 256), dim3(256), 0, st, count, x.entries, (const ErSkinEntry*)d_ent.p, (const uint32_t*)x.table->d_first,
+                           (const float4*)x.table->d_rest, x.table->total, (const float4*)x.skin->d_w, (const uint2*)x.skin->d_b, x.skin->rows, (const float*)d_pal.p, x.bones,
+                           topo.d_slot_of, b.tri_count, b.isect, b.attr, d_ids.p);
+    }
+};
+
+// The sparse refit over `L`'s triangles (its arguments checked by the caller): er_refit_sparse, er_refit_xform and er_refit_skin
 template <class Listed>
 int refit_listed(ErRefitTopo& topo, const ErRefitBuffers& b, Listed& L, hipStream_t st, ErSparseResult* out, std::string& err) {
     const uint32_t n = b.tri_count, count = L.count;
@@ -744,6 +823,60 @@ int er_refit_xform(ErRefitTopo& topo, const ErRefitBuffers& b, const ErXformCall
         !b.isect || !b.attr || !b.nodes8) { err = "transform refit: missing array"; return -1; }
     DeviceListed L(x);
     return refit_listed(topo, b, L, st, out, err);
+}
+
+hipError_t er_probe_skin(const char** which) {
+    hipFuncAttributes at;
+    *which = "k_skin_scatter (er_refit.hip)";
+    return hipFuncGetAttributes(&at, (const void*)k_skin_scatter);
+}
+
+int er_refit_skin(ErRefitTopo& topo, const ErRefitBuffers& b, const ErSkinCall& x, hipStream_t st, ErSparseResult* out, std::string& err) {
+    *out = ErSparseResult{};
+    if (b.tri_count == 0 || x.moved == 0 || x.entries == 0 || x.bones == 0 || !x.list || !x.palette || !x.table || !x.table->valid || !x.table->d_rest || !x.table->d_first ||
+        x.moved > x.table->total || !x.skin || !x.skin->valid || !x.skin->d_w || !x.skin->d_b || x.moved > x.skin->rows || !b.isect || !b.attr || !b.nodes8) {
+        err = "skin refit: missing array";
+        return -1;
+    }
+    SkinListed L(x);
+    return refit_listed(topo, b, L, st, out, err);
+}
+
+int er_skin_table_build(ErSkinDev& dev, const ErObjectTable& t, const ErSkinTable& k, hipStream_t st, uint64_t* bytes, std::string& err) {
+    dev.release();
+    *bytes = 0;
+    const uint32_t rows = k.rows(), objects = t.objects();
+    if (!rows || k.rec.size() != objects) { err = "skin: no object has a skin"; return -1; }
+    std::vector<float> w;
+    std::vector<uint16_t> bn;
+    try {
+        w.resize((size_t)rows * 3 * ER_SKIN_K);
+        bn.resize((size_t)rows * 3 * ER_SKIN_K);
+    } catch (const std::bad_alloc&) {      // (as a failed device allocation: the caller ends the render, the host copy is already marked)
+        err = "skin: out of host memory for the influences' staging";
+        return -2;
+    }
+    for (uint32_t o = 0; o < objects; o++) {
+        if (!k.has(o)) continue;
+        const ErSkinRecord& r = k.rec[o];
+        const uint32_t size = t.size_of(o);
+        for (uint32_t i = 0; i < size; i++)
+            for (uint32_t c = 0; c < 3; c++) {
+                const size_t from = ((size_t)i * 3 + c) * ER_SKIN_K, to = ((size_t)c * rows + k.row_first[o] + i) * ER_SKIN_K;
+                memcpy(&w[to], &r.weights[from], ER_SKIN_K * 4);
+                memcpy(&bn[to], &r.bones[from], ER_SKIN_K * 2);
+            }
+    }
+    RF_OK(hipMalloc((void**)&dev.d_w, w.size() * 4));
+    RF_OK(hipMalloc((void**)&dev.d_b, bn.size() * 2));
+    hipError_t e = hipMemcpyAsync(dev.d_w, w.data(), w.size() * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dev.d_b, bn.data(), bn.size() * 2, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);      // (the staging goes out of scope)
+    if (e != hipSuccess) { dev.release(); RF_OK(e); }
+    dev.rows = rows;
+    dev.valid = true;
+    *bytes = (uint64_t)rows * 72;
+    return 0;
 }
 
 int er_xform_table_build(ErXformDev& dev, const ErObjectTable& t, hipStream_t st, std::string& err) {

@@ -187,12 +187,19 @@ struct ErScene {
     ErXformDev xform_dev;
     ErSparseInfo xform{};
     uint32_t xform_objects = 0;
+    // er_skin_set / er_render_skin (er_skin.h): the skins beside the object table (empty until the first er_skin_set), the influences'
+    // device form (built by the first er_render_skin after er_skin_set or er_render_begin), and what er_skin_info reports, as above.
+    ErSkinTable skins;
+    ErSkinDev skin_dev;
+    ErSparseInfo skin{};
+    uint32_t skin_objects = 0, skin_bones = 0;
+    uint64_t skin_influence_bytes = 0;
     // er_render_topology (er_api_edit.cpp): the geometry store -- the six arrays on the device in id order, valid from a
     // topology edit whose build ran on the device until anything else writes geometry or material ids (store.release() there) -- and
     // what er_topology_info reports.
     ErGeomStore store;
     ErTopologyInfo topo{};
-    void flush_poses() noexcept { er_objects_flush(objects, vertices.data(), normals.data(), tangents.data()); }
+    void flush_poses() noexcept { er_skin_flush(objects, skins, vertices.data(), normals.data(), tangents.data()); }      // (both kinds of pending pose)
     // er_accel_cost / er_update_policy_set (er_api_edit.cpp): every build and every refit bumps accel_version; the cost last measured is kept
     // with the version it was measured at.  The baseline of ER_REBUILD_AUTO is the cost of the last BUILT tree: known once such a tree
     // has been measured, forgotten with the next build.
@@ -325,6 +332,7 @@ struct ErScene {
         d_light_tab.release(); light_emitters = 0; light_total = 0.0f;
         refit_topo.release();
         xform_dev.release();
+        skin_dev.release();
         store.release();
         d_first_hit_spill.release(); d_first_hit_counts.release();
         for (auto& c : first_hit.counts) c = 0;      // (the mode itself stays: er_first_hit_set)

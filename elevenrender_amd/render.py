@@ -244,6 +244,57 @@ class RenderingManager:
         abi.check(self.lib.er_transform_info(self.handle, C.byref(a)))
         return {n: getattr(a, n) for n, _ in abi.ErTransformInfo._fields_ if n != "reserved"}
 
+    def set_skin(self, object, bones, weights):
+        """er_skin_set: object `object` of the set_objects() table gets a skin -- `bones` (integers below the bone count) and `weights`
+        (float32 in [0, 1], used as given) of shape [triangles of the object][3][4], in the order of the object's ids; the bone count
+        is taken as max(bones) + 1 unless `bones` is a (bones, bone_count) pair.  bones=None removes the object's skin."""
+        k = abi.ErSkin()
+        if int(object) != object or not 0 <= int(object) <= 0xffffffff:
+            raise ValueError("set_skin: `object` is an object index")
+        k.object = int(object)
+        keep = []
+        if bones is not None:
+            bone_count = None
+            if isinstance(bones, tuple):
+                bones, bone_count = bones
+            b = np.ascontiguousarray(bones)
+            w = np.ascontiguousarray(weights, np.float32)
+            if b.dtype.kind not in "iu" or b.size == 0 or b.size % 12 or b.size != w.size or int(b.min()) < 0 or int(b.max()) > 0xffff:
+                raise ValueError("set_skin: bones and weights are [triangles][3][4], bones 16-bit indices")
+            b = b.astype(np.uint16)
+            keep = [b, w]      # (alive until the call returns)
+            k.bone_count = int(b.max()) + 1 if bone_count is None else int(bone_count)
+            k.bones, k.weights = b.ctypes.data_as(C.POINTER(C.c_uint16)), w.ctypes.data_as(C.POINTER(C.c_float))
+        abi.check(self.lib.er_skin_set(self.handle, C.byref(k)))
+
+    def skin(self, palettes, camera=None):
+        """er_render_skin: `palettes` maps an object's index to its palette of bone matrices ([bones][3][4] row-major, x' = L x + t;
+        anything that reshapes to [bones][12] float32).  Each listed object takes the linear-blend pose of its REST copy on the device
+        -- absolute --; the others stay.  The render starts over at sample 0 and the history is dropped.  self.scene is not changed."""
+        u = abi.ErSkinUpdate()
+        if camera is not None:
+            u.what |= abi.UPDATE_CAMERA
+            u.camera = camera
+        xs = (abi.ErSkinPose * max(1, len(palettes)))()
+        keep = []
+        for i, (obj, P) in enumerate(palettes.items()):
+            P = np.ascontiguousarray(P, np.float32)
+            if P.size == 0 or P.size % 12:
+                raise ValueError(f"skin: the palette of object {obj} has {P.size} entries, a bone is 3x4")
+            if int(obj) != obj or not 0 <= int(obj) <= 0xffffffff:
+                raise ValueError("skin: the keys of `palettes` are object indices")
+            keep.append(P)      # (alive until the call returns)
+            xs[i].object, xs[i].bone_count, xs[i].palette = int(obj), P.size // 12, P.ctypes.data_as(C.POINTER(C.c_float))
+        if len(palettes):
+            u.what |= abi.UPDATE_GEOMETRY
+            u.count, u.poses = len(palettes), xs
+        abi.check(self.lib.er_render_skin(self.handle, C.byref(u)))
+
+    def skin_info(self):
+        a = abi.ErSkinInfo()
+        abi.check(self.lib.er_skin_info(self.handle, C.byref(a)))
+        return {n: getattr(a, n) for n, _ in abi.ErSkinInfo._fields_}
+
     def update_info(self):
         a = abi.ErUpdateInfo()
         abi.check(self.lib.er_update_info(self.handle, C.byref(a)))

@@ -545,6 +545,69 @@ typedef struct ErTransformInfo {
 } ErTransformInfo;
 int er_transform_info(ErScene* scene, ErTransformInfo* out);
 
+/* Skinning: registered objects DEFORMED on the device by linear-blend skinning from bone matrices (csrc/er_skin.h gives every operation;
+ * DESIGN.md 3p).  Geometry is a triangle soup, so influences are per corner: ER_SKIN_INFLUENCES pairs (bone index, weight) for each of a
+ * triangle's three corners, in the order of the object's tri_ids.
+ * er_skin_set: gives object `object` of the er_objects_set table a skin of bone_count bones, or with bone_count 0 removes it (the arrays
+ * are then not read).  Legal any time after er_scene_create, once a table exists.  The influences are copied and belong to the scene:
+ * they survive rebuilds and a second er_render_begin.  er_objects_set and er_render_topology DROP EVERY SKIN (a pending skin pose is
+ * flushed into the host copy first, as pending matrices are; ErSkinInfo.skinned is then 0): carrying skins through a renumbering is not
+ * done.  ER_ERR_STATE without an object table.  ER_ERR_INVALID_ARG, the scene and every skin untouched: NULL arguments; an object index
+ * not below the object count; an empty object; bone_count above ER_SKIN_MAX_BONES; a bone index not below bone_count, also where its
+ * weight is 0; a weight that is not finite or outside [0, 1].  Weights are used as given: they are not renormalised.
+ * er_render_skin: every listed object takes the pose of csrc/er_skin.h from its REST copy and the given palette of row-major 3x4 bone
+ * matrices: per corner the blended matrix M = ((w0 P[b0] + w1 P[b1]) + w2 P[b2]) + w3 P[b3]; the position by M, the normal by the
+ * cofactor matrix of M's 3x3 part, the tangent by that part, both normalised (unit or zero).  The pose is ABSOLUTE: nothing composes and
+ * nothing drifts.  Objects not listed keep their current pose.  A later er_render_transform of the same object poses it by matrix from
+ * the same rest copy, and the other way round: the last call wins.  After ER_OK everything observable -- planes, samples, RNG, counters,
+ * er_state_*, er_light_info, the structure byte for byte (er_debug_read_accel), ErAccelInfo except its timings, ErUpdateInfo's counts,
+ * every decision of er_update_policy_set with its ErRebuildInfo, and what feature planes, id planes, the history (dropped: a deformation
+ * has no back matrix) and the variance state do -- equals what er_render_update_sparse would leave when given the listed objects' ids
+ * with that pose as vertices, normals and tangents, the same `what` and the same camera.  tangent_sign and the records' sign stay.
+ * What differs is the cost: the host touches no triangle, and what goes to the device follows the objects and bones listed, never their
+ * triangle counts:
+ *   ErSkinInfo.bytes_uploaded = 32 x objects + 48 x bones + 64   (+ 64 on path 2)
+ * -- one entry per listed object, the palettes, the refit's sixteen counter words.  The influences lie on the device beside the rest
+ * copy, 72 bytes per triangle of a skinned object (3 x 4 x (2 + 4)); they are uploaded with the rest copy by the first er_render_skin
+ * after an er_skin_set or an er_render_begin and counted by themselves in ErSkinInfo.influence_bytes (0 in every other call).  The
+ * scene's host copy takes a pose lazily, as after er_render_transform.
+ * ER_ERR_STATE: the scene is not begun, or ER_UPDATE_GEOMETRY names an object without a skin.  ER_ERR_INVALID_ARG, the scene untouched
+ * and still begun: NULL arguments; `what` 0 or with unknown bits; GEOMETRY with count 0; an object index not below the object count; an
+ * object listed twice; a bone_count different from the skin's; a matrix entry that is not finite; a bone whose det(L) is not > 0; a bone
+ * that fails er_render_transform's bound 1e37 against the object's largest rest |coordinate|; a bone with a linear entry |L_ij| > 16384
+ * (2^14: blended entries then stay below 2^16 and their float32 cofactors below 2^33).  The checks cost O(objects listed + bones
+ * listed) time and memory. */
+#define ER_SKIN_INFLUENCES 4
+#define ER_SKIN_MAX_BONES  1024u
+typedef struct ErSkin {
+    uint32_t object;          /* index into the er_objects_set table */
+    uint32_t bone_count;      /* 1..ER_SKIN_MAX_BONES; 0 removes the object's skin (arrays not read) */
+    const uint16_t* bones;    /* [size_of(object)][3][ER_SKIN_INFLUENCES], the object's tri_ids order */
+    const float* weights;     /* same shape */
+} ErSkin;
+int er_skin_set(ErScene* scene, const ErSkin* skin);
+typedef struct ErSkinPose { uint32_t object, bone_count; const float* palette; /* [bone_count][12] */ } ErSkinPose;
+typedef struct ErSkinUpdate {
+    uint32_t what;            /* ER_UPDATE_CAMERA | ER_UPDATE_GEOMETRY, as ErSparseUpdate */
+    ErCamera camera;          /* read iff ER_UPDATE_CAMERA */
+    uint32_t count;           /* ER_UPDATE_GEOMETRY: listed objects, each at most once */
+    const ErSkinPose* poses;
+} ErSkinUpdate;
+int er_render_skin(ErScene* scene, const ErSkinUpdate* update);
+typedef struct ErSkinInfo {
+    uint32_t calls;           /* successful er_render_skin calls with ER_UPDATE_GEOMETRY since er_scene_create */
+    uint32_t skinned;         /* objects that have a skin now */
+    uint32_t objects;         /* the last call: listed objects ... */
+    uint32_t bones;           /* ... their bones ... */
+    uint32_t moved;           /* ... and their triangles */
+    uint32_t path, why_full;  /* as ErSparseInfo */
+    uint32_t dirty_nodes2, dirty_nodes8;
+    float refit_ms;           /* device time, HIP events, as ErUpdateInfo.refit_ms */
+    uint64_t bytes_uploaded;  /* host-to-device bytes of the geometry stage: entries, palettes and the refit's counter words */
+    uint64_t influence_bytes; /* the influences, where this call uploaded them (72 x the triangles of the skinned objects), else 0 */
+} ErSkinInfo;
+int er_skin_info(ErScene* scene, ErSkinInfo* out);
+
 /* Add and remove triangles of a begun scene in place (csrc/er_topology_host.h states the numbering once).
  * The edit is applied in this order: the listed triangles are removed, the given ones appended, then `rest` -- an er_render_edit of the
  * RESULT, so a rest.material_id has the new tri_count entries and overrides the appended ones.  Survivors keep their relative order:

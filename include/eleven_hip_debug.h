@@ -310,6 +310,13 @@ void er_debug_set_gpu_build_failure(int kind);
 int er_debug_transform_apply(const float m[12], uint32_t count, const float* vertices, const float* normals, const float* tangents,
                              float* out_vertices, float* out_normals, float* out_tangents);
 
+/* The host form of er_render_skin's arithmetic (csrc/er_skin.h) on caller arrays, no device needed: a palette of bone_count row-major 3x4
+ * matrices, `count` triangles with [count][3][ER_SKIN_INFLUENCES] bones and weights and [count][3][3] rest vertices, normals and tangents
+ * -> the skinned ones in the three outputs (which must not overlap the inputs).  ER_ERR_INVALID_ARG: a NULL argument, or influences that
+ * er_skin_set would refuse (bone_count, a bone index, a weight).  The palette's own checks (er_render_skin's) are not applied here. */
+int er_debug_skin_apply(const float* palette, uint32_t bone_count, uint32_t count, const uint16_t* bones, const float* weights, const float* vertices,
+                        const float* normals, const float* tangents, float* out_vertices, float* out_normals, float* out_tangents);
+
 /* The ranking er_render_ids gives every pixel (csrc/er_ids.h er_id_rank, the function the kernel calls), on caller arrays, no device
  * needed: `count` <= 64 ids of the rays that hit (NULL with count 0) -> out_ids / out_counts [ER_ID_SLOTS] by (count descending, id
  * ascending as unsigned), unused slots (ER_ID_NONE, 0); *distinct = the number of distinct ids.  ER_ERR_INVALID_ARG: a NULL argument,

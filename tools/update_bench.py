@@ -36,6 +36,12 @@ timed apart), alternated, --rounds (at least 7) times each in one process: the f
 ones: wall time of the call, update_ms, refit_ms, bytes uploaded, the caller's numpy time, and transform / sparse.
 
     python tools/update_bench.py --transform [--rounds 7] [--log FILE]
+
+--skin (C4 only): the same two objects, each with a seeded skin of 32 bones and 4 influences per corner, deformed back and
+forth between two seeded palettes -- through er_render_skin on one manager (A) and through er_render_update_sparse on another (B),
+whose caller skins the object's rest arrays in numpy first (elevenrender_amd/skin.py; timed apart), alternated as above.
+
+    python tools/update_bench.py --skin [--rounds 7] [--log FILE]
 """
 import argparse
 import ctypes as C
@@ -46,7 +52,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from elevenrender_amd import abi, render, scenes, transform  # noqa: E402
+from elevenrender_amd import abi, render, scenes, skin, transform  # noqa: E402
 
 OUT = []
 LOG = None      # --log: every line is appended as it is said, so that a run that is cut short leaves what it measured
@@ -336,6 +342,71 @@ def transform_bench(name, sc, max_bounces, rounds, instances):
     b.close()
 
 
+def skin_bench(name, sc, max_bounces, rounds, instances, bones=32):
+    rest = [a.reshape(-1, 3, 3) for a in (sc.vertices, sc.normals, sc.tangents)]
+    v = rest[0]
+    n = len(v)
+    per = n // instances
+    mid = instances // 2
+    blob = np.arange(mid * per, (mid + 1) * per)
+    tenth = np.arange(0, (instances // 10) * per)
+    rng = np.random.default_rng(17)
+
+    def influences(size):      # 4 non-zero weights per corner, summing to 1 in float32 up to rounding, each within [0, 1]
+        b = rng.integers(0, bones, size=(size, 3, 4)).astype(np.uint16)
+        w = rng.uniform(0.1, 1.0, size=(size, 3, 4))
+        return b, np.minimum((w / w.sum(-1, keepdims=True)).astype(np.float32), np.float32(1))
+
+    def seeded_palette(ids, turn):      # per bone a small turn about z x a non-uniform scale about the object's centre, and a small shift
+        c = v[ids].reshape(-1, 3).mean(0).astype(np.float64)
+        P = np.empty((bones, 3, 4), np.float32)
+        for k in range(bones):
+            a = turn * rng.uniform(0.5, 1.0)
+            L = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]]) @ np.diag(rng.uniform(0.95, 1.0, size=3))
+            P[k] = np.concatenate([L, (c - L @ c + rng.normal(size=3) * 0.01)[:, None]], 1)
+        return P
+
+    say(f"== {name} (skinning): {n} triangles, {sc.x_res}x{sc.y_res}, max_bounces {max_bounces}; {bones} bones, 4 influences per corner")
+    a, _ = manager(sc, max_bounces)
+    b, _ = manager(sc, max_bounces)
+    rate(a, 2)
+    rate(b, 2)
+    a.set_objects([blob, tenth])
+    med = lambda xs: float(np.median(xs))
+    for tag, what, obj, ids in (("a", "one blob instance", 0, blob), ("b", "a tenth of the instances as one object", 1, tenth)):
+        say(f"   ({tag}) {what}: {len(ids)} triangles ({100.0 * len(ids) / n:.2f} %)")
+        bw = influences(len(ids))
+        t0 = time.perf_counter()
+        a.set_skin(obj, (bw[0], bones), bw[1])
+        say(f"      er_skin_set: {(time.perf_counter() - t0) * 1e3:.2f} ms wall; the influences on the device take {skin.INFLUENCE_BYTES * len(ids)} bytes")
+        palettes = (seeded_palette(ids, 0.02), seeded_palette(ids, 0.01))
+        parts = [np.ascontiguousarray(r[ids]) for r in rest]      # (the caller of the sparse path keeps its object's rest arrays)
+        rows = []
+        for k in range(rounds + 1):      # round 0: the first call of either kind on this topology (and the upload of rest copy and influences)
+            P = palettes[k % 2]
+            t0 = time.perf_counter()
+            a.skin({obj: P})
+            wa = (time.perf_counter() - t0) * 1e3
+            ki, ua = a.skin_info(), a.update_info()
+            t0 = time.perf_counter()
+            pv, pn, pt = skin.pose(P, *bw, *parts)
+            numpy_ms = (time.perf_counter() - t0) * 1e3
+            t0 = time.perf_counter()
+            b.update(tri_ids=ids, vertices=pv, normals=pn, tangents=pt)
+            wb = (time.perf_counter() - t0) * 1e3
+            si, ub = b.sparse_info(), b.update_info()
+            say(f"      round {k}: skin wall {wa:8.3f} update_ms {ua['update_ms']:8.3f} refit_ms {ki['refit_ms']:7.3f} path {ki['path']} why_full {ki['why_full']} dirty nodes {ki['dirty_nodes2']} / {ki['dirty_nodes8']}"
+                f" uploaded {ki['bytes_uploaded']} B (influences {ki['influence_bytes']} B)   sparse wall {wb:8.3f} update_ms {ub['update_ms']:8.3f} refit_ms {si['refit_ms']:7.3f} path {si['path']}"
+                f" uploaded {si['bytes_uploaded']} B   caller's numpy {numpy_ms:8.3f} ms")
+            if k:
+                rows.append((wa, ua["update_ms"], ki["refit_ms"], wb, ub["update_ms"], si["refit_ms"], numpy_ms))
+        m_ = [med([r[i] for r in rows]) for i in range(7)]
+        say(f"      medians of rounds 1..{rounds}: skin wall {m_[0]:.3f} update_ms {m_[1]:.3f} refit_ms {m_[2]:.3f}   sparse wall {m_[3]:.3f} update_ms {m_[4]:.3f} refit_ms {m_[5]:.3f}"
+            f"   caller's numpy {m_[6]:.3f}   skin / sparse: wall {m_[0] / m_[3]:.4f}, refit {m_[2] / m_[5]:.4f}; with the caller's numpy {m_[0] / (m_[3] + m_[6]):.4f}")
+    a.close()
+    b.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C2,C4")
@@ -345,6 +416,7 @@ def main():
     ap.add_argument("--rebuild", action="store_true", help="the rebuild policies of er_update_policy_set instead of the update / refit figures")
     ap.add_argument("--sparse", action="store_true", help="er_render_update_sparse against the full and the camera-only update")
     ap.add_argument("--transform", action="store_true", help="er_render_transform against er_render_update_sparse of the same pose (C4)")
+    ap.add_argument("--skin", action="store_true", help="er_render_skin against er_render_update_sparse of the same deformation (C4)")
     ap.add_argument("--ratio", type=float, default=2.0, help="--rebuild: max_cost_ratio of the ER_REBUILD_AUTO runs")
     args = ap.parse_args()
     if args.log:
@@ -353,6 +425,9 @@ def main():
         open(LOG, "w").close()
     if args.transform:
         transform_bench("C4", scenes.blob_instances(x_res=3840, y_res=2160), 8, max(7, args.rounds), 10000)
+        return
+    if args.skin:
+        skin_bench("C4", scenes.blob_instances(x_res=3840, y_res=2160), 8, max(7, args.rounds), 10000)
         return
     for cfg in args.configs.split(","):
         if args.sparse:
